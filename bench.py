@@ -8,6 +8,7 @@ inputs, dropout ENABLED (p = 0.1), config ``config/vilbert.json`` with ``v_featu
     python bench.py --gpus N --steps K --warmup W          # starts its own N ranks (one fresh process per GPU, as train.py:356-363 does)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                # ... or under a launcher that has set RANK / WORLD_SIZE already
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # ... and write what the last timed step computed to DIR/*.npy
 
 Prints ONE JSON line on rank 0:
   value        : whole-job QA-pairs/s with the batches already resident in HBM when the timed region starts (a pool of 8
@@ -70,6 +71,9 @@ TILE_NAMES = {0: "dma128x128w4s3", 1: "dma128x64w4s4", 2: "dma64x128w4s4", 3: "d
               63: "ldrp128x64w4+4s3", 64: "ldrp128x64w4+2s2", 60: "ldr256x128w4+4s3", 65: "ldr256x128w4+4s2",
               66: "ldrh256x128w4+4s3", 67: "ldrh256x128w8+4s3", 68: "ldrh128x128w4+4s3", 69: "ldrh128x64w4+2s3", 70: "ldrh128x128w8+4s3", 71: "ldrh256x128w4+4s2"}
 KERNEL_SOURCES = ("cqa-crct_amd/csrc/gemm.hip", "cqa-crct_amd/csrc/engine.cpp", "cqa-crct_amd/csrc/common.hip.h")
+STEP_OUTPUTS = ("loss", "lm_loss", "nsp_loss", "img_loss", "nsp_scores", "regression", "legend_loss")   # crct.step_adapter.forward (training)
+DUMP_SAMPLE = 1 << 21                     # --dump-outputs: elements kept of a larger output (8 MB as float32)
+DUMP_LIMIT_BYTES = 64 << 20               # ... and all files together
 
 
 def parse():
@@ -151,10 +155,17 @@ def parse():
                     "driver's own limit); each rank's last stderr lines are relayed")
     ap.add_argument("--launch-check", action="store_true", help="test hook: every rank reports its rendezvous environment (rank 0 as the JSON line) and "
                     "exits before touching a GPU -- the self-launch path of `python bench.py --gpus N` checked on a box without GPUs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step computed as "
+                    "DIR/<name>.npy (float32; float64 for integer data): the step's return values (crct.step_adapter.forward, nested "
+                    "lists flattened to <name>_<i>) and params_after_step, the parameters after its AdamW update.  An output of more "
+                    "than %d elements is a fixed sample of that many (torch.randint, CPU generator seeded 0, sorted): the same indices "
+                    "in every run.  Rank 0 only; the inputs are the same in every run with the same arguments" % DUMP_SAMPLE)
     ap.add_argument("--dtype", choices=("bf16", "fp8"), default="bf16",
                     help="bf16: the headline (BASELINE configs[1]).  fp8: BASELINE configs[4] -- the QKV / FFN GEMMs of the forward pass on "
                          "OCP e4m3 operands with per-tensor delayed scaling and fp32 accumulation, backward and everything else bf16")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.workload:
         a.batch, a.vis, a.tokens, a.feat = WORKLOADS[a.workload]
     return a
@@ -346,6 +357,43 @@ def cpu_baseline(core, cfg, params, B, T, V, Fv, budget_s=20.0, max_threads=16):
                 sample="%d x forward+backward of the fp32 CPU oracle (oracle/crct_oracle.py) at B=%d (sized from a B=4 probe of %.2f s "
                        "for a ~%.0f s budget), V=%d, T=%d, F_v=%d, dropout on; %.1f s in total on %d threads of %d logical cores (%s)"
                        % (reps, Bs, probe, budget_s, V, T, Fv, dt, threads, os.cpu_count() or 1, cpu_model()))
+
+
+def dump_outputs(path, outputs, core):
+    """--dump-outputs: what the last timed step computed -- its return values (``outputs``, the tuple of
+    crct.step_adapter.forward) and the parameters after its update -- as ``path/<name>.npy``.  Floating data is written as
+    float32 (float64 stays float64), integer / boolean data as float64.  An output of more than DUMP_SAMPLE elements is
+    flattened and sampled at DUMP_SAMPLE indices drawn by a CPU generator seeded 0 (sorted): the same indices in every run."""
+    import numpy as np
+    arrays = {}
+
+    def add(name, v):
+        if v is None:
+            return
+        if isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                add("%s_%d" % (name, i), x)
+            return
+        arrays[name] = v.detach() if torch.is_tensor(v) else torch.tensor(v)
+    for name, v in zip(STEP_OUTPUTS, outputs):
+        add(name, v)
+    arrays["params_after_step"] = core.flat_params.detach()
+    if arrays["params_after_step"].is_cuda:
+        torch.cuda.synchronize()                     # the overlapped AdamW of the last step has written the parameters
+    host = {}
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        floating = t.is_floating_point()
+        t = t.to(torch.float64 if (t.dtype == torch.float64 or not floating) else torch.float32)
+        host[name] = t.cpu().numpy()
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def launch_ranks(n, timeout_s=600.0):
@@ -590,7 +638,10 @@ def main():
 
     def run_step():
         batch = next(cur["feed"])
-        loss = step_forward(model, batch, params)[0]
+        res = step_forward(model, batch, params)
+        loss = res[0]
+        if a.dump_outputs:
+            cur["outputs"] = res
         if stats_red is not None:
             # the reference's per-iteration stats exchange (train.py:181-189): copied and all-reduced on a side stream while
             # backward runs, collected at the end of the step (no collective between forward and backward on the main stream)
@@ -639,6 +690,8 @@ def main():
                              split_k=r.split_k, n_problems=r.n_problems, flops=r.flops))
         with open(a.launch_log, "w") as f:
             json.dump(dict(steps=a.steps, source_hash=source_hash(), workload=[a.batch, a.vis, a.tokens, a.feat], dtype=a.dtype, launches=recs), f)
+    if a.dump_outputs and rank == 0:                 # before any further step overwrites them
+        dump_outputs(a.dump_outputs, cur["outputs"], core)
     host_ms = cur.get("host_ms_per_step")
     final_loss = float(loss.detach())
     # mean loss of the last timed step over the GLOBAL batch: the all-reduced stats when ranks exchange, else the local loss

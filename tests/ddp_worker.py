@@ -7,6 +7,8 @@ multi-GPU run uses with the RCCL backend.  Each rank takes its half of a batch; 
 
 backend "nccl" (a box with >= 2 GPUs: tests/test_ddp_gpu.py starts it only there): rank r runs on cuda:r and the exchange is the
 product's default route -- crct.rccl.Communicator over the ranks, ncclAllReduce on the engine's auxiliary stream.
+
+tests/conftest.py starts the ranks through ``--cases`` (``run_cases`` below): one case at a time.
 """
 import os
 import sys
@@ -154,5 +156,76 @@ def main():
     dist.destroy_process_group()
 
 
+def run_cases(outdir, limit_s, cases):
+    """The cases one after another, each as two fresh rank processes of this file: never more than two ranks on the GPU at a time.
+    This process itself never touches the GPU.  ``<outdir>/<case>.status`` (JSON) tells how each case ended; a rank that fails or
+    outlives ``limit_s`` ends its case (its peer is ended too: it would wait in a collective for ever), and no later case starts.
+    SIGTERM, or the end of the parent (the pytest process), ends the running ranks and this process.
+
+    python tests/ddp_worker.py --cases <outdir> <limit_s> <case> [<case> ...]      (case: tiny | full | tiny_rccl | full_rccl)
+    """
+    import json
+    import signal
+    import socket
+    import subprocess
+    import time
+
+    def write_status(case, st):
+        path = os.path.join(outdir, case + ".status")
+        with open(path + ".tmp", "w") as f:
+            json.dump(st, f)
+        os.replace(path + ".tmp", path)            # the test polls for the file: it appears complete or not at all
+
+    def end(procs):
+        for p in procs:
+            if p.poll() is None:
+                p.terminate()
+                try:
+                    p.wait(timeout=10)
+                except subprocess.TimeoutExpired:
+                    p.kill()
+                    p.wait()
+
+    signal.signal(signal.SIGTERM, lambda *_: sys.exit(143))       # -> the finally below
+    parent = os.getppid()
+    failed, procs = None, []
+    try:
+        for case in cases:
+            if failed is not None:
+                write_status(case, dict(ok=False, not_run="case %s failed before it" % failed))
+                continue
+            with socket.socket() as s:             # a free rendezvous port
+                s.bind(("127.0.0.1", 0))
+                port = s.getsockname()[1]
+            procs, logs = [], []
+            for rank in range(2):
+                logs.append(os.path.join(outdir, "%s_rank%d.log" % (case, rank)))
+                argv = [sys.executable, os.path.abspath(__file__), str(rank), "2", str(port), outdir, case.split("_")[0]]
+                if case.endswith("_rccl"):
+                    argv.append("nccl")
+                with open(logs[-1], "w") as log:
+                    procs.append(subprocess.Popen(argv, stdout=log, stderr=subprocess.STDOUT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")))
+            t_end = time.monotonic() + limit_s
+            timed_out = False
+            while any(p.poll() is None for p in procs) and not any(p.poll() not in (None, 0) for p in procs):
+                if os.getppid() != parent:
+                    sys.exit(1)                    # nobody is left to read the results
+                if time.monotonic() > t_end:
+                    timed_out = True
+                    break
+                time.sleep(0.1)
+            end(procs)
+            rcs = [p.returncode for p in procs]
+            ok = not timed_out and rcs == [0, 0]
+            write_status(case, dict(ok=ok, rc=rcs, timed_out=timed_out, limit_s=limit_s, logs=logs))
+            if not ok:
+                failed = case
+    finally:
+        end(procs)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1] == "--cases":
+        run_cases(sys.argv[2], float(sys.argv[3]), sys.argv[4:])
+    else:
+        main()

@@ -110,8 +110,42 @@ def test_bench_starts_its_own_ranks():
     assert res.returncode != 0 and "does not match WORLD_SIZE" in res.stderr
 
 
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs (the writer, on CPU tensors): every return value of the step as <name>.npy, nested lists flattened,
+    floating data as float32, integers as float64, an output above DUMP_SAMPLE elements as the same seeded sample in every run,
+    all of it under the 64 MB limit."""
+    import sys
+    import numpy as np
+    import torch
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+
+    class Core:
+        flat_params = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)
+    logits = torch.randn(4, 2, dtype=torch.bfloat16)
+    outputs = (torch.tensor(1.5), torch.zeros(1, 1), torch.tensor([0.25]), None, logits,
+               [torch.randn(4, 1), torch.tensor(0.5), torch.ones(4, dtype=torch.int64), (torch.tensor(3), torch.tensor(2)), None], torch.zeros(1))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outputs, Core())
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(n + ".npy" for n in ("loss", "lm_loss", "nsp_loss", "nsp_scores", "regression_0", "regression_1", "regression_2",
+                                                 "regression_3_0", "regression_3_1", "legend_loss", "params_after_step")), names
+    total = 0
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= bench.DUMP_LIMIT_BYTES
+    assert np.load(str(tmp_path / "a" / "loss.npy")) == np.float32(1.5)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "nsp_scores.npy")), logits.float().numpy())
+    assert np.load(str(tmp_path / "a" / "regression_2.npy")).dtype == np.float64
+    p = np.load(str(tmp_path / "a" / "params_after_step.npy"))
+    assert p.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(p) >= 0) and len(np.unique(p)) > bench.DUMP_SAMPLE // 2
+
+
 @pytest.mark.gpu
-def test_two_rank_bench_runs_end_to_end():
+def test_two_rank_bench_runs_end_to_end(tmp_path):
     """The N > 1 path of bench.py as the driver launches it (`python -m torch.distributed.run --nproc-per-node 2 bench.py
     --gpus 2 ...`), on this one-GPU box with both ranks on cuda:0 and gloo between them (CRCT_BENCH_SHARE_GPU: a developer
     switch that changes the process group only): FlatGradDDP in event mode, the stats all-reduce inside the step, the
@@ -151,11 +185,17 @@ def test_two_rank_bench_runs_end_to_end():
     # the same four optimizer steps by ONE rank on the concatenation of the two ranks' batches: the data-parallel run must land on
     # the same mean loss (1/world folded into the gradient seeds, SUM all-reduce, every rank applying the same update)
     env1 = {k: v for k, v in env.items() if k != "CRCT_BENCH_SHARE_GPU"}
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--emulate-ranks", "2"] + common, cwd=ROOT, env=env1,
-                         capture_output=True, text=True, timeout=600)
+    dump = str(tmp_path / "outputs")
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--emulate-ranks", "2", "--dump-outputs", dump] + common,
+                         cwd=ROOT, env=env1, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     one = json.loads([r for r in res.stdout.strip().split("\n") if r.startswith("{")][0])
     assert one["config"]["global_batch"] == 32
+    # --dump-outputs: the loss of the LAST timed step is the one the line reports
+    import numpy as np
+    assert float(np.load(os.path.join(dump, "loss.npy"))) == one["config"]["final_loss"]
+    assert np.load(os.path.join(dump, "nsp_scores.npy")).shape[0] == 32
+    assert np.isfinite(np.load(os.path.join(dump, "params_after_step.npy"))).all()
     ref = one["config"]["global_loss"]
     assert abs(losses["fp32"] - ref) <= 2e-3 * abs(ref), (losses, ref)       # different batch split -> other summation orders / bf16 roundings
     assert abs(losses["bf16"] - ref) <= 5e-3 * abs(ref), (losses, ref)

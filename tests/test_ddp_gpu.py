@@ -10,7 +10,9 @@ this module waits for them and checks what rank 0 and rank 1 wrote against the C
   * both ranks hold identical gradients, rank 1 received rank 0's parameters at construction,
   * the 9-float stats all-reduce returns the world average / sums.
 """
+import json
 import os
+import time
 
 import numpy as np
 import pytest
@@ -23,16 +25,32 @@ from crct import synthetic as S                    # noqa: E402
 from oracle import crct_oracle as O                # noqa: E402
 from helpers import seeded_weights                 # noqa: E402
 
+# "*_rccl": the same worker with one rank per GPU and the product's default route (crct.rccl: ncclCommInitRank over two
+# processes, ncclAllReduce / the stats all-reduce on the engine's auxiliary stream).  RCCL takes one GPU per rank, so these cases
+# exist where two GPUs are visible (tests/conftest.py starts exactly these cases)
+CASES = ["tiny", "full"] + (["tiny_rccl", "full_rccl"] if torch.cuda.device_count() >= 2 else [])
+
 
 def _results(case, ddp_workers):
     if ddp_workers is None:
         pytest.skip("the DDP workers were not started (no GPU visible at session start)")
-    outdir, procs = ddp_workers
-    if case not in procs:
-        pytest.skip("needs two GPUs: the RCCL workers (one rank per GPU) are only started where torch.cuda.device_count() >= 2")
-    for pr in procs[case]:
-        rc = pr.wait(timeout=240)
-        assert rc == 0, "DDP worker failed:\n" + open(pr.log_path).read()[-4000:]
+    outdir = ddp_workers["outdir"]
+    assert case in ddp_workers["cases"], (case, ddp_workers["cases"])
+    # the cases run one after another, each within limit_s: case i has its result after at most (i + 1) limits
+    status_path = os.path.join(outdir, case + ".status")
+    t_end = time.monotonic() + ddp_workers["limit_s"] * (ddp_workers["cases"].index(case) + 1) + 60
+    while not os.path.exists(status_path):
+        seq = ddp_workers["proc"].poll()
+        assert seq is None or os.path.exists(status_path), "DDP sequencer ended (exit %s) without a result for %s:\n%s" % (
+            seq, case, open(os.path.join(outdir, "sequencer.log")).read()[-4000:])
+        assert time.monotonic() < t_end, "no result of DDP case %s in time" % case
+        time.sleep(0.2)
+    with open(status_path) as f:
+        st = json.load(f)
+    assert "not_run" not in st, st["not_run"]
+    if not st["ok"]:
+        what = "ran past %.0f s" % st["limit_s"] if st["timed_out"] else "exit codes %s" % st["rc"]
+        pytest.fail("DDP worker failed (%s):\n%s" % (what, "\n".join(open(p).read()[-4000:] for p in st["logs"])))
     res = []
     for r in range(2):
         with np.load(os.path.join(outdir, "%s_rank%d.npz" % (case, r))) as z:
@@ -45,9 +63,7 @@ def _cosine(a, b):
     return float((a @ b) / (a.norm() * b.norm() + 1e-300))
 
 
-# "*_rccl": the same worker with one rank per GPU and the product's default route (crct.rccl: ncclCommInitRank over two
-# processes, ncclAllReduce / the stats all-reduce on the engine's auxiliary stream) -- only where the box has two GPUs
-@pytest.mark.parametrize("case", ["tiny", "full", "tiny_rccl", "full_rccl"])
+@pytest.mark.parametrize("case", CASES)
 def test_two_rank_gradient_exchange_matches_oracle(case, ddp_workers):
     r0, r1 = _results(case, ddp_workers)
     case = case.split("_")[0]

@@ -113,8 +113,6 @@ def test_gemm_wgrad_grouped(R):
 @pytest.mark.parametrize("R", [1600, 2880])
 def test_gemm_wgrad_with_bias_gradient(R, gemm_path):
     # rowsum_out: the bias gradient (column sums of dy) out of the weight-gradient kernel itself, single and grouped
-    if gemm_path == "generic":
-        pytest.skip("row sums exist in the LDS-DMA kernel only")
     shapes = [(768, 3072), (2304, 768), (1024, 1024)]
     probs, refs = [], []
     for i, (N, K) in enumerate(shapes):
@@ -122,6 +120,15 @@ def test_gemm_wgrad_with_bias_gradient(R, gemm_path):
         out, db = torch.zeros(N, K, device=DEV), torch.full((N,), 2.0, device=DEV)
         probs.append((dy, x, out, db))
         refs.append((dy.float().t() @ x.float(), dy.float().sum(0) + 2.0))
+    if gemm_path == "generic":
+        # row sums exist in the LDS-DMA kernel only: with every GEMM forced through the register-staged kernel a request for them
+        # is an error, single or grouped -- never a weight gradient with its bias gradient left unwritten
+        with pytest.raises(RuntimeError, match="gemm"):
+            ops.gemm_wgrad_grouped(probs)
+        dy, x, out, db = probs[0]
+        with pytest.raises(RuntimeError, match="gemm"):
+            ops.gemm(dy, x, 768, 3072, R, ta=True, tb=True, lda=768, ldb=3072, out=out, accumulate=True, rowsum_out=db)
+        return
     ops.gemm_wgrad_grouped(probs)
     for (_, _, out, db), (rw, rb) in zip(probs, refs):
         assert rel_err(out, rw) < 2e-3 and rel_err(db, rb) < 2e-3
@@ -140,9 +147,9 @@ def test_gemm_split_k_matches_unsplit_and_is_reproducible(M, N, K, tb, tile, S, 
     """CrctGemmArgs.split_k: S workgroups per output tile, slabs + ticket, the last arriver sums the slabs in slice order and
     runs the FULL epilogue (bias, pre-activation copy, GELU, dropout, residual).  Against fp32 torch within the bf16 bound,
     against the unsplit launch within the fp32 re-association bound, and twice in a row bit for bit (the summation order does not
-    depend on which slice finishes last); ragged M / N edges and a K that does not divide evenly into slices included."""
-    if gemm_path == "generic":
-        pytest.skip("split-K exists in the LDS-DMA kernel only")
+    depend on which slice finishes last); ragged M / N edges and a K that does not divide evenly into slices included.  Split-K exists
+    in the LDS-DMA kernel only: with every GEMM forced through the register-staged kernel the request runs unsplit, and must give the
+    same results under the same bounds."""
     x = bf(rand(M, K, seed=1))
     w = bf(rand(K, N, scale=0.05, seed=2)) if tb else bf(rand(N, K, scale=0.05, seed=2))
     b, add = rand(N, seed=3), bf(rand(M, N, seed=6))
@@ -815,8 +822,7 @@ def test_word_gradient_scan_matches_the_atomic_scatter_and_is_reproducible(B, T,
     """crct_embed_text_bwd's word_embeddings gradient (index_add of the token-row gradients, vilbert.py:300 has no padding_idx, so
     [PAD] collects every padded position): the fixed-order scan -- light ids by one wave, heavy ids shared by the workgroup --
     against the same launcher's float-atomics fall-back (rows_scratch = NULL), and bit-identical when repeated."""
-    if gemm_path != "pipelined":
-        pytest.skip("no GEMM in this test")
+    # no GEMM here: the test runs under both settings of the GEMM-path switch (gemm_path), which must not reach these kernels
     lib = L.load()
     H, V, n_pos, n_types = 768, 500, 64, 2
     M = B * T
@@ -887,9 +893,8 @@ def test_word_gradient_scan_matches_the_atomic_scatter_and_is_reproducible(B, T,
 @pytest.mark.parametrize("mode", ["fwd", "dgrad"])
 def test_grouped_pair_with_epilogues_equals_single_launches(mode, gemm_path):
     """crct_gemm_bf16_grouped with n = 2 and full epilogues (the text / visual pair of a co-attention layer in ONE grid): every
-    problem must come out bit-identical to its own single launch -- same K order per output element, whatever the tile."""
-    if gemm_path != "pipelined":
-        pytest.skip("grouped launches exist for the LDS-DMA kernel only")
+    problem must come out bit-identical to its own single launch -- same K order per output element, whatever the tile.  Grouped
+    launches exist for the LDS-DMA kernel only: forced through the register-staged kernel the group runs as single launches."""
     Mt, Mv = 1600, 2880
     if mode == "fwd":       # text FFN-up (bias, GELU, pre-activation kept) || visual FFN-down (bias, dropout, residual add)
         xt, wt, bt = bf(rand(Mt, 768, seed=1)), bf(rand(3072, 768, scale=0.05, seed=2)), rand(3072, seed=3)
@@ -919,8 +924,7 @@ def test_grouped_pair_with_epilogues_equals_single_launches(mode, gemm_path):
 def test_device_events_order_streams_without_the_system_fence(gemm_path):
     """crct/events.py (crct_event_*): record on one stream, wait on another, query / synchronize from the host; the consumer
     stream must see the producer's kernel results (same-device visibility is all these events promise)."""
-    if gemm_path != "pipelined":
-        pytest.skip("no GEMM in this test")
+    # no GEMM here: the test runs under both settings of the GEMM-path switch (gemm_path), which must not reach these kernels
     from crct.events import DeviceEvent, order_streams
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
     x = torch.zeros(1 << 22, device=DEV)
@@ -1016,8 +1020,7 @@ def test_attention_gives_the_same_bits_for_every_wave_count(gemm_path):
     """attention_mfma.hip splits one (batch, head) over 1, 2 or 4 waves (query tiles, then key tiles); every tile is computed the
     same way in the same summation order, so one wave per pair (crct_attention_force_split(1), the round-1 kernel), two, and the
     default must agree bit for bit -- forward, dq, dk, dv, with dropout, at 7 x 7, 3 x 7, 4 x 4, 3 x 3 and 2 x 2 tiles."""
-    if gemm_path != "pipelined":
-        pytest.skip("no GEMM in this test")
+    # no GEMM here: the test runs under both settings of the GEMM-path switch (gemm_path), which must not reach these kernels
     from crct import lib as L
     lib = L.load()
     res = {}
@@ -1119,7 +1122,7 @@ def test_gelu_epilogues_are_within_one_bf16_step_of_libm(gemm_path):
 def _perturbed_library():
     """tools/lab/libcrct_gelu_perturbed.so: this library with gelu' x 1.001 (make -C cqa-crct_amd/csrc perturbed).  A test fixture, not a
     build product (__graft_entry__.build() does not make it): built HERE when it is missing or older than the library under test --
-    the same structs must be on both sides of the call -- with the box's own hipcc; no hipcc, no sensitivity check (skipped, visibly)."""
+    the same structs must be on both sides of the call -- with the box's own hipcc (a GPU test box has one: without it the test fails)."""
     import os
     import shutil
     import subprocess
@@ -1128,27 +1131,25 @@ def _perturbed_library():
     if os.path.exists(alt) and os.path.getmtime(alt) >= os.path.getmtime(L.LIB_PATH):
         return alt
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) and shutil.which("make")):
-        pytest.skip("no hipcc / make on this box: the perturbed-GELU build cannot be made")
+    assert os.path.exists(hipcc) and shutil.which("make"), "no hipcc / make on this box: the perturbed-GELU build cannot be made"
     env = dict(os.environ, HIPCC=hipcc)
     r = subprocess.run(["make", "-C", os.path.join(root, "cqa-crct_amd", "csrc"), "perturbed"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                        text=True, timeout=1500)
-    if r.returncode != 0 or not os.path.exists(alt):
-        pytest.skip("make perturbed failed: " + r.stdout[-400:])
+    assert r.returncode == 0 and os.path.exists(alt), "make perturbed failed: " + r.stdout[-400:]
     return alt
 
 
 def test_a_build_with_a_perturbed_gelu_derivative_is_told_apart(gemm_path):
     """The sensitivity of test_gelu_epilogues_are_within_one_bf16_step_of_libm: the same check on a build whose GELU' is off by 1e-3
-    relative must FAIL its correct-rounding bound (a quarter of the roundings move), while its unchanged GELU still passes."""
-    if gemm_path != "pipelined":
-        pytest.skip("the second library has its own (default) GEMM path: one run")
+    relative must FAIL its correct-rounding bound (a quarter of the roundings move), while its unchanged GELU still passes.  The
+    second library runs the same GEMM kernel as the library under test (gemm_path): the perturbation is in both of them."""
     alt = _perturbed_library()
     lib2 = C.CDLL(alt)
     lib2.crct_gemm_bf16.restype = C.c_int
     lib2.crct_gemm_bf16.argtypes = [C.POINTER(L.GemmArgs), C.c_void_p]
     lib2.crct_abi_version.restype = C.c_int
     assert lib2.crct_abi_version() == L.load().crct_abi_version()
+    lib2.crct_gemm_force_generic(int(gemm_path == "generic"))
 
     def call2(A, B, M, N, K, **kw):
         g = L.GemmArgs()
