@@ -9,7 +9,7 @@ import ctypes as C
 import torch
 
 from . import lib as L
-from .layout import parameter_table
+from .layout import model_variant, parameter_table
 
 
 def model_dims(cfg, params, cls_dropout=0.1):
@@ -41,7 +41,24 @@ class StepEngine(object):
         # size 0 marks the tensors that never receive a gradient: they are left out of the backward segments' ranges
         sizes = (C.c_int64 * len(self.table))(*[e.numel if e.used else 0 for e in self.table])
         dims = model_dims(cfg, params, cls_dropout)
-        self.handle = self.lib.crct_engine_create(C.byref(dims), names, offs, sizes, len(self.table), *self.max)
+        kind, reg = model_variant(params)
+        self.variant = (kind, reg)
+        if (kind, reg) == ("plotqa", "plotqa"):
+            self.handle = self.lib.crct_engine_create(C.byref(dims), names, offs, sizes, len(self.table), *self.max)
+        else:                      # dvqa / figure_qa: crct_engine_create_variant with the dataset / regressor kind and dvqa_floats
+            var = L.Variant()
+            var.dataset, var.regressor = L.DATASET_KINDS[kind], L.REGRESSOR_KINDS[reg]
+            vals = [float(v) for v in params.get("dvqa_floats", ())]
+            if reg == "ce" and len(vals) != L.CE_CLASSES:
+                raise ValueError("CE_REG needs params['dvqa_floats'] with %d values (got %d)" % (L.CE_CLASSES, len(vals)))
+            if len(vals) > L.CE_CLASSES:
+                raise ValueError("params['dvqa_floats'] holds %d values, at most %d are supported" % (len(vals), L.CE_CLASSES))
+            if kind == "dvqa" and reg == "plotqa" and not vals:
+                raise ValueError("dataset 'dvqa' snaps evaluation outputs to params['dvqa_floats'] (vilbert.py:1619-1625): it is required")
+            var.n_values = len(vals)
+            for i, v in enumerate(vals):
+                var.values[i] = v
+            self.handle = self.lib.crct_engine_create_variant(C.byref(dims), names, offs, sizes, len(self.table), *self.max, C.byref(var))
         if not self.handle:
             raise RuntimeError("crct_engine_create failed: %s" % self.lib.crct_last_error().decode())
         self.device = torch.device(device)
@@ -185,8 +202,15 @@ class StepEngine(object):
         self._staged = step
         torch.ops.crct.step_backward(self._op_handle, p32, p16, g32, T.pack_batch(tensors), int(seg))
 
+    def _set_areas(self, tensors):
+        if self.variant[0] != "plotqa":
+            L.check(self.lib.crct_engine_set_areas(self.handle, L.ptr(tensors.get("areas"))), "engine_set_areas")
+        elif tensors.get("areas") is not None:
+            raise ValueError("'areas' belongs to the dvqa / figure_qa image embeddings (vilbert.py:1463-1464, 1488-1489)")
+
     def forward_native(self, p32, p16, tensors, step):
         B = tensors["tokens"].shape[0]
+        self._set_areas(tensors)
         b, c = self._batch(tensors), self._cfg(step)
         self._keep = (tensors, step)
         L.check(self.lib.crct_engine_forward(self.handle, p32.data_ptr(), p16.data_ptr(), C.byref(b), C.byref(c),
@@ -204,6 +228,7 @@ class StepEngine(object):
         return self.outputs_of(self.out.clone(), B)
 
     def backward_native(self, p32, p16, g32, tensors, step, seg=-1):
+        self._set_areas(tensors)
         b, c = self._batch(tensors), self._cfg(step)
         L.check(self.lib.crct_engine_backward(self.handle, p32.data_ptr(), p16.data_ptr(), C.byref(b), C.byref(c),
                                               self.workspace.data_ptr(), g32.data_ptr(), self.logits.data_ptr(),

@@ -87,9 +87,35 @@ def _pipe(prefix, widths):
     return out
 
 
+PLOTQA_DATASETS = ("plotqa", "plotqa_colorless")
+VARIANT_DATASETS = ("dvqa", "figure_qa")
+
+
+def model_variant(params):
+    """(dataset kind, regressor kind) of the model the reference builds for ``params`` (vilbert.py:1463-1466, 1518-1537):
+    dataset 'plotqa' (image features embedded) / 'dvqa' / 'figure_qa' (no feature term, areas_emp); regressor 'plotqa'
+    (PlotQA_Regressor_v20), 'ce' (DVQA_Regressor_v20_CE, ``CE_REG``) or 'none' (``binary_answers``, or DVQA with a '_cls'
+    question file)."""
+    ds = params.get("dataset", "plotqa")
+    if ds not in PLOTQA_DATASETS + VARIANT_DATASETS:
+        raise NotImplementedError("dataset %r: the reference's model knows plotqa, plotqa_colorless, dvqa and figure_qa" % (ds,))
+    kind = "plotqa" if ds in PLOTQA_DATASETS else ds
+    if params.get("binary_answers") or (ds == "dvqa" and "_cls" in str(params.get("qa_file", ""))):
+        reg = "none"
+    elif params.get("CE_REG"):
+        reg = "ce"
+    else:
+        reg = "plotqa"
+    if kind == "plotqa" and reg != "plotqa":
+        raise NotImplementedError("CE_REG / binary_answers belong to the dvqa / figure_qa variants; the PlotQA model is built with "
+                                  "PlotQA_Regressor_v20 only")
+    return kind, reg
+
+
 def registration_order(cfg, params):
     """[(name, shape)] in the reference's ``named_parameters()`` order (tied decoder weight omitted,
     as ``named_parameters`` does)."""
+    kind, reg = model_variant(params)
     H, Hv, Hb = cfg.hidden_size, cfg.v_hidden_size, cfg.bi_hidden_size
     e, v = "bert.embeddings.", "bert.v_embeddings."
     out = [(e + "word_embeddings.weight", (cfg.vocab_size, H)),
@@ -98,7 +124,12 @@ def registration_order(cfg, params):
     out += [(e + "plotqa_type_embeddings.weight", (cfg.plotqa_vocab_types, H))] + _ln(e + "LayerNorm", H)
     out += _linear(v + "new_image_embeddings", Hv, cfg.v_feature_size)
     out += [(v + "type_embeddings.weight", (13, Hv)), (v + "color_emb.weight", (params["categories"] + 1, Hv))]
-    out += _linear(v + "new_loc_emb", Hv, 4) + _ln(v + "LayerNorm", Hv)
+    out += _linear(v + "new_loc_emb", Hv, 4)
+    if kind != "plotqa":
+        out += _linear(v + "areas_emp", Hv, 1)                                    # vilbert.py:1463-1464
+    if kind == "figure_qa":
+        out += [(v + "sep_emb.weight", (params["max_previews"] + 1, Hv))]         # vilbert.py:1465-1466 (never used)
+    out += _ln(v + "LayerNorm", Hv)
     for i in range(cfg.num_hidden_layers):
         out += _self_layer("bert.encoder.layer.%d." % i, H, cfg.intermediate_size)
     for i in range(cfg.v_num_hidden_layers):
@@ -111,16 +142,30 @@ def registration_order(cfg, params):
     out += _linear("cls.bi_seq_relationship", 2, Hb)
     out += _linear("cls.imagePredictions.transform.dense", Hv, Hv) + _ln("cls.imagePredictions.transform.LayerNorm", Hv)
     out += _linear("cls.imagePredictions.decoder", cfg.v_target_size, Hv)
-    out += _pipe("regressor.txt_pipe", (H, H, 512, 256, 256))
-    out += _pipe("regressor.vis_pipe", (Hv, Hv, 512, 256, 256))
-    out += _pipe("regressor.fusion", (512, 512, 256, 256, 1))
+    if reg != "none":
+        out += _pipe("regressor.txt_pipe", (H, H, 512, 256, 256))
+        out += _pipe("regressor.vis_pipe", (Hv, Hv, 512, 256, 256))
+        if reg == "ce":
+            out += _pipe("regressor.ce_fusion", (512, 512, 256, 256, 65))         # regressor.py:67-75
+        else:
+            out += _pipe("regressor.fusion", (512, 512, 256, 256, 1))
     return out
 
 
-def is_unused(name):
-    """Tensors that never receive a gradient on the CRCT path."""
+def is_unused(name, params=None):
+    """Tensors that never receive a gradient on the CRCT path; for the dvqa / figure_qa variants also the image
+    feature Linear (computed but not added, vilbert.py:1476-1483) and figure_qa's sep_emb."""
+    if params is not None and model_variant(params)[0] != "plotqa":
+        if name.startswith("bert.v_embeddings.new_image_embeddings.") or name == "bert.v_embeddings.sep_emb.weight":
+            return True
     return (".biOutput.q_dense" in name or name.startswith("cls.predictions.") or name.startswith("cls.imagePredictions.")
             or name == "bert.v_embeddings.type_embeddings.weight")
+
+
+def optional_grad(name):
+    """areas_emp receives a gradient only from batches that carry ``areas`` (vilbert.py:1488-1489): after a pass without them its
+    ``.grad`` is None, as in torch."""
+    return name.startswith("bert.v_embeddings.areas_emp.")
 
 
 def _fused_order(names):
@@ -149,10 +194,10 @@ def parameter_table(cfg, params):
 
     flat = []
     flat += with_prefix("bert.embeddings.")
-    flat += [n for n in with_prefix("bert.v_embeddings.") if not is_unused(n)]
+    flat += [n for n in with_prefix("bert.v_embeddings.") if not is_unused(n, params)]
     for kind, i in encoder_schedule(cfg):
         pre = {"t": "bert.encoder.layer.%d.", "v": "bert.encoder.v_layer.%d.", "c": "bert.encoder.c_layer.%d."}[kind] % i
-        flat += _fused_order([n for n in with_prefix(pre) if not is_unused(n)])
+        flat += _fused_order([n for n in with_prefix(pre) if not is_unused(n, params)])
     flat += with_prefix("bert.t_pooler.") + with_prefix("bert.v_pooler.") + with_prefix("cls.bi_seq_relationship.")
     flat += with_prefix("regressor.")
     seen = set(flat)
@@ -171,7 +216,7 @@ def parameter_table(cfg, params):
         top += numel
         prev = n
     total = (top + ALIGN - 1) // ALIGN * ALIGN
-    table = [Entry(n, tuple(shapes[n]), offsets[n], int(math.prod(shapes[n])), not is_unused(n),
+    table = [Entry(n, tuple(shapes[n]), offsets[n], int(math.prod(shapes[n])), not is_unused(n, params),
                    not any(nd in n for nd in NO_DECAY), is_language_weight(n)) for n in names]
     return table, total
 

@@ -46,6 +46,19 @@ class HeadArgs(C.Structure):
                 ("drop_thr", c_u32), ("drop_scale", c_f32), ("drop_site", c_u32), ("seed", c_u64)]
 
 
+CE_CLASSES = 65              # CRCT_CE_CLASSES of include/crct_hip.h: outputs of DVQA_Regressor_v20_CE (regressor.py:72)
+DATASET_KINDS = {"plotqa": 0, "dvqa": 1, "figure_qa": 2}          # CRCT_DATASET_*
+REGRESSOR_KINDS = {"plotqa": 0, "none": 1, "ce": 2}              # CRCT_REGRESSOR_*
+
+
+class Variant(C.Structure):
+    _fields_ = [("dataset", c_i32), ("regressor", c_i32), ("n_values", c_i32), ("values", c_f32 * CE_CLASSES)]
+
+
+class HeadVariantArgs(C.Structure):
+    _fields_ = [("h", HeadArgs), ("variant", Variant), ("snap", c_i32), ("ce_scratch", vp)]
+
+
 class ModelDims(C.Structure):
     _fields_ = [("vocab", c_i32), ("n_pos", c_i32), ("n_types", c_i32), ("H", c_i32), ("L", c_i32), ("heads", c_i32), ("I", c_i32),
                 ("Fv", c_i32), ("Hv", c_i32), ("Lv", c_i32), ("v_heads", c_i32), ("Iv", c_i32), ("Hb", c_i32), ("b_heads", c_i32),
@@ -168,12 +181,17 @@ PROTOTYPES = {
     "crct_embed_text_bwd_indexed": (C.c_int, [vp] * 16 + [C.c_int] * 4 + _u8 + [vp, vp, C.c_int, vp, C.c_int, vp]),
     "crct_embed_image_fwd": (C.c_int, [vp] * 12 + [C.c_int] * 2 + [c_f32] + _u8 + [vp]),
     "crct_embed_image_bwd": (C.c_int, [vp] * 15 + [C.c_int] * 2 + _u8 + [vp, vp, C.c_int, vp]),
+    "crct_embed_image_var_fwd": (C.c_int, [vp] * 14 + [C.c_int] * 2 + [c_f32] + _u8 + [vp]),
+    "crct_embed_image_var_bwd": (C.c_int, [vp] * 16 + [C.c_int] * 2 + _u8 + [vp, vp, C.c_int, vp]),
     "crct_head_loss": (C.c_int, [C.POINTER(HeadArgs), vp]),
+    "crct_head_loss_variant": (C.c_int, [C.POINTER(HeadVariantArgs), vp]),
     "crct_eval_select": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, c_i64, vp, vp, vp, vp, vp, vp]),
     "crct_adamw_plan": (c_i64, [vp, C.c_int, vp, vp, c_i64]),
     "crct_adamw_step": (C.c_int, [vp] * 11 + [c_i64, c_f32, c_f32, c_f32, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "crct_adamw_advance": (C.c_int, [vp, vp, vp]),
     "crct_engine_create": (vp, [C.POINTER(ModelDims), C.c_char_p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "crct_engine_create_variant": (vp, [C.POINTER(ModelDims), C.c_char_p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Variant)]),
+    "crct_engine_set_areas": (C.c_int, [vp, vp]),
     "crct_engine_destroy": (None, [vp]),
     "crct_engine_workspace_bytes": (C.c_size_t, [vp]),
     "crct_engine_num_segments": (C.c_int, [vp]),

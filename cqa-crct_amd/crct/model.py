@@ -22,7 +22,7 @@ from . import lib as L
 from . import ops
 from .config import BertConfig
 from .engine import StepEngine
-from .layout import parameter_table
+from .layout import model_variant, optional_grad, parameter_table
 
 
 class _Node(nn.Module):
@@ -91,13 +91,18 @@ class CrctModel(nn.Module):
         super().__init__()
         if not isinstance(config, BertConfig):
             raise ValueError("Parameter config in `CrctModel(config)` should be an instance of class `BertConfig`.")
-        if params.get("CE_REG") or params.get("binary_answers") or params.get("dataset", "plotqa") not in ("plotqa", "plotqa_colorless"):
-            raise NotImplementedError("only the PlotQA regression path (PlotQA_Regressor_v20) is built (SURVEY.md section 2)")
+        # dataset / regressor variant (vilbert.py:1463-1466, 1518-1537): PlotQA, DVQA (PlotQA regressor, CE_REG or none) and FigureQA
+        self.variant = model_variant(params)
+        if self.variant != ("plotqa", "plotqa") and params.get("fp8", False):
+            raise NotImplementedError("params['fp8'] is built for the PlotQA model only; the %s / %s variant trains in bf16" % self.variant)
         self.config, self.params = config, params
         device = torch.device(params.get("device", "cuda"))
         if device.type != "cuda":
             raise RuntimeError("CrctModel needs an MI355X (params['device']=%s): the CRCT step has no CPU path" % device)
         self.table, self.total = parameter_table(config, params)
+        # areas_emp (dvqa / figure_qa): its .grad exists only once a pass with `areas` has run since the last clear, as in torch
+        self._optional = [e for e in self.table if e.used and optional_grad(e.name)]
+        self._optional_live = False
         self._flat_p = torch.zeros(self.total, device=device)
         self._flat_g = torch.zeros(self.total, device=device)
         self._flat_b16 = torch.zeros(self.total, device=device, dtype=torch.bfloat16)
@@ -155,7 +160,7 @@ class CrctModel(nn.Module):
                     node.add_module(part, _Node())
                 node = node._modules[part]
             node.register_parameter(parts[-1], p)
-            if e.used:
+            if e.used and not optional_grad(e.name):
                 p.grad = self._flat_g[e.offset:e.offset + e.numel].view(e.shape)
             if e.name == "bert.embeddings.word_embeddings.weight":
                 word = p
@@ -325,7 +330,7 @@ class CrctModel(nn.Module):
         for e in self.table:
             p = byname[e.name]
             p.data = self._flat_p[e.offset:e.offset + e.numel].view(e.shape)
-            if e.used:
+            if e.used and (self._optional_live or not optional_grad(e.name)):
                 p.grad = self._flat_g[e.offset:e.offset + e.numel].view(e.shape)
         self._rebound = list(byname.values())
         self._invalidate_shadow()
@@ -353,6 +358,7 @@ class CrctModel(nn.Module):
         each, are left as they are and WRITTEN by the next backward pass (CrctStepCfg.wgrad_overwrite).  Their ``.grad``
         therefore holds stale values between ``zero_grad()`` and ``backward()``; the values after backward are bit-identical
         to the eager path.  Falls back to the full fill until one backward pass has run."""
+        self._set_optional_grads(False)
         plan = self._lazy_zero_plan() if lazy else None
         if plan is None:
             self._flat_g.zero_()
@@ -363,6 +369,26 @@ class CrctModel(nn.Module):
         L.check(L.load().crct_zero_runs(self._flat_g.data_ptr(), off.data_ptr(), num.data_ptr(), blk_seg.data_ptr(),
                                         blk_off.data_ptr(), n_blk, L.current_stream()), "zero_runs")
         self._wgrad_overwrite_next = True
+
+    def _set_optional_grads(self, live):
+        """Attach (live) or drop the ``.grad`` views of the areas_emp tensors (their flat gradient stays zero while dropped)."""
+        self._optional_live = bool(live)
+        if not self._optional:
+            return
+        if getattr(self, "_optional_params", None) is None:      # the Parameters keep their identity (see _rebind): looked up once
+            byname = self._params_by_name()
+            self._optional_params = [byname[e.name] for e in self._optional]
+        for e, p in zip(self._optional, self._optional_params):
+            p.grad = self._flat_g[e.offset:e.offset + e.numel].view(e.shape) if live else None
+
+    @property
+    def optional_grads_live(self):
+        """False: no pass since the last clear carried ``areas`` -- areas_emp has no gradient and an optimizer leaves it alone."""
+        return self._optional_live
+
+    @property
+    def optional_entries(self):
+        return self._optional
 
     def non_owned_grad_runs(self):
         """Host list of (offset, numel) runs of the flat gradient buffer that backward ACCUMULATES into (everything but the Linear
@@ -413,7 +439,7 @@ class CrctModel(nn.Module):
         missing = False
         byname = None
         for e in self.table:
-            if not e.used:
+            if not e.used or optional_grad(e.name):
                 continue
             if byname is None:
                 byname = self._params_by_name()
@@ -424,8 +450,9 @@ class CrctModel(nn.Module):
             self._flat_g.zero_()
             self._wgrad_overwrite_next = False
             for e in self.table:
-                if e.used:
+                if e.used and not optional_grad(e.name):
                     byname[e.name].grad = self._flat_g[e.offset:e.offset + e.numel].view(e.shape)
+            self._set_optional_grads(False)
 
     # ------------------------------------------------------------------ engine plumbing
     def _get_engine(self, B, T, V):
@@ -489,6 +516,8 @@ class CrctModel(nn.Module):
                 self._flat_g.zero_()                 # an engine with another owned set: nothing else has been accumulated yet
         self._wgrad_overwrite_next = False           # a further pass before the next clear accumulates
         self._backward_passes = getattr(self, "_backward_passes", 0) + 1
+        if tensors.get("areas") is not None and not self._optional_live:
+            self._set_optional_grads(True)
         if self.fp8_backward and self._fp8 is not None and step.get("fp8") is not None and self._fp8["n_gsites"] > 0:
             # fp8 data gradients: the first pass only collects the gradient maxima (its GEMMs run in bf16), from then on the e5m2
             # copies are quantised with the scales of the previous passes (delayed scaling, running maxima over a window)
@@ -515,7 +544,7 @@ class CrctModel(nn.Module):
             self._ddp.backward(self, eng, tensors, step)
 
     def _device_inputs(self, input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
-                       image_attention_mask, image_target, R, labels):
+                       image_attention_mask, image_target, R, labels, areas=None):
         dev = self._flat_p.device
 
         def to(t, dtype):          # no kernel when the tensor is already on the device with this dtype (resident batches)
@@ -545,14 +574,16 @@ class CrctModel(nn.Module):
             t["image_keymask"] = to(image_attention_mask != 0, torch.uint8)
         if labels is not None:
             t["labels"] = to(labels.reshape(-1), torch.int64)
+        if areas is not None:                      # [B, V, 1] (encoder_decorator.py:93-96) -> fp32 [B][V]
+            t["areas"] = to(areas.reshape(B, V), torch.float32)
         return t
 
     # ------------------------------------------------------------------ forward (vilbert.py:1540-1661)
     def forward(self, input_ids, txt_loc, image_feat, image_loc, sep_indices=None, sep_len=None, token_type_ids=None,
                 attention_mask=None, image_attention_mask=None, masked_lm_labels=None, image_label=None, image_target=None,
                 next_sentence_label=None, output_all_attention_masks=False, gt_reg=None, areas=None, legend_pred=None):
-        if areas is not None:
-            raise NotImplementedError("'areas' belongs to the figure_qa / dvqa datasets (vilbert.py:1464-1489), out of scope")
+        if areas is not None and self.variant[0] == "plotqa":
+            raise ValueError("'areas' belongs to the figure_qa / dvqa image embeddings (vilbert.py:1463-1464, 1488-1489)")
         if gt_reg is None:
             raise ValueError("gt_reg=[R, kind] is required (vilbert.py:1586)")
         if image_target is None:
@@ -560,7 +591,7 @@ class CrctModel(nn.Module):
         R, kind = gt_reg[0], gt_reg[1]
         train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
         tensors = self._device_inputs(input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
-                                      image_attention_mask, image_target, R, next_sentence_label if train_branch else None)
+                                      image_attention_mask, image_target, R, next_sentence_label if train_branch else None, areas)
         B, T = tensors["tokens"].shape
         V = tensors["image_feat"].shape[1]
         eng = self._get_engine(B, T, V)

@@ -74,6 +74,14 @@ class FusedAdamW(torch.optim.Optimizer):
         self._seg_len = to_dev([e.numel for e in self._segs], torch.int64)
         blk_seg, blk_off = ops.adamw_plan([e.numel for e in self._segs])
         self._blk_seg, self._blk_off = blk_seg.to(dev), blk_off.to(dev)
+        # areas_emp (dvqa / figure_qa): block range of each of its segments -- a step after passes without `areas` leaves its weights
+        # and moments untouched, as torch.optim.AdamW does for a None gradient
+        opt_names = {e.name for e in getattr(core, "optional_entries", ())}
+        self._opt_blocks = []
+        for i, e in enumerate(self._segs):
+            if e.name in opt_names:
+                idx = (blk_seg == i).nonzero().flatten()
+                self._opt_blocks.append((int(idx.min()), int(idx.max()) + 1, e))
         self._lr_host = torch.empty(len(self._segs), dtype=torch.float32).pin_memory()
         self._wd_host = torch.empty(len(self._segs), dtype=torch.float32).pin_memory()
         self._lr_dev = torch.empty(len(self._segs), dtype=torch.float32, device=dev)
@@ -146,12 +154,23 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _launch(self, b0, b1, inv_scale, stream, max_workgroups=0):
         core, g0 = self.core, self.param_groups[0]
+        frozen = [] if getattr(core, "optional_grads_live", True) else [e for lo, hi, e in self._opt_blocks if lo < b1 and hi > b0]
+        if frozen:               # areas_emp without a gradient: its weights, moments and shadow are put back behind the update
+            side = torch.cuda.ExternalStream(stream, device=core.flat_params.device)
+            bufs = (core.flat_params, self._m, self._v, core.flat_shadow)
+            with torch.cuda.stream(side):
+                kept = [(e, [b[e.offset:e.offset + e.numel].clone() for b in bufs]) for e in frozen]
         L.check(L.load().crct_adamw_step(core.flat_params.data_ptr(), core.flat_grads.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
                                          core.flat_shadow.data_ptr(), self._seg_off.data_ptr(), self._seg_len.data_ptr(),
                                          self._lr_dev.data_ptr(), self._wd_dev.data_ptr(), self._blk_seg.data_ptr() + 4 * b0,
                                          self._blk_off.data_ptr() + 8 * b0, b1 - b0, g0["betas"][0], g0["betas"][1], g0["eps"],
                                          max(self._step, 1), L.ptr(inv_scale), self._amp_arg, self._fp8_arg(), int(max_workgroups),
                                          int(self.fuse_zero_grad), L.ptr(self._g16), stream), "adamw_step")
+        if frozen:
+            with torch.cuda.stream(side):
+                for e, saved in kept:
+                    for b, v in zip(bufs, saved):
+                        b[e.offset:e.offset + e.numel].copy_(v)
 
     # ---- torch.amp.GradScaler (train.py:157,208-212).  ``scaler.step(optimizer)`` sees ``_step_supports_amp_scaling`` and
     # hands over ``optimizer.grad_scale`` / ``optimizer.found_inf`` (device scalars) instead of unscaling 524 gradient views

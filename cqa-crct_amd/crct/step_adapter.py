@@ -4,7 +4,8 @@ Mirror of ``forward()`` and ``sequence_mask()`` of CRCT/backbone/encoder_decorat
 arguments, same return tuples (train: 7-tuple, evaluation: 6-tuple with ``loss=None``), same loss
 combination ``nsp_loss_coeff * nsp + reg_loss_coeff * mean_B(reg_loss)``.  Host tensors of the batch
 are moved to ``params['device']`` with non-blocking copies; the key-length mask is built on the
-host side of the boundary exactly as the reference does (it depends only on integer indices).
+host side of the boundary exactly as the reference does (it depends only on integer indices).  A batch with ``areas``
+(figure_qa / dvqa) hands them to the model as the reference does (:93-96).
 """
 import torch
 
@@ -30,8 +31,7 @@ def forward(dialog_encoder, batch, params, output_nsp_scores=False, output_lm_sc
     sep_indices, mask, hist_len = pick("sep_indices"), pick("mask"), pick("hist_len")
     features, image_loc, image_mask = pick("image_feat"), pick("image_loc"), pick("image_mask")
     R = pick("R")
-    if "areas" in batch:
-        raise NotImplementedError("'areas' is a figure_qa / dvqa input (encoder_decorator.py:93-96); PlotQA path only")
+    areas = pick("areas") if "areas" in batch else None      # figure_qa / dvqa (encoder_decorator.py:93-96)
     next_sentence_labels = image_label = None
     if not evaluation:
         next_sentence_labels = pick("next_sentence_labels")
@@ -54,7 +54,7 @@ def forward(dialog_encoder, batch, params, output_nsp_scores=False, output_lm_sc
         tokens, txt_loc, features, image_loc, sep_indices=sep_indices, sep_len=sep_len, token_type_ids=segments,
         masked_lm_labels=mask, attention_mask=attention_mask, next_sentence_label=next_sentence_labels,
         output_nsp_scores=output_nsp_scores, output_lm_scores=output_lm_scores, image_attention_mask=image_mask,
-        image_label=image_label, image_target=image_target, gt_reg=regression_target, areas=None)
+        image_label=image_label, image_target=image_target, gt_reg=regression_target, areas=areas)
 
     loss = None
     if not evaluation:

@@ -37,7 +37,7 @@ _LIB = torch.library.Library("crct", "DEF")
 _ENGINES = weakref.WeakValueDictionary()
 
 BATCH_KEYS = ("tokens", "segments", "loc", "image_feat", "image_loc", "image_target", "R", "labels", "sep_indices", "hist_len",
-              "image_mask", "text_keymask", "image_keymask")
+              "image_mask", "text_keymask", "image_keymask", "areas")
 
 
 def engine_handle(eng):

@@ -123,11 +123,15 @@ struct crct_engine {
   std::vector<SelfLayerA> tla, vla;
   std::vector<ConnLayerA> cla;
   struct { int64_t word, pos, type, wloc, bloc; LnP ln; } et;
-  struct { LinearP img; int64_t color, wloc, bloc; LnP ln; } ev;
+  struct { LinearP img; int64_t color, wloc, bloc; LnP ln; LinearP areas; } ev;
+  // model variant (crct_engine_create_variant): dataset / regressor kind and the value table; `feat` = the image features are embedded
+  CrctVariant var = {CRCT_DATASET_PLOTQA, CRCT_REGRESSOR_PLOTQA, 0, {}};
+  bool feat = true;
+  const float* areas = nullptr;        // crct_engine_set_areas: fp32 [B][V] of the running batch, or NULL
   struct { size_t sum, y, mean, rstd, yq; int site; } eta;
   struct { size_t soft, lin, sum, y, mean, rstd, yq; int site; } eva;
   LinearP t_pool, v_pool, cls, tp[4], vp[4], fu[4];
-  struct { size_t pooled_t, pooled_v, t[3], v[3], cat, f[3], scratch, d_pt, d_pv, g[10]; } ha;   // g: one buffer per head gradient (see heads_bwd)
+  struct { size_t pooled_t, pooled_v, t[3], v[3], cat, f[3], scratch, ce, d_pt, d_pv, g[10]; } ha;   // g: one buffer per head gradient (see heads_bwd)
   StreamScratch st, sv;          // backward scratch per data stream (dy ping-pong lives in these)
   StreamScratch st2, sv2;        // second set: layers alternate sets so weight-gradient GEMMs may lag one layer behind
   size_t partials[2], colsum_part[4];   // per internal stream: [text, visual] / [text, visual, text-wgrad, visual-wgrad]
@@ -763,6 +767,14 @@ struct Run {
     const CrctModelDims& D = e->d;
     const int Mv = b->B * b->V;
     const Drop dv = drop(D.p_hidden, 2);       // also the TEXT probability (vilbert.py:1470)
+    if (!e->feat) {                            // 'dvqa' / 'figure_qa': no feature term, the features are not read (vilbert.py:1481-1483)
+      const bool ar = e->areas != nullptr;
+      if (!rc) fail(crct_embed_image_var_fwd(b->image_loc, b->image_target, e->areas, P(e->ev.wloc), P(e->ev.bloc), P(e->ev.color),
+                                             ar ? P(e->ev.areas.w) : nullptr, ar ? P(e->ev.areas.b) : nullptr, P(e->ev.ln.g), P(e->ev.ln.b),
+                                             A(e->eva.sum), A(e->eva.y), F(e->eva.mean), F(e->eva.rstd), Mv, D.Hv, 1e-12f, dv.thr, dv.scale,
+                                             dv.site, c->seed, s));
+      return;
+    }
     if (!rc) fail(b->image_feat_bf16 ? crct_softmax_rows_bf16_bf16(b->image_feat, A(e->eva.soft), Mv, D.Fv, s)
                                      : crct_softmax_rows_f32_bf16((const float*)b->image_feat, A(e->eva.soft), Mv, D.Fv, s));
     lin_fwd(A(e->eva.soft), D.Fv, e->ev.img, Mv, A(e->eva.lin), D.Hv, Opt());
@@ -796,6 +808,14 @@ struct Run {
     const Drop dv = drop(D.p_hidden, 2);
     const StreamScratch& sc = layer_begin();
     ++tick;
+    if (!e->feat) {
+      const bool ar = e->areas != nullptr;
+      if (!rc) fail(crct_embed_image_var_bwd(A(gv), A(e->eva.sum), F(e->eva.mean), F(e->eva.rstd), b->image_loc, b->image_target, e->areas,
+                                             P(e->ev.ln.g), G(e->ev.color), G(e->ev.wloc), G(e->ev.bloc), ar ? G(e->ev.areas.w) : nullptr,
+                                             ar ? G(e->ev.areas.b) : nullptr, G(e->ev.ln.g), G(e->ev.ln.b), F(partials), Mv, D.Hv, dv.thr,
+                                             dv.scale, dv.site, c->seed, F(e->embed_rows[1]), W<int32_t>(e->embed_idx[1]), D.n_color, s));
+      return;
+    }
     if (!rc) fail(crct_embed_image_bwd(A(gv), A(e->eva.sum), F(e->eva.mean), F(e->eva.rstd), b->image_loc, b->image_target,
                                        P(e->ev.ln.g), A(sc.gc), G(e->ev.color), G(e->ev.wloc), G(e->ev.bloc), G(e->ev.img.b),
                                        G(e->ev.ln.g), G(e->ev.ln.b), F(partials), Mv, D.Hv, dv.thr, dv.scale, dv.site,
@@ -842,21 +862,36 @@ struct Run {
     Opt orelu; orelu.act = ACT_RELU;
     if (visual) {
       lin_fwd(A(seq), ld, e->v_pool, B, A(e->ha.pooled_v), D.Hb, orelu);     // vilbert.py:970-976
-      pipe_fwd(e->vp, A(seq), ld, e->ha.v, A(e->ha.cat), 512, B);            // regressor on the raw IMG state; cat = (hv, hw): regressor.py:39-41
+      if (has_regressor())
+        pipe_fwd(e->vp, A(seq), ld, e->ha.v, A(e->ha.cat), 512, B);          // regressor on the raw IMG state; cat = (hv, hw): regressor.py:39-41
     } else {
       lin_fwd(A(seq), ld, e->t_pool, B, A(e->ha.pooled_t), D.Hb, orelu);     // vilbert.py:955-961
-      pipe_fwd(e->tp, A(seq), ld, e->ha.t, A(e->ha.cat) + 256, 512, B);
+      if (has_regressor()) pipe_fwd(e->tp, A(seq), ld, e->ha.t, A(e->ha.cat) + 256, 512, B);
     }
+  }
+  bool has_regressor() const { return e->var.regressor != CRCT_REGRESSOR_NONE; }
+  bool plain_head() const { return e->var.dataset == CRCT_DATASET_PLOTQA && e->var.regressor == CRCT_REGRESSOR_PLOTQA; }
+  // the loss kernel: crct_head_loss for the PlotQA model, crct_head_loss_variant otherwise
+  int head_loss(const CrctHeadArgs& h) {
+    if (plain_head()) return crct_head_loss(&h, s);
+    CrctHeadVariantArgs va;
+    memset(&va, 0, sizeof(va));
+    va.h = h; va.variant = e->var;
+    va.snap = e->var.dataset == CRCT_DATASET_DVQA && e->var.regressor == CRCT_REGRESSOR_PLOTQA && !c->training;   // vilbert.py:1619-1625
+    va.ce_scratch = e->var.regressor == CRCT_REGRESSOR_CE ? F(e->ha.ce) : nullptr;
+    return crct_head_loss_variant(&va, s);
   }
   void fill_head_args(CrctHeadArgs& h, float* logits, float* reg, float* stats, bool with_grad) {
     const CrctModelDims& D = e->d;
     memset(&h, 0, sizeof(h));
     h.pooled_t = A(e->ha.pooled_t); h.pooled_v = A(e->ha.pooled_v); h.fus_h = A(e->ha.f[2]);
-    h.w_cls = P(e->cls.w); h.b_cls = P(e->cls.b); h.w_f6 = P(e->fu[3].w); h.b_f6 = P(e->fu[3].b);
+    h.w_cls = P(e->cls.w); h.b_cls = P(e->cls.b);
+    if (has_regressor()) { h.w_f6 = P(e->fu[3].w); h.b_f6 = P(e->fu[3].b); }
     h.R = b->R; h.labels = b->labels; h.logits = logits; h.reg = reg; h.stats = stats; h.scratch = F(e->ha.scratch);
     if (with_grad && g32) {
       h.d_pooled_t = A(e->ha.d_pt); h.d_pooled_v = A(e->ha.d_pv); h.d_fus_h = A(e->ha.g[0]);
-      h.d_w_cls = G(e->cls.w); h.d_b_cls = G(e->cls.b); h.d_w_f6 = G(e->fu[3].w); h.d_b_f6 = G(e->fu[3].b);
+      h.d_w_cls = G(e->cls.w); h.d_b_cls = G(e->cls.b);
+      if (has_regressor()) { h.d_w_f6 = G(e->fu[3].w); h.d_b_f6 = G(e->fu[3].b); }
     }
     h.g_nsp_dev = c->g_nsp_dev; h.g_reg_dev = c->g_reg_dev; h.g_loss_dev = c->g_loss_dev;
     h.B = b->B; h.Hb = D.Hb; h.fusion_sum = D.fusion_sum; h.use_l1 = c->use_l1; h.kind_l1 = c->kind_l1;
@@ -867,13 +902,15 @@ struct Run {
   void heads_tail_fwd(float* logits, float* reg, float* stats) {
     const int B = b->B;
     Opt o; o.act = ACT_LEAKY;
-    lin_fwd(A(e->ha.cat), 512, e->fu[0], B, A(e->ha.f[0]), 512, o);
-    lin_fwd(A(e->ha.f[0]), 512, e->fu[1], B, A(e->ha.f[1]), 256, o);
-    lin_fwd(A(e->ha.f[1]), 256, e->fu[2], B, A(e->ha.f[2]), 256, o);
+    if (has_regressor()) {
+      lin_fwd(A(e->ha.cat), 512, e->fu[0], B, A(e->ha.f[0]), 512, o);
+      lin_fwd(A(e->ha.f[0]), 512, e->fu[1], B, A(e->ha.f[1]), 256, o);
+      lin_fwd(A(e->ha.f[1]), 256, e->fu[2], B, A(e->ha.f[2]), 256, o);
+    }
     if (rc) return;
     CrctHeadArgs h;
     fill_head_args(h, logits, reg, stats, false);
-    fail(crct_head_loss(&h, s));
+    fail(head_loss(h));
   }
   // Heads, backward (this = text stream, V = visual stream): fills the CLS / IMG rows of the running activation gradients
   // (other rows zero).  On the critical chain are only the loss kernel and the 13 small data-gradient GEMMs -- the visual
@@ -889,7 +926,7 @@ struct Run {
     {
       CrctHeadArgs h;
       fill_head_args(h, logits, reg, stats, true);
-      if (!rc) fail(crct_head_loss(&h, s));
+      if (!rc) fail(head_loss(h));
     }
     if (rc) return;
     if (!V.rc) V.fail(order_streams(e, s, V.s));                              // d_pooled_v is ready
@@ -903,6 +940,11 @@ struct Run {
     V.bias_grad(V.A(e->ha.d_pv), D.Hb, e->v_pool, B);
     V.lin_wgrad(V.A(e->ha.d_pv), D.Hb, V.A(seq_v), ldv, e->v_pool, B);
     V.lin_dgrad(V.A(e->ha.d_pv), D.Hb, e->v_pool, B, V.A(gv), ldv, Opt());
+    if (!has_regressor()) {                    // binary answers: the poolers are the whole head
+      flush_wgrads();
+      V.flush_wgrads();
+      return;
+    }
     // fusion MLP: g[0] = grad of fusion.4's pre-activation (from the loss kernel)
     bias_grad(A(g[0]), 256, e->fu[2], B);
     lin_wgrad(A(g[0]), 256, A(e->ha.f[1]), 256, e->fu[2], B);
@@ -937,11 +979,23 @@ int check_batch(const crct_engine* e, const CrctBatch* b) {
 }  // namespace
 
 // =================================================================================== C ABI
-extern "C" crct_engine_t* crct_engine_create(const CrctModelDims* dims, const char* names, const int64_t* offsets,
-                                             const int64_t* sizes, int n_params, int max_B, int max_T, int max_V) {
+static crct_engine_t* engine_create_impl(const CrctModelDims* dims, const char* names, const int64_t* offsets, const int64_t* sizes,
+                                         int n_params, int max_B, int max_T, int max_V, const CrctVariant* variant) {
   if (!dims || !names || !offsets || !sizes) { crct_set_error("engine_create: null argument"); return nullptr; }
+  if (variant && (variant->dataset < CRCT_DATASET_PLOTQA || variant->dataset > CRCT_DATASET_FIGUREQA ||
+                  variant->regressor < CRCT_REGRESSOR_PLOTQA || variant->regressor > CRCT_REGRESSOR_CE ||
+                  variant->n_values < 0 || variant->n_values > CRCT_CE_CLASSES)) {
+    crct_set_error("engine_create: bad variant (dataset %d, regressor %d, %d values)", variant->dataset, variant->regressor, variant->n_values);
+    return nullptr;
+  }
+  if (variant && variant->regressor == CRCT_REGRESSOR_CE && variant->n_values != CRCT_CE_CLASSES) {
+    crct_set_error("engine_create: the CE regressor needs the %d class values", CRCT_CE_CLASSES);
+    return nullptr;
+  }
   crct_engine* e = new crct_engine();
   e->d = *dims; e->maxB = max_B; e->maxT = max_T; e->maxV = max_V;
+  if (variant) e->var = *variant;
+  e->feat = e->var.dataset == CRCT_DATASET_PLOTQA;
   const CrctModelDims& D = e->d;
   {
     const char* p = names;
@@ -1021,7 +1075,8 @@ extern "C" crct_engine_t* crct_engine_create(const CrctModelDims* dims, const ch
   e->et.wloc = e->P("bert.embeddings.txt_location_embeddings.weight");
   e->et.bloc = e->P("bert.embeddings.txt_location_embeddings.bias");
   e->et.ln = ln_p(e, "bert.embeddings.LayerNorm");
-  e->ev.img = linear_p(e, "bert.v_embeddings.new_image_embeddings", D.Fv, D.Hv, CRCT_SITE_IMG_EMB);
+  if (e->feat) e->ev.img = linear_p(e, "bert.v_embeddings.new_image_embeddings", D.Fv, D.Hv, CRCT_SITE_IMG_EMB);
+  else e->ev.areas = linear_p(e, "bert.v_embeddings.areas_emp", 1, D.Hv);
   e->ev.color = e->P("bert.v_embeddings.color_emb.weight");
   e->ev.wloc = e->P("bert.v_embeddings.new_loc_emb.weight");
   e->ev.bloc = e->P("bert.v_embeddings.new_loc_emb.bias");
@@ -1030,11 +1085,14 @@ extern "C" crct_engine_t* crct_engine_create(const CrctModelDims* dims, const ch
   e->v_pool = linear_p(e, "bert.v_pooler.dense", D.Hv, D.Hb);
   e->cls = linear_p(e, "cls.bi_seq_relationship", D.Hb, 2);
   {
-    const int tw[5] = {D.H, D.H, 512, 256, 256}, vw[5] = {D.Hv, D.Hv, 512, 256, 256}, fw[5] = {512, 512, 256, 256, 1};
-    for (int j = 0; j < 4; ++j) {
+    // regressor.py:5-34 (PlotQA_Regressor_v20: fusion, 1 output) / :45-79 (DVQA_Regressor_v20_CE: ce_fusion, 65 outputs); none with
+    // binary answers (vilbert.py:1518)
+    const bool ce = e->var.regressor == CRCT_REGRESSOR_CE;
+    const int tw[5] = {D.H, D.H, 512, 256, 256}, vw[5] = {D.Hv, D.Hv, 512, 256, 256}, fw[5] = {512, 512, 256, 256, ce ? CRCT_CE_CLASSES : 1};
+    for (int j = 0; j < 4 && e->var.regressor != CRCT_REGRESSOR_NONE; ++j) {
       snprintf(buf, sizeof(buf), "regressor.txt_pipe.%d", 2 * j); e->tp[j] = linear_p(e, buf, tw[j], tw[j + 1]);
       snprintf(buf, sizeof(buf), "regressor.vis_pipe.%d", 2 * j); e->vp[j] = linear_p(e, buf, vw[j], vw[j + 1]);
-      snprintf(buf, sizeof(buf), "regressor.fusion.%d", 2 * j); e->fu[j] = linear_p(e, buf, fw[j], fw[j + 1]);
+      snprintf(buf, sizeof(buf), "regressor.%s.%d", ce ? "ce_fusion" : "fusion", 2 * j); e->fu[j] = linear_p(e, buf, fw[j], fw[j + 1]);
     }
   }
   if (e->bad) return fail(nullptr);
@@ -1046,9 +1104,12 @@ extern "C" crct_engine_t* crct_engine_create(const CrctModelDims* dims, const ch
       own(l.qkv1); own(l.qkv2); own(l.proj_v.dense); own(l.proj_t.dense);
       own(l.ffn_v.up); own(l.ffn_v.down); own(l.ffn_t.up); own(l.ffn_t.down);
     }
-    own(e->ev.img); own(e->t_pool); own(e->v_pool);
-    for (int j = 0; j < 4; ++j) { own(e->tp[j]); own(e->vp[j]); }
-    for (int j = 0; j < 3; ++j) own(e->fu[j]);     // fusion.6 (fu[3]) and bi_seq_relationship are produced by the head kernel: accumulate-only
+    if (e->feat) own(e->ev.img);                   // (areas_emp: produced by the embedding kernel, accumulate-only)
+    own(e->t_pool); own(e->v_pool);
+    if (e->var.regressor != CRCT_REGRESSOR_NONE) {
+      for (int j = 0; j < 4; ++j) { own(e->tp[j]); own(e->vp[j]); }
+      for (int j = 0; j < 3; ++j) own(e->fu[j]);   // fusion.6 (fu[3]) and bi_seq_relationship are produced by the head kernel: accumulate-only
+    }
   }
   {
     // fp8: every Linear of the encoder whose two dimensions are whole numbers of 128-deep fp8 K tiles gets an e4m3 weight shadow
@@ -1070,7 +1131,7 @@ extern "C" crct_engine_t* crct_engine_create(const CrctModelDims* dims, const ch
   Arena ar;
   const size_t Mt = (size_t)max_B * max_T, Mv = (size_t)max_B * max_V, B = max_B;
   e->eta.sum = ar.take(Mt * D.H * 2); e->eta.y = ar.take(Mt * D.H * 2); e->eta.mean = ar.take(Mt * 4); e->eta.rstd = ar.take(Mt * 4);
-  e->eva.soft = ar.take(Mv * D.Fv * 2); e->eva.lin = ar.take(Mv * D.Hv * 2); e->eva.sum = ar.take(Mv * D.Hv * 2);
+  e->eva.soft = ar.take(e->feat ? Mv * D.Fv * 2 : 0); e->eva.lin = ar.take(e->feat ? Mv * D.Hv * 2 : 0); e->eva.sum = ar.take(Mv * D.Hv * 2);
   e->eva.y = ar.take(Mv * D.Hv * 2); e->eva.mean = ar.take(Mv * 4); e->eva.rstd = ar.take(Mv * 4);
   e->eta.yq = ar.take(Mt * D.H); e->eva.yq = ar.take(Mv * D.Hv);
   e->eta.site = e->n_sites++; e->eva.site = e->n_sites++;
@@ -1101,6 +1162,7 @@ extern "C" crct_engine_t* crct_engine_create(const CrctModelDims* dims, const ch
   e->ha.cat = ar.take(B * 512 * 2);
   e->ha.f[0] = ar.take(B * 512 * 2); e->ha.f[1] = ar.take(B * 256 * 2); e->ha.f[2] = ar.take(B * 256 * 2);
   e->ha.scratch = ar.take(B * 8 * 4);
+  e->ha.ce = ar.take(e->var.regressor == CRCT_REGRESSOR_CE ? B * CRCT_CE_CLASSES * 4 : 0);
   e->ha.d_pt = ar.take(B * D.Hb * 2); e->ha.d_pv = ar.take(B * D.Hb * 2);
   {
     size_t w = 512;
@@ -1187,6 +1249,22 @@ extern "C" crct_engine_t* crct_engine_create(const CrctModelDims* dims, const ch
   return e;
 }
 
+extern "C" crct_engine_t* crct_engine_create(const CrctModelDims* dims, const char* names, const int64_t* offsets,
+                                             const int64_t* sizes, int n_params, int max_B, int max_T, int max_V) {
+  return engine_create_impl(dims, names, offsets, sizes, n_params, max_B, max_T, max_V, nullptr);
+}
+extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, const char* names, const int64_t* offsets,
+                                                     const int64_t* sizes, int n_params, int max_B, int max_T, int max_V,
+                                                     const CrctVariant* variant) {
+  return engine_create_impl(dims, names, offsets, sizes, n_params, max_B, max_T, max_V, variant);
+}
+extern "C" int crct_engine_set_areas(crct_engine_t* e, const float* areas) {
+  CRCT_REQUIRE(e, "engine_set_areas: null engine");
+  CRCT_REQUIRE(!areas || !e->feat, "engine_set_areas: the 'plotqa' image embeddings have no areas term (vilbert.py:1463-1465)");
+  e->areas = areas;
+  return 0;
+}
+
 extern "C" void crct_engine_destroy(crct_engine_t* e) {
   if (!e) return;
   for (auto ev : e->evpool) (void)hipEventDestroy(ev);
@@ -1257,6 +1335,8 @@ static int engine_forward_impl(crct_engine_t* e, const float* params_f32, const 
                                crct_stream_t stream) {
   CRCT_REQUIRE(e && params_f32 && params_bf16 && cfg && workspace && logits && reg && stats, "engine_forward: null argument");
   if (int r = check_batch(e, batch)) return r;
+  CRCT_REQUIRE(!cfg->fp8 || (e->feat && e->var.regressor == CRCT_REGRESSOR_PLOTQA),
+               "engine_forward: the fp8 step is built for the PlotQA model only, not for the dvqa / figure_qa variants");
   if (int r = ensure_streams(e, (hipStream_t)stream)) return r;
   e->evnext = 0;
   // key masks the caller did not supply are built here (one launch) and kept in the workspace for the backward pass

@@ -24,8 +24,15 @@ __device__ __forceinline__ bool head_keep(const CrctHeadArgs& a, int b, int c) {
   return (philox_keep8(a.seed, a.drop_site, idx >> 3, a.drop_thr) >> ((uint32_t)idx & 7u)) & 1u;
 }
 
+// values of the variants' regressors (CrctVariant), passed by value
+struct HeadValues { float v[CRCT_CE_CLASSES]; int n; };
+
+// the PlotQA regressor's tail: MODE 0 = PlotQA, 1 = DVQA evaluation snap (vilbert.py:1619-1625), 2 = no regressor
+enum { HEAD_PLOTQA = 0, HEAD_SNAP = 1, HEAD_NONE = 2 };
+
 // scratch row layout (fp32 x 8): dlogit0, dlogit1, dz, nsp_loss_b, valid, ok5, okt, needs
-__global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, float* scratch) {
+template <int MODE>
+__global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, float* scratch, const HeadValues hv) {
   __shared__ float red[4];
   const int b = blockIdx.x, tid = threadIdx.x;
   const bf16_t* pt = reinterpret_cast<const bf16_t*>(a.pooled_t) + (long)b * a.Hb;
@@ -44,9 +51,11 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, fl
   l1 = block_sum(l1, red) + a.b_cls[1];
   // ---- regression tail
   float z = 0.f;
-  for (int c = tid; c < 256; c += 256) z += bf2f(fh[c]) * a.w_f6[c];
-  z = block_sum(z, red) + a.b_f6[0];
-  const float r = tanhf(z);
+  if (MODE != HEAD_NONE) {
+    for (int c = tid; c < 256; c += 256) z += bf2f(fh[c]) * a.w_f6[c];
+    z = block_sum(z, red) + a.b_f6[0];
+  }
+  float r = tanhf(z);
   // ---- labels: count of rows that enter the CE mean (ignore_index = -1)
   int n_valid = 0;
   long label = -1;
@@ -75,6 +84,16 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, fl
   const float* Rb = a.R + (long)b * 4;
   const bool needs = Rb[1] == 1.0f;
   const float target = Rb[0] / Rb[3];
+  const float raw = r;
+  if (MODE == HEAD_SNAP && needs) {       // nearest table value of r * scale (first on a tie), divided back
+    const float x = r * Rb[3];
+    float best = hv.v[0], bd = fabsf(hv.v[0] - x);
+    for (int k = 1; k < hv.n; ++k) {
+      const float d = fabsf(hv.v[k] - x);
+      if (d < bd) { bd = d; best = hv.v[k]; }
+    }
+    r = best / Rb[3];
+  }
   const float diff = r - target, l1v = fabsf(diff);
   float rl, drl;   // reg loss and d(reg loss)/dr
   if (a.use_l1) { rl = l1v; drl = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f); }
@@ -90,13 +109,23 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, fl
   const bool okt = (l1v <= a.tol_margin) && needs;
   if (!a.kind_l1 && fabsf(target) > 1.f) { rl = 0.f; drl = 0.f; }
   if (!needs) { rl = 0.f; drl = 0.f; }
+  if (MODE == HEAD_SNAP) drl = 0.f;       // the snapped value is a constant
   const float dz = drl * g_reg * (1.f - r * r);
+  if (MODE == HEAD_NONE) {                // no regressor module: reg rows stay zero (vilbert.py:1592-1598)
+    if (tid == 0) {
+      a.logits[b * 2] = l0; a.logits[b * 2 + 1] = l1;
+      for (int k = 0; k < 5; ++k) a.reg[k * a.B + b] = 0.f;
+      float* s = scratch + (long)b * 8;
+      s[0] = dl0; s[1] = dl1; s[2] = 0.f; s[3] = nsp_b; s[4] = valid ? 1.f : 0.f;
+      s[5] = 0.f; s[6] = 0.f; s[7] = needs ? 1.f : 0.f;
+    }
+  } else
   if (tid == 0) {
     a.logits[b * 2] = l0; a.logits[b * 2 + 1] = l1;
     a.reg[0 * a.B + b] = needs ? r * Rb[3] : 0.f;
     a.reg[1 * a.B + b] = rl;
     a.reg[2 * a.B + b] = needs ? l1v : 0.f;
-    a.reg[3 * a.B + b] = r;                       // raw tanh output (diagnostic)
+    a.reg[3 * a.B + b] = raw;                     // raw tanh output (diagnostic)
     a.reg[4 * a.B + b] = needs ? d5 : 0.f;
     float* s = scratch + (long)b * 8;
     s[0] = dl0; s[1] = dl1; s[2] = dz; s[3] = nsp_b; s[4] = valid ? 1.f : 0.f;
@@ -114,10 +143,12 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, fl
       dpt[c] = f2bf(t > 0.f ? gt : 0.f);        // relu'(pre) == (post > 0)
       dpv[c] = f2bf(v > 0.f ? gv : 0.f);
     }
-    bf16_t* dfh = reinterpret_cast<bf16_t*>(a.d_fus_h) + (long)b * 256;
-    for (int c = tid; c < 256; c += 256) {
-      const float hval = bf2f(fh[c]);
-      dfh[c] = f2bf(dz * a.w_f6[c] * (hval > 0.f ? 1.f : 0.01f));
+    if (MODE != HEAD_NONE) {
+      bf16_t* dfh = reinterpret_cast<bf16_t*>(a.d_fus_h) + (long)b * 256;
+      for (int c = tid; c < 256; c += 256) {
+        const float hval = bf2f(fh[c]);
+        dfh[c] = f2bf(dz * a.w_f6[c] * (hval > 0.f ? 1.f : 0.01f));
+      }
     }
   }
 }
@@ -187,6 +218,133 @@ __global__ __launch_bounds__(256) void head_reduce_kernel(const CrctHeadArgs a, 
   }
 }
 
+// ------------------------------------------------------------------ DVQA_Regressor_v20_CE tail
+// regressor.py:72-79 + vilbert.py:1603-1615.  One workgroup per row: logits / NSP terms as head_rows_kernel, z = ce_fusion.6(fus_h)
+// (65 outputs, the four waves take them in turn), p = softmax(z), CrossEntropyLoss(p, target) -- the reference feeds the Softmax
+// output to CrossEntropyLoss, so the softmax is taken twice -- argmax (first maximum), value lookup and flags.  Writes the gradient
+// seed w.r.t. ce_fusion.4's pre-activation and the per-row dL/dz (ce [B][65]) for the weight gradients of ce_fusion.6.
+__global__ __launch_bounds__(256) void head_ce_rows_kernel(const CrctHeadArgs a, float* scratch, float* ce, const HeadValues hv) {
+  __shared__ float red[4];
+  __shared__ float zs[CRCT_CE_CLASSES], ps[CRCT_CE_CLASSES], dzs[CRCT_CE_CLASSES];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bf16_t* pt = reinterpret_cast<const bf16_t*>(a.pooled_t) + (long)b * a.Hb;
+  const bf16_t* pv = reinterpret_cast<const bf16_t*>(a.pooled_v) + (long)b * a.Hb;
+  const bf16_t* fh = reinterpret_cast<const bf16_t*>(a.fus_h) + (long)b * 256;
+  const float dsc = a.drop_thr ? a.drop_scale : 1.0f;
+  float l0 = 0.f, l1 = 0.f;
+  for (int c = tid; c < a.Hb; c += 256) {
+    const float t = bf2f(pt[c]), v = bf2f(pv[c]);
+    float f = a.fusion_sum ? t + v : t * v;
+    f = head_keep(a, b, c) ? f * dsc : 0.f;
+    l0 += f * a.w_cls[c]; l1 += f * a.w_cls[a.Hb + c];
+  }
+  l0 = block_sum(l0, red) + a.b_cls[0];
+  l1 = block_sum(l1, red) + a.b_cls[1];
+  int n_valid = 0;
+  long label = -1;
+  if (a.labels) {
+    for (int i = tid; i < a.B; i += 256) n_valid += (a.labels[i] != -1);
+    n_valid = (int)(block_sum((float)n_valid, red) + 0.5f);
+    label = a.labels[b];
+  }
+  for (int k = wave; k < CRCT_CE_CLASSES; k += 4) {
+    float acc = 0.f;
+    for (int c = lane; c < 256; c += 64) acc += bf2f(fh[c]) * a.w_f6[(long)k * 256 + c];
+    acc = wave_sum(acc);
+    if (lane == 0) zs[k] = acc + a.b_f6[k];
+  }
+  __syncthreads();
+  const float g_loss = (a.g_loss_dev ? a.g_loss_dev[0] : 1.0f) * a.grad_scale;
+  const float g_nsp = a.g_nsp_dev ? a.g_nsp_dev[0] * a.grad_scale : a.nsp_coeff * g_loss;
+  const float g_reg = a.g_reg_dev ? a.g_reg_dev[b] * a.grad_scale : a.reg_coeff * g_loss / (float)a.B;
+  const float mx = fmaxf(l0, l1);
+  const float lse = mx + logf(expf(l0 - mx) + expf(l1 - mx));
+  float nsp_b = 0.f, dl0 = 0.f, dl1 = 0.f;
+  const bool valid = a.labels && label != -1;
+  if (valid) {
+    nsp_b = lse - (label == 0 ? l0 : l1);
+    const float w = g_nsp / (float)max(n_valid, 1);
+    dl0 = (expf(l0 - lse) - (label == 0 ? 1.f : 0.f)) * w;
+    dl1 = (expf(l1 - lse) - (label == 1 ? 1.f : 0.f)) * w;
+  }
+  // p = softmax(z)
+  float zm = zs[0];
+  for (int k = 1; k < CRCT_CE_CLASSES; ++k) zm = fmaxf(zm, zs[k]);
+  float se = 0.f;
+  for (int k = 0; k < CRCT_CE_CLASSES; ++k) se += expf(zs[k] - zm);
+  if (tid < CRCT_CE_CLASSES) ps[tid] = expf(zs[tid] - zm) / se;
+  __syncthreads();
+  // CrossEntropyLoss over p, argmax of p
+  const float* Rb = a.R + (long)b * 4;
+  const bool needs = Rb[1] == 1.0f;
+  const float tf = Rb[0];
+  const bool tok = tf > -1.f && tf < (float)CRCT_CE_CLASSES;      // (int64) R[:,0] truncates towards zero
+  const int t = tok ? (int)tf : 0;
+  int am = 0;
+  float pm = ps[0];
+  for (int k = 1; k < CRCT_CE_CLASSES; ++k) if (ps[k] > pm) { pm = ps[k]; am = k; }
+  float s2 = 0.f;
+  for (int k = 0; k < CRCT_CE_CLASSES; ++k) s2 += expf(ps[k] - pm);
+  const float lse2 = pm + logf(s2);
+  float pdp = 0.f;                                                   // sum_j p_j dL/dp_j
+  for (int k = 0; k < CRCT_CE_CLASSES; ++k) pdp += ps[k] * (expf(ps[k] - lse2) - (k == t ? 1.f : 0.f));
+  const float w = (needs && tok) ? g_reg : 0.f;
+  if (tid < CRCT_CE_CLASSES) {
+    const float dp = expf(ps[tid] - lse2) - (tid == t ? 1.f : 0.f);
+    const float dz = w * ps[tid] * (dp - pdp);
+    dzs[tid] = dz;
+    if (ce) ce[(long)b * CRCT_CE_CLASSES + tid] = dz;
+  }
+  const float rl = needs ? (tok ? lse2 - ps[t] : NAN) : 0.f;
+  const float err = (needs && tok) ? fabsf(hv.v[am] - hv.v[t]) : 0.f;
+  const bool ok = needs && tok && am == t;
+  if (tid == 0) {
+    a.logits[b * 2] = l0; a.logits[b * 2 + 1] = l1;
+    a.reg[0 * a.B + b] = needs ? hv.v[am] : 0.f;
+    a.reg[1 * a.B + b] = rl;
+    a.reg[2 * a.B + b] = err;
+    a.reg[3 * a.B + b] = pm;                      // probability of the chosen class (diagnostic)
+    a.reg[4 * a.B + b] = err;
+    float* s = scratch + (long)b * 8;
+    s[0] = dl0; s[1] = dl1; s[2] = 0.f; s[3] = nsp_b; s[4] = valid ? 1.f : 0.f;
+    s[5] = ok ? 1.f : 0.f; s[6] = ok ? 1.f : 0.f; s[7] = needs ? 1.f : 0.f;
+  }
+  if (a.d_pooled_t) {
+    __syncthreads();                              // dzs complete
+    bf16_t* dpt = reinterpret_cast<bf16_t*>(a.d_pooled_t) + (long)b * a.Hb;
+    bf16_t* dpv = reinterpret_cast<bf16_t*>(a.d_pooled_v) + (long)b * a.Hb;
+    for (int c = tid; c < a.Hb; c += 256) {
+      const float tv = bf2f(pt[c]), v = bf2f(pv[c]);
+      float df = dl0 * a.w_cls[c] + dl1 * a.w_cls[a.Hb + c];
+      df = head_keep(a, b, c) ? df * dsc : 0.f;
+      const float gt = a.fusion_sum ? df : df * v, gv = a.fusion_sum ? df : df * tv;
+      dpt[c] = f2bf(tv > 0.f ? gt : 0.f);
+      dpv[c] = f2bf(v > 0.f ? gv : 0.f);
+    }
+    bf16_t* dfh = reinterpret_cast<bf16_t*>(a.d_fus_h) + (long)b * 256;
+    for (int c = tid; c < 256; c += 256) {
+      float g = 0.f;
+      for (int k = 0; k < CRCT_CE_CLASSES; ++k) g += dzs[k] * a.w_f6[(long)k * 256 + c];
+      const float hval = bf2f(fh[c]);
+      dfh[c] = f2bf(g * (hval > 0.f ? 1.f : 0.01f));
+    }
+  }
+}
+
+// ce_fusion.6 gradients: d_w[k][c] += sum_b dz[b][k] fus_h[b][c], d_b[k] += sum_b dz[b][k]; one workgroup per class, rows in order
+__global__ __launch_bounds__(256) void head_ce_wgrad_kernel(const CrctHeadArgs a, const float* __restrict__ ce) {
+  const int k = blockIdx.x, c = threadIdx.x;
+  const bf16_t* fh = reinterpret_cast<const bf16_t*>(a.fus_h);
+  float g = 0.f, gb = 0.f;
+  for (int b = 0; b < a.B; ++b) {
+    const float d = ce[(long)b * CRCT_CE_CLASSES + k];
+    g += d * bf2f(fh[(long)b * 256 + c]);
+    gb += d;
+  }
+  a.d_w_f6[(long)k * 256 + c] += g;
+  if (c == 0 && a.d_b_f6) a.d_b_f6[k] += gb;
+}
+
 // ------------------------------------------------------------------ evaluation: per-question answer selection
 // One wave per question.  Question q owns the candidate rows [off_q, off_q + num_ans[q]) with off_q = sum of the
 // earlier counts (recomputed by every wave: Q is a few hundred at most).  p0 = softmax(logits)[0] in fp32; the
@@ -253,10 +411,51 @@ extern "C" int crct_head_loss(const CrctHeadArgs* args, crct_stream_t stream) {
   CRCT_REQUIRE(args && args->B > 0 && args->Hb > 0, "head_loss: bad sizes");
   CRCT_REQUIRE(args->scratch, "head_loss: scratch (fp32 [B][8]) is required");
   hipStream_t s = (hipStream_t)stream;
-  crct_launch(head_rows_kernel, dim3(args->B), dim3(256), 0, s, *args, args->scratch);
+  crct_launch(head_rows_kernel<HEAD_PLOTQA>, dim3(args->B), dim3(256), 0, s, *args, args->scratch, HeadValues{});
   CRCT_CHECK_HIP(hipGetLastError());
   const int nb = ((args->Hb > 256 ? args->Hb : 256) + 31) / 32;
   crct_launch(head_reduce_kernel, dim3(nb), dim3(256), 0, s, *args, (const float*)args->scratch);
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int crct_head_loss_variant(const CrctHeadVariantArgs* args, crct_stream_t stream) {
+  CRCT_REQUIRE(args && args->h.B > 0 && args->h.Hb > 0, "head_loss_variant: bad sizes");
+  CRCT_REQUIRE(args->h.scratch, "head_loss_variant: scratch (fp32 [B][8]) is required");
+  const CrctVariant& v = args->variant;
+  CRCT_REQUIRE(v.n_values >= 0 && v.n_values <= CRCT_CE_CLASSES, "head_loss_variant: %d table values (at most %d)", v.n_values, CRCT_CE_CLASSES);
+  HeadValues hv = {};
+  for (int k = 0; k < v.n_values; ++k) hv.v[k] = v.values[k];
+  hv.n = v.n_values;
+  hipStream_t s = (hipStream_t)stream;
+  const CrctHeadArgs& a = args->h;
+  CrctHeadArgs r = a;                     // the reduce pass: bi_seq_relationship gradients + stats (fusion.6 / ce_fusion.6: see below)
+  if (v.regressor == CRCT_REGRESSOR_PLOTQA) {
+    CRCT_REQUIRE(a.fus_h && a.w_f6 && a.b_f6, "head_loss_variant: the PlotQA regressor needs fus_h, w_f6, b_f6");
+    if (args->snap) {
+      CRCT_REQUIRE(v.n_values > 0, "head_loss_variant: the DVQA snap needs the value table");
+      crct_launch(head_rows_kernel<HEAD_SNAP>, dim3(a.B), dim3(256), 0, s, a, a.scratch, hv);
+    } else {
+      crct_launch(head_rows_kernel<HEAD_PLOTQA>, dim3(a.B), dim3(256), 0, s, a, a.scratch, hv);
+    }
+  } else if (v.regressor == CRCT_REGRESSOR_NONE) {
+    crct_launch(head_rows_kernel<HEAD_NONE>, dim3(a.B), dim3(256), 0, s, a, a.scratch, hv);
+    r.d_w_f6 = nullptr; r.d_b_f6 = nullptr;
+  } else if (v.regressor == CRCT_REGRESSOR_CE) {
+    CRCT_REQUIRE(v.n_values == CRCT_CE_CLASSES, "head_loss_variant: the CE regressor needs %d table values, got %d", CRCT_CE_CLASSES, v.n_values);
+    CRCT_REQUIRE(a.fus_h && a.w_f6 && a.b_f6 && args->ce_scratch, "head_loss_variant: the CE regressor needs fus_h, w_f6, b_f6, ce_scratch");
+    crct_launch(head_ce_rows_kernel, dim3(a.B), dim3(256), 0, s, a, a.scratch, args->ce_scratch, hv);
+    CRCT_CHECK_HIP(hipGetLastError());
+    if (a.d_w_f6) {
+      crct_launch(head_ce_wgrad_kernel, dim3(CRCT_CE_CLASSES), dim3(256), 0, s, a, (const float*)args->ce_scratch);
+    }
+    r.d_w_f6 = nullptr; r.d_b_f6 = nullptr;
+  } else {
+    CRCT_REQUIRE(false, "head_loss_variant: unknown regressor kind %d", v.regressor);
+  }
+  CRCT_CHECK_HIP(hipGetLastError());
+  const int nb = ((a.Hb > 256 ? a.Hb : 256) + 31) / 32;
+  crct_launch(head_reduce_kernel, dim3(nb), dim3(256), 0, s, r, (const float*)a.scratch);
   CRCT_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -1235,6 +1235,85 @@ __global__ __launch_bounds__(256) void embed_image_bwd_kernel(
   row_store_f32(aw3, partials + (6 * nr + pr) * H, H, lane);
 }
 
+// ------------------------------------------------------------------------------ image embedding, 'dvqa' / 'figure_qa'
+// vilbert.py:1478-1489: sum = new_loc_emb(loc) + color_emb(target) (+ areas_emp(areas)); no feature term.
+template <int NCH, bool AREAS>
+__global__ __launch_bounds__(256) void embed_image_var_fwd_kernel(
+    const float* __restrict__ loc, const int64_t* __restrict__ target, const float* __restrict__ areas,
+    const float* __restrict__ w_loc, const float* __restrict__ b_loc, const float* __restrict__ color,
+    const float* __restrict__ w_areas, const float* __restrict__ b_areas,
+    const float* __restrict__ gamma, const float* __restrict__ beta, bf16_t* __restrict__ sum_out,
+    bf16_t* __restrict__ y, float* __restrict__ mean_o, float* __restrict__ rstd_o, int M, int H, float eps,
+    uint32_t thr, float scale, uint32_t site, uint64_t seed) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += (long)gridDim.x * ROWS_PER_BLOCK) {
+    Row<NCH> r;
+    row_zero(r);
+    const float4 lv = *reinterpret_cast<const float4*>(loc + row * 4);
+    const float l[4] = {lv.x, lv.y, lv.z, lv.w};
+    row_add_loc_linear(r, w_loc, b_loc, l, H, lane);
+    row_add_f32(r, color + target[row] * (long)H, H, lane);
+    if (AREAS) {
+      const float a = areas[row];
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        const int c = (lane + 64 * i) * 8;
+        if (c < H) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) r.v[i][j] += w_areas[c + j] * a + b_areas[c + j];
+        }
+      }
+    }
+    row_store_bf16(r, sum_out + row * H, H, lane);
+    row_round_bf16(r);
+    float mean, rstd;
+    row_stats(r, H, lane, eps, mean, rstd);
+    row_normalize(r, gamma, beta, H, lane, mean, rstd, row, thr, scale, site, seed);
+    row_store_bf16(r, y + row * H, H, lane);
+    if (lane == 0) { mean_o[row] = mean; rstd_o[row] = rstd; }
+  }
+}
+
+// the backward of embed_image_bwd_kernel without the d_sum store (no image Linear behind it) and with the areas weight sums as
+// partial row set 7
+template <int NCH, bool AREAS>
+__global__ __launch_bounds__(256) void embed_image_var_bwd_kernel(
+    const bf16_t* __restrict__ dy_p, const bf16_t* __restrict__ sum_p, const float* __restrict__ mean_p,
+    const float* __restrict__ rstd_p, const float* __restrict__ loc, const int64_t* __restrict__ target,
+    const float* __restrict__ areas, const float* __restrict__ gamma, float* __restrict__ d_color,
+    float* __restrict__ partials, int M, int H, uint32_t thr, float scale, uint32_t site, uint64_t seed,
+    float* __restrict__ rows_scratch, int* __restrict__ idx_scratch) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Row<NCH> adg, adb, abl, aw0, aw1, aw2, aw3, awa;
+  row_zero(adg); row_zero(adb); row_zero(abl); row_zero(aw0); row_zero(aw1); row_zero(aw2); row_zero(aw3); row_zero(awa);
+  for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += (long)gridDim.x * ROWS_PER_BLOCK) {
+    Row<NCH> dy, x;
+    row_load_bf16(dy, dy_p + row * H, H, lane);
+    row_load_bf16(x, sum_p + row * H, H, lane);
+    row_apply_dropmask(dy, H, lane, row, thr, scale, site, seed);
+    row_ln_bwd(dy, x, gamma, H, lane, mean_p[row], rstd_p[row], adg, adb);
+    if (rows_scratch) {
+      row_store_f32(dy, rows_scratch + row * H, H, lane);
+      if (lane == 0) idx_scratch[row] = (int)target[row];
+    } else {
+      row_atomic_add(dy, d_color + target[row] * (long)H, H, lane);
+    }
+    const float4 lv = *reinterpret_cast<const float4*>(loc + row * 4);
+    row_acc(abl, dy);       // = d b_loc = d b_areas
+    row_acc(aw0, dy, lv.x); row_acc(aw1, dy, lv.y); row_acc(aw2, dy, lv.z); row_acc(aw3, dy, lv.w);
+    if (AREAS) row_acc(awa, dy, areas[row]);
+  }
+  const long nr = (long)gridDim.x * ROWS_PER_BLOCK, pr = (long)blockIdx.x * ROWS_PER_BLOCK + wave;
+  row_store_f32(adg, partials + (0 * nr + pr) * H, H, lane);
+  row_store_f32(adb, partials + (1 * nr + pr) * H, H, lane);
+  row_store_f32(abl, partials + (2 * nr + pr) * H, H, lane);
+  row_store_f32(aw0, partials + (3 * nr + pr) * H, H, lane);
+  row_store_f32(aw1, partials + (4 * nr + pr) * H, H, lane);
+  row_store_f32(aw2, partials + (5 * nr + pr) * H, H, lane);
+  row_store_f32(aw3, partials + (6 * nr + pr) * H, H, lane);
+  if (AREAS) row_store_f32(awa, partials + (7 * nr + pr) * H, H, lane);
+}
+
 inline int nch_for(int H) { return (H / 8 + 63) / 64; }
 inline int row_grid(long M, int cap) {
   long g = (M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
@@ -1782,6 +1861,70 @@ extern "C" int crct_embed_image_bwd(const void* dy, const void* sum_saved, const
   if (d_bimg) {
     FinalizeArgs fb = {};
     fb.out[0] = d_bimg; fb.stride[0] = 1; fb.Q = 1; fb.nblk = nb * ROWS_PER_BLOCK; fb.H = H; fb.accumulate = 1;
+    fb.partials = partials + (size_t)2 * nb * ROWS_PER_BLOCK * H;
+    return launch_finalize(fb, s);
+  }
+  return 0;
+}
+
+extern "C" int crct_embed_image_var_fwd(const float* loc, const int64_t* target, const float* areas, const float* w_loc,
+                                        const float* b_loc, const float* color, const float* w_areas, const float* b_areas,
+                                        const float* gamma, const float* beta, void* sum_out, void* y, float* mean, float* rstd,
+                                        int M, int H, float eps, uint32_t drop_thr, float drop_scale, uint32_t drop_site,
+                                        uint64_t seed, crct_stream_t stream) {
+  CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_image_var: H=%d must be a positive multiple of 8", H);
+  CRCT_REQUIRE(!areas || (w_areas && b_areas), "embed_image_var: areas needs the areas_emp weight and bias");
+  if (M <= 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (areas) {
+    DISPATCH_NCH(H, crct_launch((embed_image_var_fwd_kernel<NCH, true>), dim3(row_grid(M, 2048)), dim3(256), 0, s, loc, target, areas,
+                                w_loc, b_loc, color, w_areas, b_areas, gamma, beta, (bf16_t*)sum_out, (bf16_t*)y, mean, rstd, M, H, eps,
+                                drop_thr, drop_scale, drop_site, seed));
+  } else {
+    DISPATCH_NCH(H, crct_launch((embed_image_var_fwd_kernel<NCH, false>), dim3(row_grid(M, 2048)), dim3(256), 0, s, loc, target, areas,
+                                w_loc, b_loc, color, w_areas, b_areas, gamma, beta, (bf16_t*)sum_out, (bf16_t*)y, mean, rstd, M, H, eps,
+                                drop_thr, drop_scale, drop_site, seed));
+  }
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int crct_embed_image_var_bwd(const void* dy, const void* sum_saved, const float* mean, const float* rstd,
+                                        const float* loc, const int64_t* target, const float* areas, const float* gamma,
+                                        float* d_color, float* d_wloc, float* d_bloc, float* d_wareas, float* d_bareas,
+                                        float* d_gamma, float* d_beta, float* partials, int M, int H, uint32_t drop_thr,
+                                        float drop_scale, uint32_t drop_site, uint64_t seed, float* rows_scratch,
+                                        int32_t* idx_scratch, int n_color, crct_stream_t stream) {
+  CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_image_var_bwd: H=%d must be a positive multiple of 8", H);
+  if (M <= 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (!idx_scratch || M > GATHER_MAX_ROWS || n_color <= 0) rows_scratch = nullptr;      // atomics fall-back
+  const int nb = embed_bwd_blocks(M);
+  if (areas) {
+    DISPATCH_NCH(H, crct_launch((embed_image_var_bwd_kernel<NCH, true>), dim3(nb), dim3(256), 0, s, (const bf16_t*)dy,
+                                (const bf16_t*)sum_saved, mean, rstd, loc, target, areas, gamma, d_color, partials, M, H, drop_thr,
+                                drop_scale, drop_site, seed, rows_scratch, rows_scratch ? idx_scratch : nullptr));
+  } else {
+    DISPATCH_NCH(H, crct_launch((embed_image_var_bwd_kernel<NCH, false>), dim3(nb), dim3(256), 0, s, (const bf16_t*)dy,
+                                (const bf16_t*)sum_saved, mean, rstd, loc, target, areas, gamma, d_color, partials, M, H, drop_thr,
+                                drop_scale, drop_site, seed, rows_scratch, rows_scratch ? idx_scratch : nullptr));
+  }
+  CRCT_CHECK_HIP(hipGetLastError());
+  if (rows_scratch) {
+    crct_launch(gather_sum_kernel, dim3(n_color), dim3(256), (size_t)M * sizeof(int), s, rows_scratch, idx_scratch, M, H, d_color,
+                n_color, (const int*)nullptr, (float*)nullptr);
+    CRCT_CHECK_HIP(hipGetLastError());
+  }
+  FinalizeArgs fa = {};
+  fa.out[0] = d_gamma; fa.out[1] = d_beta; fa.out[2] = d_bloc;
+  fa.stride[0] = fa.stride[1] = fa.stride[2] = 1;
+  for (int k = 0; k < 4; ++k) { fa.out[3 + k] = d_wloc ? d_wloc + k : nullptr; fa.stride[3 + k] = 4; }
+  fa.Q = 7; fa.nblk = nb * ROWS_PER_BLOCK; fa.H = H; fa.accumulate = 1; fa.partials = partials;
+  if (areas) { fa.out[7] = d_wareas; fa.stride[7] = 1; fa.Q = 8; }      // areas_emp.weight [H][1]
+  if (launch_finalize(fa, s)) return 1;
+  if (areas && d_bareas) {       // the column-sum partial (index 2) once more: b_areas
+    FinalizeArgs fb = {};
+    fb.out[0] = d_bareas; fb.stride[0] = 1; fb.Q = 1; fb.nblk = nb * ROWS_PER_BLOCK; fb.H = H; fb.accumulate = 1;
     fb.partials = partials + (size_t)2 * nb * ROWS_PER_BLOCK * H;
     return launch_finalize(fb, s);
   }

@@ -406,6 +406,23 @@ int crct_embed_image_bwd(const void* dy, const void* sum_saved, const float* mea
                          float* rows_scratch, int32_t* idx_scratch, int n_color,
                          crct_stream_t stream);
 
+/* Image embeddings of the 'dvqa' / 'figure_qa' datasets (vilbert.py:1474-1489): no feature term (the reference computes
+ * new_image_embeddings(softmax(feat)) and drops it), sum = W_loc loc + b_loc + color_emb[target] (+ W_a areas + b_a when areas != NULL:
+ * areas_emp = Linear(1, H), areas fp32 [M]); y = dropout(LN(sum)).  Backward: colour-table sums as crct_embed_image_bwd, loc-Linear,
+ * areas-Linear (d_wareas[c] = sum_r dsum[r][c] areas[r], d_bareas = column sum; skipped when areas == NULL) and LayerNorm gradients,
+ * all ACCUMULATED, all summed in a fixed order.  partials: fp32 [8][4 * nblk][H]. */
+int crct_embed_image_var_fwd(const float* loc, const int64_t* target, const float* areas,
+                             const float* w_loc, const float* b_loc, const float* color, const float* w_areas, const float* b_areas,
+                             const float* gamma, const float* beta, void* sum_out, void* y, float* mean, float* rstd,
+                             int M, int H, float eps, uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
+                             crct_stream_t stream);
+int crct_embed_image_var_bwd(const void* dy, const void* sum_saved, const float* mean, const float* rstd,
+                             const float* loc, const int64_t* target, const float* areas, const float* gamma,
+                             float* d_color, float* d_wloc, float* d_bloc, float* d_wareas, float* d_bareas,
+                             float* d_gamma, float* d_beta, float* partials, int M, int H,
+                             uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
+                             float* rows_scratch, int32_t* idx_scratch, int n_color, crct_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Heads + losses: BertPreTrainingHeads.forward (vilbert.py:1048-1062), the tail of
  * PlotQA_Regressor_v20 (regressor.py:31-41: Linear(256,1)+Tanh), the regression bookkeeping and
@@ -443,6 +460,33 @@ typedef struct CrctHeadArgs {
   uint32_t drop_thr; float drop_scale; uint32_t drop_site; uint64_t seed;   /* cls.dropout (0.1) */
 } CrctHeadArgs;
 int crct_head_loss(const CrctHeadArgs* args, crct_stream_t stream);
+
+/* Model variants of the reference's three datasets (vilbert.py:1459-1537, 1596-1625).  dataset: PLOTQA = 'plotqa' /
+ * 'plotqa_colorless' (image features embedded), DVQA / FIGUREQA = 'dvqa' / 'figure_qa' (no feature term, areas_emp).  regressor:
+ * PLOTQA = PlotQA_Regressor_v20 (fusion.6 + Tanh), NONE = no regressor module (binary_answers, or DVQA '_cls' question files: reg
+ * rows stay zero), CE = DVQA_Regressor_v20_CE (ce_fusion.6 = Linear(256, 65) + Softmax, CrossEntropyLoss on the probabilities).
+ * values[0 .. n_values) = params['dvqa_floats'] (the CE classes' values; the evaluation snap of DVQA with the PLOTQA regressor). */
+#define CRCT_CE_CLASSES 65
+enum { CRCT_DATASET_PLOTQA = 0, CRCT_DATASET_DVQA = 1, CRCT_DATASET_FIGUREQA = 2 };
+enum { CRCT_REGRESSOR_PLOTQA = 0, CRCT_REGRESSOR_NONE = 1, CRCT_REGRESSOR_CE = 2 };
+typedef struct CrctVariant {
+  int32_t dataset, regressor, n_values;
+  float values[CRCT_CE_CLASSES];
+} CrctVariant;
+/* crct_head_loss for the variants.  regressor PLOTQA: crct_head_loss, and with snap != 0 (DVQA evaluation) the prediction
+ * r = tanh(z) becomes nearest(r * R[:,3]) / R[:,3] -- nearest of values[], first on a tie, distances in fp32 -- before the losses
+ * and flags, with no regression gradient.  NONE: reg rows zero, no regression gradient, fus_h / w_f6 / b_f6 unused.  CE: w_f6 [65][256]
+ * and b_f6 [65] are ce_fusion.6, target class = (int64) R[:,0]: reg[0] = values[argmax p] (first maximum), reg[1] = CE(p, target)
+ * with p = softmax(z) (the softmax taken twice, as the reference does), reg[2] = reg[4] = |values[argmax] - values[target]|, both
+ * right-flags = (argmax == target); d_fus_h = gradient w.r.t. ce_fusion.4's pre-activation; d_w_f6 / d_b_f6 accumulated.
+ * ce_scratch: fp32 [B][CRCT_CE_CLASSES] (CE only).  A target class outside [0, 65) gives NaN loss and no gradient. */
+typedef struct CrctHeadVariantArgs {
+  CrctHeadArgs h;
+  CrctVariant variant;
+  int32_t snap;
+  float* ce_scratch;
+} CrctHeadVariantArgs;
+int crct_head_loss_variant(const CrctHeadVariantArgs* args, crct_stream_t stream);
 
 /* Evaluation scoring, answer selection per question (replaces the per-question Python loop with .item() syncs of
  * evaluation.py:281-292): question q owns num_ans[q] consecutive candidate rows of the N scored rows;
@@ -546,6 +590,15 @@ typedef struct crct_engine crct_engine_t;
  * that never receives a gradient (it is then excluded from the backward segments' gradient ranges). */
 crct_engine_t* crct_engine_create(const CrctModelDims* dims, const char* names, const int64_t* offsets,
                                   const int64_t* sizes, int n_params, int max_B, int max_T, int max_V);
+/* The same for a model variant (CrctVariant; NULL or dataset PLOTQA with regressor PLOTQA = crct_engine_create).  DVQA / FIGUREQA
+ * skip the feature softmax and the new_image_embeddings GEMM (the features are never read) and need
+ * bert.v_embeddings.areas_emp.*; regressor CE resolves regressor.ce_fusion.*, NONE no regressor.* tensor at all. */
+crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, const char* names, const int64_t* offsets,
+                                          const int64_t* sizes, int n_params, int max_B, int max_T, int max_V,
+                                          const CrctVariant* variant);
+/* areas (fp32 [B][V], device) of the batch the next forward / backward calls run on; NULL = no areas term.  Forward and backward
+ * of one batch must see the same value.  Variants DVQA / FIGUREQA only. */
+int crct_engine_set_areas(crct_engine_t*, const float* areas);
 void crct_engine_destroy(crct_engine_t*);
 size_t crct_engine_workspace_bytes(const crct_engine_t*);
 int crct_engine_num_segments(const crct_engine_t*);
