@@ -21,6 +21,8 @@ void crct_set_error(const char* fmt, ...);
     }                                           \
   } while (0)
 
+// whether a GEMM configuration id (CrctGemmArgs.tile) is built (gemm.hip, k_configs and the fp8 ids)
+bool crct_gemm_config_built(int id);
 hipError_t crct_gemm_launch(const CrctGemmArgs& g, hipStream_t s);
 hipError_t crct_gemm_launch_grouped(const CrctGemmArgs* gs, int n, hipStream_t s);
 // target_wgs > 0: a grouped bf16 weight-gradient launch runs as a persistent grid of about that many workgroups (gemm.hip, group_grid)

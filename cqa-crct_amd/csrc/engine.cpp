@@ -53,6 +53,7 @@ extern "C" int crct_gemm_bf16(const CrctGemmArgs* a, crct_stream_t stream) {
   CRCT_REQUIRE(!(a->ta && !a->tb), "gemm: (ta=1, tb=0) is not built (not used by the step)");
   CRCT_REQUIRE(!a->ta || a->M % 8 == 0, "gemm: transposed A needs M %% 8 == 0 (M=%d)", a->M);
   CRCT_REQUIRE(!a->tb || a->N % 8 == 0, "gemm: transposed B needs N %% 8 == 0 (N=%d)", a->N);
+  CRCT_REQUIRE(a->tile < 0 || crct_gemm_config_built(a->tile), "gemm: configuration %d is not built", a->tile);
   CRCT_CHECK_HIP(crct_gemm_launch(*a, (hipStream_t)stream));
   return 0;
 }
@@ -65,6 +66,7 @@ static int gemm_grouped_checked(const CrctGemmArgs* a, int n, crct_stream_t stre
     CRCT_REQUIRE(a[i].N % 4 == 0 && a[i].lda % 8 == 0 && a[i].ldb % 8 == 0 && a[i].ldc % 4 == 0, "gemm_grouped: alignment of problem %d", i);
     CRCT_REQUIRE((a[i].ta && a[i].tb) || a[i].K % 8 == 0, "gemm_grouped: K of problem %d", i);
     CRCT_REQUIRE(!(a[i].ta && !a[i].tb) && (!a[i].ta || a[i].M % 8 == 0) && (!a[i].tb || a[i].N % 8 == 0), "gemm_grouped: layout of problem %d", i);
+    CRCT_REQUIRE(a[i].tile < 0 || crct_gemm_config_built(a[i].tile), "gemm_grouped: configuration %d of problem %d is not built", a[i].tile, i);
   }
   if (target_wgs < 0) CRCT_CHECK_HIP(crct_gemm_launch_grouped(a, n, (hipStream_t)stream));
   else CRCT_CHECK_HIP(crct_gemm_launch_grouped_wgs(a, n, (hipStream_t)stream, target_wgs));
@@ -1597,7 +1599,8 @@ extern "C" int crct_engine_set_wgrad_flush(crct_engine_t* e, int mode) {
 extern "C" int crct_engine_set_site_policy(crct_engine_t* e, int site, int kind, int phase, int cfg, int split_k) {
   CRCT_REQUIRE(e && site > 0 && site < CRCT_SITE_COUNT && kind >= CRCT_KIND_FWD && kind <= CRCT_KIND_WGRAD && phase <= 1,
                "set_site_policy: bad site / kind / phase (%d, %d, %d)", site, kind, phase);
-  CRCT_REQUIRE(cfg >= -1 && cfg <= 71 && split_k >= 0 && split_k <= 4, "set_site_policy: cfg %d / split_k %d out of range", cfg, split_k);
+  CRCT_REQUIRE(cfg == -1 || crct_gemm_config_built(cfg), "set_site_policy: configuration %d is not built", cfg);
+  CRCT_REQUIRE(split_k >= 0 && split_k <= 4, "set_site_policy: split_k %d out of range", split_k);
   for (int ph = 0; ph < 2; ++ph)
     if (phase < 0 || phase == ph) { e->policy[site][kind][ph].cfg = cfg; e->policy[site][kind][ph].split_k = split_k; }
   return 0;

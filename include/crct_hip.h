@@ -48,7 +48,7 @@ typedef struct CrctGemmArgs {
   int32_t ta, tb;
   int32_t act, dact;
   int32_t c_is_f32, accumulate;
-  int32_t tile;             /* -1 = auto; 0: 128x128, 1: 128x64, 2: 64x128, 3: 64x64 */
+  int32_t tile;             /* -1 = auto, else a built configuration id (gemm.hip, k_configs; fp8: 20 / 21 / 36 / 37); any other id is an error */
   float alpha;
   uint32_t drop_thr;        /* 0 = no dropout, else keep iff a 16-bit Philox slice >= thr >> 16 (drop probability thr / 2^32 to within 2^-16) */
   float drop_scale;         /* 1/(1-p) */
@@ -120,14 +120,14 @@ int crct_gemm_group_concat(int on);
 /* Test hook: on != 0 makes crct_embed_text_bwd launch the position / type sums and the word-table scatter as two kernels one after
  * the other instead of one merged launch (identical results; tests/test_kernels_gpu.py, bench.py --embed-scatter-split). */
 void crct_embed_scatter_split(int on);
-/* Kernel configuration of the grouped weight-gradient launches of the step (all 128 x 128 tiles; see gemm.hip): 4 = plain loop,
- * 48 / 53 = loader waves (8 + 4 / 4 + 4 waves), 58 / 59 = loader waves + two fragment register sets.  Returns
- * the previous value; other values are ignored. */
+/* Kernel configuration of the grouped weight-gradient launches of the step: 4 (128 x 128, see gemm.hip) is the only one built.
+ * Returns the previous value (4); other values are ignored. */
 int crct_gemm_group_wgrad_config(int cfg);
 
 /* Kernel configuration of one shape class of the forward / data-gradient GEMMs: cls = 3 * rows_bucket + column_class with
  * rows_bucket 0: M <= 2000, 1: M <= 4000, 2: M > 4000 and column_class 0: N >= 2304 (wide), 1: N <= 1024 with K <= 1024, 2: N <= 1024
- * with K > 1024 (gemm.hip, pick_pipe_config).  cfg < 0 only reads.  Returns the previous configuration id (-1: bad class).  For
+ * with K > 1024 (gemm.hip, pick_pipe_config).  cfg < 0 only reads.  Returns the previous configuration id (-1: bad class, or a cfg
+ * that is not a built bf16 configuration: the entry is left as it was).  For
  * in-step sweeps (bench.py --class-policy); per-site overrides: crct_engine_set_site_policy. */
 int crct_gemm_class_config(int cls, int cfg);
 
@@ -724,7 +724,7 @@ int crct_engine_set_wgrad_workgroups(crct_engine_t* e, int target_wgs, int max_r
 /* Per-site launch policy of the forward / data-gradient GEMMs (A/B switch of the developer tools and the tests; the defaults
  * are the measured choices).  phase 0 = the text-only part of the schedule (layers t0 .. before the first
  * co-attention layer: nothing else on the chip's data path), phase 1 = beside the visual stream; phase < 0 sets both.
- * cfg = kernel configuration id (-1 = the shape-class default), split_k = K slices (0 / 1 = off).  kind = CRCT_KIND_WGRAD: cfg
+ * cfg = kernel configuration id (-1 = the shape-class default; an id that is not built is refused), split_k = K slices (0 / 1 = off).  kind = CRCT_KIND_WGRAD: cfg
  * only (4 / 9: the layer's grouped weight-gradient launch takes the configuration of its first problem).  Every choice computes
  * the same function; split_k changes the summation order over K (deterministically). */
 int crct_engine_set_site_policy(crct_engine_t*, int site, int kind, int phase, int cfg, int split_k);

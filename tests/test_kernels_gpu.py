@@ -47,7 +47,7 @@ def gemm_path(request):
 
 @pytest.mark.parametrize("M,N,K", [(1600, 3072, 768), (2880, 1024, 2048), (1600, 768, 3072), (80, 1024, 768),
                                    (21, 64, 96), (15, 128, 32), (300, 2304, 768)])
-@pytest.mark.parametrize("tile", [-1, 0, 3, 9, 11, 12])
+@pytest.mark.parametrize("tile", [-1, 0, 3, 9, 11, 12, 50])
 def test_gemm_forward(M, N, K, tile):
     x, w, b = bf(rand(M, K, seed=1)), bf(rand(N, K, scale=0.05, seed=2)), rand(N, seed=3)
     y = ops.gemm(x, w, M, N, K, bias=b, tile=tile)
@@ -55,6 +55,14 @@ def test_gemm_forward(M, N, K, tile):
     assert rel_err(y, ref) < 1e-2
     y32 = ops.gemm(x, w, M, N, K, bias=b, out_f32=True, tile=tile)
     assert rel_err(y32, ref) < 2e-3
+
+
+def test_gemm_refuses_a_configuration_that_is_not_built():
+    # an explicit CrctGemmArgs.tile without a launcher is an error that names it, on either kernel path (gemm_path) -- never
+    # a quiet run of another configuration
+    x, w = bf(rand(1600, 768, seed=1)), bf(rand(768, 768, scale=0.05, seed=2))
+    with pytest.raises(RuntimeError, match="configuration 22 is not built"):
+        ops.gemm(x, w, 1600, 768, 768, tile=22)
 
 
 def test_gemm_identity_asymmetric():
@@ -67,7 +75,7 @@ def test_gemm_identity_asymmetric():
 
 
 @pytest.mark.parametrize("M,N,K", [(1600, 768, 2304), (2880, 1024, 3072), (21, 64, 192), (80, 768, 1024)])
-@pytest.mark.parametrize("tile", [-1, 3, 9, 12])
+@pytest.mark.parametrize("tile", [-1, 3, 9, 12, 50])
 def test_gemm_dgrad(M, N, K, tile):
     # dx[M][N=in] = dy[M][K=out] @ W[K=out][N=in]
     dy, w = bf(rand(M, K, seed=4)), bf(rand(K, N, scale=0.05, seed=5))

@@ -113,6 +113,29 @@ def test_struct_mirrors_and_error_path():
     assert lib.crct_gemm_pick_tile(1600, 3072) in (0, 1, 2, 3)
 
 
+def test_only_built_gemm_configurations_are_accepted():
+    lib = L.load()
+    # crct_gemm_class_config: an id that is not built is refused (-1) and leaves the entry; a built one round-trips
+    cls = L.CLASS_NAMES.index("L.n")
+    old = lib.crct_gemm_class_config(cls, -1)
+    try:
+        assert lib.crct_gemm_class_config(cls, 22) == -1
+        assert lib.crct_gemm_class_config(cls, -1) == old
+        assert lib.crct_gemm_class_config(cls, 15) == old
+        assert lib.crct_gemm_class_config(cls, -1) == 15
+    finally:
+        lib.crct_gemm_class_config(cls, old)
+    assert lib.crct_gemm_class_config(cls, -1) == old
+    # crct_gemm_bf16: the same id as CrctGemmArgs.tile is rejected before anything touches a GPU, and the message names it
+    g = L.GemmArgs()
+    g.M, g.N, g.K = 8, 8, 8
+    g.A = g.B = g.C = 16
+    g.lda = g.ldb = g.ldc = 8
+    g.tile = 22
+    assert lib.crct_gemm_bf16(C.byref(g), None) != 0
+    assert b"configuration 22 is not built" in lib.crct_last_error()
+
+
 def test_model_refuses_cpu():
     from crct.model import VisualDialogEncoder
     with pytest.raises(RuntimeError):

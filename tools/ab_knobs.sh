@@ -6,7 +6,4 @@ EXTRA="--adamw-wgs 128" run wgs128 A=1
 EXTRA="--adamw-wgs 512" run wgs512 A=1
 EXTRA="--adamw-wgs 0" run wgs0 A=1
 EXTRA="--no-opt-overlap" run noov A=1
-EXTRA="" run group12 CRCT_GEMM_GROUP=12
-EXTRA="" run group9 CRCT_GEMM_GROUP=9
-EXTRA="" run streams1 CRCT_STREAMS=1
 EXTRA="" run base2 A=1

@@ -1,7 +1,7 @@
 // Developer microbenchmark: two independent forward GEMMs of a co-attention layer (text side, visual side) launched
 //   seq: back to back on one stream     par: on two streams at once     grp: as ONE grouped launch (crct_gemm_bf16_grouped)
 //   hipcc -O2 -std=c++17 --offload-arch=gfx950 -Iinclude tools/group_lab.cpp -Lcqa-crct_amd/crct -lcrct_hip \
-//         -Wl,-rpath,'$ORIGIN/../cqa-crct_amd/crct' -o tools/group_lab.bin ;  CRCT_GEMM_GROUP=12 ./tools/group_lab.bin
+//         -Wl,-rpath,'$ORIGIN/../cqa-crct_amd/crct' -o tools/group_lab.bin ;  ./tools/group_lab.bin
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -2,7 +2,7 @@
 (--wgrad-cfg) for one workload, every variant a fresh bench.py process on the same box; the first and last rows are the
 unmodified step (box drift).  Usage on the GPU box:
 
-    python tools/lab/class_sweep.py --workload plotqa-real "L.w=50" "L.w=9" "wgrad=48" "L.w=50,L.n=15" "s:t.ffn_up:fwd:50"
+    python tools/lab/class_sweep.py --workload plotqa-real "L.w=50" "L.w=9" "L.w=50,L.n=15" "s:t.ffn_up:fwd:50"
 """
 import argparse
 import json

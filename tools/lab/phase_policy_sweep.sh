@@ -16,7 +16,4 @@ run "text phase 1, every site on 128x64 two stages (cfg 12)" "$T1all12"
 run "text phase 1, every FFN / QKV site on 128x128 two stages (cfg 9)" "$T1all9"
 run "text phase 1, FFN-up fwd only on cfg 4" "t.ffn_up:fwd:1:4:1"
 run "text phase 1, FFN-down dgrad only on cfg 4" "t.ffn_down:dgrad:1:4:1"
-run "text phase 1, long-K sites (FFN-down fwd, FFN-up dgrad) on loader waves (cfg 54)" "t.ffn_down:fwd:1:54:1,t.ffn_up:dgrad:1:54:1"
-run "text phase 0 (text-only prefix / tail), long-K sites on loader waves (cfg 54)" "t.ffn_down:fwd:0:54:1,t.ffn_up:dgrad:0:54:1,t.qkv:dgrad:0:54:1"
-run "text phase 0, every FFN / QKV site on cfg 46 (loader waves 8+4)" "t.ffn_down:fwd:0:46:1,t.ffn_up:dgrad:0:46:1,t.qkv:dgrad:0:46:1,t.ffn_up:fwd:0:46:1,t.ffn_down:dgrad:0:46:1,t.qkv:fwd:0:46:1"
 done

@@ -3,7 +3,7 @@
 //   grp : ONE stream, the four GEMM pairs as grouped launches, attention / LayerNorm of both sides back to back
 //   seq : ONE stream, nothing grouped
 //   hipcc -O2 -std=c++17 --offload-arch=gfx950 -Iinclude tools/pair_lab.cpp -Lcqa-crct_amd/crct -lcrct_hip \
-//         -Wl,-rpath,'$ORIGIN/../cqa-crct_amd/crct' -o tools/pair_lab.bin ;  CRCT_GEMM_GROUP=12 ./tools/pair_lab.bin
+//         -Wl,-rpath,'$ORIGIN/../cqa-crct_amd/crct' -o tools/pair_lab.bin ;  ./tools/pair_lab.bin
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
