@@ -586,6 +586,11 @@ class CrctModel(nn.Module):
             raise ValueError("'areas' belongs to the figure_qa / dvqa image embeddings (vilbert.py:1463-1464, 1488-1489)")
         if gt_reg is None:
             raise ValueError("gt_reg=[R, kind] is required (vilbert.py:1586)")
+        if self.training and float(self.params.get("mask_prob_img", 0.0) or 0.0) > 0.0:
+            # vilbert.py:1491-1493 zeroes whole visual elements in training when mask_prob_img > 0; this step has no such masking, and
+            # training on without it would train a different model than the one asked for
+            raise RuntimeError("params['mask_prob_img'] = %g: masking of visual elements in training (vilbert.py:1491-1493) is not "
+                               "supported; set it to 0" % float(self.params["mask_prob_img"]))
         if image_target is None:
             raise ValueError("image_target is required by the image embeddings (vilbert.py:1479)")
         R, kind = gt_reg[0], gt_reg[1]

@@ -213,10 +213,12 @@ def colsum(x, M, N, ld=None, out=None, accumulate=False):
 
 
 def softmax_rows(x):
+    """Row softmax of fp32 or bf16 features [M, F] -> bf16 (the step's F.softmax(image_feat), either input type)."""
     lib = L.load()
     M, F = x.shape
     y = torch.empty(M, F, device=x.device, dtype=torch.bfloat16)
-    L.check(lib.crct_softmax_rows_f32_bf16(L.ptr(_chk(x, torch.float32)), L.ptr(y), M, F, L.current_stream()), "softmax_rows")
+    fn = lib.crct_softmax_rows_bf16_bf16 if x.dtype == torch.bfloat16 else lib.crct_softmax_rows_f32_bf16
+    L.check(fn(L.ptr(_chk(x, x.dtype if x.dtype == torch.bfloat16 else torch.float32)), L.ptr(y), M, F, L.current_stream()), "softmax_rows")
     return y
 
 

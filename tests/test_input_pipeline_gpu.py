@@ -57,21 +57,25 @@ def test_one_copy_per_batch_and_buffer_reuse():
 
 
 def test_training_from_host_batches_equals_resident_batches():
+    """... with fp32 and with bf16 features (bench.py's prefetch legs ship bf16 by default: --host-feat bf16)."""
     z, meta, cfg, params, batch = load_case("tiny_L1")
-    host = [{k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()} for _ in range(4)]
-    for i, b in enumerate(host):
-        b["R"] = b["R"] * (1.0 - 0.1 * i)
-    losses = []
-    for mode in ("resident", "prefetch"):
-        model, p = build_model(cfg, params, weights=z)
-        src = DevicePrefetcher(host, DEV) if mode == "prefetch" else [{k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in b.items()} for b in host]
-        cur = []
-        for b in src:
-            loss = step_forward(model, b, p)[0]
-            loss.backward()
-            cur.append(float(loss))
-        losses.append(cur)
-    assert np.allclose(losses[0], losses[1], rtol=0, atol=1e-6), losses
+    for feat in (torch.float32, torch.bfloat16):
+        host = [{k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()} for _ in range(4)]
+        for i, b in enumerate(host):
+            b["R"] = b["R"] * (1.0 - 0.1 * i)
+            b["image_feat"] = b["image_feat"].to(feat)
+        losses = []
+        for mode in ("resident", "prefetch"):
+            model, p = build_model(cfg, params, weights=z)
+            src = DevicePrefetcher(host, DEV) if mode == "prefetch" else [{k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in b.items()} for b in host]
+            cur = []
+            for b in src:
+                assert b["image_feat"].dtype == feat
+                loss = step_forward(model, b, p)[0]
+                loss.backward()
+                cur.append(float(loss))
+            losses.append(cur)
+        assert np.allclose(losses[0], losses[1], rtol=0, atol=1e-6), (feat, losses)
 
 
 def test_refuses_cpu_and_single_slot():

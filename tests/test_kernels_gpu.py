@@ -346,6 +346,19 @@ def test_colsum_softmax_cast():
     assert rel_err(ops.softmax_rows(f), torch.softmax(f, -1)) < 1e-2
     f2 = rand(15, 32, seed=4) * 5
     assert rel_err(ops.softmax_rows(f2), torch.softmax(f2, -1)) < 1e-2
+    # both input types element by element against fp64 (F.softmax(image_feat), vilbert.py:1476; bf16 features: bench.py --host-feat bf16):
+    # 13 rows (not a multiple of 4) of which one sits at +80 (exp overflows fp32 without the max shift) and one is constant
+    for F in (4, 260, 1024, 2048):
+        f = rand(13, F, scale=3.0, seed=F)
+        f[3] += 80.0
+        f[7] = 0.25
+        fb = bf(f)                                             # bf16 features, and the same values in fp32
+        y32, y16 = ops.softmax_rows(fb.float()), ops.softmax_rows(fb)
+        assert torch.equal(y32, y16), F                        # the same fp32 math on the same values
+        ref = torch.softmax(fb.double().cpu(), -1)
+        _assert_within_bf16_step(y16, ref, ref, "softmax F=%d" % F)
+        ref = torch.softmax(f.double().cpu(), -1)
+        _assert_within_bf16_step(ops.softmax_rows(f), ref, ref, "fp32 softmax F=%d" % F)
     w = rand(100003, seed=5)
     assert torch.equal(ops.cast_bf16(w), w.to(torch.bfloat16))
 
@@ -824,77 +837,419 @@ def test_fp8_quantisers_and_layernorm_copy():
     assert float(am2.max()) == float(y.float().abs().max())
 
 
-# ------------------------------------------------------------------------------------------- word-gradient scan
-@pytest.mark.parametrize("B,T", [(80, 20), (7, 9), (64, 40), (80, 124)])
+# ------------------------------------------------------------------------------------------- embeddings against fp64
+# The kernels at the front of the step (rowops.hip: crct_embed_text_* / crct_embed_image_*) against plain fp64 restatements on the CPU.
+# Forward: the saved pre-norm sum, y and the row statistics element by element.  Backward: every gradient output per element against
+# fp64 autograd fed the kernel's own saved sum (the LayerNorm backward is taken where the kernel takes it), bound
+#   |got - ref| <= 1e-4 * sum|contributions| + 1e-6
+# where the sum runs over the pre-filled value and every per-token term that reaches the element (a per-tensor norm would hide one
+# missing row of one id).
+
+def _bf16_step(x):
+    """Spacing of the bf16 numbers at |x| (fp64): 2^(exponent - 7); the smallest normal's below it."""
+    a = x.double().abs().clamp_min(2.0 ** -126)
+    return torch.exp2(torch.floor(torch.log2(a)) - 7)
+
+
+def _assert_within_bf16_step(got, ref, scale, what):
+    """|got - ref| <= one bf16 step at max(|got|, |ref|) + 2^-20 * scale.  scale = the magnitude of the fp32 terms the kernel combined before
+    rounding to bf16: their own fp32 roundings may move a result that sits at a rounding boundary, or one that cancels, by that much
+    (2^-20 is 1/8192 of a bf16 step at the same magnitude)."""
+    got, ref = got.double().cpu(), ref.double().cpu()
+    err = (got - ref).abs()
+    tol = _bf16_step(torch.maximum(got.abs(), ref.abs())) + 2.0 ** -20 * scale
+    bad = err > tol
+    assert not bool(bad.any()), "%s: %d elements beyond one bf16 step, first at %s (got %r, fp64 %r)" % (
+        what, int(bad.sum()), tuple(int(i) for i in bad.nonzero()[0]), float(got[bad][0]), float(ref[bad][0]))
+
+
+def _assert_sums(got, ref, mag, what):
+    """Per element: |got - ref| <= 1e-4 * mag + 1e-6, mag = sum of |contributions| (the pre-filled value included)."""
+    err = (got.double().cpu() - ref).abs()
+    bad = err > 1e-4 * mag + 1e-6
+    assert not bool(bad.any()), "%s: %d elements off, first at %s (got %r, fp64 %r, sum|terms| %r)" % (
+        what, int(bad.sum()), tuple(int(i) for i in bad.nonzero()[0]), float(got.double().cpu()[bad][0]), float(ref[bad][0]),
+        float(mag[bad][0]))
+
+
+def _ln_stats64(x):
+    mean = x.mean(-1)
+    var = ((x - mean[:, None]) ** 2).mean(-1)
+    return mean, var.sqrt(), 1.0 / torch.sqrt(var + O.LN_EPS)
+
+
+def _check_ln_forward(sum_b, y, mean, rstd, gamma, beta, p, site, seed, what):
+    """mean / rstd against fp64 statistics of the saved (bf16) sum, y against fp64 LayerNorm of it (kept elements / (1 - p) under
+    dropout, dropped ones exactly 0) -- and, under dropout, against crct_layernorm_fwd of the saved sum with the same (site, seed)."""
+    x = sum_b.double().cpu()
+    m64, sd64, r64 = _ln_stats64(x)
+    assert float(((mean.double().cpu() - m64).abs() / (m64.abs() + sd64)).max()) <= 1e-5, what + ": mean"
+    assert float(((rstd.double().cpu() - r64).abs() / r64).max()) <= 1e-5, what + ": rstd"
+    g, b = gamma.double().cpu(), beta.double().cpu()
+    xn = (x - m64[:, None]) * r64[:, None]
+    ref = g * xn + b
+    scale = (g * xn).abs() + b.abs()
+    yc = y.cpu()
+    if p == 0.0:
+        _assert_within_bf16_step(yc, ref, scale, what + ": y")
+        return torch.ones_like(ref)
+    # The embedding kernels and crct_layernorm_fwd both normalise through row_stats / row_normalize on the same bf16 values of the same row
+    # index with the same (site, seed): the same mask and the same bits.
+    y_ln, _, _ = ops.layernorm_fwd(sum_b, gamma, beta, p_drop=p, site=site, seed=seed)
+    keep = yc != 0
+    assert torch.equal(keep, y_ln.cpu() != 0), what + ": dropout mask differs from crct_layernorm_fwd's"
+    if keep.numel() > 20000:
+        assert abs(float(keep.double().mean()) - (1 - p)) < 0.02, what + ": dropout rate"
+    _assert_within_bf16_step(yc[keep], ref[keep] / (1 - p), scale[keep] / (1 - p), what + ": kept y")
+    assert torch.equal(y, y_ln), what + ": y differs from crct_layernorm_fwd of the saved sum"
+    return keep.double() / (1 - p)
+
+
+def _ln_backward64(sum_b, dy, keep_scale, gamma):
+    """fp64 autograd of LayerNorm at the saved sum, fed dy * keep / (1 - p): (d_sum, d_gamma, d_beta, |dy'| * |xhat|, |dy'|)."""
+    x = sum_b.double().cpu().requires_grad_(True)
+    g = gamma.double().cpu().requires_grad_(True)
+    b = torch.zeros_like(g).requires_grad_(True)
+    dyv = dy.double().cpu() * keep_scale
+    O.layer_norm(x, g, b).backward(dyv)
+    m64, _, r64 = _ln_stats64(x.detach())
+    xn = (x.detach() - m64[:, None]) * r64[:, None]
+    return x.grad, g.grad, b.grad, (dyv * xn).abs().sum(0), dyv.abs().sum(0)
+
+
+_TEXT_V, _TEXT_NPOS, _TEXT_NTYPES = 4099, 512, 5
+# (B, T) -> (H, dropout p): configs[1]; the test's original small shapes; plotqa-real (word scan above 64 KiB of LDS); one token; the NCH 1
+# and NCH 4 row widths; positions up to 511; 16 384 rows > GATHER_MAX_ROWS (every table sum through float atomics)
+_TEXT_CASES = {(80, 20): (768, 0.1), (7, 9): (768, 0.0), (64, 40): (768, 0.0), (80, 124): (768, 0.1), (1, 1): (768, 0.0),
+               (3, 7): (64, 0.1), (2, 9): (2048, 0.1), (1, 512): (768, 0.0), (32, 512): (768, 0.1)}
+_GATHER_MAX_ROWS = 15360      # rowops.hip: above it the table sums fall back to float atomics
+
+
+def _text_batch(B, T, seed):
+    """ids / segments / loc crafted for the gates and the word-gradient scan's edge cases: [PAD]-like id 0 on half of all rows (hundreds of
+    matches: the heavy path), [CLS]-like id 1 once per batch row, four heavy ids (9 / 15 / 16 / 17 matches) whose first rows fill one 4-row
+    workgroup, an id whose matches straddle a 64-row and a 256-row window (light, and heavy), ids with exactly 1, 2, 3, 8, 9, 11, 15, 16 and
+    17 matches, id V - 1, an id that first occurs in the last row; segments -1 / 0 / 1 / 2.. n_types - 1 with batch rows without a
+    question / answer token and rows whose first one sits mid-row; all-zero loc rows, rows with one non-zero coordinate, rows whose
+    coordinates sum to 0."""
+    M, V = B * T, _TEXT_V
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(24, V - 1, (M,), generator=g)            # filler: ids 24 .. V-2, one to a few matches each
+    ids.view(B, T)[:, T // 2:] = 0
+    ids.view(B, T)[:, 0] = 1
+    free = [r for r in range(M) if 0 < r % T < T // 2]
+    taken = set()
+
+    def put(i, rows):
+        for r in rows:
+            assert r not in taken
+            taken.add(r)
+            ids[r] = i
+
+    def rest(after=-1):
+        return [r for r in free if r not in taken and r > after]
+
+    # four heavy ids whose first rows are the four rows of one workgroup
+    grp = next((r for r in free if r % 4 == 0 and all(r + k in free for k in range(4))), None)
+    if grp is not None and len(rest(grp + 3)) >= 9 + 15 + 16 + 17 - 4:
+        for k, n in enumerate((9, 15, 16, 17)):
+            later = rest(grp + 3)
+            pick = sorted(later[int(j)] for j in torch.randperm(len(later), generator=g)[:n - 1])
+            put(2 + k, [grp + k] + pick)
+    # matches across the 64-row and the 256-row windows of the scans: first row just below 64, then 64 and beyond, then beyond the first
+    # 256-row window of the indexed scan ((r + 1) & ~63 .. + 255)
+    lo = [r for r in rest() if r < 64]
+    if lo and len(rest(lo[-1] + 256)) >= 14:
+        r0 = lo[-1]
+        a = rest(r0)
+        b = rest(((r0 + 1) & ~63) + 255)
+        put(6, [r0, a[0], a[1], b[0], b[1]])                       # 5 matches: the light path
+        lo = [r for r in rest() if r < 64]
+        r1 = lo[-1]
+        far = rest(((r1 + 1) & ~63) + 255)
+        near = rest(r1)[:3]
+        put(7, [r1] + near + far[:8])                               # 12 matches: the heavy path
+    for i, n in zip(range(8, 17), (1, 2, 3, 8, 9, 11, 15, 16, 17)):
+        avail = rest()
+        if len(avail) < n + 2:
+            break
+        put(i, sorted(avail[int(j)] for j in torch.randperm(len(avail), generator=g)[:n]))
+    avail = rest()
+    if len(avail) >= 2:
+        put(V - 1, avail[-2:])
+    if M > 1:
+        ids[M - 1] = 23                                              # first (and only) occurrence in the last row
+    else:
+        ids[0] = V - 1
+    # segments: row kind (b + 2) % 4 -- 2, 3: a QA token at t = 0 and at t = T - 1 (positions up to T - 1); 0: no QA token; 1: the first
+    # QA token at T // 3
+    segs = torch.randint(-1, _TEXT_NTYPES, (B, T), generator=g)
+    for b in range(B):
+        kind = (b + 2) % 4
+        row = segs[b]
+        no_qa = torch.tensor([0, 2, 3, 4])[torch.randint(0, 4, (T,), generator=g)]
+        if kind == 0:
+            row.copy_(no_qa)
+        elif kind == 1:
+            row[:T // 3] = no_qa[:T // 3]
+            row[T // 3] = -1
+        else:
+            row[0], row[T - 1] = 1, -1 if T > 1 else 1
+    loc = torch.rand(M, 4, generator=g) * 2 - 1
+    r = torch.arange(M)
+    loc[r % 5 == 0] = 0.0
+    one = r % 5 == 1
+    keepc = torch.nn.functional.one_hot((r // 5) % 4, 4).bool()
+    loc[one] = torch.where(keepc[one], loc[one], torch.zeros(()))
+    zs = r % 7 == 3
+    loc[zs] = torch.tensor([0.7, -0.7, 0.0, 0.0])                  # sums to 0: the gate is on |loc|_1
+    return ids.view(B, T), segs, loc.view(B, T, 4)
+
+
+def _text_terms(tab, ids, segs, loc):
+    """vilbert.py:320-354 in fp64 (oracle.embed_text without its LayerNorm and dropout): the pre-norm sum as a function of the tables."""
+    B, T = ids.shape
+    not_qa = (segs != -1) & (segs != 1)
+    pos = torch.arange(T).unsqueeze(0).expand(B, T).clone()
+    pos[not_qa] = T
+    pos = pos - pos.min(dim=-1)[0].unsqueeze(1)
+    pos[not_qa] = 0
+    tt = segs.clone()
+    tt[tt == -1] = 0
+    loc_e = (loc @ tab["w_loc"].t() + tab["b_loc"]) * (loc.abs().sum(-1) != 0).unsqueeze(-1)
+    return (tab["word"][ids] + tab["pos"][pos] * (~not_qa).unsqueeze(-1) + tab["type"][tt] * (segs != 0).unsqueeze(-1)
+            + loc_e).reshape(B * T, -1)
+
+
+@pytest.mark.parametrize("B,T", list(_TEXT_CASES))
 def test_word_gradient_scan_matches_the_atomic_scatter_and_is_reproducible(B, T, gemm_path):
-    """crct_embed_text_bwd's word_embeddings gradient (index_add of the token-row gradients, vilbert.py:300 has no padding_idx, so
-    [PAD] collects every padded position): the fixed-order scan -- light ids by one wave, heavy ids shared by the workgroup --
-    against the same launcher's float-atomics fall-back (rows_scratch = NULL), and bit-identical when repeated."""
+    """crct_embed_text_fwd / _bwd (BertEmbeddingLocation.forward, vilbert.py:320-358) against fp64, in every form of the backward: indexed
+    (the step engine's call), the scan (no index), the two-launch test form and the float-atomics fall-back (rows_scratch = NULL).  The
+    word_embeddings gradient is the index_add of the token-row gradients (vilbert.py:300 has no padding_idx, so [PAD] collects every padded
+    position); the fixed-order forms -- light ids by one wave, heavy ids shared by the workgroup -- give the same bits as each other and when
+    repeated, and the float atomics the same sums to rounding."""
     # no GEMM here: the test runs under both settings of the GEMM-path switch (gemm_path), which must not reach these kernels
     lib = L.load()
-    H, V, n_pos, n_types = 768, 500, 64, 2
+    H, p = _TEXT_CASES[(B, T)]
+    V, n_pos, n_types = _TEXT_V, _TEXT_NPOS, _TEXT_NTYPES
     M = B * T
-    g = torch.Generator(device="cpu").manual_seed(B * 100 + T)
-    ids = torch.randint(3, V, (B, T), generator=g)
-    ids[:, 0] = 1                                          # [CLS]-like: B matches
-    ids[:, T // 2:] = 0                                    # [PAD]-like: half of all rows -> the heavy path
-    ids[0, 1:4] = 2                                        # 3 matches -> the light path with repeats
-    ids = ids.to(DEV)
-    segs = torch.randint(0, n_types, (B, T), generator=g).to(DEV)
-    loc = torch.rand(B, T, 4, generator=g).to(DEV)
-    dy, saved = bf(rand(M, H, seed=1)), bf(rand(M, H, seed=2))
-    mean, rstd = rand(M, seed=3), rand(M, seed=4).abs() + 0.5
-    gamma = rand(H, seed=5)
-    stream = torch.cuda.current_stream().cuda_stream
+    site, seed = 5, 0x5EED + B
+    ids_c, segs_c, loc_c = _text_batch(B, T, seed=B * 100 + T)
+    ids, segs, loc = ids_c.to(DEV), segs_c.to(DEV), loc_c.contiguous().to(DEV)
+    tab = dict(word=rand(V, H, scale=0.5, seed=11), pos=rand(n_pos, H, scale=0.5, seed=12), type=rand(n_types, H, scale=0.5, seed=13),
+               w_loc=rand(H, 4, scale=0.5, seed=14), b_loc=rand(H, scale=0.5, seed=15))
+    gamma, beta = 1 + 0.1 * rand(H, seed=16), 0.1 * rand(H, seed=17)
+    stream = L.current_stream()
+    thr, sc, st = ops._drop(p, site)
+
+    # forward
+    sum_b, y = (torch.empty(M, H, device=DEV, dtype=torch.bfloat16) for _ in range(2))
+    mean, rstd = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
+    L.check(lib.crct_embed_text_fwd(ids.data_ptr(), segs.data_ptr(), loc.data_ptr(), tab["word"].data_ptr(), tab["pos"].data_ptr(),
+                                    tab["type"].data_ptr(), tab["w_loc"].data_ptr(), tab["b_loc"].data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                    sum_b.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), B, T, H, n_pos, 1e-12, thr, sc, st, seed,
+                                    stream), "embed_text_fwd")
+    torch.cuda.synchronize()
+    t64 = {k: v.double().cpu().requires_grad_(True) for k, v in tab.items()}
+    ids64, segs64, loc64 = ids_c, segs_c, loc_c.double()
+    s64 = _text_terms(t64, ids64, segs64, loc64)
+    s_abs = _text_terms({k: v.detach().abs() for k, v in t64.items()}, ids64, segs64, loc64.abs())
+    # the restatement is the oracle's embedding up to its LayerNorm
+    import types
+    ref_e = O.embed_text({"bert.embeddings." + k: v.detach() for k, v in dict(
+        [("word_embeddings.weight", t64["word"]), ("position_embeddings.weight", t64["pos"]), ("plotqa_type_embeddings.weight", t64["type"]),
+         ("txt_location_embeddings.weight", t64["w_loc"]), ("txt_location_embeddings.bias", t64["b_loc"]),
+         ("LayerNorm.weight", gamma.double().cpu()), ("LayerNorm.bias", beta.double().cpu())]).items()},
+        types.SimpleNamespace(hidden_dropout_prob=p), ids64, segs64, loc64, training=False)
+    assert float((ref_e.reshape(M, H) - O.layer_norm(s64.detach(), gamma.double().cpu(), beta.double().cpu())).abs().max()) < 1e-9
+    _assert_within_bf16_step(sum_b, s64.detach(), s_abs, "text sum")
+    keep_scale = _check_ln_forward(sum_b, y, mean, rstd, gamma, beta, p, site, seed, "text")
+
+    # fp64 backward: LayerNorm at the saved sum, then the (linear) restatement's table gradients
+    dy = bf(rand(M, H, seed=1))
+    ds, dg64, db64, dg_mag, db_mag = _ln_backward64(sum_b, dy, keep_scale, gamma)
+    names = ("word", "pos", "type", "w_loc", "b_loc")
+    refs = torch.autograd.grad(s64, [t64[k] for k in names], ds)
+    # sum |terms|: the same linear map applied to |d_sum| with |loc| (every coefficient then non-negative)
+    t_abs = {k: v.detach().abs().requires_grad_(True) for k, v in t64.items()}
+    mags = torch.autograd.grad(_text_terms(t_abs, ids64, segs64, loc64.abs()), [t_abs[k] for k in names], ds.abs())
+    shapes = dict(word=(V, H), pos=(n_pos, H), type=(n_types, H), w_loc=(H, 4), b_loc=(H,), gamma=(H,), beta=(H,))
+    pre = {k: rand(*s, seed=40 + i) for i, (k, s) in enumerate(shapes.items())}      # outputs are accumulated into
+    ref = {k: pre[k].double().cpu() + r for k, r in zip(names, refs)}
+    ref.update(gamma=pre["gamma"].double().cpu() + dg64, beta=pre["beta"].double().cpu() + db64)
+    mag = {k: pre[k].double().cpu().abs() + m for k, m in zip(names, mags)}
+    mag.update(gamma=pre["gamma"].double().cpu().abs() + dg_mag, beta=pre["beta"].double().cpu().abs() + db_mag)
+    touched = {k: m.cpu() != pre[k].double().cpu().abs() for k, m in mag.items()}
 
     index = torch.zeros(2 * V, dtype=torch.int32, device=DEV)
+    nblk = lib.crct_layernorm_bwd_blocks(M)
 
-    def run(deterministic, indexed=False):
-        d_word = torch.zeros(V, H, device=DEV)
-        d_pos, d_type = torch.zeros(n_pos, H, device=DEV), torch.zeros(n_types, H, device=DEV)
-        d_wloc, d_bloc = torch.zeros(H, 4, device=DEV), torch.zeros(H, device=DEV)
-        d_g, d_b = torch.zeros(H, device=DEV), torch.zeros(H, device=DEV)
-        partials = torch.zeros(10 * 4 * 256 * H, device=DEV)
-        rows = torch.zeros(M, H, device=DEV)
-        idx = torch.zeros(2 * M, dtype=torch.int32, device=DEV)
-        if indexed:      # crct_embed_text_bwd_indexed: first / last row per id left by the row kernel, no scan of all ids per row
-            rc = lib.crct_embed_text_bwd_indexed(dy.data_ptr(), saved.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ids.data_ptr(),
-                                                 segs.data_ptr(), loc.data_ptr(), gamma.data_ptr(), d_word.data_ptr(), d_pos.data_ptr(),
-                                                 d_type.data_ptr(), d_wloc.data_ptr(), d_bloc.data_ptr(), d_g.data_ptr(), d_b.data_ptr(),
-                                                 partials.data_ptr(), B, T, H, n_pos, 0, 1.0, 0, 0, rows.data_ptr(), idx.data_ptr(), n_types,
-                                                 index.data_ptr(), V, stream)
-        else:
-            rc = lib.crct_embed_text_bwd(dy.data_ptr(), saved.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ids.data_ptr(),
-                                         segs.data_ptr(), loc.data_ptr(), gamma.data_ptr(), d_word.data_ptr(), d_pos.data_ptr(),
-                                         d_type.data_ptr(), d_wloc.data_ptr(), d_bloc.data_ptr(), d_g.data_ptr(), d_b.data_ptr(),
-                                         partials.data_ptr(), B, T, H, n_pos, 0, 1.0, 0, 0,
-                                         rows.data_ptr() if deterministic else None, idx.data_ptr(), n_types, stream)
-        L.check(rc, "embed_text_bwd")
+    def run(mode):
+        out = {k: v.clone() for k, v in pre.items()}
+        partials = torch.empty(9 * 4 * nblk * H, device=DEV)
+        rows = torch.empty(M, H, device=DEV) if mode != "atomic" else None
+        idx = torch.empty(2 * M, dtype=torch.int32, device=DEV)
+        a = [dy.data_ptr(), sum_b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ids.data_ptr(), segs.data_ptr(), loc.data_ptr(),
+             gamma.data_ptr()] + [out[k].data_ptr() for k in ("word", "pos", "type", "w_loc", "b_loc", "gamma", "beta")] + [
+            partials.data_ptr(), B, T, H, n_pos, thr, sc, st, seed, L.ptr(rows), idx.data_ptr(), n_types]
+        if mode == "split":
+            lib.crct_embed_scatter_split(1)
+        try:
+            if mode == "indexed":      # crct_embed_text_bwd_indexed: first / last row per id left by the row kernel, no scan of all ids per row
+                rc = lib.crct_embed_text_bwd_indexed(*a, index.data_ptr(), V, stream)
+            else:
+                rc = lib.crct_embed_text_bwd(*a, stream)
+        finally:
+            lib.crct_embed_scatter_split(0)
+        L.check(rc, "embed_text_bwd " + mode)
         torch.cuda.synchronize()
-        return d_word, d_pos, d_type
+        if mode == "indexed":
+            assert int(index.abs().max()) == 0      # the index is all zero again after every call
+        return {k: v.cpu() for k, v in out.items()}
 
-    w_atomic, p_atomic, t_atomic = run(False)
-    w1, p1, t1 = run(True)
-    w2, p2, t2 = run(True)
-    assert torch.equal(w1, w2) and torch.equal(p1, p2) and torch.equal(t1, t2)
-    # the position / type sums and the word scatter leave as ONE launch; as two launches (test hook) they give the same bits
-    lib.crct_embed_scatter_split(1)
-    try:
-        w3, p3, t3 = run(True)
-    finally:
-        lib.crct_embed_scatter_split(0)
-    assert torch.equal(w1, w3) and torch.equal(p1, p3) and torch.equal(t1, t3)
-    # the indexed form (what the step engine calls): same owner, same order, same bits -- twice, and the index is all zero again each time
-    for _ in range(2):
-        w4, p4, t4 = run(True, indexed=True)
-        assert torch.equal(w1, w4) and torch.equal(p1, p4) and torch.equal(t1, t4)
-        assert int(index.abs().max()) == 0
-    assert float(w1[0].abs().max()) > 0 and float(w1[V - 1].abs().max()) >= 0
-    for a, b in ((w1, w_atomic), (p1, p_atomic), (t1, t_atomic)):
-        assert float((a - b).abs().max()) <= 2e-5 * float(b.abs().max()) + 1e-6
-    untouched = torch.ones(V, dtype=torch.bool, device=DEV)
-    untouched[ids.flatten()] = False
-    assert not bool(untouched.any()) or float(w1[untouched].abs().max()) == 0.0
+    got = {m: run(m) for m in ("indexed", "scan", "split", "atomic")}
+    for m, o in got.items():
+        for k in shapes:
+            _assert_sums(o[k], ref[k], mag[k], "%s d_%s" % (m, k))
+            untouched = ~touched[k]
+            assert torch.equal(o[k][untouched], pre[k].cpu()[untouched]), "%s d_%s: a row no token reaches changed" % (m, k)
+    w1, p1, t1 = (got["scan"][k] for k in ("word", "pos", "type"))
+    assert float((w1[0] - pre["word"][0].cpu()).abs().max()) > 0 or M == 1
+    if M <= _GATHER_MAX_ROWS:
+        # the fixed-order forms: the same bits as each other (one launch or two, index or scan) and when repeated -- the index twice
+        again = run("scan")
+        for k in shapes:
+            assert torch.equal(got["scan"][k], again[k]), k
+            assert torch.equal(got["scan"][k], got["split"][k]), k
+            assert torch.equal(got["scan"][k], got["indexed"][k]), k
+        again = run("indexed")
+        for k in shapes:
+            assert torch.equal(got["indexed"][k], again[k]), k
+    # ... and the float atomics: the same sums up to their arrival-order rounding
+    for k in ("word", "pos", "type"):
+        a, b = got["scan"][k], got["atomic"][k]
+        assert float((a - b).abs().max()) <= 2e-5 * float(b.abs().max()) + 1e-6, k
+
+
+_IMG_NCOLOR = 229      # categories + 1 (PlotQA: 228)
+# (M, H, dropout p): configs[1] (80 x 36), plotqa-real (80 x 44), configs[3] (64 x 100), one element, NCH 1, NCH 4, 16 000 rows >
+# GATHER_MAX_ROWS (the colour sums through float atomics)
+_IMG_CASES = [(2880, 1024, 0.1), (3520, 1024, 0.0), (6400, 1024, 0.1), (1, 1024, 0.0), (7, 64, 0.1), (5, 2048, 0.0), (16000, 1024, 0.1)]
+
+
+@pytest.mark.parametrize("M,H,p", _IMG_CASES)
+def test_image_embedding_against_fp64(M, H, p, gemm_path):
+    """crct_embed_image_fwd / _bwd (BertImageEmbeddings.forward, dataset 'plotqa', vilbert.py:1474-1496) against fp64: the saved sum, y and
+    the row statistics; d_sum within one bf16 rounding; the colour-table, loc-Linear, image-Linear-bias and LayerNorm gradients per element,
+    accumulated onto pre-filled outputs, through the fixed-order gather and through the float atomics."""
+    lib = L.load()
+    n_color, site, seed = _IMG_NCOLOR, 9, 0xC0FFEE + M
+    g = torch.Generator().manual_seed(M + H)
+    target = torch.randint(0, n_color, (M,), generator=g)
+    target[: M // 3] = 17                                            # one heavily repeated colour
+    target[-1] = 0
+    if M > 1:
+        target[M // 2] = n_color - 1                                 # 0 and `categories`, the last row of the table
+    loc = torch.rand(M, 4, generator=g)
+    img = bf(rand(M, H, scale=0.5, seed=21))                         # new_image_embeddings(softmax(feat)) as the GEMM leaves it (bf16)
+    tab = dict(color=rand(n_color, H, scale=0.5, seed=22), w_loc=rand(H, 4, scale=0.5, seed=23), b_loc=rand(H, scale=0.5, seed=24))
+    gamma, beta = 1 + 0.1 * rand(H, seed=25), 0.1 * rand(H, seed=26)
+    target_d, loc_d = target.to(DEV), loc.to(DEV)
+    stream = L.current_stream()
+    thr, sc, st = ops._drop(p, site)
+    sum_b, y = (torch.empty(M, H, device=DEV, dtype=torch.bfloat16) for _ in range(2))
+    mean, rstd = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
+    L.check(lib.crct_embed_image_fwd(img.data_ptr(), loc_d.data_ptr(), target_d.data_ptr(), tab["w_loc"].data_ptr(), tab["b_loc"].data_ptr(),
+                                     tab["color"].data_ptr(), gamma.data_ptr(), beta.data_ptr(), sum_b.data_ptr(), y.data_ptr(), mean.data_ptr(),
+                                     rstd.data_ptr(), M, H, 1e-12, thr, sc, st, seed, stream), "embed_image_fwd")
+    torch.cuda.synchronize()
+    # vilbert.py:1478-1486 in fp64 (oracle.embed_image after its feature Linear, before its LayerNorm)
+    t64 = {k: v.double().cpu().requires_grad_(True) for k, v in tab.items()}
+    img64, loc64 = img.double().cpu(), loc.double()
+    s64 = img64 + loc64 @ t64["w_loc"].t() + t64["b_loc"] + t64["color"][target]
+    s_abs = img64.abs() + loc64 @ t64["w_loc"].detach().abs().t() + t64["b_loc"].detach().abs() + t64["color"].detach().abs()[target]
+    _assert_within_bf16_step(sum_b, s64.detach(), s_abs, "image sum")
+    keep_scale = _check_ln_forward(sum_b, y, mean, rstd, gamma, beta, p, site, seed, "image")
+
+    dy = bf(rand(M, H, seed=2))
+    ds, dg64, db64, dg_mag, db_mag = _ln_backward64(sum_b, dy, keep_scale, gamma)
+    names = ("color", "w_loc", "b_loc")
+    refs = torch.autograd.grad(s64, [t64[k] for k in names], ds)
+    t_abs = {k: v.detach().abs().requires_grad_(True) for k, v in t64.items()}
+    mags = torch.autograd.grad(loc64 @ t_abs["w_loc"].t() + t_abs["b_loc"] + t_abs["color"][target], [t_abs[k] for k in names], ds.abs())
+    shapes = dict(color=(n_color, H), w_loc=(H, 4), b_loc=(H,), b_img=(H,), gamma=(H,), beta=(H,))
+    pre = {k: rand(*s, seed=60 + i) for i, (k, s) in enumerate(shapes.items())}
+    ref = {k: pre[k].double().cpu() + r for k, r in zip(names, refs)}
+    mag = {k: pre[k].double().cpu().abs() + m for k, m in zip(names, mags)}
+    ref.update(b_img=pre["b_img"].double().cpu() + ds.sum(0), gamma=pre["gamma"].double().cpu() + dg64, beta=pre["beta"].double().cpu() + db64)
+    mag.update(b_img=pre["b_img"].double().cpu().abs() + ds.abs().sum(0), gamma=pre["gamma"].double().cpu().abs() + dg_mag,
+               beta=pre["beta"].double().cpu().abs() + db_mag)
+    # d_sum: the fp32 row gradient rounded to bf16 once; its fp32 terms are rstd * (|g dy'| + mean|g dy'| + |xhat| mean|g dy' xhat|) -- the two
+    # row means are fp32 sums over H terms, whose rounding goes with the terms' magnitude, not the mean's (a dropped element's d_sum is
+    # nothing but those means)
+    x = sum_b.double().cpu()
+    m64, _, r64 = _ln_stats64(x)
+    xn = (x - m64[:, None]) * r64[:, None]
+    gd = dy.double().cpu() * keep_scale * gamma.double().cpu()
+    ds_scale = r64[:, None] * (gd.abs() + gd.abs().mean(-1, keepdim=True) + xn.abs() * (gd * xn).abs().mean(-1, keepdim=True))
+    nblk = lib.crct_layernorm_bwd_blocks(M)
+
+    def run(mode):
+        out = {k: v.clone() for k, v in pre.items()}
+        d_sum = torch.empty(M, H, device=DEV, dtype=torch.bfloat16)
+        partials = torch.empty(7 * 4 * nblk * H, device=DEV)
+        rows = torch.empty(M, H, device=DEV) if mode == "gather" else None
+        idx = torch.empty(M, dtype=torch.int32, device=DEV)
+        L.check(lib.crct_embed_image_bwd(dy.data_ptr(), sum_b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), loc_d.data_ptr(), target_d.data_ptr(),
+                                         gamma.data_ptr(), d_sum.data_ptr(), out["color"].data_ptr(), out["w_loc"].data_ptr(), out["b_loc"].data_ptr(),
+                                         out["b_img"].data_ptr(), out["gamma"].data_ptr(), out["beta"].data_ptr(), partials.data_ptr(), M, H,
+                                         thr, sc, st, seed, L.ptr(rows), idx.data_ptr(), n_color, stream), "embed_image_bwd " + mode)
+        torch.cuda.synchronize()
+        return d_sum.cpu(), {k: v.cpu() for k, v in out.items()}
+
+    res = {m: run(m) for m in ("gather", "atomic")}
+    used = torch.zeros(n_color, dtype=torch.bool)
+    used[target] = True
+    for m, (d_sum, o) in res.items():
+        _assert_within_bf16_step(d_sum, ds, ds_scale, "%s d_sum" % m)
+        for k in shapes:
+            _assert_sums(o[k], ref[k], mag[k], "%s d_%s" % (m, k))
+        assert torch.equal(o["color"][~used], pre["color"].cpu()[~used]), m
+    assert torch.equal(res["gather"][0], res["atomic"][0])
+    if M <= _GATHER_MAX_ROWS:
+        d2, o2 = run("gather")
+        assert torch.equal(d2, res["gather"][0]) and all(torch.equal(o2[k], res["gather"][1][k]) for k in shapes)
+
+
+# ------------------------------------------------------------------------------------------- key masks
+@pytest.mark.parametrize("B,T,V,S", [(5, 20, 9, 6), (3, 7, 40, 4), (80, 124, 44, 9), (1, 1, 1, 1)])
+def test_build_keymasks_against_the_oracle_masks(B, T, V, S):
+    """crct_build_keymasks against oracle.text_key_mask (encoder_decorator.py:118-120) and image_mask != 0: hist_len at 0 and at sep_stride - 1,
+    sep_indices + 1 at 0 and at or beyond T, image_mask values other than 0 and 1, T > V and V > T (the grid covers the larger one), and
+    each mask alone (NULL for the other).  Every output byte starts as 0xAB: each one must be written."""
+    lib = L.load()
+    g = torch.Generator().manual_seed(B * T + V)
+    sep = torch.randint(-1, T + 3, (B, S), generator=g)
+    hist = torch.randint(0, S, (B,), generator=g)
+    hist[0] = 0
+    hist[-1] = S - 1
+    sep[0, 0] = -1                                                   # sep + 1 == 0: no text key
+    if B > 1:
+        sep[1, hist[1]] = T - 1                                      # sep + 1 == T: every key
+        sep[-1, S - 1] = T + 2                                       # beyond T
+    imask = torch.randint(-2, 4, (B, V), generator=g)
+    imask[0, 0] = 7
+    sd, hd, md = sep.to(DEV), hist.to(DEV), imask.to(DEV)
+    want_t = O.text_key_mask(sep, hist, T).to(torch.uint8)
+    want_v = (imask != 0).to(torch.uint8)
+    for with_t, with_v in ((True, True), (True, False), (False, True)):
+        kt = torch.full((B, T), 0xAB, dtype=torch.uint8, device=DEV)
+        kv = torch.full((B, V), 0xAB, dtype=torch.uint8, device=DEV)
+        L.check(lib.crct_build_keymasks(sd.data_ptr(), hd.data_ptr(), S, md.data_ptr(), kt.data_ptr() if with_t else None,
+                                        kv.data_ptr() if with_v else None, B, T, V, L.current_stream()), "build_keymasks")
+        torch.cuda.synchronize()
+        assert torch.equal(kt.cpu(), want_t if with_t else torch.full((B, T), 0xAB, dtype=torch.uint8))
+        assert torch.equal(kv.cpu(), want_v if with_v else torch.full((B, V), 0xAB, dtype=torch.uint8))
 
 
 # ------------------------------------------------------------------------------------------- grouped forward / dgrad pairs

@@ -334,6 +334,33 @@ def test_areas_embedding_against_autograd(H):
     assert float((o3["sum"].float() - ref3).abs().max()) <= 1e-2 * float(ref3.abs().max())
 
 
+@pytest.mark.parametrize("case", ["tiny_L1", "variant_tiny_dvqa_ce", "variant_tiny_dvqa", "variant_tiny_figureqa"])
+def test_mask_prob_img_is_refused_in_training(case):
+    """params['mask_prob_img'] > 0 zeroes whole visual elements in the reference's training forward (vilbert.py:1491-1493); this step
+    has no such masking, so a training forward with it is an error that names the option, on every dataset variant.  Evaluation
+    forwards (where the reference does not mask) and the value 0 are unaffected."""
+    if case.startswith("variant"):
+        z, meta, cfg, params, batch = load_variant(case)
+        model, params = variant_model(meta, cfg, params)
+    else:
+        z, meta, cfg, params, batch = load_case(case)
+        model, params = build_model(cfg, params, weights=z)
+    core = model.bert_pretrained
+    assert core.params is params
+    model.eval()
+    ev = step_forward(model, batch, params, evaluation=True)[4].clone()
+    model.train()
+    params["mask_prob_img"] = 0.15
+    with pytest.raises(RuntimeError, match="mask_prob_img"):
+        step_forward(model, batch, params)
+    model.eval()
+    assert torch.equal(step_forward(model, batch, params, evaluation=True)[4], ev)
+    model.train()
+    params["mask_prob_img"] = 0.0
+    out = step_forward(model, batch, params)
+    assert torch.isfinite(out[0])
+
+
 # ---------------------------------------------------------------- optimizer / checkpoint
 def test_adamw_leaves_areas_emp_alone_without_areas():
     z, meta, cfg, params, batch = load_variant("variant_tiny_dvqa_ce")
