@@ -54,6 +54,8 @@ extern "C" int crct_gemm_bf16(const CrctGemmArgs* a, crct_stream_t stream) {
   CRCT_REQUIRE(!a->ta || a->M % 8 == 0, "gemm: transposed A needs M %% 8 == 0 (M=%d)", a->M);
   CRCT_REQUIRE(!a->tb || a->N % 8 == 0, "gemm: transposed B needs N %% 8 == 0 (N=%d)", a->N);
   CRCT_REQUIRE(a->tile < 0 || crct_gemm_config_built(a->tile), "gemm: configuration %d is not built", a->tile);
+  // the staged epilogue stores a c_cached output without reading it, the register-staged one adds the old value: refused on both paths
+  CRCT_REQUIRE(!(a->c_cached && a->accumulate), "gemm: c_cached with accumulate is not supported (c_cached is a plain fp32 store)");
   CRCT_CHECK_HIP(crct_gemm_launch(*a, (hipStream_t)stream));
   return 0;
 }
@@ -67,6 +69,7 @@ static int gemm_grouped_checked(const CrctGemmArgs* a, int n, crct_stream_t stre
     CRCT_REQUIRE((a[i].ta && a[i].tb) || a[i].K % 8 == 0, "gemm_grouped: K of problem %d", i);
     CRCT_REQUIRE(!(a[i].ta && !a[i].tb) && (!a[i].ta || a[i].M % 8 == 0) && (!a[i].tb || a[i].N % 8 == 0), "gemm_grouped: layout of problem %d", i);
     CRCT_REQUIRE(a[i].tile < 0 || crct_gemm_config_built(a[i].tile), "gemm_grouped: configuration %d of problem %d is not built", a[i].tile, i);
+    CRCT_REQUIRE(!(a[i].c_cached && a[i].accumulate), "gemm_grouped: c_cached with accumulate is not supported (problem %d)", i);
   }
   if (target_wgs < 0) CRCT_CHECK_HIP(crct_gemm_launch_grouped(a, n, (hipStream_t)stream));
   else CRCT_CHECK_HIP(crct_gemm_launch_grouped_wgs(a, n, (hipStream_t)stream, target_wgs));

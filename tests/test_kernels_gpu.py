@@ -4,7 +4,9 @@ plain fp32 PyTorch / the CPU oracle on identical seeded inputs.
 Tolerances (stated per SURVEY.md 8c): kernels take bf16 operands and accumulate in fp32, so against an
 fp32 reference evaluated on the SAME bf16-rounded operands the only differences are accumulation
 order and the final bf16 rounding of the output: |err| <= 1e-2 * max|ref| for bf16 outputs,
-<= 2e-3 * max|ref| for fp32 outputs.
+<= 2e-3 * max|ref| for fp32 outputs.  That bound is normalised by the whole output and cannot see a local error: the sections
+"against fp64" below check per element -- the GEMMs bit for bit on exact operands (tests/gemm_ref.py), the row kernels within one
+rounding of fp64.
 """
 import ctypes as C
 import math
@@ -2077,3 +2079,592 @@ def test_head_dropout_mask_is_the_host_stream():
             dl = out["scratch"][:, :2].double()
             pre = out["prefill"]["d_w_cls"].double()
             _assert_sums(out["d_w_cls"], pre + grads["d_w_cls"], dl.abs().t() @ fd.abs() + pre.abs(), "d_w_cls")
+
+
+# ------------------------------------------------------------------------------------------- GEMM bit for bit against fp64
+# tests/gemm_ref.py: integer-valued operands scaled by powers of two, every entry non-zero, every partial sum below 2^24 (2^20 for
+# fp8) in units of the product's scale.  The fp32 accumulator of any tile, K order or split is then the fp64 product, so an fp32
+# output must equal the fp64 reference bit for bit and a bf16 output its round-to-nearest-even (ties included).  A dropped, doubled or
+# misplaced product, a ragged-tail store into a neighbour or an accumulator rounded on the way fails here however small it is next
+# to the largest output.  Every case also checks, through the launch log, which configuration (and split) actually ran, and every
+# output lives inside a larger buffer whose elements outside [M, N] must keep the sentinel.
+import gemm_ref as GR        # noqa: E402
+
+SENT = -1.5 * 2.0 ** 100      # exact in bf16 and fp32; no exact result comes near it
+GEMM_CFGS = (0, 3, 4, 9, 11, 12, 15, 50)
+
+
+def _logged(fn):
+    """fn() under crct_launch_log_enable: (its result, [(cfg, split_k, n_problems)] of every GEMM launch it made)."""
+    lib = L.load()
+    lib.crct_launch_log_enable(1)
+    try:
+        out = fn()
+    finally:
+        recs = []
+        for i in range(lib.crct_launch_log_count()):
+            r = L.LaunchRec()
+            lib.crct_launch_log_read(i, C.byref(r))
+            recs.append((r.cfg, r.split_k, r.n_problems))
+        lib.crct_launch_log_enable(0)
+    return out, recs
+
+
+def _ran_cfg(gemm_path, tile, M, N, K, ta=False):
+    """The configuration crct_gemm_launch runs for an explicit `tile`: the id itself on the LDS-DMA kernel, else 16 + the register-staged
+    kernel's tile (an id 0 - 3 is taken as that tile, 0 meaning 1; any other id, or -1, as crct_gemm_pick_tile's)."""
+    if gemm_path == "pipelined" and K % 64 == 0 and tile >= 0:
+        return tile
+    t = tile if 0 <= tile <= 3 else L.load().crct_gemm_pick_tile(M, N)
+    return 16 + (1 if t == 0 else t)
+
+
+def _canvas(M, N, ld, dtype, extra_rows=3, inner=None):
+    """[M + extra_rows][ld] buffer of the sentinel, [M][N] = inner (or the sentinel)."""
+    buf = torch.full((M + extra_rows, ld), SENT, device=DEV, dtype=dtype)
+    if inner is not None:
+        buf[:M, :N] = inner.to(dtype)
+    return buf
+
+
+def _assert_canary(buf, M, N, what):
+    mask = torch.ones(buf.shape, dtype=torch.bool, device=buf.device)
+    mask[:M, :N] = False
+    out = buf[mask].double()
+    bad = out != SENT
+    assert not bool(bad.any()), "%s: %d elements outside [%d, %d] of the output buffer were written" % (what, int(bad.sum()), M, N)
+
+
+def _assert_bits(got, ref, what):
+    g, r = got.double(), ref.double().to(got.device)
+    bad = g != r
+    if bool(bad.any()):
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError("%s: %d of %d elements differ from the exact result, first at %s (got %r, exact %r)"
+                             % (what, int(bad.sum()), bad.numel(), i, float(g[i]), float(r[i])))
+
+
+def _operands(layout, M, N, K, amax, bmax, seed, ea=-3, eb=-5, extra=0):
+    """(A, B, layout keywords, exact product [M][N] fp64): A, B bf16 on the GPU with leading dimensions larger than their rows."""
+    a, b = GR.operands(M, N, K, amax, bmax, seed, ea=ea, eb=eb, extra=extra)
+    a, b = a.to(DEV), b.to(DEV)
+    ref = GR.ref_nt(a, b)
+    if layout == "nt":
+        A, B, kw = GR.strided(a, K + 16), GR.strided(b, K + 8), dict(lda=K + 16, ldb=K + 8)
+    elif layout == "tb":
+        A, B, kw = GR.strided(a, K + 16), GR.strided(b.t(), N + 8), dict(tb=True, lda=K + 16, ldb=N + 8)
+    else:
+        A, B, kw = GR.strided(a.t(), M + 8), GR.strided(b.t(), N + 8), dict(ta=True, tb=True, lda=M + 8, ldb=N + 8)
+    return bf(A), bf(B), kw, ref
+
+
+def _run_exact(A, B, M, N, K, kw, ref, expect, what, out_f32):
+    """One launch into a sentinel canvas (ldc = N + 24), checked bit for bit against the exact product and through the launch log."""
+    buf = _canvas(M, N, N + 24, torch.float32 if out_f32 else torch.bfloat16)
+    _, recs = _logged(lambda: ops.gemm(A, B, M, N, K, out=buf, ldc=N + 24, **kw))
+    assert recs == [expect], (what, recs, expect)
+    _assert_bits(buf[:M, :N], GR.f32(ref) if out_f32 else GR.bf16(ref), what)
+    _assert_canary(buf, M, N, what)
+    return buf[:M, :N]
+
+
+@pytest.mark.parametrize("layout", ["nt", "tb", "tt"])
+@pytest.mark.parametrize("tile", GEMM_CFGS)
+def test_gemm_every_configuration_and_layout_bit_for_bit(tile, layout, gemm_path):
+    """Every built bf16 configuration in every layout: forward (NT), data gradient (tb) and weight gradient (ta + tb), M = 128 k +- 1
+    (or 128 k + 8 where M % 8 == 0 is required) and N = 8 (mod 64): ragged in both tile dimensions.  K = 64 (one K step, shorter than
+    every ring), 128 and 192 (2 - 3 steps against the 3- and 4-stage prologues) and 3072."""
+    M = 264 if layout == "tt" else (255 if tile in (3, 11, 15) else 257)
+    N = 200
+    ties = 0
+    for K in (64, 128, 192, 3072):
+        A, B, kw, ref = _operands(layout, M, N, K, 48, 48, seed=K + tile)
+        expect = (_ran_cfg(gemm_path, tile, M, N, K), 1, 1)
+        what = "cfg %d %s K=%d" % (tile, layout, K)
+        _run_exact(A, B, M, N, K, dict(kw, tile=tile), ref, expect, what + " fp32", True)
+        _run_exact(A, B, M, N, K, dict(kw, tile=tile), ref, expect, what + " bf16", False)
+        ties += GR.bf16_ties(ref)
+    assert ties > 0                                  # round-to-nearest-even was exercised on exact ties
+
+
+# register-staged kernel: K % 64 != 0 or N % 8 == 4 (no LDS-DMA path), and weight gradients of any R; its three tiles
+# (crct_gemm_pick_tile: 1 = 4x2 waves of 128 x 64, 2 = 2x4 of 64 x 128, 3 = 2x2 of 64 x 64) reached by the output shape
+_RS_CASES = [("nt", 100, 4, 8, 3), ("nt", 77, 12, 72, 3), ("nt", 130, 100, 776, 3), ("tb", 97, 104, 776, 3), ("tb", 33, 8, 8, 3),
+             ("nt", 1700, 1092, 72, 1), ("nt", 7681, 136, 8, 2), ("tb", 7681, 136, 72, 2), ("tb", 1700, 1096, 776, 1)]
+_RS_WGRAD_R = (1, 7, 63, 65, 129, 257, 1601)
+
+
+@pytest.mark.parametrize("layout,M,N,K,t", _RS_CASES)
+def test_gemm_register_staged_kernel_bit_for_bit(layout, M, N, K, t, gemm_path):
+    assert L.load().crct_gemm_pick_tile(M, N) == t or (t == 1 and L.load().crct_gemm_pick_tile(M, N) == 0)
+    A, B, kw, ref = _operands(layout, M, N, K, 64, 64, seed=M + N + K)
+    for out_f32 in (True, False):
+        _run_exact(A, B, M, N, K, kw, ref, (16 + t, 1, 1), "%s %dx%dx%d" % (layout, M, N, K), out_f32)
+
+
+@pytest.mark.parametrize("M,N,t", [(136, 200, 3), (1704, 1096, 1), (7688, 136, 2)])
+def test_gemm_register_staged_weight_gradients_of_any_R(M, N, t, gemm_path):
+    """ta + tb with R (the contraction) not a multiple of 64 -- or of 8 -- always runs the register-staged kernel; accumulate onto a
+    prefilled fp32 gradient as the step does."""
+    assert L.load().crct_gemm_pick_tile(M, N) in ((0, 1) if t == 1 else (t,))
+    for R in (_RS_WGRAD_R if M < 1000 else (1, 65, 1601)):
+        A, B, kw, ref = _operands("tt", M, N, R, 64, 64, seed=R, extra=1 << 12)
+        pre = GR.unit_ints((M, N), 64, R + 5, 2.0 ** -8).to(DEV)
+        buf = _canvas(M, N, N + 8, torch.float32, inner=pre)
+        _, recs = _logged(lambda: ops.gemm(A, B, M, N, R, out=buf, ldc=N + 8, accumulate=True, **kw))
+        assert recs == [(16 + t, 1, 1)], (R, recs)
+        _assert_bits(buf[:M, :N], GR.f32(ref + pre), "wgrad %dx%d R=%d" % (M, N, R))
+        _assert_canary(buf, M, N, "wgrad R=%d" % R)
+
+
+def _epi_case(layout, M, N, K, seed):
+    """Operands at a magnitude where GELU / tanh are not trivial (|acc| up to 12, typically ~0.3), unit 2^-12."""
+    return _operands(layout, M, N, K, 16, 16, seed, ea=-6, eb=-6, extra=1 << 16)
+
+
+@pytest.mark.parametrize("layout,M,N,K,tile", [("nt", 333, 264, 192, 15), ("tb", 257, 136, 128, 50), ("nt", 130, 100, 72, -1),
+                                                ("tb", 255, 200, 3072, 9)])
+def test_gemm_exact_epilogues_bit_for_bit(layout, M, N, K, tile, gemm_path):
+    """bias, preact_out, relu, dropout at p = 0.5 / 0.75 (scale 2 / 4: exact) and 0.1 (one fp32 multiply by the kernel's scale), bf16
+    and fp32 addend, accumulate onto bf16 and fp32 outputs, c_cached: all bit for bit.  preact_out lives in a sentinel canvas too
+    (ld_aux > N)."""
+    unit = 2.0 ** -12
+    A, B, kw, acc = _epi_case(layout, M, N, K, seed=M + K)
+    cfg = _ran_cfg(gemm_path, tile, M, N, K) if tile >= 0 else 16 + L.load().crct_gemm_pick_tile(M, N)
+    kw = dict(kw, tile=tile)
+    bias = GR.unit_ints((N,), 255, 1, unit * 4).to(DEV)
+    add_b = GR.unit_ints((M, N), 255, 2, unit * 8).to(DEV)               # bf16-exact: <= 8 significant bits
+    add_f = GR.unit_ints((M, N), 255, 3, unit).to(DEV) * 33               # fp32 only
+    pre_b = GR.unit_ints((M, N), 255, 4, unit * 16).to(DEV)
+    pre_f = GR.unit_ints((M, N), 255, 5, unit).to(DEV) * 77
+    ties = 0
+    for seed, site, p in ((DROP_SEEDS[0], 16, 0.5), (DROP_SEEDS[1], 41, 0.75), (DROP_SEEDS[0], 3, 0.1)):
+        keep = host_keep(seed, site, M, N, p)
+        ds = 1.0 / (1.0 - p)
+        drop = dict(p_drop=p, site=site, seed=seed)
+        # bias -> preact_out -> relu -> dropout -> bf16 addend -> bf16 store
+        pre = _canvas(M, N, N + 16, torch.bfloat16)
+        y = _canvas(M, N, N + 24, torch.bfloat16)
+        _, recs = _logged(lambda: ops.gemm(A, B, M, N, K, out=y, ldc=N + 24, bias=bias.float(), act="relu", preact_out=pre, ld_aux=N + 16,
+                                           addend=bf(add_b), **drop, **kw))
+        assert recs == [(cfg, 1, 1)], recs
+        r = GR.epilogue(acc, bias=bias, act="relu", keep=keep, drop_scale=ds, addend=add_b, out="bf16")
+        what = "%s p=%g" % (layout, p)
+        _assert_bits(pre[:M, :N], r["pre"], what + ": preact_out")
+        _assert_bits(y[:M, :N], r["y"], what + ": bias relu dropout bf16-addend")
+        _assert_canary(pre, M, N, what + ": preact_out")
+        _assert_canary(y, M, N, what + ": y")
+        ties += GR.bf16_ties(r["v"])
+        # bias -> dropout -> fp32 addend -> fp32 c_cached store (the fp32 residual stream)
+        y = _canvas(M, N, N + 8, torch.float32)
+        ops.gemm(A, B, M, N, K, out=y, ldc=N + 8, bias=bias.float(), addend=add_f.float(), c_cached=True, **drop, **kw)
+        _assert_bits(y[:M, :N], GR.epilogue(acc, bias=bias, keep=keep, drop_scale=ds, addend=add_f, out="f32")["y"], what + ": c_cached")
+        _assert_canary(y, M, N, what + ": c_cached")
+        if p == 0.1:
+            continue                # below: products and sums of two roundings (a fused multiply-add may take one)
+        # dropout -> bf16 addend -> accumulate onto bf16 / onto fp32
+        y = _canvas(M, N, N + 24, torch.bfloat16, inner=pre_b)
+        ops.gemm(A, B, M, N, K, out=y, ldc=N + 24, addend=bf(add_b), accumulate=True, **drop, **kw)
+        r = GR.epilogue(acc, keep=keep, drop_scale=ds, addend=add_b, prev=pre_b, out="bf16")
+        _assert_bits(y[:M, :N], r["y"], what + ": accumulate onto bf16")
+        _assert_canary(y, M, N, what + ": accumulate bf16")
+        ties += GR.bf16_ties(r["v"] + pre_b)
+        y = _canvas(M, N, N + 8, torch.float32, inner=pre_f)
+        ops.gemm(A, B, M, N, K, out=y, ldc=N + 8, bias=bias.float(), addend=bf(add_b), accumulate=True, **drop, **kw)
+        r = GR.epilogue(acc, bias=bias, keep=keep, drop_scale=ds, addend=add_b, prev=pre_f, out="f32")
+        _assert_bits(y[:M, :N], r["y"], what + ": accumulate onto fp32")
+        _assert_canary(y, M, N, what + ": accumulate fp32")
+    assert ties > 0
+
+
+@pytest.mark.parametrize("layout,M,N,K,tile", [("nt", 333, 264, 192, 15), ("nt", 130, 100, 72, -1), ("tb", 257, 200, 768, 4)])
+def test_gemm_rounded_epilogues_within_one_rounding(layout, M, N, K, tile, gemm_path):
+    """gelu, tanh, leaky, dact gelu / leaky and dropout at p = 0.1 in front of an addend: fp64 of the exact accumulator, the bf16 output
+    within one bf16 step (+ 2^-20 of the terms' magnitude: the kernel's own fp32 roundings)."""
+    unit = 2.0 ** -12
+    A, B, kw, acc = _epi_case(layout, M, N, K, seed=M + N)
+    kw = dict(kw, tile=tile)
+    bias = GR.unit_ints((N,), 255, 11, unit * 4).to(DEV)
+    add_b = GR.unit_ints((M, N), 255, 12, unit * 8).to(DEV)
+    src = bf(rand(M, N, scale=1.5, seed=13)).double()
+    for act in ("gelu", "tanh", "leaky"):
+        y = _canvas(M, N, N + 24, torch.bfloat16)
+        ops.gemm(A, B, M, N, K, out=y, ldc=N + 24, bias=bias.float(), act=act, **kw)
+        r = GR.epilogue(acc, bias=bias, act=act)
+        _assert_within_bf16_step(y[:M, :N], r["v"], r["v"].abs().cpu(), "%s %s" % (layout, act))
+        _assert_canary(y, M, N, act)
+    for dact, s in (("gelu", src), ("leaky", src)):
+        y = _canvas(M, N, N + 24, torch.bfloat16)
+        ops.gemm(A, B, M, N, K, out=y, ldc=N + 24, dact_src=bf(s), dact=dact, **kw)
+        r = GR.epilogue(acc, dact=dact, dact_src=s)
+        # gelu'(s) = 0.5 (1 + erf(s / sqrt 2)) + s phi(s): its two terms cancel near s = -0.75, where the fp32 evaluation keeps an error
+        # of their magnitude, not of the result's
+        terms = 0.5 * (1 + torch.erf(s / math.sqrt(2)).abs()) + (s * torch.exp(-0.5 * s * s)).abs() / math.sqrt(2 * math.pi)
+        _assert_within_bf16_step(y[:M, :N], r["v"], (acc.abs() * terms).cpu(), "%s dact %s" % (layout, dact))
+        _assert_canary(y, M, N, "dact " + dact)
+    keep = host_keep(DROP_SEEDS[1], 23, M, N, 0.1)
+    y = _canvas(M, N, N + 24, torch.bfloat16)
+    ops.gemm(A, B, M, N, K, out=y, ldc=N + 24, bias=bias.float(), act="gelu", p_drop=0.1, site=23, seed=DROP_SEEDS[1], addend=bf(add_b), **kw)
+    r = GR.epilogue(acc, bias=bias, act="gelu", keep=keep, drop_scale=1.0 / 0.9, addend=add_b)
+    _assert_within_bf16_step(y[:M, :N], r["v"], (r["v"] - add_b).abs().cpu() + add_b.abs().cpu(), layout + " gelu dropout 0.1 addend")
+
+
+@pytest.mark.parametrize("tile", (4, 9, 12, 15))
+def test_gemm_split_k_bit_for_bit(tile, gemm_path):
+    """Split-K S = 2 .. 8 with the full epilogue: K / 64 = 2 S (the smallest split allowed), 2 S + 1 and 48 (slices of uneven length) run
+    split, 2 S - 1 falls back to one unsplit launch -- both checked through the launch log -- and every result is the exact one (so also
+    the unsplit bits).  On the register-staged kernel (gemm_path) the request runs unsplit."""
+    M, N = 257, 200
+    unit = 2.0 ** -8
+    bias = GR.unit_ints((N,), 255, 21, unit).to(DEV)
+    add_b = GR.unit_ints((M, N), 255, 22, unit * 4).to(DEV)
+    cases = [(S, nk) for S in range(2, 9) for nk in (2 * S - 1, 2 * S, 2 * S + 1)] + [(3, 48), (5, 48), (8, 48)]
+    for S, nk in cases:
+        K = 64 * nk
+        layout = "tb" if S % 2 else "nt"
+        A, B, kw, acc = _operands(layout, M, N, K, 48, 48, seed=S * 100 + nk, extra=1 << 12)
+        keep = host_keep(DROP_SEEDS[0], 17, M, N, 0.5)
+        split = S if (gemm_path == "pipelined" and nk >= 2 * S) else 1
+        expect = (_ran_cfg(gemm_path, tile, M, N, K), split, 1)
+        pre = _canvas(M, N, N + 8, torch.bfloat16)
+        y = _canvas(M, N, N + 24, torch.bfloat16)
+        _, recs = _logged(lambda: ops.gemm(A, B, M, N, K, out=y, ldc=N + 24, bias=bias.float(), preact_out=pre, ld_aux=N + 8, act="relu",
+                                           p_drop=0.5, site=17, seed=DROP_SEEDS[0], addend=bf(add_b), tile=tile, split_k=S, **kw))
+        assert recs == [expect], (S, nk, recs, expect)
+        r = GR.epilogue(acc, bias=bias, act="relu", keep=keep, drop_scale=2.0, addend=add_b)
+        what = "cfg %d S=%d K/64=%d" % (tile, S, nk)
+        _assert_bits(y[:M, :N], r["y"], what)
+        _assert_bits(pre[:M, :N], r["pre"], what + ": preact_out")
+        _assert_canary(y, M, N, what)
+        _assert_canary(pre, M, N, what + ": preact_out")
+        y32 = _canvas(M, N, N + 8, torch.float32)
+        ops.gemm(A, B, M, N, K, out=y32, ldc=N + 8, tile=tile, split_k=S, **kw)
+        _assert_bits(y32[:M, :N], GR.f32(acc), what + ": fp32")
+        _assert_canary(y32, M, N, what + ": fp32")
+
+
+def _wgrad_rowsum_case(M, N, R, seed):
+    A, B, kw, ref = _operands("tt", M, N, R, 32, 32, seed=seed, extra=1 << 14)
+    pre = GR.unit_ints((M, N), 64, seed + 1, 2.0 ** -8).to(DEV)
+    rs_pre = GR.unit_ints((M,), 64, seed + 2, 2.0 ** -3).to(DEV)
+    # rowsum_out[m] += sum_k A'[m][k]: the column sums of dy as stored, [R][M] -> exact (integers * 2^-3, |sum| < 2^24 units)
+    rs_ref = rs_pre + A[:R, :M].double().sum(0)
+    return A, B, kw, ref, pre, rs_pre, rs_ref
+
+
+def test_gemm_rowsum_bias_gradient_bit_for_bit(gemm_path):
+    """rowsum_out (the bias gradient of a weight-gradient launch), single on every configuration that runs weight gradients and grouped,
+    exact, in a sentinel canvas of M + 8 words.  LDS-DMA kernel only: on the register-staged kernel (gemm_path) a request is refused."""
+    if gemm_path == "generic":
+        A, B, kw, *_ = _wgrad_rowsum_case(136, 200, 192, 1)
+        with pytest.raises(RuntimeError, match="gemm"):
+            ops.gemm(A, B, 136, 200, 192, out=torch.zeros(136, 200, device=DEV), accumulate=True, rowsum_out=torch.zeros(136, device=DEV), **kw)
+        return
+    for tile in GEMM_CFGS:
+        for M, N, R in ((136, 200, 192), (264, 72, 3072)):
+            A, B, kw, ref, pre, rs_pre, rs_ref = _wgrad_rowsum_case(M, N, R, seed=tile * 7 + R)
+            out = _canvas(M, N, N + 8, torch.float32, inner=pre)
+            rs = torch.full((M + 8,), SENT, device=DEV)
+            rs[:M] = rs_pre.float()
+            _, recs = _logged(lambda: ops.gemm(A, B, M, N, R, out=out, ldc=N + 8, accumulate=True, rowsum_out=rs, tile=tile, **kw))
+            assert recs == [(tile, 1, 1)], recs
+            what = "cfg %d %dx%d R=%d" % (tile, M, N, R)
+            _assert_bits(out[:M, :N], GR.f32(ref + pre), what)
+            _assert_bits(rs[:M], rs_ref, what + ": rowsum_out")
+            assert bool((rs[M:] == SENT).all()), what + ": rowsum_out written past M"
+            _assert_canary(out, M, N, what)
+
+
+def _group_problems(mode, seed):
+    """Up to 8 problems of one grouped launch: weight gradients (ta + tb, accumulate, row sums on every other one) or forward / data
+    gradients (nt / tb) with full epilogues; each with its exact result and canvases."""
+    if mode == "wgrad":
+        shapes = [(264, 200, 192), (128, 64, 64), (520, 136, 1088), (104, 776, 192), (200, 128, 3072), (136, 1032, 128), (1024, 512, 192),
+                  (776, 264, 640)]
+    else:
+        shapes = [(257, 200, 192), (1600, 264, 768), (130, 1032, 128), (1023, 72, 3072), (300, 520, 64)]
+    probs, checks = [], []
+    for i, (M, N, K) in enumerate(shapes):
+        s = seed + 10 * i
+        if mode == "wgrad":
+            A, B, kw, acc, pre, rs_pre, rs_ref = _wgrad_rowsum_case(M, N, K, s)
+            out = _canvas(M, N, N + 8, torch.float32, inner=pre)
+            d = dict(A=A, B=B, M=M, N=N, K=K, out=out, ldc=N + 8, accumulate=True, **kw)
+            rs = None
+            if i % 2 == 0:
+                rs = torch.full((M + 8,), SENT, device=DEV)
+                rs[:M] = rs_pre.float()
+                d["rowsum_out"] = rs
+            probs.append(d)
+            checks.append((out, GR.f32(acc + pre), None, None, rs, rs_ref))
+            continue
+        A, B, kw, acc = _operands(mode, M, N, K, 24, 24, seed=s, extra=1 << 14)
+        unit = 2.0 ** -8
+        bias = GR.unit_ints((N,), 255, s + 1, unit).to(DEV)
+        p = (0.5, 0.75, 0.0)[i % 3]
+        keep = host_keep(DROP_SEEDS[1], 30 + i, M, N, p) if p else None
+        f32_out = i % 2 == 1
+        add = GR.unit_ints((M, N), 255, s + 2, unit * 2).to(DEV)
+        out = _canvas(M, N, N + 24, torch.float32 if f32_out else torch.bfloat16)
+        pre = _canvas(M, N, N + 8, torch.bfloat16)
+        d = dict(A=A, B=B, M=M, N=N, K=K, out=out, ldc=N + 24, bias=bias.float(), act="relu" if i % 2 else "none", preact_out=pre,
+                 ld_aux=N + 8, addend=add.float() if f32_out else bf(add), p_drop=p, site=30 + i, seed=DROP_SEEDS[1], **kw)
+        r = GR.epilogue(acc, bias=bias, act=d["act"], keep=keep, drop_scale=1.0 / (1.0 - p), addend=add, out="f32" if f32_out else "bf16")
+        probs.append(d)
+        checks.append((out, r["y"], pre, r["pre"], None, None))
+    return probs, checks
+
+
+@pytest.mark.parametrize("mode", ["wgrad", "nt", "tb"])
+@pytest.mark.parametrize("tile", (4, 9))
+def test_gemm_grouped_bit_for_bit(mode, tile, gemm_path):
+    """crct_gemm_bf16_grouped with up to 8 problems (GROUP_MAX) on both grouped configurations: weight gradients (+ row sums) and forward
+    / data-gradient groups with full epilogues; also with crct_gemm_group_target_workgroups at 1 and 7, so that each workgroup walks the
+    tiles of several problems.  Every problem against its exact result, not only against its single launch.  On the register-staged
+    kernel (gemm_path) the group runs as single launches, without row sums."""
+    lib = L.load()
+    for target in (0, 1, 7):
+        probs, checks = _group_problems(mode, seed=100 * tile + target)
+        for d in probs:
+            d["tile"] = tile
+            if gemm_path == "generic":
+                d.pop("rowsum_out", None)
+        old = lib.crct_gemm_group_target_workgroups(target)
+        try:
+            _, recs = _logged(lambda: ops.gemm_grouped(probs))
+        finally:
+            lib.crct_gemm_group_target_workgroups(old)
+        if gemm_path == "pipelined":
+            assert recs == [(tile, 1, len(probs))], recs
+        else:
+            assert recs == [(_ran_cfg(gemm_path, tile, d["M"], d["N"], d["K"]), 1, 1) for d in probs], recs
+        for i, ((out, ref, pre, pre_ref, rs, rs_ref), d) in enumerate(zip(checks, probs)):
+            what = "%s cfg %d target %d problem %d" % (mode, tile, target, i)
+            M, N = d["M"], d["N"]
+            _assert_bits(out[:M, :N], ref, what)
+            _assert_canary(out, M, N, what)
+            if pre is not None:
+                _assert_bits(pre[:M, :N], pre_ref, what + ": preact_out")
+                _assert_canary(pre, M, N, what + ": preact_out")
+            if rs is not None and gemm_path == "pipelined":
+                _assert_bits(rs[:M], rs_ref, what + ": rowsum_out")
+                assert bool((rs[M:] == SENT).all()), what + ": rowsum_out written past M"
+
+
+def test_gemm_refuses_c_cached_with_accumulate(gemm_path):
+    """c_cached is a plain fp32 store: the LDS-DMA epilogue writes it without reading the old value, the register-staged one added it.
+    The combination is refused by crct_gemm_bf16 and crct_gemm_bf16_grouped on both kernel paths, and nothing is written."""
+    for K in (64, 72):             # LDS-DMA kernel (unless gemm_path forces the other) and register-staged kernel
+        A, B, kw, _ = _operands("nt", 130, 64, K, 8, 8, seed=K)
+        out = torch.full((130, 64), 3.0, device=DEV)
+        with pytest.raises(RuntimeError, match="c_cached with accumulate"):
+            ops.gemm(A, B, 130, 64, K, out=out, accumulate=True, c_cached=True, **kw)
+        other = dict(A=A, B=B, M=130, N=64, K=K, out=torch.zeros(130, 64, device=DEV), **kw)
+        with pytest.raises(RuntimeError, match="c_cached with accumulate"):
+            ops.gemm_grouped([other, dict(other, out=out, accumulate=True, c_cached=True)])
+        torch.cuda.synchronize()
+        assert bool((out == 3.0).all()) and bool((other["out"] == 0).all())
+        ops.gemm(A, B, 130, 64, K, out=out, c_cached=True, **kw)          # each flag alone is fine
+        ops.gemm(A, B, 130, 64, K, out=out, accumulate=True, **kw)
+
+
+# ------------------------------------------------------------------------------------------- fp8 GEMMs bit for bit against fp64
+def _f8(x, kind):
+    return x.float().to(torch.float8_e4m3fn if kind == "e4m3" else torch.float8_e5m2).to(DEV)
+
+
+@pytest.mark.parametrize("M,N,K,cfg", [(257, 520, 384, 20), (300, 1000, 2048, 21), (130, 1032, 2048, 20), (1600, 768, 3072, 21)])
+def test_gemm_fp8_forward_bit_for_bit(M, N, K, cfg):
+    """e4m3 integers 1 .. 16 (either sign), power-of-two scales: alpha = 1 / (sa sb) is exact, every sum below 2^20 is exact.  bias, relu,
+    preact_out, the e4m3 copy (q_out = _q8 of the exact value) and its amax (exactly max |value|), bf16 and fp32 outputs; ids 20 and 21
+    by shape (21: N <= 1024 with K >= 2048)."""
+    amax = 16 if K <= 2048 else 8
+    qa, qb = GR.operands(M, N, K, amax, amax, seed=M + K, kind="e4m3", extra=1 << 16)
+    sa, sb = 8.0, 4.0                                        # q = x * scale: x = q / scale
+    acc = GR.ref_nt(qa.to(DEV), qb.to(DEV))                  # in units of 1 / (sa sb)
+    bias = GR.unit_ints((N,), 255, 5, 1.0 / 32).to(DEV)
+    sa_d, sb_d = torch.tensor([sa], device=DEV), torch.tensor([sb], device=DEV)
+    xa, xb = _f8(qa, "e4m3"), _f8(qb, "e4m3")
+    for out_f32 in (True, False):
+        pre = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
+        q_out = torch.zeros(M, N, device=DEV, dtype=torch.uint8)
+        qs = torch.tensor([0.25], device=DEV)
+        am = torch.zeros(L.FP8_AMAX_LANES, device=DEV)
+        y, recs = _logged(lambda: ops.gemm_fp8(xa, xb, sa_d, sb_d, M, N, K, bias=bias.float(), act="relu", preact_out=pre, out_f32=out_f32,
+                                               q_out=q_out, q_scale=qs, q_amax=am))
+        assert recs == [(cfg, 1, 1)], recs
+        r = GR.epilogue(acc, alpha=1.0 / (sa * sb), bias=bias, act="relu", out="f32" if out_f32 else "bf16", q_scale=0.25, q_kind="e4m3")
+        what = "fp8 fwd %dx%dx%d" % (M, N, K)
+        _assert_bits(y, r["y"], what)
+        _assert_bits(pre, r["pre"], what + ": preact_out")
+        _assert_bits(q_out.view(torch.float8_e4m3fn).double(), r["q"], what + ": q_out")
+        assert float(am.max()) == r["amax"], what + ": amax"
+
+
+@pytest.mark.parametrize("M,N,K,cfg", [(257, 264, 1024, 20), (300, 520, 2048, 21)])
+def test_gemm_fp8_data_gradient_bit_for_bit(M, N, K, cfg):
+    """e5m2 A (integers 1 .. 8) x e4m3 B, dact relu (an exact 0 / 1 factor), the e5m2 q_out copy and its amax."""
+    qa, qb = GR.operands(M, N, K, 8, 16, seed=M + N, kind="e5m2", kind_b="e4m3")
+    sa, sb = 2.0, 16.0
+    acc = GR.ref_nt(qa.to(DEV), qb.to(DEV))
+    src = GR.unit_ints((M, N), 8, 9, 1.0).to(DEV)
+    sa_d, sb_d = torch.tensor([sa], device=DEV), torch.tensor([sb], device=DEV)
+    q_out = torch.zeros(M, N, device=DEV, dtype=torch.uint8)
+    qs = torch.tensor([4.0], device=DEV)
+    am = torch.zeros(L.FP8_AMAX_LANES, device=DEV)
+    y, recs = _logged(lambda: ops.gemm_fp8(_f8(qa, "e5m2"), _f8(qb, "e4m3"), sa_d, sb_d, M, N, K, a_bf8=True, q_bf8=True, dact_src=bf(src),
+                                           dact="relu", q_out=q_out, q_scale=qs, q_amax=am))
+    assert recs == [(cfg, 1, 1)], recs
+    r = GR.epilogue(acc, alpha=1.0 / (sa * sb), dact="relu", dact_src=src, q_scale=4.0, q_kind="e5m2")
+    what = "fp8 dgrad %dx%dx%d" % (M, N, K)
+    _assert_bits(y, r["y"], what)
+    _assert_bits(q_out.view(torch.float8_e5m2).double(), r["q"], what + ": q_out")
+    assert float(am.max()) == r["amax"], what + ": amax"
+
+
+@pytest.mark.parametrize("tile", (36, 37))
+def test_gemm_fp8_weight_gradient_bit_for_bit(tile):
+    """dW = dy^T x from token-major e5m2 dy (1 .. 8) and e4m3 x (1 .. 16): R not a multiple of 128, N and K multiples of 16 but not of
+    the tile, overwrite and accumulate; then grouped launches of 8 problems."""
+    sd, sx = 4.0, 8.0
+    sd_d, sx_d = torch.tensor([sd], device=DEV), torch.tensor([sx], device=DEV)
+    for R in (1, 16, 100, 129, 2880):
+        N, K = 144, 208
+        GR.check_exact(R, 8, 16, 1 << 12, "e5m2")
+        dq, xq = GR.ints((R, N), 8, R, "e5m2"), GR.ints((R, K), 16, R + 3, "e4m3")
+        ref = GR.ref_tt(dq.to(DEV), xq.to(DEV)) / (sd * sx)
+        pre = GR.unit_ints((N, K), 64, R + 4, 1.0 / 32).to(DEV)
+        out = torch.full((N, K), 7.0, device=DEV)
+        _, recs = _logged(lambda: ops.gemm_wgrad_fp8([(_f8(dq, "e5m2"), _f8(xq, "e4m3"), sd_d, sx_d, out)], accumulate=False, tile=tile))
+        assert recs == [(tile, 1, 1)], recs
+        _assert_bits(out, GR.f32(ref), "fp8 wgrad R=%d" % R)
+        out = pre.float().clone()
+        ops.gemm_wgrad_fp8([(_f8(dq, "e5m2"), _f8(xq, "e4m3"), sd_d, sx_d, out)], accumulate=True, tile=tile)
+        _assert_bits(out, GR.f32(ref + pre), "fp8 wgrad accumulate R=%d" % R)
+    R = 129
+    probs, refs = [], []
+    for i, (N, K) in enumerate(((144, 208), (16, 16), (768, 3072), (3072, 768), (272, 48), (64, 1040), (1024, 1024), (48, 336))):
+        dq = GR.ints((R, N), 8, 50 + i, "e5m2")
+        xq = GR.ints((R, K), 16, 60 + i, "e4m3")
+        pre = GR.unit_ints((N, K), 64, 70 + i, 1.0 / 32).to(DEV)
+        probs.append((_f8(dq, "e5m2"), _f8(xq, "e4m3"), sd_d, sx_d, pre.float().clone()))
+        refs.append(GR.f32(GR.ref_tt(dq.to(DEV), xq.to(DEV)) / (sd * sx) + pre))
+    _, recs = _logged(lambda: ops.gemm_wgrad_fp8(probs, accumulate=True, tile=tile))
+    assert recs == [(tile, 1, 8)], recs
+    for i, (p, ref) in enumerate(zip(probs, refs)):
+        _assert_bits(p[4], ref, "fp8 grouped wgrad problem %d" % i)
+
+
+# ------------------------------------------------------------------------------------------- LayerNorm and column sums against fp64
+_LN_CASES = [(1, 64), (7, 96), (255, 520), (1600, 768), (9920, 1024), (255, 2048), (7, 2048), (1600, 520), (1, 1024), (9920, 64)]
+
+
+def _ln_rows(M, H, seed):
+    """Rows N(0.3, 2) with row 0 constant (var = 0: y = beta exactly)."""
+    x = rand(M, H, scale=2.0, seed=seed) + 0.3
+    x[0] = 0.75
+    return x
+
+
+def _check_ln_forward_terms(x, y, mean, rstd, gamma, beta, what):
+    """As _check_ln_forward without dropout, y within one bf16 step + 2^-20 of the terms the kernel combined: gamma (x - mean) rstd is
+    formed from x and mean (fp32 each), so where y cancels to near 0 the roundings of |x| rstd and |mean| rstd remain."""
+    xd = x.double().cpu()
+    m64, sd64, r64 = _ln_stats64(xd)
+    assert float(((mean.double().cpu() - m64).abs() / (m64.abs() + sd64)).max()) <= 1e-5, what + ": mean"
+    assert float(((rstd.double().cpu() - r64).abs() / r64).max()) <= 1e-5, what + ": rstd"
+    g, b = gamma.double().cpu(), beta.double().cpu()
+    ref = g * ((xd - m64[:, None]) * r64[:, None]) + b
+    scale = g.abs() * (xd.abs() + m64.abs()[:, None]) * r64[:, None] + b.abs()
+    _assert_within_bf16_step(y, ref, scale, what + ": y")
+
+
+def _ln_check_backward(x, dy, mean, rstd, gamma, keep_post, p_post, keep_lin, p_lin, out, what, pre=None):
+    """dx (and dx_lin) per element within one bf16 step of fp64 autograd at x, fed dy * keep / (1 - p); dgamma / dbeta / dbias by
+    _assert_sums (pre: the accumulated-onto values)."""
+    dx, dxl, dg, db, dbias = out
+    ks = keep_post.double().cpu() / (1 - p_post) if keep_post is not None else torch.ones(x.shape, dtype=torch.float64)
+    ds, dg64, db64, dg_mag, db_mag = _ln_backward64(x, dy, ks, gamma)
+    # magnitude of the terms behind dx: rstd * (|g dy'| + mean |g dy'| + |xhat| mean |g dy' xhat|)
+    xd = x.double().cpu()
+    m64, _, r64 = _ln_stats64(xd)
+    xn = (xd - m64[:, None]) * r64[:, None]
+    gdy = gamma.double().cpu() * dy.double().cpu() * ks
+    mag = r64[:, None] * (gdy.abs() + gdy.abs().mean(1, keepdim=True) + xn.abs() * (gdy * xn).abs().mean(1, keepdim=True))
+    _assert_within_bf16_step(dx, ds, mag, what + ": dx")
+    lin = ds
+    if keep_lin is not None:
+        lin = ds * keep_lin.double().cpu() / (1 - p_lin)
+        _assert_within_bf16_step(dxl, lin, mag / (1 - p_lin), what + ": dx_lin")
+    z = torch.zeros_like(dg64) if pre is None else pre[0].double().cpu()
+    _assert_sums(dg, z + dg64, dg_mag + z.abs(), what + ": dgamma")
+    z = torch.zeros_like(db64) if pre is None else pre[1].double().cpu()
+    _assert_sums(db, z + db64, db_mag + z.abs(), what + ": dbeta")
+    z = torch.zeros_like(db64) if pre is None else pre[2].double().cpu()
+    _assert_sums(dbias, z + lin.sum(0), (mag * (lin.abs() > 0)).sum(0) + lin.abs().sum(0) + z.abs(), what + ": dbias")
+
+
+@pytest.mark.parametrize("M,H", _LN_CASES)
+def test_layernorm_against_fp64(M, H, gemm_path):
+    """crct_layernorm_fwd / _fwd_args (bf16 and fp32 rows, with and without the y_f32 copy) and crct_layernorm_bwd / _bwd_rows_args +
+    finalize, per element against fp64: H up to 2048 (520: not a multiple of 64), M over the block counts of crct_layernorm_bwd_blocks
+    (the dgamma / dbeta / dbias partials reduced across blocks), constant rows, post- and lin-dropout masks, accumulate.  LayerNorm
+    does not go through a GEMM: the register-staged parametrisation (gemm_path) has nothing to add and returns at once."""
+    if gemm_path == "generic":
+        return
+    x = _ln_rows(M, H, seed=M + H)
+    gamma, beta = 1 + 0.1 * rand(H, seed=2), 0.1 * rand(H, seed=3)
+    dy = bf(rand(M, H, seed=4))
+    for xin in (bf(x), x):
+        kind = "bf16" if xin.dtype == torch.bfloat16 else "fp32"
+        for y32 in (False, True):
+            res = ops.layernorm_fwd(xin, gamma, beta, y_f32=y32)
+            y, mean, rstd = res[:3]
+            what = "%dx%d %s rows%s" % (M, H, kind, " + y_f32" if y32 else "")
+            _check_ln_forward_terms(xin, y, mean, rstd, gamma, beta, what)
+            assert bool((y[0] == bf(beta)).all()), what + ": a constant row is beta"
+            if y32:
+                y32v = res[3]
+                assert torch.equal(y, y32v.to(torch.bfloat16)), what
+                ref = GR.f32(gamma.double() * ((xin.double() - mean.double()[:, None]) * rstd.double()[:, None]) + beta.double())
+                err = (y32v.double() - ref).abs()
+                tol = 2.0 ** -21 * ((gamma.double() * (xin.double() - mean.double()[:, None]) * rstd.double()[:, None]).abs() + beta.double().abs())
+                assert bool((err <= tol + 2.0 ** -22 * ref.abs()).all()), what + ": y_f32 beyond fp32 rounding of the kernel's own statistics"
+        out = ops.layernorm_bwd(dy, xin, mean, rstd, gamma)
+        _ln_check_backward(xin, dy, mean, rstd, gamma, None, 0.0, None, 0.0, out, "%dx%d %s bwd" % (M, H, kind))
+        # post-norm (p = 0.5) and lin (p = 0.1) dropout, accumulate onto prefilled column sums
+        pre = [rand(H, seed=s) for s in (7, 8, 9)]
+        seed = DROP_SEEDS[1]
+        out = ops.layernorm_bwd(dy, xin, mean, rstd, gamma, want_lin=True, p_lin=0.1, lin_site=19, p_post=0.5, post_site=2, seed=seed,
+                                dgamma=pre[0].clone(), dbeta=pre[1].clone(), dbias=pre[2].clone(), accumulate=True)
+        _ln_check_backward(xin, dy, mean, rstd, gamma, host_keep(seed, 2, M, H, 0.5), 0.5, host_keep(seed, 19, M, H, 0.1), 0.1, out,
+                           "%dx%d %s bwd dropout accumulate" % (M, H, kind), pre=pre)
+
+
+def test_layernorm_fp32_rows_with_a_large_mean(gemm_path):
+    """fp32 rows of mean 1e3 and standard deviation 1e-2 (a pre-LayerNorm sum far from zero): the statistics must hold up to the fp64
+    ones (a one-pass E[x^2] - E[x]^2 variance loses every digit here)."""
+    if gemm_path == "generic":
+        return
+    M, H = 255, 768
+    x = rand(M, H, scale=1e-2, seed=31) + 1e3
+    mean, rstd = ops.layernorm_fwd(x, torch.ones(H, device=DEV), torch.zeros(H, device=DEV))[1:3]
+    m64, _, r64 = _ln_stats64(x.double().cpu())
+    assert float(((mean.double().cpu() - m64).abs() / (m64.abs() + 1e-2)).max()) <= 1e-5
+    assert float(((rstd.double().cpu() - r64).abs() / r64).max()) <= 1e-3, "rstd of a large-mean row"
+
+
+@pytest.mark.parametrize("M,N,ld", [(1, 64, 64), (255, 520, 528), (1600, 3072, 3072), (9920, 768, 776), (7, 8, 16)])
+def test_colsum_on_integers_is_exact(M, N, ld, gemm_path):
+    """crct_colsum_bf16 on integer-valued bf16 rows (ld > N: the columns past N are never read), written and accumulated: exact."""
+    if gemm_path == "generic":
+        return
+    x = GR.strided(GR.ints((M, N), 255, M + N).to(DEV), ld, fill=SENT)
+    xb = bf(x)
+    ref = x[:, :N].sum(0)
+    out = ops.colsum(xb, M, N, ld=ld)
+    _assert_bits(out, ref, "colsum %dx%d" % (M, N))
+    pre = GR.ints((N,), 255, 3).to(DEV)
+    out = pre.float().clone()
+    ops.colsum(xb, M, N, ld=ld, out=out, accumulate=True)
+    _assert_bits(out, ref + pre, "colsum accumulate %dx%d" % (M, N))
