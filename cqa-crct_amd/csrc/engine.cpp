@@ -794,18 +794,11 @@ struct Run {
     const Drop dt = drop(D.p_hidden, 1);
     layer_begin();
     ++tick;
-    // the word-table index (first / last row per token id) is the ENGINE's memory: it must be zero whenever the call starts -- allocated and
-    // zeroed once, kept zero by the kernels themselves (include/crct_hip.h) -- which a caller-provided workspace cannot promise
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (!rc && !e->word_index && hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {      // never allocate inside a capture
-      if (hipMalloc((void**)&e->word_index, (size_t)2 * D.vocab * sizeof(int32_t)) != hipSuccess) { e->word_index = nullptr; (void)hipGetLastError(); }
-      else if (hipMemsetAsync(e->word_index, 0, (size_t)2 * D.vocab * sizeof(int32_t), s) != hipSuccess) { crct_set_error("engine: memset of the word index failed"); rc = 1; }
-    }
     if (!rc) fail(crct_embed_text_bwd_indexed(A(gt), A(e->eta.sum), F(e->eta.mean), F(e->eta.rstd), b->tokens, b->segments, b->loc,
                                               P(e->et.ln.g), G(e->et.word), G(e->et.pos), G(e->et.type), G(e->et.wloc), G(e->et.bloc),
                                               G(e->et.ln.g), G(e->et.ln.b), F(partials), b->B, b->T, D.H, D.n_pos, dt.thr, dt.scale,
                                               dt.site, c->seed, F(e->embed_rows[0]), W<int32_t>(e->embed_idx[0]), D.n_types, e->word_index,
-                                              e->word_index ? D.vocab : 0, s));
+                                              D.vocab, s));
   }
   void embed_image_bwd(size_t gv) {
     const CrctModelDims& D = e->d;
@@ -1298,6 +1291,17 @@ int ensure_streams(crct_engine* e, hipStream_t main) {
     hipStream_t out[4];
     if (int r = crct_streams_place(main, out, &e->queue_classes)) return r;
     e->side[0] = out[0]; e->side[1] = out[1]; e->aux = out[2]; e->side[2] = out[3];
+    // the word-table index (first / last row per token id) is the ENGINE's memory: it must be zero whenever a backward pass starts --
+    // zeroed here once, kept zero by the kernels themselves (include/crct_hip.h) -- which a caller-provided workspace cannot promise
+    const size_t index_bytes = (size_t)2 * e->d.vocab * sizeof(int32_t);
+    if (hipMalloc((void**)&e->word_index, index_bytes) != hipSuccess) {
+      e->word_index = nullptr;
+      (void)hipGetLastError();
+      crct_set_error("engine: cannot allocate the word index (%zu bytes)", index_bytes);
+      return 1;
+    }
+    CRCT_CHECK_HIP(hipMemsetAsync(e->word_index, 0, index_bytes, main));
+    CRCT_CHECK_HIP(hipStreamSynchronize(main));      // zero before any stream the backward may run on reads it
   }
   for (int k = 0; k < 3; ++k) {
     const bool need = k == 0 ? e->use_vis_stream : (e->use_wgrad_stream && !(k == 2 && e->one_wgrad_stream));

@@ -457,118 +457,21 @@ __global__ __launch_bounds__(256) void gather_sum_kernel(const float* __restrict
 }
 
 // word_embeddings gradient without float atomics: table[ids[r]][:] += rows[r][:] summed in a FIXED order.  One wave per token
-// row r: if an earlier row carries the same id the wave has nothing to do; otherwise it owns that table row and adds the
-// fp32 gradient rows of ALL tokens with this id in increasing row order (ballot over 64 ids at a time).  The 30 522-row
-// table is touched by <= B*T rows, most ids occur once, [PAD] / [CLS] / [SEP] a few hundred times: the result is bitwise
-// reproducible, which the atomics were not (arrival-order rounding: 1 of ~12 runs ended a 38-step training run on a
-// different loss, round-2 tools/det_check.sh).
-// One workgroup of 4 waves serves 4 consecutive token rows (one wave each); the ids of ALL rows sit in LDS (int32, one
-// coalesced pass), so the scans are LDS reads.  A wave keeps its whole output row in registers (H / 64 columns per lane, 16-byte
-// pieces).  Light ids (<= WORD_HEAVY matches, nearly all of them) are summed by the owning wave alone.  A heavy id ([PAD]: a few
-// hundred rows) would leave one wave walking hundreds of dependent 3 KB loads while the chip idles (106 us in the round-2
-// timeline), so its workgroup shares it: the owner lists the matches in LDS, match e goes to wave (e / 4) % 4, accumulator e % 4
-// (four independent rows in flight per wave), and the 4 x 4 partial rows are folded in a fixed tree -- still bit-reproducible.
+// row r: the wave whose row is the first of its id owns that table row and adds the fp32 gradient rows of ALL tokens with this id in
+// increasing row order; the other waves have no row of their own to add.  The 30 522-row table is touched by <= B*T rows, most ids occur once,
+// [PAD] / [CLS] / [SEP] a few hundred times: the result is bitwise reproducible, which the atomics were not (arrival-order rounding:
+// 1 of ~12 runs ended a 38-step training run on a different loss, round-2 tools/det_check.sh).
+// The kernel that produced the gradient rows has left, per token id, first[id] = M - (smallest row with this id) and last[id] = (largest
+// such row) + 1 (integer atomic maxima: order-free), in two zero-initialised tables of vocabulary size.  An id that occurs once (nearly
+// all of them) costs its owner one row; otherwise the owner scans ids[r .. last] only, straight from global memory.  The owner puts its
+// two table entries back to zero (nobody else reads them any more: a later wave of the same id sees 0 != its own code and returns, as it
+// would have anyway).
+// One workgroup of 4 waves serves 4 consecutive token rows (one wave each).  A wave keeps its whole output row in registers (H / 64
+// columns per lane, 16-byte pieces).  Light ids (<= WORD_HEAVY matches, nearly all of them) are summed by the owning wave alone.  A heavy
+// id ([PAD]: a few hundred rows) would leave one wave walking hundreds of dependent 3 KB loads while the chip idles (106 us in the round-2
+// timeline), so its workgroup shares it: the owner lists the matches in LDS, match e goes to wave (e / 4) % 4, accumulator e % 4 (four
+// independent rows in flight per wave), and the 4 x 4 partial rows are folded in a fixed tree -- still bit-reproducible.
 constexpr int WORD_HEAVY = 8;
-template <int NCH>
-__device__ __forceinline__ void word_scatter_body(const float* __restrict__ rows, const int64_t* __restrict__ ids, int M, int H,
-                                                  float* __restrict__ table, const int blk, char* smem) {
-  int* sid = reinterpret_cast<int*>(smem);               // [M]
-  int* list = sid + M;                                   // [M]   matches of a heavy id
-  float* part = reinterpret_cast<float*>(sid + ((2 * M + 3) & ~3));      // [4][H] per-wave partial rows of a heavy id
-  __shared__ int s_cnt[ROWS_PER_BLOCK];
-  for (int i = threadIdx.x; i < M; i += 256) sid[i] = (int)ids[i];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = blk * ROWS_PER_BLOCK + w;
-  const int id = r < M ? sid[r] : -1;
-  bool earlier = r >= M;
-  for (int i = lane; i < r && i < M; i += 64) earlier |= sid[i] == id;
-  const bool own = __ballot(earlier) == 0ull;            // no earlier row carries this id: this wave owns the table row
-  int cnt = 0;
-  if (own)
-    for (int base = r & ~63; base < M; base += 64) {
-      const int i = base + lane;
-      cnt += __builtin_popcountll(__ballot(i >= r && i < M && sid[i] == id));
-    }
-  if (lane == 0) s_cnt[w] = cnt;
-  __syncthreads();
-  if (own && cnt <= WORD_HEAVY) {
-    Row<NCH> acc;
-    row_zero(acc);
-    for (int base = r & ~63; base < M; base += 64) {
-      const int i = base + lane;
-      unsigned long long m = __ballot(i >= r && i < M && sid[i] == id);
-      while (m) {                                        // increasing row order: a fixed summation order
-        const int j = base + __builtin_ctzll(m);
-        m &= m - 1;
-        row_add_f32(acc, rows + (long)j * H, H, lane);
-      }
-    }
-    row_add_f32(acc, table + (long)id * H, H, lane);
-    row_store_f32(acc, table + (long)id * H, H, lane);
-  }
-  for (int k = 0; k < ROWS_PER_BLOCK; ++k) {             // workgroup-uniform: s_cnt is shared
-    const int n = s_cnt[k];
-    if (n <= WORD_HEAVY) continue;
-    const int rk = blk * ROWS_PER_BLOCK + k, idk = sid[rk];
-    if (w == k) {
-      int at = 0;
-      for (int base = rk & ~63; base < M; base += 64) {
-        const int i = base + lane;
-        const bool hit = i >= rk && i < M && sid[i] == idk;
-        const unsigned long long m = __ballot(hit);
-        if (hit) list[at + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = i;
-        at += __builtin_popcountll(m);
-      }
-    }
-    __syncthreads();
-    Row<NCH> a0, a1, a2, a3;
-    row_zero(a0); row_zero(a1); row_zero(a2); row_zero(a3);
-    int e = w * 4;
-    for (; e + 3 < n; e += 16) {
-      const int j0 = list[e], j1 = list[e + 1], j2 = list[e + 2], j3 = list[e + 3];
-      row_add_f32(a0, rows + (long)j0 * H, H, lane);
-      row_add_f32(a1, rows + (long)j1 * H, H, lane);
-      row_add_f32(a2, rows + (long)j2 * H, H, lane);
-      row_add_f32(a3, rows + (long)j3 * H, H, lane);
-    }
-    if (e < n) row_add_f32(a0, rows + (long)list[e] * H, H, lane);
-    if (e + 1 < n) row_add_f32(a1, rows + (long)list[e + 1] * H, H, lane);
-    if (e + 2 < n) row_add_f32(a2, rows + (long)list[e + 2] * H, H, lane);
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a0.v[i][j] = (a0.v[i][j] + a1.v[i][j]) + (a2.v[i][j] + a3.v[i][j]);
-    row_store_f32(a0, part + (long)w * H, H, lane);
-    __syncthreads();
-    if (w == k) {
-      Row<NCH> t, u;
-      row_load_f32(t, part, H, lane);
-      row_load_f32(u, part + H, H, lane);
-#pragma unroll
-      for (int i = 0; i < NCH; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t.v[i][j] += u.v[i][j];
-      row_load_f32(u, part + 2 * (long)H, H, lane);
-      Row<NCH> v;
-      row_load_f32(v, part + 3 * (long)H, H, lane);
-#pragma unroll
-      for (int i = 0; i < NCH; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t.v[i][j] += u.v[i][j] + v.v[i][j];
-      row_add_f32(t, table + (long)idk * H, H, lane);
-      row_store_f32(t, table + (long)idk * H, H, lane);
-    }
-    __syncthreads();
-  }
-}
-
-// The same sums (same owner, same order, same bits) WITHOUT the O(M^2 / 64) scans: the kernel that produced the gradient rows has left,
-// per token id, first[id] = M - (smallest row with this id) and last[id] = (largest such row) + 1 (integer atomic maxima: order-free),
-// in two zero-initialised tables of vocabulary size.  A wave whose row is not its id's first row returns at once; an id that occurs once
-// (nearly all of them) costs its owner one row; otherwise the owner scans ids[r .. last] only, straight from global memory -- no LDS
-// image of all ids (40 KB per workgroup at 9 920 rows), no "does an earlier row carry my id" scan per row.  The owner puts its two table
-// entries back to zero (nobody else reads them any more: a later wave of the same id sees 0 != its own code and returns, as it would
-// have anyway).  embed_scatter: 320 -> 35 us at 9 920 rows, 68 -> 17 us at 1 600 (EXPERIMENTS.md round 6).
 template <int NCH>
 __device__ __forceinline__ void word_scatter_indexed_body(const float* __restrict__ rows, const int64_t* __restrict__ ids, int M, int H,
                                                           float* __restrict__ table, int* __restrict__ first, int* __restrict__ last,
@@ -680,9 +583,9 @@ __device__ __forceinline__ void word_scatter_indexed_body(const float* __restric
 
 template <int NCH>
 __global__ __launch_bounds__(256) void word_scatter_kernel(const float* __restrict__ rows, const int64_t* __restrict__ ids, int M, int H,
-                                                           float* __restrict__ table) {
+                                                           float* __restrict__ table, int* __restrict__ first, int* __restrict__ last) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  word_scatter_body<NCH>(rows, ids, M, H, table, blockIdx.x, smem);
+  word_scatter_indexed_body<NCH>(rows, ids, M, H, table, first, last, blockIdx.x, smem);
 }
 // the position / type sums and the word-table scatter of the text embedding's backward in ONE launch (independent outputs, both
 // read the per-token gradient rows): the few long gather workgroups first, the word workgroups fill in beside them
@@ -693,8 +596,7 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(const float* __restr
                                                             float* __restrict__ d_word, int* __restrict__ w_first, int* __restrict__ w_last) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if ((int)blockIdx.x < n_gather) gather_sum_body(rows, idx, M, H, d_pos, n0, idx1, d_type, blockIdx.x, smem);
-  else if (w_first) word_scatter_indexed_body<NCH>(rows, ids, M, H, d_word, w_first, w_last, (int)blockIdx.x - n_gather, smem);
-  else word_scatter_body<NCH>(rows, ids, M, H, d_word, (int)blockIdx.x - n_gather, smem);
+  else word_scatter_indexed_body<NCH>(rows, ids, M, H, d_word, w_first, w_last, (int)blockIdx.x - n_gather, smem);
 }
 
 // ------------------------------------------------------------------------------ LayerNorm fwd
@@ -1119,7 +1021,7 @@ __global__ __launch_bounds__(256) void embed_text_bwd_kernel(
     row_load_bf16(x, sum_p + row * H, H, lane);
     row_apply_dropmask(dy, H, lane, row, thr, scale, site, seed);
     row_ln_bwd(dy, x, gamma, H, lane, mean_p[row], rstd_p[row], adg, adb);
-    if (!rows_scratch) row_atomic_add(dy, d_word + ids[row] * (long)H, H, lane);     // fall-back only: see word_scatter_kernel
+    if (!rows_scratch) row_atomic_add(dy, d_word + ids[row] * (long)H, H, lane);     // fall-back only: see word_scatter_indexed_body
     int pid = -1;
     if (qa) {
       const int fq = first_qa_index(segs + (long)b * T, T, lane);
@@ -1170,90 +1072,29 @@ __global__ __launch_bounds__(256) void embed_text_bwd_kernel(
 }
 
 // ------------------------------------------------------------------------------ image embedding
-template <int NCH>
+// BertImageEmbeddings, vilbert.py:1478-1489: sum = [term] + new_loc_emb(loc) + color_emb(target), where the source term is the image
+// Linear's bf16 output row ('plotqa': the feature row first), or nothing ('dvqa' / 'figure_qa'), or areas_emp(areas) added last ('dvqa' /
+// 'figure_qa' with areas)
+enum ImgSrc { IMG_FEAT, IMG_NONE, IMG_AREAS };
+
+template <int NCH, ImgSrc SRC>
 __global__ __launch_bounds__(256) void embed_image_fwd_kernel(
     const bf16_t* __restrict__ img, const float* __restrict__ loc, const int64_t* __restrict__ target,
     const float* __restrict__ w_loc, const float* __restrict__ b_loc, const float* __restrict__ color,
     const float* __restrict__ gamma, const float* __restrict__ beta, bf16_t* __restrict__ sum_out,
     bf16_t* __restrict__ y, float* __restrict__ mean_o, float* __restrict__ rstd_o, int M, int H, float eps,
-    uint32_t thr, float scale, uint32_t site, uint64_t seed) {
+    uint32_t thr, float scale, uint32_t site, uint64_t seed, const float* __restrict__ areas,
+    const float* __restrict__ w_areas, const float* __restrict__ b_areas) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += (long)gridDim.x * ROWS_PER_BLOCK) {
     Row<NCH> r;
-    row_load_bf16(r, img + row * H, H, lane);
+    if (SRC == IMG_FEAT) row_load_bf16(r, img + row * H, H, lane);
+    else row_zero(r);
     const float4 lv = *reinterpret_cast<const float4*>(loc + row * 4);
     const float l[4] = {lv.x, lv.y, lv.z, lv.w};
     row_add_loc_linear(r, w_loc, b_loc, l, H, lane);
     row_add_f32(r, color + target[row] * (long)H, H, lane);
-    row_store_bf16(r, sum_out + row * H, H, lane);
-    row_round_bf16(r);
-    float mean, rstd;
-    row_stats(r, H, lane, eps, mean, rstd);
-    row_normalize(r, gamma, beta, H, lane, mean, rstd, row, thr, scale, site, seed);
-    row_store_bf16(r, y + row * H, H, lane);
-    if (lane == 0) { mean_o[row] = mean; rstd_o[row] = rstd; }
-  }
-}
-
-template <int NCH>
-__global__ __launch_bounds__(256) void embed_image_bwd_kernel(
-    const bf16_t* __restrict__ dy_p, const bf16_t* __restrict__ sum_p, const float* __restrict__ mean_p,
-    const float* __restrict__ rstd_p, const float* __restrict__ loc, const int64_t* __restrict__ target,
-    const float* __restrict__ gamma, bf16_t* __restrict__ dsum_p, float* __restrict__ d_color,
-    float* __restrict__ partials, int M, int H, uint32_t thr, float scale, uint32_t site, uint64_t seed,
-    float* __restrict__ rows_scratch, int* __restrict__ idx_scratch) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  Row<NCH> adg, adb, abl, aw0, aw1, aw2, aw3;
-  row_zero(adg); row_zero(adb); row_zero(abl); row_zero(aw0); row_zero(aw1); row_zero(aw2); row_zero(aw3);
-  for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += (long)gridDim.x * ROWS_PER_BLOCK) {
-    Row<NCH> dy, x;
-    row_load_bf16(dy, dy_p + row * H, H, lane);
-    row_load_bf16(x, sum_p + row * H, H, lane);
-    row_apply_dropmask(dy, H, lane, row, thr, scale, site, seed);
-    row_ln_bwd(dy, x, gamma, H, lane, mean_p[row], rstd_p[row], adg, adb);
-    row_store_bf16(dy, dsum_p + row * H, H, lane);
-    if (rows_scratch) {                                                 // colour sums: gather_sum_kernel afterwards
-      row_store_f32(dy, rows_scratch + row * H, H, lane);
-      if (lane == 0) idx_scratch[row] = (int)target[row];
-    } else {
-      row_atomic_add(dy, d_color + target[row] * (long)H, H, lane);
-    }
-    const float4 lv = *reinterpret_cast<const float4*>(loc + row * 4);
-    row_acc(abl, dy);       // = d b_loc = d b_img (both are plain column sums of d_sum)
-    row_acc(aw0, dy, lv.x); row_acc(aw1, dy, lv.y); row_acc(aw2, dy, lv.z); row_acc(aw3, dy, lv.w);
-  }
-  // every WAVE stores its own partial rows ([7][4 * gridDim.x][H]; the finalize pass sums them): no LDS tree and no
-  // workgroup barrier in this kernel.  (The wrong lanes 48..63 once seen here beside the dgrad / wgrad GEMMs came from
-  // packed-fp32 instructions, not from LDS: DESIGN.md section 8, tools/embed_stress.py; the build bans them.)
-  const long nr = (long)gridDim.x * ROWS_PER_BLOCK, pr = (long)blockIdx.x * ROWS_PER_BLOCK + wave;
-  row_store_f32(adg, partials + (0 * nr + pr) * H, H, lane);
-  row_store_f32(adb, partials + (1 * nr + pr) * H, H, lane);
-  row_store_f32(abl, partials + (2 * nr + pr) * H, H, lane);
-  row_store_f32(aw0, partials + (3 * nr + pr) * H, H, lane);
-  row_store_f32(aw1, partials + (4 * nr + pr) * H, H, lane);
-  row_store_f32(aw2, partials + (5 * nr + pr) * H, H, lane);
-  row_store_f32(aw3, partials + (6 * nr + pr) * H, H, lane);
-}
-
-// ------------------------------------------------------------------------------ image embedding, 'dvqa' / 'figure_qa'
-// vilbert.py:1478-1489: sum = new_loc_emb(loc) + color_emb(target) (+ areas_emp(areas)); no feature term.
-template <int NCH, bool AREAS>
-__global__ __launch_bounds__(256) void embed_image_var_fwd_kernel(
-    const float* __restrict__ loc, const int64_t* __restrict__ target, const float* __restrict__ areas,
-    const float* __restrict__ w_loc, const float* __restrict__ b_loc, const float* __restrict__ color,
-    const float* __restrict__ w_areas, const float* __restrict__ b_areas,
-    const float* __restrict__ gamma, const float* __restrict__ beta, bf16_t* __restrict__ sum_out,
-    bf16_t* __restrict__ y, float* __restrict__ mean_o, float* __restrict__ rstd_o, int M, int H, float eps,
-    uint32_t thr, float scale, uint32_t site, uint64_t seed) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += (long)gridDim.x * ROWS_PER_BLOCK) {
-    Row<NCH> r;
-    row_zero(r);
-    const float4 lv = *reinterpret_cast<const float4*>(loc + row * 4);
-    const float l[4] = {lv.x, lv.y, lv.z, lv.w};
-    row_add_loc_linear(r, w_loc, b_loc, l, H, lane);
-    row_add_f32(r, color + target[row] * (long)H, H, lane);
-    if (AREAS) {
+    if (SRC == IMG_AREAS) {
       const float a = areas[row];
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
@@ -1274,15 +1115,15 @@ __global__ __launch_bounds__(256) void embed_image_var_fwd_kernel(
   }
 }
 
-// the backward of embed_image_bwd_kernel without the d_sum store (no image Linear behind it) and with the areas weight sums as
-// partial row set 7
-template <int NCH, bool AREAS>
-__global__ __launch_bounds__(256) void embed_image_var_bwd_kernel(
+// d_sum (bf16, the image Linear's weight gradient reads it) is stored for IMG_FEAT only; IMG_AREAS adds the areas weight sums as partial
+// row set 7
+template <int NCH, ImgSrc SRC>
+__global__ __launch_bounds__(256) void embed_image_bwd_kernel(
     const bf16_t* __restrict__ dy_p, const bf16_t* __restrict__ sum_p, const float* __restrict__ mean_p,
     const float* __restrict__ rstd_p, const float* __restrict__ loc, const int64_t* __restrict__ target,
-    const float* __restrict__ areas, const float* __restrict__ gamma, float* __restrict__ d_color,
+    const float* __restrict__ gamma, bf16_t* __restrict__ dsum_p, float* __restrict__ d_color,
     float* __restrict__ partials, int M, int H, uint32_t thr, float scale, uint32_t site, uint64_t seed,
-    float* __restrict__ rows_scratch, int* __restrict__ idx_scratch) {
+    float* __restrict__ rows_scratch, int* __restrict__ idx_scratch, const float* __restrict__ areas) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   Row<NCH> adg, adb, abl, aw0, aw1, aw2, aw3, awa;
   row_zero(adg); row_zero(adb); row_zero(abl); row_zero(aw0); row_zero(aw1); row_zero(aw2); row_zero(aw3); row_zero(awa);
@@ -1292,17 +1133,21 @@ __global__ __launch_bounds__(256) void embed_image_var_bwd_kernel(
     row_load_bf16(x, sum_p + row * H, H, lane);
     row_apply_dropmask(dy, H, lane, row, thr, scale, site, seed);
     row_ln_bwd(dy, x, gamma, H, lane, mean_p[row], rstd_p[row], adg, adb);
-    if (rows_scratch) {
+    if (SRC == IMG_FEAT) row_store_bf16(dy, dsum_p + row * H, H, lane);
+    if (rows_scratch) {                                                 // colour sums: gather_sum_kernel afterwards
       row_store_f32(dy, rows_scratch + row * H, H, lane);
       if (lane == 0) idx_scratch[row] = (int)target[row];
     } else {
       row_atomic_add(dy, d_color + target[row] * (long)H, H, lane);
     }
     const float4 lv = *reinterpret_cast<const float4*>(loc + row * 4);
-    row_acc(abl, dy);       // = d b_loc = d b_areas
+    row_acc(abl, dy);       // = d b_loc = d b_img / d b_areas (plain column sums of d_sum)
     row_acc(aw0, dy, lv.x); row_acc(aw1, dy, lv.y); row_acc(aw2, dy, lv.z); row_acc(aw3, dy, lv.w);
-    if (AREAS) row_acc(awa, dy, areas[row]);
+    if (SRC == IMG_AREAS) row_acc(awa, dy, areas[row]);
   }
+  // every WAVE stores its own partial rows ([7 or 8][4 * gridDim.x][H]; the finalize pass sums them): no LDS tree and no
+  // workgroup barrier in this kernel.  (The wrong lanes 48..63 once seen here beside the dgrad / wgrad GEMMs came from
+  // packed-fp32 instructions, not from LDS: DESIGN.md section 8, tools/embed_stress.py; the build bans them.)
   const long nr = (long)gridDim.x * ROWS_PER_BLOCK, pr = (long)blockIdx.x * ROWS_PER_BLOCK + wave;
   row_store_f32(adg, partials + (0 * nr + pr) * H, H, lane);
   row_store_f32(adb, partials + (1 * nr + pr) * H, H, lane);
@@ -1311,7 +1156,7 @@ __global__ __launch_bounds__(256) void embed_image_var_bwd_kernel(
   row_store_f32(aw1, partials + (4 * nr + pr) * H, H, lane);
   row_store_f32(aw2, partials + (5 * nr + pr) * H, H, lane);
   row_store_f32(aw3, partials + (6 * nr + pr) * H, H, lane);
-  if (AREAS) row_store_f32(awa, partials + (7 * nr + pr) * H, H, lane);
+  if (SRC == IMG_AREAS) row_store_f32(awa, partials + (7 * nr + pr) * H, H, lane);
 }
 
 inline int nch_for(int H) { return (H / 8 + 63) / 64; }
@@ -1733,19 +1578,7 @@ int crct_embed_text_fwd(const int64_t* ids, const int64_t* segs, const float* lo
 
 static int g_embed_scatter_split = 0;
 extern "C" void crct_embed_scatter_split(int on) { g_embed_scatter_split = on ? 1 : 0; }
-static int g_embed_word_index = 1;      // crct_embed_word_index(0): crct_embed_text_bwd_indexed ignores its index (A/B timing, tests; same bits)
-extern "C" void crct_embed_word_index(int on) { g_embed_word_index = on ? 1 : 0; }
 
-extern "C" int crct_embed_text_bwd(const void* dy, const void* sum_saved, const float* mean, const float* rstd,
-                                        const int64_t* ids, const int64_t* segs, const float* loc, const float* gamma,
-                                        float* d_word, float* d_pos, float* d_type, float* d_wloc, float* d_bloc,
-                                        float* d_gamma, float* d_beta, float* partials, int B, int T, int H, int n_pos,
-                                        uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
-                                        float* rows_scratch, int32_t* idx_scratch, int n_types, crct_stream_t stream) {
-  return crct_embed_text_bwd_indexed(dy, sum_saved, mean, rstd, ids, segs, loc, gamma, d_word, d_pos, d_type, d_wloc, d_bloc, d_gamma, d_beta,
-                                     partials, B, T, H, n_pos, drop_thr, drop_scale, drop_site, seed, rows_scratch, idx_scratch, n_types, nullptr, 0,
-                                     stream);
-}
 extern "C" int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved, const float* mean, const float* rstd,
                                                 const int64_t* ids, const int64_t* segs, const float* loc, const float* gamma,
                                                 float* d_word, float* d_pos, float* d_type, float* d_wloc, float* d_bloc,
@@ -1756,12 +1589,13 @@ extern "C" int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved
   CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_text_bwd: H=%d must be a positive multiple of 8", H);
   const long M = (long)B * T;
   if (M <= 0) return 0;
+  CRCT_REQUIRE(!rows_scratch || !idx_scratch || (word_index && n_vocab > 0),
+               "embed_text_bwd: rows_scratch and idx_scratch need the word index (int32 [2][n_vocab], all zero; n_vocab = %d)", n_vocab);
   hipStream_t s = (hipStream_t)stream;
   if (!idx_scratch || M > GATHER_MAX_ROWS || n_types <= 0) rows_scratch = nullptr;      // atomics fall-back
   const int nb = embed_bwd_blocks(M);
-  // word_index: int32 [2][n_vocab] (first / last row per id), zero on entry and on exit; without it (or in the two-launch test form) the scanning kernel
-  int* w_first = (rows_scratch && word_index && n_vocab > 0 && !g_embed_scatter_split && g_embed_word_index) ? word_index : nullptr;
-  int* w_last = w_first ? word_index + n_vocab : nullptr;
+  int* w_first = rows_scratch ? word_index : nullptr;     // first / last row per id, zero on entry and on exit
+  int* w_last = rows_scratch ? word_index + n_vocab : nullptr;
   const int type_partials = rows_scratch && n_types >= 2 && d_type;     // partials then hold 9 row sets
   DISPATCH_NCH(H, crct_launch((embed_text_bwd_kernel<NCH>), dim3(nb), dim3(256), 0, s, (const bf16_t*)dy,
                                      (const bf16_t*)sum_saved, mean, rstd, ids, segs, loc, gamma, d_word, d_pos, d_type,
@@ -1770,8 +1604,8 @@ extern "C" int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved
   CRCT_CHECK_HIP(hipGetLastError());
   if (rows_scratch) {
     const int used_pos = n_pos < T ? n_pos : T;            // position ids are clamped to [0, n_pos) and never exceed T - 1
-    const size_t word_lds = (size_t)(((w_first ? 1 : 2) * M + 3) & ~3L) * sizeof(int) + (size_t)ROWS_PER_BLOCK * H * sizeof(float);     // >= the gather's M ints
-    CRCT_REQUIRE(word_lds <= 152 * 1024, "embed_text_bwd: B*T=%ld rows need %zu bytes of LDS for the word-gradient scan", M, word_lds);
+    const size_t word_lds = (size_t)((M + 3) & ~3L) * sizeof(int) + (size_t)ROWS_PER_BLOCK * H * sizeof(float);     // >= the gather's M ints
+    CRCT_REQUIRE(word_lds <= 152 * 1024, "embed_text_bwd: B*T=%ld rows need %zu bytes of LDS for the word-gradient sums", M, word_lds);
     const int n_gather = used_pos + n_types;
     if (g_embed_scatter_split) {      // test hook: the two launches the merged kernel replaces (same bits)
       crct_launch(gather_sum_kernel, dim3(n_gather), dim3(256), (size_t)M * sizeof(int), s,
@@ -1785,12 +1619,12 @@ extern "C" int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved
           big_lds_w = true;
         }
         crct_launch((word_scatter_kernel<NCH>), dim3((int)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), word_lds, s,
-                           (const float*)rows_scratch, ids, (int)M, H, d_word);
+                           (const float*)rows_scratch, ids, (int)M, H, d_word, w_first, w_last);
       });
       CRCT_CHECK_HIP(hipGetLastError());
     } else
     DISPATCH_NCH(H, {
-      static bool big_lds = false;                         // ids + match list of every row: above 64 KiB from ~6 600 rows on
+      static bool big_lds = false;                         // a heavy id's match list (M ints) + 4 partial rows: above 64 KiB from ~12 300 rows on at H = 1024
       if (word_lds > 64 * 1024 && !big_lds) {
         CRCT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&embed_scatter_kernel<NCH>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
@@ -1815,19 +1649,69 @@ extern "C" int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved
   return launch_finalize(fa, s);
 }
 
+// the image embedding's launches for every source term (embed_image_fwd_kernel); areas, w_areas, b_areas are read for IMG_AREAS only
+template <ImgSrc SRC>
+static int embed_image_fwd_run(const void* img_lin, const float* loc, const int64_t* target, const float* areas, const float* w_loc,
+                               const float* b_loc, const float* color, const float* w_areas, const float* b_areas, const float* gamma,
+                               const float* beta, void* sum_out, void* y, float* mean, float* rstd, int M, int H, float eps,
+                               uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed, crct_stream_t stream) {
+  CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_image: H=%d must be a positive multiple of 8", H);
+  if (M <= 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  DISPATCH_NCH(H, crct_launch((embed_image_fwd_kernel<NCH, SRC>), dim3(row_grid(M, 2048)), dim3(256), 0, s,
+                                     (const bf16_t*)img_lin, loc, target, w_loc, b_loc, color, gamma, beta, (bf16_t*)sum_out,
+                                     (bf16_t*)y, mean, rstd, M, H, eps, drop_thr, drop_scale, drop_site, seed, areas, w_areas, b_areas));
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ... and the backward: the row kernel, the colour sums (gather pass, or float atomics), the finalize of the 7 partial row sets (8 with
+// the areas weight), then partial row 2 once more into d_bias when given: the column sum is the gradient of b_loc and also of the image
+// Linear's bias (IMG_FEAT) or of the areas bias (IMG_AREAS)
+template <ImgSrc SRC>
+static int embed_image_bwd_run(const void* dy, const void* sum_saved, const float* mean, const float* rstd, const float* loc,
+                               const int64_t* target, const float* areas, const float* gamma, void* d_sum, float* d_color, float* d_wloc,
+                               float* d_bloc, float* d_wareas, float* d_bias, float* d_gamma, float* d_beta, float* partials, int M, int H,
+                               uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed, float* rows_scratch,
+                               int32_t* idx_scratch, int n_color, crct_stream_t stream) {
+  CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_image_bwd: H=%d must be a positive multiple of 8", H);
+  if (M <= 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (!idx_scratch || M > GATHER_MAX_ROWS || n_color <= 0) rows_scratch = nullptr;      // atomics fall-back
+  const int nb = embed_bwd_blocks(M);
+  DISPATCH_NCH(H, crct_launch((embed_image_bwd_kernel<NCH, SRC>), dim3(nb), dim3(256), 0, s, (const bf16_t*)dy,
+                                     (const bf16_t*)sum_saved, mean, rstd, loc, target, gamma, (bf16_t*)d_sum, d_color,
+                                     partials, M, H, drop_thr, drop_scale, drop_site, seed, rows_scratch,
+                                     rows_scratch ? idx_scratch : nullptr, areas));
+  CRCT_CHECK_HIP(hipGetLastError());
+  if (rows_scratch) {
+    crct_launch(gather_sum_kernel, dim3(n_color), dim3(256), (size_t)M * sizeof(int), s, rows_scratch, idx_scratch, M, H, d_color,
+                       n_color, (const int*)nullptr, (float*)nullptr);
+    CRCT_CHECK_HIP(hipGetLastError());
+  }
+  FinalizeArgs fa = {};
+  fa.out[0] = d_gamma; fa.out[1] = d_beta; fa.out[2] = d_bloc;
+  fa.stride[0] = fa.stride[1] = fa.stride[2] = 1;
+  for (int k = 0; k < 4; ++k) { fa.out[3 + k] = d_wloc ? d_wloc + k : nullptr; fa.stride[3 + k] = 4; }
+  fa.Q = 7; fa.nblk = nb * ROWS_PER_BLOCK; fa.H = H; fa.accumulate = 1; fa.partials = partials;
+  if (SRC == IMG_AREAS) { fa.out[7] = d_wareas; fa.stride[7] = 1; fa.Q = 8; }      // areas_emp.weight [H][1]
+  if (launch_finalize(fa, s)) return 1;
+  if (d_bias) {
+    FinalizeArgs fb = {};
+    fb.out[0] = d_bias; fb.stride[0] = 1; fb.Q = 1; fb.nblk = nb * ROWS_PER_BLOCK; fb.H = H; fb.accumulate = 1;
+    fb.partials = partials + (size_t)2 * nb * ROWS_PER_BLOCK * H;
+    return launch_finalize(fb, s);
+  }
+  return 0;
+}
+
 extern "C" int crct_embed_image_fwd(const void* img_lin, const float* loc, const int64_t* target, const float* w_loc,
                                     const float* b_loc, const float* color, const float* gamma, const float* beta,
                                     void* sum_out, void* y, float* mean, float* rstd, int M, int H, float eps,
                                     uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
                                     crct_stream_t stream) {
-  CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_image: H=%d must be a positive multiple of 8", H);
-  if (M <= 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  DISPATCH_NCH(H, crct_launch((embed_image_fwd_kernel<NCH>), dim3(row_grid(M, 2048)), dim3(256), 0, s,
-                                     (const bf16_t*)img_lin, loc, target, w_loc, b_loc, color, gamma, beta,
-                                     (bf16_t*)sum_out, (bf16_t*)y, mean, rstd, M, H, eps, drop_thr, drop_scale, drop_site, seed));
-  CRCT_CHECK_HIP(hipGetLastError());
-  return 0;
+  return embed_image_fwd_run<IMG_FEAT>(img_lin, loc, target, nullptr, w_loc, b_loc, color, nullptr, nullptr, gamma, beta, sum_out, y, mean,
+                                       rstd, M, H, eps, drop_thr, drop_scale, drop_site, seed, stream);
 }
 
 extern "C" int crct_embed_image_bwd(const void* dy, const void* sum_saved, const float* mean, const float* rstd,
@@ -1836,35 +1720,9 @@ extern "C" int crct_embed_image_bwd(const void* dy, const void* sum_saved, const
                                     float* d_beta, float* partials, int M, int H, uint32_t drop_thr, float drop_scale,
                                     uint32_t drop_site, uint64_t seed, float* rows_scratch, int32_t* idx_scratch, int n_color,
                                     crct_stream_t stream) {
-  CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_image_bwd: H=%d must be a positive multiple of 8", H);
-  if (M <= 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (!idx_scratch || M > GATHER_MAX_ROWS || n_color <= 0) rows_scratch = nullptr;      // atomics fall-back
-  const int nb = embed_bwd_blocks(M);
-  DISPATCH_NCH(H, crct_launch((embed_image_bwd_kernel<NCH>), dim3(nb), dim3(256), 0, s, (const bf16_t*)dy,
-                                     (const bf16_t*)sum_saved, mean, rstd, loc, target, gamma, (bf16_t*)d_sum, d_color,
-                                     partials, M, H, drop_thr, drop_scale, drop_site, seed, rows_scratch,
-                                     rows_scratch ? idx_scratch : nullptr));
-  CRCT_CHECK_HIP(hipGetLastError());
-  if (rows_scratch) {
-    crct_launch(gather_sum_kernel, dim3(n_color), dim3(256), (size_t)M * sizeof(int), s, rows_scratch, idx_scratch, M, H, d_color,
-                       n_color, (const int*)nullptr, (float*)nullptr);
-    CRCT_CHECK_HIP(hipGetLastError());
-  }
-  // two finalize passes share the column-sum partial (index 2): b_loc and b_img
-  FinalizeArgs fa = {};
-  fa.out[0] = d_gamma; fa.out[1] = d_beta; fa.out[2] = d_bloc;
-  fa.stride[0] = fa.stride[1] = fa.stride[2] = 1;
-  for (int k = 0; k < 4; ++k) { fa.out[3 + k] = d_wloc ? d_wloc + k : nullptr; fa.stride[3 + k] = 4; }
-  fa.Q = 7; fa.nblk = nb * ROWS_PER_BLOCK; fa.H = H; fa.accumulate = 1; fa.partials = partials;
-  if (launch_finalize(fa, s)) return 1;
-  if (d_bimg) {
-    FinalizeArgs fb = {};
-    fb.out[0] = d_bimg; fb.stride[0] = 1; fb.Q = 1; fb.nblk = nb * ROWS_PER_BLOCK; fb.H = H; fb.accumulate = 1;
-    fb.partials = partials + (size_t)2 * nb * ROWS_PER_BLOCK * H;
-    return launch_finalize(fb, s);
-  }
-  return 0;
+  return embed_image_bwd_run<IMG_FEAT>(dy, sum_saved, mean, rstd, loc, target, nullptr, gamma, d_sum, d_color, d_wloc, d_bloc, nullptr,
+                                       d_bimg, d_gamma, d_beta, partials, M, H, drop_thr, drop_scale, drop_site, seed, rows_scratch,
+                                       idx_scratch, n_color, stream);
 }
 
 extern "C" int crct_embed_image_var_fwd(const float* loc, const int64_t* target, const float* areas, const float* w_loc,
@@ -1872,21 +1730,11 @@ extern "C" int crct_embed_image_var_fwd(const float* loc, const int64_t* target,
                                         const float* gamma, const float* beta, void* sum_out, void* y, float* mean, float* rstd,
                                         int M, int H, float eps, uint32_t drop_thr, float drop_scale, uint32_t drop_site,
                                         uint64_t seed, crct_stream_t stream) {
-  CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_image_var: H=%d must be a positive multiple of 8", H);
   CRCT_REQUIRE(!areas || (w_areas && b_areas), "embed_image_var: areas needs the areas_emp weight and bias");
-  if (M <= 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (areas) {
-    DISPATCH_NCH(H, crct_launch((embed_image_var_fwd_kernel<NCH, true>), dim3(row_grid(M, 2048)), dim3(256), 0, s, loc, target, areas,
-                                w_loc, b_loc, color, w_areas, b_areas, gamma, beta, (bf16_t*)sum_out, (bf16_t*)y, mean, rstd, M, H, eps,
-                                drop_thr, drop_scale, drop_site, seed));
-  } else {
-    DISPATCH_NCH(H, crct_launch((embed_image_var_fwd_kernel<NCH, false>), dim3(row_grid(M, 2048)), dim3(256), 0, s, loc, target, areas,
-                                w_loc, b_loc, color, w_areas, b_areas, gamma, beta, (bf16_t*)sum_out, (bf16_t*)y, mean, rstd, M, H, eps,
-                                drop_thr, drop_scale, drop_site, seed));
-  }
-  CRCT_CHECK_HIP(hipGetLastError());
-  return 0;
+  return areas ? embed_image_fwd_run<IMG_AREAS>(nullptr, loc, target, areas, w_loc, b_loc, color, w_areas, b_areas, gamma, beta, sum_out,
+                                                y, mean, rstd, M, H, eps, drop_thr, drop_scale, drop_site, seed, stream)
+               : embed_image_fwd_run<IMG_NONE>(nullptr, loc, target, nullptr, w_loc, b_loc, color, nullptr, nullptr, gamma, beta, sum_out,
+                                               y, mean, rstd, M, H, eps, drop_thr, drop_scale, drop_site, seed, stream);
 }
 
 extern "C" int crct_embed_image_var_bwd(const void* dy, const void* sum_saved, const float* mean, const float* rstd,
@@ -1895,38 +1743,10 @@ extern "C" int crct_embed_image_var_bwd(const void* dy, const void* sum_saved, c
                                         float* d_gamma, float* d_beta, float* partials, int M, int H, uint32_t drop_thr,
                                         float drop_scale, uint32_t drop_site, uint64_t seed, float* rows_scratch,
                                         int32_t* idx_scratch, int n_color, crct_stream_t stream) {
-  CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_image_var_bwd: H=%d must be a positive multiple of 8", H);
-  if (M <= 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (!idx_scratch || M > GATHER_MAX_ROWS || n_color <= 0) rows_scratch = nullptr;      // atomics fall-back
-  const int nb = embed_bwd_blocks(M);
-  if (areas) {
-    DISPATCH_NCH(H, crct_launch((embed_image_var_bwd_kernel<NCH, true>), dim3(nb), dim3(256), 0, s, (const bf16_t*)dy,
-                                (const bf16_t*)sum_saved, mean, rstd, loc, target, areas, gamma, d_color, partials, M, H, drop_thr,
-                                drop_scale, drop_site, seed, rows_scratch, rows_scratch ? idx_scratch : nullptr));
-  } else {
-    DISPATCH_NCH(H, crct_launch((embed_image_var_bwd_kernel<NCH, false>), dim3(nb), dim3(256), 0, s, (const bf16_t*)dy,
-                                (const bf16_t*)sum_saved, mean, rstd, loc, target, areas, gamma, d_color, partials, M, H, drop_thr,
-                                drop_scale, drop_site, seed, rows_scratch, rows_scratch ? idx_scratch : nullptr));
-  }
-  CRCT_CHECK_HIP(hipGetLastError());
-  if (rows_scratch) {
-    crct_launch(gather_sum_kernel, dim3(n_color), dim3(256), (size_t)M * sizeof(int), s, rows_scratch, idx_scratch, M, H, d_color,
-                n_color, (const int*)nullptr, (float*)nullptr);
-    CRCT_CHECK_HIP(hipGetLastError());
-  }
-  FinalizeArgs fa = {};
-  fa.out[0] = d_gamma; fa.out[1] = d_beta; fa.out[2] = d_bloc;
-  fa.stride[0] = fa.stride[1] = fa.stride[2] = 1;
-  for (int k = 0; k < 4; ++k) { fa.out[3 + k] = d_wloc ? d_wloc + k : nullptr; fa.stride[3 + k] = 4; }
-  fa.Q = 7; fa.nblk = nb * ROWS_PER_BLOCK; fa.H = H; fa.accumulate = 1; fa.partials = partials;
-  if (areas) { fa.out[7] = d_wareas; fa.stride[7] = 1; fa.Q = 8; }      // areas_emp.weight [H][1]
-  if (launch_finalize(fa, s)) return 1;
-  if (areas && d_bareas) {       // the column-sum partial (index 2) once more: b_areas
-    FinalizeArgs fb = {};
-    fb.out[0] = d_bareas; fb.stride[0] = 1; fb.Q = 1; fb.nblk = nb * ROWS_PER_BLOCK; fb.H = H; fb.accumulate = 1;
-    fb.partials = partials + (size_t)2 * nb * ROWS_PER_BLOCK * H;
-    return launch_finalize(fb, s);
-  }
-  return 0;
+  return areas ? embed_image_bwd_run<IMG_AREAS>(dy, sum_saved, mean, rstd, loc, target, areas, gamma, nullptr, d_color, d_wloc, d_bloc,
+                                                d_wareas, d_bareas, d_gamma, d_beta, partials, M, H, drop_thr, drop_scale, drop_site, seed,
+                                                rows_scratch, idx_scratch, n_color, stream)
+               : embed_image_bwd_run<IMG_NONE>(dy, sum_saved, mean, rstd, loc, target, nullptr, gamma, nullptr, d_color, d_wloc, d_bloc,
+                                               nullptr, nullptr, d_gamma, d_beta, partials, M, H, drop_thr, drop_scale, drop_site, seed,
+                                               rows_scratch, idx_scratch, n_color, stream);
 }

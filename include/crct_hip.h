@@ -117,7 +117,7 @@ int crct_gemm_group_target_workgroups(int n);
  * fetches ~1/8 of the group's operand panels.  Results are identical; measured neutral to slightly slower in the step
  * (EXPERIMENTS.md round 3), kept as the developer A/B switch behind that statement (bench.py --wgrad-concat). */
 int crct_gemm_group_concat(int on);
-/* Test hook: on != 0 makes crct_embed_text_bwd launch the position / type sums and the word-table scatter as two kernels one after
+/* Test hook: on != 0 makes crct_embed_text_bwd_indexed launch the position / type sums and the word-table sums as two kernels one after
  * the other instead of one merged launch (identical results; tests/test_kernels_gpu.py, bench.py --embed-scatter-split). */
 void crct_embed_scatter_split(int on);
 /* Kernel configuration of the grouped weight-gradient launches of the step: 4 (128 x 128, see gemm.hip) is the only one built.
@@ -360,20 +360,11 @@ int crct_embed_text_fwd(const int64_t* ids, const int64_t* segs, const float* lo
  * position / type tables by one workgroup per table row; with rows_scratch == NULL all three fall back to fp32 atomics.  Reduces the
  * loc-Linear and LayerNorm parameter gradients.  partials: fp32 [9][4 * nblk][H], nblk = crct_layernorm_bwd_blocks(B*T)
  * (7 row sets + the sums of token types 0 and 1).
- * n_types = rows of the type table.  All parameter-gradient outputs are ACCUMULATED (caller zeroes per step). */
-int crct_embed_text_bwd(const void* dy, const void* sum_saved, const float* mean, const float* rstd,
-                        const int64_t* ids, const int64_t* segs, const float* loc, const float* gamma,
-                        float* d_word, float* d_pos, float* d_type, float* d_wloc, float* d_bloc,
-                        float* d_gamma, float* d_beta, float* partials,
-                        int B, int T, int H, int n_pos,
-                        uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
-                        float* rows_scratch, int32_t* idx_scratch, int n_types,
-                        crct_stream_t stream);
-/* The same with an index for the word-table sums: word_index = int32 [2][n_vocab] in device memory, ALL ZERO on entry and all zero again on
- * exit (the kernels clean up what they set).  The row kernel leaves the first and last token row of every id there; the scatter kernel then
- * lets every wave that is not its id's first row return at once and scans only [first, last] for the others -- same owner, same summation
- * order, same bits as crct_embed_text_bwd, without its scan of all B*T ids per row (B*T = 9 920: 320 -> 35 us).  NULL / n_vocab 0: the scan. */
-void crct_embed_word_index(int on);      /* test / timing hook: 0 = crct_embed_text_bwd_indexed ignores its index (default 1) */
+ * n_types = rows of the type table.  All parameter-gradient outputs are ACCUMULATED (caller zeroes per step).
+ * word_index = int32 [2][n_vocab] in device memory, ALL ZERO on entry and all zero again on exit (the kernels clean up what they set);
+ * required (non-NULL, n_vocab > 0) with rows_scratch and idx_scratch, or the call fails before any launch.  The row kernel leaves the
+ * first and last token row of every id there; the word-table sums then let every wave that is not its id's first row return at once
+ * and scan only [first, last] for the others. */
 int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved, const float* mean, const float* rstd,
                                 const int64_t* ids, const int64_t* segs, const float* loc, const float* gamma,
                                 float* d_word, float* d_pos, float* d_type, float* d_wloc, float* d_bloc,

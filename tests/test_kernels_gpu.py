@@ -1140,15 +1140,15 @@ def _ln_backward64(sum_b, dy, keep_scale, gamma):
 
 
 _TEXT_V, _TEXT_NPOS, _TEXT_NTYPES = 4099, 512, 5
-# (B, T) -> (H, dropout p): configs[1]; the test's original small shapes; plotqa-real (word scan above 64 KiB of LDS); one token; the NCH 1
-# and NCH 4 row widths; positions up to 511; 16 384 rows > GATHER_MAX_ROWS (every table sum through float atomics)
+# (B, T) -> (H, dropout p): configs[1]; the test's original small shapes; plotqa-real; one token; the NCH 1 and NCH 4 row widths; positions
+# up to 511; 14 336 rows (the word-table sums above 64 KiB of LDS); 16 384 rows > GATHER_MAX_ROWS (every table sum through float atomics)
 _TEXT_CASES = {(80, 20): (768, 0.1), (7, 9): (768, 0.0), (64, 40): (768, 0.0), (80, 124): (768, 0.1), (1, 1): (768, 0.0),
-               (3, 7): (64, 0.1), (2, 9): (2048, 0.1), (1, 512): (768, 0.0), (32, 512): (768, 0.1)}
+               (3, 7): (64, 0.1), (2, 9): (2048, 0.1), (1, 512): (768, 0.0), (112, 128): (768, 0.1), (32, 512): (768, 0.1)}
 _GATHER_MAX_ROWS = 15360      # rowops.hip: above it the table sums fall back to float atomics
 
 
 def _text_batch(B, T, seed):
-    """ids / segments / loc crafted for the gates and the word-gradient scan's edge cases: [PAD]-like id 0 on half of all rows (hundreds of
+    """ids / segments / loc crafted for the gates and the word-gradient sums' edge cases: [PAD]-like id 0 on half of all rows (hundreds of
     matches: the heavy path), [CLS]-like id 1 once per batch row, four heavy ids (9 / 15 / 16 / 17 matches) whose first rows fill one 4-row
     workgroup, an id whose matches straddle a 64-row and a 256-row window (light, and heavy), ids with exactly 1, 2, 3, 8, 9, 11, 15, 16 and
     17 matches, id V - 1, an id that first occurs in the last row; segments -1 / 0 / 1 / 2.. n_types - 1 with batch rows without a
@@ -1244,12 +1244,12 @@ def _text_terms(tab, ids, segs, loc):
 
 
 @pytest.mark.parametrize("B,T", list(_TEXT_CASES))
-def test_word_gradient_scan_matches_the_atomic_scatter_and_is_reproducible(B, T, gemm_path):
-    """crct_embed_text_fwd / _bwd (BertEmbeddingLocation.forward, vilbert.py:320-358) against fp64, in every form of the backward: indexed
-    (the step engine's call), the scan (no index), the two-launch test form and the float-atomics fall-back (rows_scratch = NULL).  The
-    word_embeddings gradient is the index_add of the token-row gradients (vilbert.py:300 has no padding_idx, so [PAD] collects every padded
-    position); the fixed-order forms -- light ids by one wave, heavy ids shared by the workgroup -- give the same bits as each other and when
-    repeated, and the float atomics the same sums to rounding."""
+def test_word_gradient_indexed_split_and_atomic_forms_agree_and_are_reproducible(B, T, gemm_path):
+    """crct_embed_text_fwd / _bwd_indexed (BertEmbeddingLocation.forward, vilbert.py:320-358) against fp64, in every form of the backward:
+    indexed (the step engine's call), the two-launch test form and the float-atomics fall-back (rows_scratch = NULL).  The word_embeddings
+    gradient is the index_add of the token-row gradients (vilbert.py:300 has no padding_idx, so [PAD] collects every padded position); the
+    fixed-order forms -- light ids by one wave, heavy ids shared by the workgroup -- give the same bits as each other and when repeated, and
+    the float atomics the same sums to rounding."""
     # no GEMM here: the test runs under both settings of the GEMM-path switch (gemm_path), which must not reach these kernels
     lib = L.load()
     H, p = _TEXT_CASES[(B, T)]
@@ -1316,40 +1316,32 @@ def test_word_gradient_scan_matches_the_atomic_scatter_and_is_reproducible(B, T,
             partials.data_ptr(), B, T, H, n_pos, thr, sc, st, seed, L.ptr(rows), idx.data_ptr(), n_types]
         if mode == "split":
             lib.crct_embed_scatter_split(1)
-        try:
-            if mode == "indexed":      # crct_embed_text_bwd_indexed: first / last row per id left by the row kernel, no scan of all ids per row
-                rc = lib.crct_embed_text_bwd_indexed(*a, index.data_ptr(), V, stream)
-            else:
-                rc = lib.crct_embed_text_bwd(*a, stream)
+        try:      # first / last row per id left by the row kernel
+            rc = lib.crct_embed_text_bwd_indexed(*a, index.data_ptr(), V, stream)
         finally:
             lib.crct_embed_scatter_split(0)
         L.check(rc, "embed_text_bwd " + mode)
         torch.cuda.synchronize()
-        if mode == "indexed":
-            assert int(index.abs().max()) == 0      # the index is all zero again after every call
+        assert int(index.abs().max()) == 0      # the index is all zero again after every call
         return {k: v.cpu() for k, v in out.items()}
 
-    got = {m: run(m) for m in ("indexed", "scan", "split", "atomic")}
+    got = {m: run(m) for m in ("indexed", "split", "atomic")}
     for m, o in got.items():
         for k in shapes:
             _assert_sums(o[k], ref[k], mag[k], "%s d_%s" % (m, k))
             untouched = ~touched[k]
             assert torch.equal(o[k][untouched], pre[k].cpu()[untouched]), "%s d_%s: a row no token reaches changed" % (m, k)
-    w1, p1, t1 = (got["scan"][k] for k in ("word", "pos", "type"))
+    w1 = got["indexed"]["word"]
     assert float((w1[0] - pre["word"][0].cpu()).abs().max()) > 0 or M == 1
     if M <= _GATHER_MAX_ROWS:
-        # the fixed-order forms: the same bits as each other (one launch or two, index or scan) and when repeated -- the index twice
-        again = run("scan")
-        for k in shapes:
-            assert torch.equal(got["scan"][k], again[k]), k
-            assert torch.equal(got["scan"][k], got["split"][k]), k
-            assert torch.equal(got["scan"][k], got["indexed"][k]), k
+        # the fixed-order forms: the same bits as each other (one launch or two) and when repeated
         again = run("indexed")
         for k in shapes:
             assert torch.equal(got["indexed"][k], again[k]), k
+            assert torch.equal(got["indexed"][k], got["split"][k]), k
     # ... and the float atomics: the same sums up to their arrival-order rounding
     for k in ("word", "pos", "type"):
-        a, b = got["scan"][k], got["atomic"][k]
+        a, b = got["indexed"][k], got["atomic"][k]
         assert float((a - b).abs().max()) <= 2e-5 * float(b.abs().max()) + 1e-6, k
 
 

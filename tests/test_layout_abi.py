@@ -113,6 +113,16 @@ def test_struct_mirrors_and_error_path():
     assert lib.crct_gemm_pick_tile(1600, 3072) in (0, 1, 2, 3)
 
 
+def test_embed_text_bwd_refuses_scratch_without_a_word_index():
+    # the fixed-order word-table sums need the first / last-row index: without it the call fails before anything touches a GPU
+    lib = L.load()
+    B, T, H, n_pos, n_types = 2, 3, 64, 8, 4
+    for index, n_vocab in ((None, 100), (16, 0)):
+        a = [16] * 16 + [B, T, H, n_pos, 0, 1.0, 0, 0, 16, 16, n_types, index, n_vocab, None]
+        assert lib.crct_embed_text_bwd_indexed(*a) != 0
+        assert b"word index" in lib.crct_last_error()
+
+
 def test_only_built_gemm_configurations_are_accepted():
     lib = L.load()
     # crct_gemm_class_config: an id that is not built is refused (-1) and leaves the entry; a built one round-trips
