@@ -27,6 +27,7 @@ all-reduce (train.py:181-189).  Here:
     accumulates in fp32 (biases, LayerNorm, embeddings, heads: 5 % of the elements) are written back and the
     fp32 views of the Linear weight gradients, which then exist in the bf16 buffer only, are filled with NaN:
     a reader gets the reduced value or a NaN, never a local or stale gradient.  True / False force either.
+    (Clipping by the global norm does not need the write-back: ``crct.optim.clip_grad_norm_`` reads the bf16 buffer too.)
     ``grad_dtype=torch.float32`` is the reference's payload;
   * the 1/world averaging is folded into the loss-gradient seeds (no extra pass over the gradients);
   * tensors that never receive a gradient sit at the tail of the layout and are never sent;

@@ -187,6 +187,9 @@ PROTOTYPES = {
     "crct_adamw_plan": (c_i64, [vp, C.c_int, vp, vp, c_i64]),
     "crct_adamw_step": (C.c_int, [vp] * 11 + [c_i64, c_f32, c_f32, c_f32, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "crct_adamw_advance": (C.c_int, [vp, vp, vp]),
+    "crct_grad_sumsq": (C.c_int, [vp] * 6 + [c_i64, vp, C.c_int, C.c_int, vp]),
+    "crct_grad_norm_finalize": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, c_f32, vp, vp, vp, vp, vp]),
+    "crct_scale_runs": (C.c_int, [vp] * 6 + [c_i64, C.c_int, vp]),
     "crct_engine_create": (vp, [C.POINTER(ModelDims), C.c_char_p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "crct_engine_create_variant": (vp, [C.POINTER(ModelDims), C.c_char_p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Variant)]),
     "crct_engine_set_areas": (C.c_int, [vp, vp]),

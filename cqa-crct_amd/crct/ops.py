@@ -322,3 +322,38 @@ def adamw_plan(seg_len):
     blk_off = torch.empty(n, dtype=torch.int64)
     lib.crct_adamw_plan(lens.data_ptr(), lens.numel(), blk_seg.data_ptr(), blk_off.data_ptr(), n)
     return blk_seg, blk_off
+
+
+def grad_sumsq(grads, seg_off, seg_len, blk_seg, blk_off, partials=None, norm_kind=0, max_workgroups=0):
+    """crct_grad_sumsq over the chunk table of ``adamw_plan``: ``grads`` is the flat gradient buffer, fp32 or bf16 (the dtype picks
+    the source).  Returns partials fp32 [n_blk]: per chunk the sum of squares (norm_kind 0) or max |g| (1, NaN propagating)."""
+    if grads.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("grad_sumsq: fp32 or bf16 gradient buffer expected (got %s)" % grads.dtype)
+    n_blk = blk_seg.numel()
+    if partials is None:
+        partials = torch.empty(n_blk, dtype=torch.float32, device=grads.device)
+    bf = grads.dtype == torch.bfloat16
+    L.check(L.load().crct_grad_sumsq(None if bf else grads.data_ptr(), grads.data_ptr() if bf else None, seg_off.data_ptr(),
+                                     seg_len.data_ptr(), blk_seg.data_ptr(), blk_off.data_ptr(), n_blk, _chk(partials, torch.float32).data_ptr(),
+                                     int(norm_kind), int(max_workgroups), L.current_stream()), "grad_sumsq")
+    return partials
+
+
+def grad_norm_finalize(partials, blk_seg, n_seg, max_norm, norm_kind=0, grad_scale=None, mul=None, seg_norm=True):
+    """crct_grad_norm_finalize: (out fp32 [2] = (norm, clip coefficient), seg_norm fp32 [n_seg] or None), all on the device.
+    ``grad_scale`` / ``mul``: optional device fp32 scalars (the norm is divided by the first, the coefficient multiplied by the second)."""
+    out = torch.empty(2, dtype=torch.float32, device=partials.device)
+    per = torch.empty(n_seg, dtype=torch.float32, device=partials.device) if seg_norm else None
+    L.check(L.load().crct_grad_norm_finalize(_chk(partials, torch.float32).data_ptr(), blk_seg.data_ptr(), blk_seg.numel(), int(n_seg),
+                                             int(norm_kind), float(max_norm), L.ptr(_chk(grad_scale, torch.float32)),
+                                             L.ptr(_chk(mul, torch.float32)), out.data_ptr(), L.ptr(per), L.current_stream()),
+            "grad_norm_finalize")
+    return out, per
+
+
+def scale_runs(grads, coef, seg_off, seg_len, blk_seg, blk_off, max_workgroups=0):
+    """crct_scale_runs: grads (flat fp32) *= coef (device fp32 scalar) over the chunk table, in place."""
+    L.check(L.load().crct_scale_runs(_chk(grads, torch.float32).data_ptr(), _chk(coef, torch.float32).data_ptr(), seg_off.data_ptr(),
+                                     seg_len.data_ptr(), blk_seg.data_ptr(), blk_off.data_ptr(), blk_seg.numel(), int(max_workgroups),
+                                     L.current_stream()), "scale_runs")
+    return grads

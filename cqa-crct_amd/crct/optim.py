@@ -90,6 +90,9 @@ class FusedAdamW(torch.optim.Optimizer):
         self._step_dev, self._amp_arg, self._amp_keep = None, None, None
         self._fp8_keep = None
         self._g16 = None                     # bf16 gradient source of the running update (data-parallel bf16 exchange), else None
+        # clip_grad_norm_: the pending clip coefficient (device scalar, folded into exactly the next step()) and what it came from
+        self._clip = None
+        self._clip_partials = self._clip_seg_norms = self._clip_keep = None
         # crct/ddp.py: while THIS optimizer is alive and covers every gradient, a bf16 exchange need not write the weight gradients
         # back to fp32 (a weak reference: an optimizer that was built and discarded must not change what .grad holds)
         import weakref
@@ -328,6 +331,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._last = None
         self._upload_done = None
         self._fp8_keep = self._events = self._opt_stream = self._seg_blocks = None
+        self._clip = self._clip_partials = self._clip_seg_norms = self._clip_keep = None
         self._step_dev = self._step_dev.to(dev) if self._step_dev is not None else None
 
     @torch.no_grad()
@@ -344,6 +348,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._g16 is not None and (amp or inv_scale is not None):
             raise RuntimeError("GradScaler / unscaling reads the fp32 .grad views: construct FlatGradDDP(..., materialize_grads=True) "
                                "(or grad_dtype=torch.float32) when training with a GradScaler")
+        inv_scale = self._take_clip_coefficient(inv_scale)
         if self.overlap and not amp and (self._seg_blocks is not None or self._plan_overlap()):
             cur = torch.cuda.current_stream()
             self._opt_stream = core.aux_stream()          # the engine's auxiliary stream (re-fetched: an engine rebuilt for a larger batch has new streams)
@@ -416,6 +421,94 @@ class FusedAdamW(torch.optim.Optimizer):
             core._grads_dirty = False                         # until the next backward pass
         return loss
 
+    # ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_ on the flat buffers)
+    def _grad_buffer(self):
+        """The buffer the next step() reads its gradients from: the data-parallel exchange's bf16 buffer, else the fp32 one."""
+        ddp = getattr(self.core, "_ddp", None)
+        g16 = ddp.grad_source() if ddp is not None else None
+        return g16 if g16 is not None else self.core.flat_grads
+
+    @torch.no_grad()
+    def clip_grad_norm_(self, max_norm, norm_type=2.0, error_if_nonfinite=False, grad_scaler=None, in_place=False):
+        """``torch.nn.utils.clip_grad_norm_`` over every gradient this optimizer updates: one streaming pass over the buffer the
+        next ``step()`` reads (the bf16 exchange buffer of ``FlatGradDDP`` when that holds the reduced gradients, else the flat
+        fp32 one) and one small launch.  Returns the total norm as a 0-d device tensor; nothing waits for the GPU unless
+        ``error_if_nonfinite`` is set.  Call it after ``backward()`` and before ``step()``.
+
+        By default NOTHING IS RESCALED: ``.grad`` keeps the unclipped values, and the clip coefficient (a device scalar) is
+        multiplied into the gradients inside the update kernel by exactly the next ``step()``; that ``step()`` and ``zero_grad()``
+        drop it.  ``in_place=True`` multiplies the fp32 gradient buffer now instead, for callers that read ``.grad`` afterwards
+        (refused while the gradients live in the bf16 exchange buffer: the fp32 views of the Linear weights are NaN there).
+
+        ``grad_scaler``: the ``torch.amp.GradScaler`` whose factor is still on the gradients (the call sits between
+        ``scaler.scale(loss).backward()`` and ``scaler.step(optimizer)``, without ``scaler.unscale_``): the norm returned and
+        compared with ``max_norm`` is then the norm of the unscaled gradients.  ``norm_type``: 2 or ``inf``.
+        ``max_norm=float('inf')`` never clips: a cheap gradient-health probe (see ``grad_norms()``)."""
+        norm_type = float(norm_type)
+        if norm_type == 2.0:
+            kind = 0
+        elif norm_type == float("inf"):
+            kind = 1
+        else:
+            raise ValueError("clip_grad_norm_: norm_type must be 2 or inf (got %r)" % (norm_type,))
+        if self.early:
+            raise RuntimeError("clip_grad_norm_: in early mode the update of a segment starts before the last gradient exists, so a "
+                               "global norm cannot be applied; call set_early(False)")
+        self._follow_device()
+        core = self.core
+        src = self._grad_buffer()
+        if in_place and src is not core.flat_grads:
+            raise ValueError("clip_grad_norm_(in_place=True) rescales the fp32 .grad views, which do not hold the exchanged bf16 "
+                             "gradients: use the default (deferred) mode, or construct FlatGradDDP(..., materialize_grads=True)")
+        scale = None
+        if grad_scaler is not None and grad_scaler.is_enabled():
+            scale = grad_scaler._get_scale_async()
+            if scale is None:
+                raise RuntimeError("clip_grad_norm_(grad_scaler=...): the scaler has not scaled a loss yet; call it between "
+                                   "scaler.scale(loss).backward() and scaler.step(optimizer)")
+            scale = scale.to(device=src.device, dtype=torch.float32).reshape(1)
+        if self._clip_partials is None or self._clip_partials.numel() != self._blk_seg.numel():
+            self._clip_partials = torch.empty(self._blk_seg.numel(), dtype=torch.float32, device=src.device)
+        ops.grad_sumsq(src, self._seg_off, self._seg_len, self._blk_seg, self._blk_off, partials=self._clip_partials, norm_kind=kind)
+        out, per = ops.grad_norm_finalize(self._clip_partials, self._blk_seg, len(self._segs), max_norm, norm_kind=kind, grad_scale=scale)
+        self._clip_seg_norms = per
+        self._clip = None
+        if in_place:
+            ops.scale_runs(core.flat_grads, out[1:2], self._seg_off, self._seg_len, self._blk_seg, self._blk_off)
+        else:
+            self._clip = dict(out=out, kind=kind, max_norm=float(max_norm), scale=scale)
+        self._clip_keep = (out, scale)          # alive until the kernels that read them have been launched
+        if error_if_nonfinite and not bool(torch.isfinite(out[0])):
+            self._clip = None
+            raise RuntimeError("The total norm of order %s for gradients is non-finite, so it cannot be clipped" % norm_type)
+        return out[0]
+
+    def _take_clip_coefficient(self, inv_scale):
+        """The ``inv_scale_dev`` argument of this step's launches: the pending clip coefficient (consumed here), times the caller's
+        ``inv_scale`` where both exist (the finalize launch again, over the partials it kept)."""
+        clip, self._clip = self._clip, None
+        if clip is None:
+            return inv_scale
+        if inv_scale is None:
+            coef = clip["out"][1:2]
+        else:
+            mul = inv_scale.to(device=self._clip_partials.device, dtype=torch.float32).reshape(1)
+            out, _ = ops.grad_norm_finalize(self._clip_partials, self._blk_seg, len(self._segs), clip["max_norm"], norm_kind=clip["kind"],
+                                            grad_scale=clip["scale"], mul=mul, seg_norm=False)
+            coef = out[1:2]
+        self._clip_keep = (clip["out"], clip["scale"], coef)
+        return coef
+
+    def grad_norms(self):
+        """Per-tensor gradient norms of the last ``clip_grad_norm_`` pass (its ``norm_type``, unscaled like its result): fp32 device
+        tensor ``[len(grad_norm_names)]``; None before the first pass."""
+        return self._clip_seg_norms
+
+    @property
+    def grad_norm_names(self):
+        """State-dict keys of the tensors ``grad_norms()`` lists, in its order."""
+        return [e.name for e in self._segs]
+
     def synchronize(self):
         """Order the current stream after an in-flight overlapped update (before reading weights outside forward)."""
         if self._opt_stream is not None:
@@ -423,6 +516,7 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none=True):
         # one memset; .grad views stay attached (set_to_none would only force a re-attach next step)
+        self._clip = None                                     # a clip coefficient belongs to the gradients it was computed from
         if getattr(self, "_grads_cleared", False) and not self.core._grads_dirty:
             return                                            # step() has already zeroed them (fuse_zero_grad)
         if self.overlap and self._opt_stream is not None:
@@ -462,6 +556,19 @@ class FusedAdamW(torch.optim.Optimizer):
         self._step = step
         self._step_dev = None
         self._last = None
+
+
+def clip_grad_norm_(model_or_optimizer, max_norm, **kw):
+    """``torch.nn.utils.clip_grad_norm_`` for a model trained by ``FusedAdamW``: finds the optimizer attached to the model (or
+    takes the optimizer itself, or a ``FlatGradDDP`` wrapper) and calls its ``clip_grad_norm_``; see there for the keywords and
+    for what happens to ``.grad`` (nothing, by default)."""
+    opt = model_or_optimizer
+    if not isinstance(opt, FusedAdamW):
+        ref = getattr(_crct_core(model_or_optimizer), "_fused_optimizer", None)
+        opt = ref() if callable(ref) else None
+        if opt is None:
+            raise RuntimeError("clip_grad_norm_: no live FusedAdamW is attached to this model (crct.optim.get_optimizer builds one)")
+    return opt.clip_grad_norm_(max_norm, **kw)
 
 
 def get_optimizer(params, dialog_encoder, language_weights_json=None):

@@ -171,6 +171,213 @@ __global__ __launch_bounds__(256) void zero_runs_kernel(float* __restrict__ g, c
     for (int64_t i = head + nv * 4 + threadIdx.x; i < n; i += 256) g[base + i] = 0.f;
   }
 }
+// ---- global-norm gradient clipping (crct_grad_sumsq / crct_grad_norm_finalize / crct_scale_runs) ----------------------
+// One streaming, read-only pass over the gradient buffer the next update will consume, walked by the update's own chunk
+// table: one fp32 partial per chunk, no atomics and no hand-off between workgroups, so every result is bit-reproducible.
+// KIND 0 = sum of squares, KIND 1 = max |g|.  Both work on non-negative values, and the maximum is taken on the BIT
+// PATTERNS (for non-negative floats the unsigned order is the float order, with every NaN above +inf): a NaN anywhere
+// comes out as NaN, which fmaxf alone would drop.
+template <int KIND>
+__device__ __forceinline__ float nrm_join(float a, float b) {
+  if (KIND) {
+    const uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
+    return __uint_as_float(ua > ub ? ua : ub);
+  }
+  return a + b;
+}
+// four consecutive elements -> one value.  The fused multiply-adds are spelled out: the fp32 and the bf16 source must round
+// alike (two steps from either buffer are compared bit for bit), which a contraction left to the compiler does not promise.
+template <int KIND>
+__device__ __forceinline__ float nrm_quad(float x0, float x1, float x2, float x3) {
+  if (KIND) return nrm_join<1>(nrm_join<1>(nrm_join<1>(fabsf(x0), fabsf(x1)), fabsf(x2)), fabsf(x3));
+  return fmaf(x3, x3, fmaf(x2, x2, fmaf(x1, x1, x0 * x0)));
+}
+template <int KIND>
+__device__ __forceinline__ float nrm_wave(float v) {       // the DPP tree of wave_sum / wave_max (common.hip.h) with nrm_join
+  v = nrm_join<KIND>(v, dpp_f32<0xB1>(v));
+  v = nrm_join<KIND>(v, dpp_f32<0x4E>(v));
+  v = nrm_join<KIND>(v, dpp_f32<0x141>(v));
+  v = nrm_join<KIND>(v, dpp_f32<0x140>(v));
+  return nrm_join<KIND>(nrm_join<KIND>(lane_f32(v, 0), lane_f32(v, 16)), nrm_join<KIND>(lane_f32(v, 32), lane_f32(v, 48)));
+}
+// A chunk (<= 4096 elements of one tensor, 16-byte aligned base) is 1024 quads.  Every lane loads 16 bytes at a time -- one quad
+// of fp32, two of bf16 -- and leaves its quad values in LDS; from there on the tree depends on neither the source format nor
+// the workgroup that runs it: lane t joins quads t, t + 256, t + 512, t + 768, then the wave tree, then the four waves.
+// Longest chain of dependent fp32 roundings: 4 (quad) + 3 + 6 (wave) + 2 = 15.  Quads past the end of the chunk count as 0.
+template <int KIND, bool BF16>
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, const bf16_t* __restrict__ g16,
+                                                         const int64_t* __restrict__ seg_off, const int64_t* __restrict__ seg_len,
+                                                         const int32_t* __restrict__ blk_seg, const int64_t* __restrict__ blk_off,
+                                                         float* __restrict__ partials, int n_blk) {
+  __shared__ float quad[1024];
+  __shared__ float wave_part[4];
+  const int tid = threadIdx.x;
+  for (int blk = blockIdx.x; blk < n_blk; blk += gridDim.x) {
+    const int sgi = blk_seg[blk];
+    const int64_t off = blk_off[blk], base = seg_off[sgi] + off;
+    int64_t n = seg_len[sgi] - off;
+    if (n > ADAMW_CHUNK) n = ADAMW_CHUNK;
+    if (BF16) {
+      typedef unsigned u4_t __attribute__((ext_vector_type(4)));
+      float x[2][8];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int64_t i = (int64_t)k * 2048 + tid * 8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[k][j] = 0.f;
+        if (i + 8 <= n) {      // streamed once: non-temporal, as in adamw_kernel
+          const u4_t raw = __builtin_nontemporal_load(reinterpret_cast<const u4_t*>(g16 + base + i));
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            x[k][2 * j] = bf2f((bf16_t)(raw[j] & 0xffff));
+            x[k][2 * j + 1] = bf2f((bf16_t)(raw[j] >> 16));
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (i + j < n) x[k][j] = bf2f(g16[base + i + j]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        *reinterpret_cast<float2*>(&quad[k * 512 + tid * 2]) = make_float2(nrm_quad<KIND>(x[k][0], x[k][1], x[k][2], x[k][3]),
+                                                                           nrm_quad<KIND>(x[k][4], x[k][5], x[k][6], x[k][7]));
+    } else {
+      float x[4][4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int64_t i = (int64_t)k * 1024 + tid * 4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[k][j] = 0.f;
+        if (i + 4 <= n) {
+          const f4_t v = __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(g + base + i));
+          x[k][0] = v[0]; x[k][1] = v[1]; x[k][2] = v[2]; x[k][3] = v[3];
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (i + j < n) x[k][j] = g[base + i + j];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) quad[k * 256 + tid] = nrm_quad<KIND>(x[k][0], x[k][1], x[k][2], x[k][3]);
+    }
+    __syncthreads();
+    float a = nrm_join<KIND>(nrm_join<KIND>(nrm_join<KIND>(quad[tid], quad[tid + 256]), quad[tid + 512]), quad[tid + 768]);
+    a = nrm_wave<KIND>(a);
+    if ((tid & 63) == 0) wave_part[tid >> 6] = a;
+    __syncthreads();           // also: every read of quad[] is done before the next chunk overwrites it
+    if (tid == 0) partials[blk] = nrm_join<KIND>(nrm_join<KIND>(wave_part[0], wave_part[1]), nrm_join<KIND>(wave_part[2], wave_part[3]));
+  }
+}
+
+// fp64 from here on.  kind 1: the larger value, a NaN on either side wins.
+__device__ __forceinline__ double nrm_join64(double a, double b, int kind) {
+  if (kind) return (a != a) ? a : ((b != b) ? b : (a > b ? a : b));
+  return a + b;
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, 0xf, 0xf, true);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), CTRL, 0xf, 0xf, true);
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double lane_f64(double v, int lane) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, lane);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), lane);
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double nrm_wave64(double v, int kind) {
+  v = nrm_join64(v, dpp_f64<0xB1>(v), kind);
+  v = nrm_join64(v, dpp_f64<0x4E>(v), kind);
+  v = nrm_join64(v, dpp_f64<0x141>(v), kind);
+  v = nrm_join64(v, dpp_f64<0x140>(v), kind);
+  return nrm_join64(nrm_join64(lane_f64(v, 0), lane_f64(v, 16), kind), nrm_join64(lane_f64(v, 32), lane_f64(v, 48), kind), kind);
+}
+// First index i of the ascending a[0 .. n) with a[i] >= key, found by the whole wave: 64 probes per round instead of one (four
+// rounds of one load each for 60 k chunks; a one-lane bisection is 16 dependent loads).  Every lane returns the same value.
+__device__ __forceinline__ int wave_lower_bound(const int32_t* __restrict__ a, int n, int key, int lane) {
+  int lo = 0, hi = n;                                   // the answer lies in [lo, hi]
+  while (hi > lo) {
+    const int step = (hi - lo + 63) / 64;
+    const int idx = lo + step * (lane + 1) - 1;         // ascending over the lanes, so the lanes that see "less" are the first cnt
+    const bool less = idx < hi && a[idx] < key;
+    const int cnt = __popcll(__ballot(less));
+    const int top = lo + step * (cnt + 1) - 1;          // the first probe that is not less (or lies behind the range)
+    lo += step * cnt;
+    hi = top < hi ? top : hi;
+  }
+  return lo;
+}
+// sum / max of p[b0 + lane], p[b0 + lane + stride], ... below b1 in that order, eight loads in flight at a time (0 is neutral for both
+// kinds: every partial is non-negative)
+__device__ __forceinline__ double nrm_strided64(const float* __restrict__ p, int b0, int b1, int stride, int kind) {
+  double a = 0.0;
+  for (int i = b0; i < b1; i += 8 * stride) {
+    float x[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = (i + k * stride < b1) ? p[i + k * stride] : 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a = nrm_join64(a, (double)x[k], kind);
+  }
+  return a;
+}
+// One small launch, fixed order, no hand-off between its workgroups.  Workgroup 0, the total: lane t of the workgroup takes partials
+// t, t + 1024, ..., then the wave tree, then the 16 waves in order; from it the coefficient, torch's clip_grad_norm_ arithmetic in
+// fp32 and not special-cased: an inf norm gives 0, a NaN norm gives NaN, a norm that needs no clipping gives exactly 1.  Workgroups
+// 1 ..: a wave per tensor, whose chunks are one run of the table (crct_adamw_plan lists them tensor by tensor).
+__global__ __launch_bounds__(1024) void grad_norm_finalize_kernel(const float* __restrict__ partials, const int32_t* __restrict__ blk_seg,
+                                                                  int n_blk, int n_seg, int kind, float max_norm,
+                                                                  const float* __restrict__ grad_scale, const float* __restrict__ mul,
+                                                                  float* __restrict__ out, float* __restrict__ seg_norm) {
+  __shared__ double wave_part[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double gs = grad_scale ? (double)grad_scale[0] : 1.0;
+  if (blockIdx.x > 0) {
+    const int s = ((int)blockIdx.x - 1) * 16 + wave;
+    if (s >= n_seg) return;
+    const int b0 = wave_lower_bound(blk_seg, n_blk, s, lane), b1 = wave_lower_bound(blk_seg, n_blk, s + 1, lane);
+    const double v = nrm_wave64(nrm_strided64(partials, b0 + lane, b1, 64, kind), kind);
+    if (lane == 0) seg_norm[s] = (float)((kind ? v : sqrt(v)) / gs);
+    return;
+  }
+  const double a = nrm_wave64(nrm_strided64(partials, tid, n_blk, 1024, kind), kind);
+  if (lane == 0) wave_part[wave] = a;
+  __syncthreads();
+  if (tid == 0) {
+    double t = wave_part[0];
+    for (int w = 1; w < 16; ++w) t = nrm_join64(t, wave_part[w], kind);
+    const float norm = (float)((kind ? t : sqrt(t)) / gs);
+    float c = max_norm / (norm + 1e-6f);
+    c = c > 1.0f ? 1.0f : c;
+    out[0] = norm;
+    out[1] = c * (mul ? mul[0] : 1.0f);
+  }
+}
+
+// g *= *coef over the chunk table, one fp32 product per element.  A coefficient of exactly 1 (nothing to clip: the common step)
+// ends every workgroup before its first gradient load.
+__global__ __launch_bounds__(256) void scale_runs_kernel(float* __restrict__ g, const float* __restrict__ coef,
+                                                         const int64_t* __restrict__ seg_off, const int64_t* __restrict__ seg_len,
+                                                         const int32_t* __restrict__ blk_seg, const int64_t* __restrict__ blk_off, int n_blk) {
+  const float c = coef[0];
+  if (c == 1.0f) return;
+  for (int blk = blockIdx.x; blk < n_blk; blk += gridDim.x) {
+    const int sgi = blk_seg[blk];
+    const int64_t off = blk_off[blk], base = seg_off[sgi] + off;
+    int64_t n = seg_len[sgi] - off;
+    if (n > ADAMW_CHUNK) n = ADAMW_CHUNK;
+    for (int64_t i = (int64_t)threadIdx.x * 4; i < n; i += 1024) {
+      if (i + 4 <= n) {
+        const f4_t v = __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(g + base + i));
+        __builtin_nontemporal_store(f4_t{v[0] * c, v[1] * c, v[2] * c, v[3] * c}, reinterpret_cast<f4_t*>(g + base + i));
+      } else {
+        for (int64_t k = i; k < n; ++k) g[base + k] *= c;
+      }
+    }
+  }
+}
 }  // namespace
 
 extern "C" int crct_zero_runs(float* base, const int64_t* off, const int64_t* len, const int32_t* blk_seg,
@@ -231,6 +438,57 @@ extern "C" int crct_adamw_step(float* p, float* g, float* m, float* v, void* p_b
 extern "C" int crct_adamw_advance(int32_t* step_dev, const float* found_inf_dev, crct_stream_t stream) {
   CRCT_REQUIRE(step_dev, "adamw_advance: null step counter");
   crct_launch(adamw_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_dev, found_inf_dev);
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int crct_grad_sumsq(const float* g_f32, const void* g_bf16, const int64_t* seg_off, const int64_t* seg_len,
+                               const int32_t* blk_seg, const int64_t* blk_off, int64_t n_blk, float* partials, int norm_kind,
+                               int max_workgroups, crct_stream_t stream) {
+  CRCT_REQUIRE(g_f32 || g_bf16, "grad_sumsq: no gradient buffer (g_f32 and g_bf16 are both null)");
+  CRCT_REQUIRE(seg_off && seg_len && blk_seg && blk_off, "grad_sumsq: null chunk table");
+  CRCT_REQUIRE(partials, "grad_sumsq: null partials");
+  CRCT_REQUIRE(n_blk >= 0 && n_blk <= INT32_MAX, "grad_sumsq: n_blk out of range (got %lld)", (long long)n_blk);
+  CRCT_REQUIRE(norm_kind == 0 || norm_kind == 1, "grad_sumsq: norm_kind must be 0 (sum of squares) or 1 (max), got %d", norm_kind);
+  CRCT_REQUIRE(max_workgroups >= 0, "grad_sumsq: negative max_workgroups (%d)", max_workgroups);
+  if (n_blk == 0) return 0;
+  const long grid = (max_workgroups > 0 && n_blk > max_workgroups) ? max_workgroups : n_blk;
+  const bf16_t* g16 = (const bf16_t*)g_bf16;
+#define CRCT_SUMSQ_LAUNCH(KIND, BF)                                                                                          \
+  crct_launch(grad_sumsq_kernel<KIND, BF>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, g_f32, g16, seg_off, seg_len, \
+              blk_seg, blk_off, partials, (int)n_blk)
+  if (g16) { if (norm_kind) CRCT_SUMSQ_LAUNCH(1, true); else CRCT_SUMSQ_LAUNCH(0, true); }
+  else     { if (norm_kind) CRCT_SUMSQ_LAUNCH(1, false); else CRCT_SUMSQ_LAUNCH(0, false); }
+#undef CRCT_SUMSQ_LAUNCH
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int crct_grad_norm_finalize(const float* partials, const int32_t* blk_seg, int64_t n_blk, int n_seg, int norm_kind,
+                                       float max_norm, const float* grad_scale_dev, const float* mul_dev, float* out,
+                                       float* seg_norm, crct_stream_t stream) {
+  CRCT_REQUIRE(out, "grad_norm_finalize: null out");
+  CRCT_REQUIRE(n_blk >= 0 && n_blk <= INT32_MAX && n_seg >= 0, "grad_norm_finalize: negative count (n_blk %lld, n_seg %d)", (long long)n_blk, n_seg);
+  CRCT_REQUIRE(n_blk == 0 || partials, "grad_norm_finalize: null partials");
+  CRCT_REQUIRE(!seg_norm || n_blk == 0 || blk_seg, "grad_norm_finalize: per-tensor norms need the chunk table (null blk_seg)");
+  CRCT_REQUIRE(norm_kind == 0 || norm_kind == 1, "grad_norm_finalize: norm_kind must be 0 (sum of squares) or 1 (max), got %d", norm_kind);
+  CRCT_REQUIRE(!(max_norm < 0.f), "grad_norm_finalize: negative max_norm (%g)", (double)max_norm);
+  crct_launch(grad_norm_finalize_kernel, dim3(1u + (seg_norm ? (unsigned)((n_seg + 15) / 16) : 0u)), dim3(1024), 0, (hipStream_t)stream, partials, blk_seg, (int)n_blk, n_seg, norm_kind,
+              max_norm, grad_scale_dev, mul_dev, out, seg_norm);
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int crct_scale_runs(float* g_f32, const float* coef_dev, const int64_t* seg_off, const int64_t* seg_len,
+                               const int32_t* blk_seg, const int64_t* blk_off, int64_t n_blk, int max_workgroups, crct_stream_t stream) {
+  CRCT_REQUIRE(g_f32 && coef_dev, "scale_runs: null gradient buffer or coefficient");
+  CRCT_REQUIRE(seg_off && seg_len && blk_seg && blk_off, "scale_runs: null chunk table");
+  CRCT_REQUIRE(n_blk >= 0 && n_blk <= INT32_MAX, "scale_runs: n_blk out of range (got %lld)", (long long)n_blk);
+  CRCT_REQUIRE(max_workgroups >= 0, "scale_runs: negative max_workgroups (%d)", max_workgroups);
+  if (n_blk == 0) return 0;
+  const long grid = (max_workgroups > 0 && n_blk > max_workgroups) ? max_workgroups : n_blk;
+  crct_launch(scale_runs_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, g_f32, coef_dev, seg_off, seg_len, blk_seg,
+              blk_off, (int)n_blk);
   CRCT_CHECK_HIP(hipGetLastError());
   return 0;
 }

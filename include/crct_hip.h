@@ -532,6 +532,26 @@ int crct_adamw_step(float* p, float* g, float* m, float* v, void* p_bf16,
  * (crct/ddp.py: each bucket is packed to bf16, all-reduced, and consumed here as it lies: 2 B instead of 4 B per parameter on
  * the wire and in this kernel's reads).  When set, every gradient element is read from it; g is only written (zero_grads). */
 
+/* Global-norm gradient clipping on the flat gradient buffer, over the chunk table (seg_off, seg_len, blk_seg, blk_off, n_blk) of
+ * crct_adamw_plan and with the source rule of crct_adamw_step: g_bf16 != NULL -> EVERY element is read from it and g_f32 is never
+ * read, else everything is read from g_f32 -- the norm is the norm of exactly what the next update consumes.
+ * crct_grad_sumsq: one read-only streaming pass, partials[b] (device fp32 [n_blk]) = the sum of squares (norm_kind 0) or max |g|
+ *   (norm_kind 1, a NaN propagates) of chunk b.  No atomics, a fixed summation tree of at most 15 dependent fp32 roundings per
+ *   chunk that depends on neither the source format nor the workgroup: bit-reproducible, also over max_workgroups (> 0 = a
+ *   grid-stride launch of at most that many workgroups, as in crct_adamw_step).
+ * crct_grad_norm_finalize: one small launch, fixed order, fp64: seg_norm[s] (device fp32 [n_seg], may be NULL) = the norm of tensor s,
+ *   out[0] = the norm over all chunks, both divided by *grad_scale_dev (may be NULL: the GradScaler factor that is still on the
+ *   gradients), out[1] = min(1, max_norm / (out[0] + 1e-6)) * (mul_dev ? *mul_dev : 1) in fp32 -- torch.nn.utils.clip_grad_norm_'s
+ *   coefficient, ready for the inv_scale_dev slot of crct_adamw_step.  An inf norm gives 0, a NaN norm NaN, no clipping exactly 1.
+ * crct_scale_runs: g_f32 *= *coef_dev over the table, one fp32 product per element; returns before the first load when
+ *   *coef_dev == 1.  All pointers are device memory. */
+int crct_grad_sumsq(const float* g_f32, const void* g_bf16, const int64_t* seg_off, const int64_t* seg_len, const int32_t* blk_seg,
+                    const int64_t* blk_off, int64_t n_blk, float* partials, int norm_kind, int max_workgroups, crct_stream_t stream);
+int crct_grad_norm_finalize(const float* partials, const int32_t* blk_seg, int64_t n_blk, int n_seg, int norm_kind, float max_norm,
+                            const float* grad_scale_dev, const float* mul_dev, float* out, float* seg_norm, crct_stream_t stream);
+int crct_scale_runs(float* g_f32, const float* coef_dev, const int64_t* seg_off, const int64_t* seg_len, const int32_t* blk_seg,
+                    const int64_t* blk_off, int64_t n_blk, int max_workgroups, crct_stream_t stream);
+
 /* fp8 copies of the attention results (BASELINE configs[4]): ctx also as OCP e4m3 (the input of the attention-output
  * projection's fp8 forward GEMM and weight gradient), dq / dk / dv also as OCP e5m2 (the input of the QKV projections' fp8
  * data and weight gradients).  Every copy has the shape and leading dimension of its bf16 twin (one byte per element), is
