@@ -1,5 +1,6 @@
 // Step engine: schedules the hand-written gfx950 kernels for one CRCT training step
-// (forward + joint loss + backward) on one HIP stream, without host synchronisation.
+// (forward + joint loss + backward) on four HIP streams -- the caller's (text layers), one for the visual layers and one per data
+// stream for its weight-gradient GEMMs, ordered by events -- without host synchronisation.
 //
 // Reference path it replaces (levymsn/CQA-CRCT):
 //   encoder_decorator.forward            CRCT/backbone/encoder_decorator.py:73-158
@@ -43,19 +44,28 @@ void crct_set_error(const char* fmt, ...) {
 extern "C" const char* crct_last_error(void) { return g_err; }
 extern "C" int crct_abi_version(void) { return 7; }
 
+// What every GEMM launch must satisfy, stated once: `who` prefixes the message ("gemm" / "gemm_grouped"), idx >= 0 names the
+// problem of a grouped launch.
+static int gemm_check(const CrctGemmArgs& a, const char* who, int idx) {
+  char of[32] = "";
+  if (idx >= 0) snprintf(of, sizeof(of), " (problem %d)", idx);
+  CRCT_REQUIRE(a.A && a.B && a.C, "%s: null operand%s", who, of);
+  CRCT_REQUIRE(a.N % 4 == 0, "%s: N=%d must be a multiple of 4%s", who, a.N, of);
+  CRCT_REQUIRE((a.ta && a.tb) || a.K % 8 == 0, "%s: K=%d must be a multiple of 8 for a K-contiguous operand%s", who, a.K, of);
+  CRCT_REQUIRE(a.lda % 8 == 0 && a.ldb % 8 == 0, "%s: lda=%ld ldb=%ld must be multiples of 8%s", who, (long)a.lda, (long)a.ldb, of);
+  CRCT_REQUIRE(a.ldc % 4 == 0, "%s: ldc=%ld must be a multiple of 4%s", who, (long)a.ldc, of);
+  CRCT_REQUIRE(!(a.ta && !a.tb), "%s: (ta=1, tb=0) is not built (not used by the step)%s", who, of);
+  CRCT_REQUIRE(!a.ta || a.M % 8 == 0, "%s: transposed A needs M %% 8 == 0 (M=%d)%s", who, a.M, of);
+  CRCT_REQUIRE(!a.tb || a.N % 8 == 0, "%s: transposed B needs N %% 8 == 0 (N=%d)%s", who, a.N, of);
+  CRCT_REQUIRE(a.tile < 0 || crct_gemm_config_built(a.tile), "%s: configuration %d is not built%s", who, a.tile, of);
+  // the staged epilogue stores a c_cached output without reading it, the register-staged one adds the old value: refused on both paths
+  CRCT_REQUIRE(!(a.c_cached && a.accumulate), "%s: c_cached with accumulate is not supported (c_cached is a plain fp32 store)%s", who, of);
+  return 0;
+}
+
 extern "C" int crct_gemm_bf16(const CrctGemmArgs* a, crct_stream_t stream) {
   CRCT_REQUIRE(a != nullptr, "gemm: null args");
-  CRCT_REQUIRE(a->A && a->B && a->C, "gemm: null operand");
-  CRCT_REQUIRE(a->N % 4 == 0, "gemm: N=%d must be a multiple of 4", a->N);
-  CRCT_REQUIRE((a->ta && a->tb) || a->K % 8 == 0, "gemm: K=%d must be a multiple of 8 for a K-contiguous operand", a->K);
-  CRCT_REQUIRE(a->lda % 8 == 0 && a->ldb % 8 == 0, "gemm: lda=%ld ldb=%ld must be multiples of 8", (long)a->lda, (long)a->ldb);
-  CRCT_REQUIRE(a->ldc % 4 == 0, "gemm: ldc=%ld must be a multiple of 4", (long)a->ldc);
-  CRCT_REQUIRE(!(a->ta && !a->tb), "gemm: (ta=1, tb=0) is not built (not used by the step)");
-  CRCT_REQUIRE(!a->ta || a->M % 8 == 0, "gemm: transposed A needs M %% 8 == 0 (M=%d)", a->M);
-  CRCT_REQUIRE(!a->tb || a->N % 8 == 0, "gemm: transposed B needs N %% 8 == 0 (N=%d)", a->N);
-  CRCT_REQUIRE(a->tile < 0 || crct_gemm_config_built(a->tile), "gemm: configuration %d is not built", a->tile);
-  // the staged epilogue stores a c_cached output without reading it, the register-staged one adds the old value: refused on both paths
-  CRCT_REQUIRE(!(a->c_cached && a->accumulate), "gemm: c_cached with accumulate is not supported (c_cached is a plain fp32 store)");
+  if (int r = gemm_check(*a, "gemm", -1)) return r;
   CRCT_CHECK_HIP(crct_gemm_launch(*a, (hipStream_t)stream));
   return 0;
 }
@@ -63,14 +73,8 @@ extern "C" int crct_gemm_bf16(const CrctGemmArgs* a, crct_stream_t stream) {
 // target_wgs < 0: the library's default (crct_gemm_group_target_workgroups)
 static int gemm_grouped_checked(const CrctGemmArgs* a, int n, crct_stream_t stream, int target_wgs) {
   CRCT_REQUIRE(a != nullptr && n >= 1, "gemm_grouped: bad arguments");
-  for (int i = 0; i < n; ++i) {
-    CRCT_REQUIRE(a[i].A && a[i].B && a[i].C, "gemm_grouped: null operand in problem %d", i);
-    CRCT_REQUIRE(a[i].N % 4 == 0 && a[i].lda % 8 == 0 && a[i].ldb % 8 == 0 && a[i].ldc % 4 == 0, "gemm_grouped: alignment of problem %d", i);
-    CRCT_REQUIRE((a[i].ta && a[i].tb) || a[i].K % 8 == 0, "gemm_grouped: K of problem %d", i);
-    CRCT_REQUIRE(!(a[i].ta && !a[i].tb) && (!a[i].ta || a[i].M % 8 == 0) && (!a[i].tb || a[i].N % 8 == 0), "gemm_grouped: layout of problem %d", i);
-    CRCT_REQUIRE(a[i].tile < 0 || crct_gemm_config_built(a[i].tile), "gemm_grouped: configuration %d of problem %d is not built", a[i].tile, i);
-    CRCT_REQUIRE(!(a[i].c_cached && a[i].accumulate), "gemm_grouped: c_cached with accumulate is not supported (problem %d)", i);
-  }
+  for (int i = 0; i < n; ++i)
+    if (int r = gemm_check(a[i], "gemm_grouped", i)) return r;
   if (target_wgs < 0) CRCT_CHECK_HIP(crct_gemm_launch_grouped(a, n, (hipStream_t)stream));
   else CRCT_CHECK_HIP(crct_gemm_launch_grouped_wgs(a, n, (hipStream_t)stream, target_wgs));
   return 0;
@@ -103,10 +107,23 @@ struct SelfLayerP { LinearP qkv; ProjP proj; FfnP ffn; int H, heads; float p_att
 struct ConnLayerP { LinearP qkv1, qkv2; ProjP proj_v, proj_t; FfnP ffn_v, ffn_t; uint32_t site; };
 
 // ---- activation offsets (bytes into the workspace)
+constexpr size_t NONE = (size_t)-1;
+// An activation as the blocks hand it on: the bf16 tensor, its e4m3 copy with the activation scale site (site -1: no copy) and
+// the fp32 copy a LayerNorm leaves of its output for the fp32 residual stream (NONE: the embeddings' outputs, bf16 there)
+struct Act { size_t x = 0, q = NONE; int site = -1; size_t x32 = NONE; };
+// the e5m2 copy of a gradient and its gradient scale site (-1: no copy)
+struct GradQ { size_t q = NONE; int site = -1; };
 // s: the pre-LayerNorm sum, room for fp32 (the fp32 residual stream, CrctStepCfg.residual_fp32; bf16 in the first half otherwise);
 // y32 / a32: the fp32 copy of the LayerNorm output that the NEXT block's epilogue adds as its residual
-struct FfnA { size_t u, h, s, y, y32, mean, rstd, hq, yq; int site_h, site_y; int g_dl, g_du; };      // g_*: gradient scale sites (fp8 backward)      // hq / yq: e4m3 copies (fp8 forward), site_*: their scale slots
-struct ProjA { size_t s, a, a32, mean, rstd, aq; int site_a; int g_dl; };
+// hq / yq: e4m3 copies (fp8 forward), site_*: their scale slots; g_*: gradient scale sites (fp8 backward)
+struct FfnA {
+  size_t u, h, s, y, y32, mean, rstd, hq, yq; int site_h, site_y; int g_dl, g_du;
+  Act out() const { return {y, yq, site_y, y32}; }
+};
+struct ProjA {
+  size_t s, a, a32, mean, rstd, aq; int site_a; int g_dl;
+  Act out() const { return {a, aq, site_a, a32}; }
+};
 // ctxq / site_ctx: e4m3 copy of the attention context and its activation scale site; g_dqkv: gradient scale site of the fused dqkv buffer
 // lse*: softmax row statistics [B][heads][Tq] fp32 the long-sequence attention forward leaves for its backward (CrctAttnQuant.row_lse)
 struct SelfLayerA { size_t qkv, ctx, ctxq, lse; int site_ctx, g_dqkv; ProjA proj; FfnA ffn; };
@@ -114,6 +131,7 @@ struct ConnLayerA { size_t qkv1, qkv2, ctx1, ctx2, ctx1q, ctx2q, lse1, lse2; int
 struct StreamScratch { size_t dy[2], dres_a, dlin_a, dres_b, dlin_b, gc, du, dctx, dqkv, part_a, part_b, dlq_a, dlq_b, duq, dqkvq; };      // *q: e5m2 copies (fp8 backward)
 
 struct Step { char kind; int idx; };
+struct StepIn { Act t, v; };      // the two hidden states a schedule step starts from
 struct Tap { std::string name; size_t off; char stream; };
 
 }  // namespace
@@ -150,7 +168,6 @@ struct crct_engine {
   int sk_tickets = 0;
   // fp8 forward (BASELINE configs[4]): scale slot of every Linear weight that has an e4m3 shadow, number of activation scale sites
   std::unordered_map<int64_t, int> wq_slot;
-  std::unordered_map<size_t, size_t> res32;      // workspace offset of a LayerNorm's bf16 output -> offset of its fp32 copy (fp32 residual stream)
   int32_t* word_index = nullptr;      // device memory owned by the engine: crct_embed_text_bwd_indexed's first / last row per token id, zero between calls
   std::vector<std::pair<int64_t, int64_t>> wq_list;      // slot -> (flat offset, numel)
   int n_sites = 0;
@@ -184,7 +201,7 @@ struct crct_engine {
   std::unordered_map<int64_t, int> wgrad_pass;
   void wgrad_pass_begin() { wgrad_pass.clear(); }
   std::vector<Tap> taps;
-  size_t final_t = 0, final_v = 0;   // offsets of the last-layer outputs
+  std::vector<StepIn> in;            // in[i]: the hidden states schedule step i starts from; in[sched.size()]: the encoder's outputs
   int cur_t = 0, cur_v = 0;          // ping-pong index of the running activation gradients
   bool bad = false;
   int64_t P(const std::string& k) {
@@ -216,6 +233,31 @@ LinearP fused3(crct_engine* e, const std::string& a, const std::string& b, const
   return l;
 }
 
+// A self-attention layer (BertLayer / BertImageLayer) from the prefix of its parameter names, its sizes and dropout probabilities,
+// its first dropout site and the first of its four GEMM sites (QKV, OUT, FFN_UP, FFN_DN)
+static_assert(CRCT_SITE_T_OUT == CRCT_SITE_T_QKV + 1 && CRCT_SITE_T_FFN_UP == CRCT_SITE_T_QKV + 2 && CRCT_SITE_T_FFN_DN == CRCT_SITE_T_QKV + 3 &&
+              CRCT_SITE_V_OUT == CRCT_SITE_V_QKV + 1 && CRCT_SITE_V_FFN_UP == CRCT_SITE_V_QKV + 2 && CRCT_SITE_V_FFN_DN == CRCT_SITE_V_QKV + 3,
+              "the GEMM sites of a self-attention layer are consecutive");
+SelfLayerP self_layer_p(crct_engine* e, const std::string& p, int H, int I, int heads, float p_attn, float p_hid, uint32_t drop_site, int gemm_site) {
+  SelfLayerP l;
+  l.H = H; l.heads = heads; l.p_attn = p_attn; l.p_hid = p_hid; l.site = drop_site;
+  l.qkv = fused3(e, p + "attention.self.query", p + "attention.self.key", p + "attention.self.value", H, H, gemm_site);
+  l.proj.dense = linear_p(e, p + "attention.output.dense", H, H, gemm_site + 1);
+  l.proj.ln = ln_p(e, p + "attention.output.LayerNorm");
+  l.ffn.up = linear_p(e, p + "intermediate.dense", H, I, gemm_site + 2);
+  l.ffn.down = linear_p(e, p + "output.dense", I, H, gemm_site + 3);
+  l.ffn.ln = ln_p(e, p + "output.LayerNorm");
+  return l;
+}
+// every Linear of the encoder layers, in the order their fp8 scale slots are numbered
+template <class F> void each_encoder_linear(const crct_engine* e, F f) {
+  for (const std::vector<SelfLayerP>* stack : {&e->tl, &e->vl})
+    for (const SelfLayerP& l : *stack) { f(l.qkv); f(l.ffn.up); f(l.ffn.down); f(l.proj.dense); }
+  for (const ConnLayerP& l : e->cl) {
+    f(l.qkv1); f(l.qkv2); f(l.ffn_v.up); f(l.ffn_v.down); f(l.ffn_t.up); f(l.ffn_t.down); f(l.proj_v.dense); f(l.proj_t.dense);
+  }
+}
+
 FfnA ffn_a(Arena& ar, size_t M, int H, int I, int& sites, int& gsites) {
   FfnA a;
   a.g_dl = gsites++; a.g_du = gsites++;
@@ -231,6 +273,14 @@ ProjA proj_a(Arena& ar, size_t M, int H, int& sites, int& gsites) {
   a.s = ar.take(M * H * 4); a.a = ar.take(M * H * 2); a.a32 = ar.take(M * H * 4); a.mean = ar.take(M * 4); a.rstd = ar.take(M * 4);
   a.aq = ar.take(M * H);
   a.site_a = sites++;
+  return a;
+}
+// the activations of a self-attention layer over M rows (the order of the takes and of the site numbers is the workspace's layout)
+SelfLayerA self_layer_a(Arena& ar, size_t M, int H, int I, int heads, int& sites, int& gsites) {
+  SelfLayerA a;
+  a.qkv = ar.take(M * 3 * H * 2); a.ctx = ar.take(M * H * 2); a.ctxq = ar.take(M * H); a.lse = ar.take(M * heads * 4);
+  a.site_ctx = sites++; a.g_dqkv = gsites++;
+  a.proj = proj_a(ar, M, H, sites, gsites); a.ffn = ffn_a(ar, M, H, I, sites, gsites);
   return a;
 }
 StreamScratch scratch_a(Arena& ar, size_t M, int H, int I, int Hb) {
@@ -270,8 +320,10 @@ int order_streams(crct_engine* e, hipStream_t from, hipStream_t to) {
   return 0;
 }
 
-// fp8 copies of a weight gradient's operands (Run::lin_wgrad)
-struct WgQ8 { size_t dyq = (size_t)-1; int g_dy = -1; size_t xq = (size_t)-1; int site_x = -1; };
+// fp8 copies of a weight gradient's operands (Run::lin_wgrad): the e5m2 copy of dy, the e4m3 copy of x
+struct WgQ8 { GradQ dy; Act x; };
+// an fp8 tensor of the workspace with its scale and amax words, as pointers (q == nullptr: none)
+struct Q8 { uint8_t* q = nullptr; const float* scale = nullptr; float* amax = nullptr; };
 
 struct Run {
   crct_engine* e;
@@ -335,127 +387,132 @@ struct Run {
   void fail(int r) { if (!rc && r) rc = r; }
 
   struct Opt {
-    const float* bias = nullptr; void* preact = nullptr; const void* dact_src = nullptr; int dact = 0; int act = 0;
+    void* preact = nullptr; const void* dact_src = nullptr; int dact = 0; int act = 0;
     const void* addend = nullptr; int64_t ld_aux = 0, ld_add = 0; Drop drop; bool f32 = false; bool acc = false;
     bool add_f32 = false, c_cached = false;      // the fp32 residual stream: fp32 addend; fp32 output that the next kernel reads
-    int site = 0;
-    void* q_out = nullptr; const float* q_scale = nullptr; float* q_amax = nullptr; int64_t ld_q = 0;      // fp8 copy of the result (calibration passes):
-    bool q_e4m3 = false;                                                                                   // e5m2 (a gradient) unless q_e4m3 (an activation)
   };
-  void gemm(const void* Ap, int64_t lda, bool ta, const void* Bp, int64_t ldb, bool tb, void* C, int64_t ldc, int M, int N,
-            int K, const Opt& o, hipStream_t st = nullptr) {
-    if (rc) return;
-    if (!st) st = s;
-    if (st == s) ++tick;
-    CrctGemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = Ap; g.B = Bp; g.C = C; g.bias = o.bias; g.preact_out = o.preact; g.dact_src = o.dact_src; g.addend = o.addend;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ld_aux = o.ld_aux; g.ld_add = o.ld_add;
-    g.M = M; g.N = N; g.K = K; g.ta = ta; g.tb = tb; g.act = o.act; g.dact = o.dact; g.c_is_f32 = o.f32; g.accumulate = o.acc;
-    g.tile = -1; g.alpha = 1.0f; g.drop_thr = o.drop.thr; g.drop_scale = o.drop.scale; g.drop_site = o.drop.site; g.seed = c->seed;
-    g.site = o.site; g.addend_f32 = o.add_f32; g.c_cached = o.c_cached;
-    if (o.q_out) { g.q_out = o.q_out; g.q_scale = o.q_scale; g.q_amax = o.q_amax; g.ld_q = o.ld_q; g.fp8 = o.q_e4m3 ? 0 : 4; }      // bf16 GEMM + fp8 copy of its result
-    if (!ta && st == s && o.site > 0 && o.site < CRCT_SITE_COUNT) {      // forward / data gradient on the data stream: the site's policy
-      const crct_engine::SitePolicy& pol = e->policy[o.site][tb ? 1 : 0][phase];
-      if (pol.cfg >= 0) g.tile = pol.cfg;
-      if (pol.split_k > 1 && crct_gemm_splitk_ws_elems(M, N, pol.split_k) <= (int64_t)e->sk_ws_elems[which] &&
-          crct_gemm_splitk_tickets(M, N) <= e->sk_tickets) {
-        g.split_k = pol.split_k; g.splitk_ws = F(e->sk_ws[which]); g.splitk_cnt = W<uint32_t>(e->sk_cnt[which]);
-      }
-    }
-    fail(crct_gemm_bf16(&g, st));
-  }
   // both sides reach this point before either goes on: the two data streams are ordered against each other
   void cross_sync(Run& V) {
     if (!rc) fail(order_streams(e, V.s, s));
     if (!V.rc) V.fail(order_streams(e, s, V.s));
   }
-  // y[M][out] = x W^T + b (+ epilogue)
-  void lin_fwd(const void* x, int64_t ldx, const LinearP& l, int M, void* y, int64_t ldy, Opt o) {
-    o.bias = P(l.b); o.site = l.site;
-    gemm(x, ldx, false, PB(l.w), l.in, false, y, ldy, M, l.out, l.in, o);
-  }
-  // ---- fp8 forward (CrctStepCfg.fp8): the same Linear from the e4m3 copies of its input (scale site `site_in`) and of its
-  // weight; optionally also emits the e4m3 copy of its own output (hq, site_out) for the next fp8 GEMM
+  // ---- fp8 forward (CrctStepCfg.fp8): a Linear reads the e4m3 copies of its input and of its weight; optionally it also emits the
+  // e4m3 copy of its own output for the next fp8 GEMM
   // CrctStepCfg.fp8 == 2 (calibration, the dry pass before the first fp8 forward): every producer writes its copy and collects its
   // maximum, the GEMMs themselves still read the bf16 operands -- the maxima are then those of the bf16 forward, not of a forward
   // whose GEMMs ran on unscaled (scale 1) e4m3 inputs
   int f8() const { return (c->fp8 && c->params_fp8 && c->fp8_w_scale && c->fp8_act_scale && c->fp8_act_amax) ? c->fp8 : 0; }
   bool f8_lin(const LinearP& l) const { return f8() && e->wq_slot.count(l.w) != 0; }
   // ---- fp8 backward (CrctStepCfg.fp8_bwd): data gradients dx = dy W of the FFN and attention-output Linears from the e5m2 copy
-  // of dy (written by the producing LayerNorm-backward / GELU' epilogue, scale site g) and the TRANSPOSED e4m3 weight shadow.
+  // of dy (written by the producing LayerNorm-backward / GELU' epilogue / attention backward) and the TRANSPOSED e4m3 weight shadow.
   // fp8_bwd == 2 (calibration, the first backward pass): the producers collect the gradient maxima, the GEMMs still run in bf16.
   int f8b() const { return (c->fp8 && c->fp8_bwd && c->params_fp8_t && c->fp8_w_scale && c->fp8_grad_scale && c->fp8_grad_amax) ? c->fp8_bwd : 0; }
   bool f8b_lin(const LinearP& l) const { return f8b() && e->wq_slot.count(l.w) != 0; }
+  // scale and amax words of an activation / gradient scale site
+  const float* ascale(int site) const { return c->fp8_act_scale + site; }
+  float* aamax(int site) const { return c->fp8_act_amax + (int64_t)site * CRCT_FP8_AMAX_LANES; }
   const float* gscale(int g) const { return c->fp8_grad_scale + g; }
   float* gamax(int g) const { return c->fp8_grad_amax + (int64_t)g * CRCT_FP8_AMAX_LANES; }
-  // dx[M][in] = dyq[M][out] Wt[in][out]^T (+ epilogue); q_out / g_out: optional e5m2 copy of the result for the next data gradient
-  void lin_dgrad_f8(size_t dyq, int g_in, const void* dy_bf16, int64_t lddy, const LinearP& l, int M, void* dx, int64_t lddx, Opt o,
-                    size_t q_out = (size_t)-1, int g_out = -1) {
-    if (rc) return;
-    if (f8b() != 1) {          // calibration pass: the bf16 GEMM, which still emits the e5m2 copy / amax of its result
-      o.site = l.site;
-      if (g_out >= 0) { o.q_out = W<uint8_t>(q_out); o.q_scale = gscale(g_out); o.q_amax = gamax(g_out); o.ld_q = l.in; }
-      gemm(dy_bf16, lddy, false, PB(l.w), l.in, true, dx, lddx, M, l.in, l.out, o);
-      return;
-    }
-    ++tick;
+  Q8 q8(const Act& a) const { return a.site < 0 ? Q8() : Q8{W<uint8_t>(a.q), ascale(a.site), aamax(a.site)}; }
+  Q8 q8(const GradQ& g) const { return g.site < 0 ? Q8() : Q8{W<uint8_t>(g.q), gscale(g.site), gamax(g.site)}; }
+
+  enum Dir { FWD = CRCT_KIND_FWD, DGRAD = CRCT_KIND_DGRAD, WGRAD = CRCT_KIND_WGRAD };
+  // The one place a CrctGemmArgs is filled in: the three GEMMs of Linear l over M rows.
+  //   FWD    C[M][out] = a[M][in] W^T + b      DGRAD  C[M][in] = a[M][out] W      WGRAD  C[out][in] = a[M][out]^T x[M][in]
+  // (x is read by WGRAD only).  a8: the fp8 copy of `a` -- when given the GEMM runs on fp8 operands, against the e4m3 weight shadow
+  // (FWD), its transpose (DGRAD) or x8, the e4m3 copy of x (WGRAD).  out: where to leave an fp8 copy of the result and its maximum
+  // (e4m3 of a forward result, e5m2 of a gradient) -- also behind bf16 operands, which is what the calibration passes run.
+  // The site's launch policy: its configuration for every kind; split-K only for the bf16 forward / data-gradient GEMMs (all of them
+  // run on the data stream, whose split-K workspace `which` this Run owns).
+  CrctGemmArgs gemm_args(Dir dir, const LinearP& l, int M, const void* a, int64_t lda, const void* x, int64_t ldx, void* C, int64_t ldc,
+                         const Opt& o, const Q8& a8 = Q8(), const Q8& x8 = Q8(), const Q8& out = Q8()) const {
+    const bool q = a8.q != nullptr;
     CrctGemmArgs g;
     memset(&g, 0, sizeof(g));
-    g.A = W<uint8_t>(dyq); g.B = reinterpret_cast<const uint8_t*>(c->params_fp8_t) + l.w; g.C = dx;
-    g.preact_out = o.preact; g.dact_src = o.dact_src; g.addend = o.addend;
-    g.lda = l.out; g.ldb = l.out; g.ldc = lddx; g.ld_aux = o.ld_aux; g.ld_add = o.ld_add;
-    g.M = M; g.N = l.in; g.K = l.out; g.act = o.act; g.dact = o.dact; g.c_is_f32 = o.f32; g.accumulate = o.acc;
-    g.tile = -1; g.alpha = 1.0f; g.seed = c->seed; g.site = l.site;
-    g.fp8 = 1 | 2 | 8;                                   // A = e5m2 gradient, B = e4m3 weight; labelled as a data gradient
-    if (l.site > 0 && l.site < CRCT_SITE_COUNT && e->policy[l.site][1][phase].cfg >= 0) g.tile = e->policy[l.site][1][phase].cfg;
-    g.scale_a = gscale(g_in); g.scale_b = c->fp8_w_scale + e->wq_slot.at(l.w);
-    if (g_out >= 0) { g.fp8 |= 4; g.q_out = W<uint8_t>(q_out); g.ld_q = l.in; g.q_scale = gscale(g_out); g.q_amax = gamax(g_out); }
-    fail(crct_gemm_bf16(&g, s));
-  }
-  // x: the bf16 input (leading dimension l.in), read instead of xq by the calibration pass
-  void lin_fwd_f8(const void* x, size_t xq, int site_in, const LinearP& l, int M, void* y, int64_t ldy, Opt o, size_t hq = (size_t)-1, int site_out = -1) {
-    if (rc) return;
-    if (f8() != 1) {           // calibration: the bf16 GEMM, which still emits the e4m3 copy / maximum of its result
-      if (site_out >= 0) {
-        o.q_out = W<uint8_t>(hq); o.ld_q = l.out; o.q_scale = c->fp8_act_scale + site_out;
-        o.q_amax = c->fp8_act_amax + (int64_t)site_out * CRCT_FP8_AMAX_LANES; o.q_e4m3 = true;
+    g.A = q ? a8.q : a; g.C = C; g.ldc = ldc;
+    if (dir == WGRAD) {
+      g.B = q ? x8.q : x; g.M = l.out; g.N = l.in; g.K = M; g.ta = 1; g.tb = 1; g.lda = lda; g.ldb = ldx;
+    } else {
+      const bool fwd = dir == FWD;
+      g.M = M; g.N = fwd ? l.out : l.in; g.K = fwd ? l.in : l.out;
+      // the fp8 copies are dense, and the transposed shadow is K-contiguous for the data gradient as the weight is for the forward
+      g.lda = q ? g.K : lda; g.ldb = q ? g.K : l.in; g.tb = !fwd && !q;
+      if (q) g.B = reinterpret_cast<const uint8_t*>(fwd ? c->params_fp8 : c->params_fp8_t) + l.w;
+      else g.B = PB(l.w);
+      if (fwd) g.bias = P(l.b);
+    }
+    g.preact_out = o.preact; g.dact_src = o.dact_src; g.addend = o.addend; g.ld_aux = o.ld_aux; g.ld_add = o.ld_add;
+    g.act = o.act; g.dact = o.dact; g.c_is_f32 = o.f32; g.accumulate = o.acc; g.addend_f32 = o.add_f32; g.c_cached = o.c_cached;
+    g.alpha = 1.0f; g.drop_thr = o.drop.thr; g.drop_scale = o.drop.scale; g.drop_site = o.drop.site; g.seed = c->seed; g.site = l.site;
+    if (q) {
+      // bit 0: fp8 operands, bit 1: A is an e5m2 gradient, bit 3: labelled as a data gradient (no transposed B tells it apart)
+      g.fp8 = dir == FWD ? 1 : (dir == DGRAD ? 1 | 2 | 8 : 1 | 2);
+      g.scale_a = a8.scale; g.scale_b = dir == WGRAD ? x8.scale : c->fp8_w_scale + e->wq_slot.at(l.w);
+    }
+    if (out.q) {
+      g.q_out = out.q; g.q_scale = out.scale; g.q_amax = out.amax; g.ld_q = g.N;
+      if (dir == DGRAD) g.fp8 |= 4;                       // bit 2: the copy is e5m2 (a gradient), not e4m3 (an activation)
+    }
+    g.tile = -1;
+    if (l.site > 0 && l.site < CRCT_SITE_COUNT) {
+      const crct_engine::SitePolicy& pol = e->policy[l.site][dir][phase];
+      if (pol.cfg >= 0) g.tile = pol.cfg;
+      if (dir != WGRAD && !q && pol.split_k > 1 && crct_gemm_splitk_ws_elems(g.M, g.N, pol.split_k) <= (int64_t)e->sk_ws_elems[which] &&
+          crct_gemm_splitk_tickets(g.M, g.N) <= e->sk_tickets) {
+        g.split_k = pol.split_k; g.splitk_ws = F(e->sk_ws[which]); g.splitk_cnt = W<uint32_t>(e->sk_cnt[which]);
       }
-      lin_fwd(x, l.in, l, M, y, ldy, o);
-      return;
     }
-    ++tick;
-    CrctGemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = W<uint8_t>(xq); g.B = reinterpret_cast<const uint8_t*>(c->params_fp8) + l.w; g.C = y; g.bias = P(l.b);
-    g.preact_out = o.preact; g.dact_src = o.dact_src; g.addend = o.addend;
-    g.lda = l.in; g.ldb = l.in; g.ldc = ldy; g.ld_aux = o.ld_aux; g.ld_add = o.ld_add;
-    g.M = M; g.N = l.out; g.K = l.in; g.act = o.act; g.dact = o.dact; g.c_is_f32 = o.f32; g.accumulate = o.acc;
-    g.tile = -1; g.alpha = 1.0f; g.drop_thr = o.drop.thr; g.drop_scale = o.drop.scale; g.drop_site = o.drop.site; g.seed = c->seed;
-    g.addend_f32 = o.add_f32; g.c_cached = o.c_cached;
-    g.fp8 = 1; g.scale_a = c->fp8_act_scale + site_in; g.scale_b = c->fp8_w_scale + e->wq_slot.at(l.w); g.site = l.site;
-    if (l.site > 0 && l.site < CRCT_SITE_COUNT && e->policy[l.site][0][phase].cfg >= 0) g.tile = e->policy[l.site][0][phase].cfg;
-    if (site_out >= 0) { g.q_out = W<uint8_t>(hq); g.ld_q = l.out; g.q_scale = c->fp8_act_scale + site_out; g.q_amax = c->fp8_act_amax + (int64_t)site_out * CRCT_FP8_AMAX_LANES; }
-    fail(crct_gemm_bf16(&g, s));
+    return g;
+  }
+  void launch(const CrctGemmArgs& g) { ++tick; fail(crct_gemm_bf16(&g, s)); }      // on the data stream: one tick per launch
+
+  // y[M][out] = x W^T + b (+ epilogue), in the precision the Linear itself decides.  The forward rules, all of them:
+  //  * fp8 operands iff the weight has an e4m3 shadow in an fp8 forward (f8_lin) AND the input comes with an e4m3 copy
+  //    (x.site >= 0).  Every hidden state and every attention-output LayerNorm's result has one (ln_fwd, the embeddings); the
+  //    attention context only where the attention kernel wrote it (ctx_act: attn_q_ok); the FFN's h only when the up projection
+  //    qualified and the down projection is fp8-capable (ffn_h) -- the returned Act says so.
+  //  * y.site >= 0 asks for the e4m3 copy and maximum of the result; only a Linear that qualifies for fp8 writes them.
+  //  * calibration (f8() == 2): the GEMM reads the bf16 operands and still writes the copy and maximum it was asked for.
+  // Returns y, with site -1 where no copy was written.
+  Act lin_fwd(const Act& x, int64_t ldx, const LinearP& l, int M, Act y, int64_t ldy, const Opt& o) {
+    const bool q = f8_lin(l) && x.site >= 0;
+    if (!q) y.site = -1;
+    if (rc) return y;
+    launch(gemm_args(FWD, l, M, A(x.x), ldx, nullptr, 0, A(y.x), ldy, o, q && f8() == 1 ? q8(x) : Q8(), Q8(), q8(y)));
+    return y;
+  }
+  // dx[M][in] = dy W (+ epilogue).  The data-gradient rules:
+  //  * fp8 operands iff the weight has a transposed e4m3 shadow in an fp8 backward (f8b_lin) AND dy comes with an e5m2 copy
+  //    (dyq.site >= 0): the LayerNorm backward writes one for an fp8-backward-capable Linear (ln_bwd), the FFN-down data gradient
+  //    for an fp8-backward-capable up projection (ffn_bwd), the attention backward for QKV projections that also ran their forward
+  //    in fp8 (self_bwd / conn_bwd: the weight gradient reads the same copy against the layer input's e4m3 copy).
+  //  * out.site >= 0 asks for the e5m2 copy and maximum of dx; only a Linear that qualifies writes them.
+  //  * calibration (f8b() != 1): the GEMM reads the bf16 operands and still writes the copy and maximum it was asked for.
+  // Returns `out`, with site -1 where no copy was written.
+  GradQ lin_dgrad(const void* dy, int64_t lddy, const LinearP& l, int M, void* dx, int64_t lddx, const Opt& o, const GradQ& dyq = GradQ(),
+                  GradQ out = GradQ()) {
+    const bool q = f8b_lin(l) && dyq.site >= 0;
+    if (!q) out.site = -1;
+    if (rc) return out;
+    launch(gemm_args(DGRAD, l, M, dy, lddy, nullptr, 0, dx, lddx, o, q && f8b() == 1 ? q8(dyq) : Q8(), Q8(), q8(out)));
+    return out;
   }
   // dW[out][in] += dy^T x
   // with_bias: also db[out] += column sums of dy.  When the contraction length qualifies for the LDS-DMA kernel the
   // sums come out of the weight-gradient kernel itself (CrctGemmArgs.rowsum_out); otherwise a column-sum launch.
-  // q8: the fp8 copies of both operands where the other passes left them (fp8 backward, CrctStepCfg.fp8_wgrad): dy as OCP e5m2
-  // with gradient scale site g_dy, x as e4m3 with activation scale site site_x -- the weight gradient then reads half the bytes
-  // (gemm.hip, fp8 weight gradients); the bias gradient still sums the bf16 dy.
-  void lin_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, const LinearP& l, int M, bool with_bias = false, WgQ8 q8 = WgQ8()) {
+  // w8: the fp8 copies of both operands where the other passes left them (fp8 backward, CrctStepCfg.fp8_wgrad): dy as OCP e5m2
+  // with its gradient scale site, x as e4m3 with its activation scale site -- x's copy is only there behind an fp8 forward of this
+  // Linear (f8_lin).  The weight gradient then reads half the bytes (gemm.hip, fp8 weight gradients); the bias gradient still sums
+  // the bf16 dy.
+  void lin_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, const LinearP& l, int M, bool with_bias = false, const WgQ8& w8 = WgQ8()) {
     if (rc) return;
-    const bool f8w = f8b() == 1 && c->fp8_wgrad && defer_wgrad && q8.g_dy >= 0 && q8.site_x >= 0 && q8.dyq != (size_t)-1 && q8.xq != (size_t)-1 &&
+    const bool f8w = f8b() == 1 && c->fp8_wgrad && defer_wgrad && f8_lin(l) && w8.dy.site >= 0 && w8.x.site >= 0 &&
                      l.in % 16 == 0 && l.out % 16 == 0 && lddy % 16 == 0 && ldx % 16 == 0;
     const bool fold = !f8w && with_bias && M % 64 == 0 && l.in % 8 == 0 && l.out % 8 == 0 && lddy % 8 == 0 && ldx % 8 == 0;
     if (with_bias && !fold) bias_grad(dy, lddy, l, M);
     if (rc) return;
-    CrctGemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = dy; g.B = x; g.C = G(l.w); g.lda = lddy; g.ldb = ldx; g.ldc = l.in; g.M = l.out; g.N = l.in; g.K = M;
-    g.ta = 1; g.tb = 1; g.c_is_f32 = 1; g.accumulate = 1; g.tile = -1; g.alpha = 1.0f; g.site = l.site;
-    if (l.site > 0 && l.site < CRCT_SITE_COUNT && e->policy[l.site][2][phase].cfg >= 0) g.tile = e->policy[l.site][2][phase].cfg;
+    Opt o; o.f32 = true; o.acc = true;
+    CrctGemmArgs g = gemm_args(WGRAD, l, M, dy, lddy, x, ldx, G(l.w), l.in, o, f8w ? q8(w8.dy) : Q8(), f8w ? q8(w8.x) : Q8());
     if (c->wgrad_overwrite && e->wgrad_owned.count(l.w)) {
       if (++e->wgrad_pass[l.w] > 1) { rc = 1; crct_set_error("engine_backward: weight gradient at offset %lld is produced twice in one pass but is listed as owned", (long long)l.w); return; }
       g.accumulate = 0;               // the only producer of this gradient: write it, whatever the buffer held
@@ -466,22 +523,15 @@ struct Run {
     }
     if (fold) g.rowsum_out = G(l.b);
     if (f8w) {
-      g.A = W<uint8_t>(q8.dyq); g.B = W<uint8_t>(q8.xq); g.fp8 = 1 | 2;
       if (g.tile != 36) g.tile = 37;                      // 2 stages (two workgroups per CU) unless the site policy asks for 3
-      g.scale_a = gscale(q8.g_dy); g.scale_b = c->fp8_act_scale + q8.site_x;
       pending_f8.push_back(g);
       return;
     }
-    if (!defer_wgrad) { ++tick; fail(crct_gemm_bf16(&g, s)); return; }     // head chain: in order, right now
+    if (!defer_wgrad) { launch(g); return; }              // head chain: in order, right now
     // queued also without a side stream (sw == s): the same groups, hence the same kernels and summation orders,
     // in every stream mode -- results stay bit-identical across modes
     pending.push_back(g);
     if (pending.size() == 8) flush_wgrads();
-  }
-  // dx[M][in] = dy W (+ epilogue)
-  void lin_dgrad(const void* dy, int64_t lddy, const LinearP& l, int M, void* dx, int64_t lddx, Opt o) {
-    o.site = l.site;
-    gemm(dy, lddy, false, PB(l.w), l.in, true, dx, lddx, M, l.in, l.out, o);
   }
   // launch the queued weight-gradient GEMMs on the side stream, ordered after everything enqueued on s so far
   std::vector<CrctGemmArgs> pending_f8;      // the layer's fp8 weight gradients: one grouped launch of their own
@@ -520,70 +570,67 @@ struct Run {
     if (rc) return;
     fail(crct_colsum_bf16(dy, lddy, G(l.b), F(sw != s ? colsum_part_w : colsum_part), M, l.out, 1, sw));
   }
-  void ln_fwd(size_t x, const LnP& ln, size_t y, size_t mean, size_t rstd, int M, int H, size_t yq, int site) {
+  // y: the LayerNorm's output with its e4m3 and fp32 copies (ProjA::out / FfnA::out)
+  void ln_fwd(size_t x, const LnP& ln, const Act& y, size_t mean, size_t rstd, int M, int H) {
     if (rc) return;
     ++tick;
-    CrctLnFwdArgs a = {A(x), P(ln.g), P(ln.b), A(y), F(mean), F(rstd), M, H, 1e-12f, 0, 1.f, 0, c->seed, nullptr, nullptr, nullptr, 0, nullptr};
-    if (r32()) { a.x_f32 = 1; a.y_f32 = F(e->res32.at(y)); }
-    if (f8()) { a.q_out = W<uint8_t>(yq); a.q_scale = c->fp8_act_scale + site; a.q_amax = c->fp8_act_amax + (int64_t)site * CRCT_FP8_AMAX_LANES; }
-    fail(launch_ln_fwd(a, s));
+    CrctLnFwdArgs a = {A(x), P(ln.g), P(ln.b), A(y.x), F(mean), F(rstd), M, H, 1e-12f, 0, 1.f, 0, c->seed, nullptr, nullptr, nullptr, 0, nullptr};
+    if (r32()) { a.x_f32 = 1; a.y_f32 = F(y.x32); }
+    if (f8()) { a.q_out = W<uint8_t>(y.q); a.q_scale = ascale(y.site); a.q_amax = aamax(y.site); }
+    fail(crct_layernorm_fwd_args(&a, s));
   }
-  static int launch_ln_fwd(const CrctLnFwdArgs& a, hipStream_t st) { return crct_layernorm_fwd_args(&a, st); }
   // The fp32 residual stream (CrctStepCfg.residual_fp32): the pre-LayerNorm sums are written and read as fp32, and every block adds
   // the fp32 copy of its input where the producing LayerNorm left one (the embeddings' outputs have none: bf16 there, one rounding)
   bool r32() const { return c->residual_fp32 != 0; }
-  void residual(Opt& o, size_t x, int64_t ld) const {
+  void residual(Opt& o, const Act& x, int64_t ld) const {
     o.ld_add = ld;
     if (r32()) {
       o.f32 = true; o.c_cached = true;
-      auto it = e->res32.find(x);
-      if (it != e->res32.end()) { o.addend = F(it->second); o.add_f32 = true; return; }
+      if (x.x32 != NONE) { o.addend = F(x.x32); o.add_f32 = true; return; }
     }
-    o.addend = A(x);
+    o.addend = A(x.x);
   }
-  static int launch_ln_bwd(const CrctLnBwdArgs& a, hipStream_t st) { return crct_layernorm_bwd_rows_args(&a, st); }
-  // returns the buffer that holds the gradient of the producing Linear's output
+  // returns the buffer that holds the gradient of the producing Linear's output; dlq: where its e5m2 copy may go -- written for an
+  // fp8-backward-capable Linear, site -1 on return otherwise
   size_t ln_bwd(size_t dy, size_t x, size_t mean, size_t rstd, const LnP& ln, const LinearP& lin, size_t dres, size_t dlin,
-                size_t part, int M, int H, const Drop& dr, size_t dlq = (size_t)-1, int g_site = -1) {
+                size_t part, int M, int H, const Drop& dr, GradQ& dlq) {
+    if (!f8b_lin(lin)) dlq.site = -1;
     if (rc) return dres;
     // rows pass on the data stream; the column pass (dgamma, dbeta, bias gradient of the producing Linear) joins the
     // weight-gradient work on the side stream -- `part` belongs to this layer's scratch set
     ++tick;
     CrctLnBwdArgs a = {A(dy), A(x), F(mean), F(rstd), P(ln.g), A(dres), dr.thr ? A(dlin) : nullptr, F(part), M, H,
                        0, 1.f, 0, dr.thr, dr.scale, dr.site, c->seed, nullptr, nullptr, nullptr, r32() ? 1 : 0};
-    if (g_site >= 0 && f8b() && f8b_lin(lin)) { a.q_out = W<uint8_t>(dlq); a.q_scale = gscale(g_site); a.q_amax = gamax(g_site); }
-    fail(launch_ln_bwd(a, s));
+    if (dlq.site >= 0) { const Q8 d8 = q8(dlq); a.q_out = d8.q; a.q_scale = d8.scale; a.q_amax = d8.amax; }
+    fail(crct_layernorm_bwd_rows_args(&a, s));
     // the column pass is queued like the weight gradients: ONE ordering event per layer covers all of them
     if (defer_wgrad) pending_fin.push_back(FinJob{F(part), G(ln.g), G(ln.b), G(lin.b), M, H});
     else { wgrad_after_main(); if (!rc) fail(crct_layernorm_bwd_finalize(F(part), G(ln.g), G(ln.b), G(lin.b), M, H, 1, sw)); }
     return dr.thr ? dlin : dres;
   }
-  // ctxq / site_ctx: also the e4m3 copy of ctx (the fp8 forward GEMM and weight gradient of the attention-output projection read it)
-  void attn_fwd(const bf16_t* q, int64_t ldq, const bf16_t* k, const bf16_t* v, int64_t ldk, const uint8_t* km, bf16_t* ctx,
-                int64_t ldo, int B, int heads, int Tq, int Tk, int d, const Drop& dr, size_t ctxq = (size_t)-1, int site_ctx = -1,
-                size_t lse = (size_t)-1) {
+  // ctx.site >= 0: also the e4m3 copy of ctx (the fp8 forward GEMM and weight gradient of the attention-output projection read it)
+  void attn_fwd(const bf16_t* q, int64_t ldq, const bf16_t* k, const bf16_t* v, int64_t ldk, const uint8_t* km, const Act& ctx,
+                int64_t ldo, int B, int heads, int Tq, int Tk, int d, const Drop& dr, size_t lse = NONE) {
     if (rc) return;
     ++tick;
     const uint64_t seed = c->seed;
     CrctAttnQuant qz;
     memset(&qz, 0, sizeof(qz));
-    if (lse != (size_t)-1) qz.row_lse = F(lse);
-    if (ctxq != (size_t)-1 && site_ctx >= 0) {
-      qz.ctx_q = W<uint8_t>(ctxq); qz.ctx_scale = c->fp8_act_scale + site_ctx; qz.ctx_amax = c->fp8_act_amax + (int64_t)site_ctx * CRCT_FP8_AMAX_LANES;
-    }
-    fail(crct_attention_fwd_q(q, k, v, km, ctx, B, heads, Tq, Tk, d, ldq, ldk, ldk, ldo, dr.thr, dr.scale, dr.site, seed, &qz, s));
+    if (lse != NONE) qz.row_lse = F(lse);
+    if (ctx.site >= 0) { const Q8 c8 = q8(ctx); qz.ctx_q = c8.q; qz.ctx_scale = c8.scale; qz.ctx_amax = c8.amax; }
+    fail(crct_attention_fwd_q(q, k, v, km, A(ctx.x), B, heads, Tq, Tk, d, ldq, ldk, ldk, ldo, dr.thr, dr.scale, dr.site, seed, &qz, s));
   }
   // dqq / g_dq, dkq / dvq / g_dkv: also e5m2 copies of dq and of dk / dv (columns of fused dqkv buffers: one scale site per buffer)
   void attn_bwd(const bf16_t* q, int64_t ldq, const bf16_t* k, const bf16_t* v, int64_t ldk, const uint8_t* km,
                 const bf16_t* dctx, int64_t ldo, bf16_t* dq, int64_t lddq, bf16_t* dk, bf16_t* dv, int64_t lddk, int B,
                 int heads, int Tq, int Tk, int d, const Drop& dr, uint8_t* dqq = nullptr, int g_dq = -1, uint8_t* dkq = nullptr,
-                uint8_t* dvq = nullptr, int g_dkv = -1, size_t lse = (size_t)-1, const bf16_t* ctx = nullptr, int64_t ldc = 0) {
+                uint8_t* dvq = nullptr, int g_dkv = -1, size_t lse = NONE, const bf16_t* ctx = nullptr, int64_t ldc = 0) {
     if (rc) return;
     ++tick;
     const uint64_t seed = c->seed;
     CrctAttnQuant qz;
     memset(&qz, 0, sizeof(qz));
-    if (lse != (size_t)-1 && ctx) { qz.row_lse = F(lse); qz.ctx = ctx; qz.ld_ctx = ldc; }
+    if (lse != NONE && ctx) { qz.row_lse = F(lse); qz.ctx = ctx; qz.ld_ctx = ldc; }
     if (dqq && g_dq >= 0) { qz.dq_q = dqq; qz.dq_scale = gscale(g_dq); qz.dq_amax = gamax(g_dq); }
     if (dkq && dvq && g_dkv >= 0) { qz.dk_q = dkq; qz.dv_q = dvq; qz.dkv_scale = gscale(g_dkv); qz.dkv_amax = gamax(g_dkv); }
     fail(crct_attention_bwd_q(q, k, v, km, dctx, dq, dk, dv, B, heads, Tq, Tk, d, ldq, ldk, ldk, ldo, lddq, lddk, lddk, dr.thr, dr.scale,
@@ -591,56 +638,47 @@ struct Run {
   }
   // the attention kernels that write fp8 copies cover this shape (MFMA kernels: include/crct_hip.h, CrctAttnQuant)
   static bool attn_q_ok(int Tq, int Tk, int d) { return crct_attention_quant_ok(Tq, Tk, d) != 0; }
+  // The attention context as both passes see it: its e4m3 copy exists where the attention kernel covers the shape (aq) and the
+  // output projection `dense` runs its forward in fp8
+  Act ctx_act(size_t ctx, size_t ctxq, int site, const LinearP& dense, bool aq) const { return {ctx, ctxq, aq && f8_lin(dense) ? site : -1}; }
+  // The FFN's hidden activation as both passes see it: hq exists when both forward GEMMs run in fp8
+  Act ffn_h(const FfnP& p, const FfnA& a) const { return {a.h, a.hq, f8_lin(p.up) && f8_lin(p.down) ? a.site_h : -1}; }
 
   // ---------------------------------------------------------------- sub-blocks
   // a = LN(dropout(dense(ctx)) + x)          vilbert.py:424-428 / :555-559 / :749-756
-  // ctxq / site_ctx: the e4m3 copy of ctx the attention kernel wrote (-1: none, the projection runs in bf16)
-  void proj_fwd(const ProjP& p, const ProjA& a, size_t ctx, size_t x, int M, const Drop& dr, size_t ctxq = (size_t)-1, int site_ctx = -1) {
+  void proj_fwd(const ProjP& p, const ProjA& a, const Act& ctx, const Act& x, int M, const Drop& dr) {
     Opt o; o.drop = dr; residual(o, x, p.dense.out);
-    if (site_ctx >= 0 && f8_lin(p.dense)) lin_fwd_f8(A(ctx), ctxq, site_ctx, p.dense, M, A(a.s), p.dense.out, o);
-    else lin_fwd(A(ctx), p.dense.in, p.dense, M, A(a.s), p.dense.out, o);
-    ln_fwd(a.s, p.ln, a.a, a.mean, a.rstd, M, p.dense.out, a.aq, a.site_a);
+    lin_fwd(ctx, p.dense.in, p.dense, M, Act{a.s}, p.dense.out, o);
+    ln_fwd(a.s, p.ln, a.out(), a.mean, a.rstd, M, p.dense.out);
   }
-  // in: g = grad of a.  out: dres (residual gradient), dctx.  Parameter gradients accumulated.
-  void proj_bwd(const ProjP& p, const ProjA& a, size_t ctx, size_t g, size_t dres, size_t dlin, size_t dctx, size_t part, int M, const Drop& dr,
-                size_t dlq, size_t ctxq = (size_t)-1, int site_ctx = -1) {
-    const size_t dl = ln_bwd(g, a.s, a.mean, a.rstd, p.ln, p.dense, dres, dlin, part, M, p.dense.out, dr, dlq, a.g_dl);
-    WgQ8 w8;
-    if (site_ctx >= 0 && f8b_lin(p.dense)) { w8.dyq = dlq; w8.g_dy = a.g_dl; w8.xq = ctxq; w8.site_x = site_ctx; }
-    lin_wgrad(A(dl), p.dense.out, A(ctx), p.dense.in, p.dense, M, false, w8);
-    if (f8b_lin(p.dense)) lin_dgrad_f8(dlq, a.g_dl, A(dl), p.dense.out, p.dense, M, A(dctx), p.dense.in, Opt());
-    else lin_dgrad(A(dl), p.dense.out, p.dense, M, A(dctx), p.dense.in, Opt());
+  // in: g = grad of a.  out: sc.dres_b (residual gradient), sc.dctx.  Parameter gradients accumulated.
+  void proj_bwd(const ProjP& p, const ProjA& a, const Act& ctx, size_t g, const StreamScratch& sc, int M, const Drop& dr) {
+    GradQ dlq{sc.dlq_b, a.g_dl};
+    const size_t dl = ln_bwd(g, a.s, a.mean, a.rstd, p.ln, p.dense, sc.dres_b, sc.dlin_b, sc.part_b, M, p.dense.out, dr, dlq);
+    lin_wgrad(A(dl), p.dense.out, A(ctx.x), p.dense.in, p.dense, M, false, WgQ8{dlq, ctx});
+    lin_dgrad(A(dl), p.dense.out, p.dense, M, A(sc.dctx), p.dense.in, Opt(), dlq);
     if (e->wgrad_flush & 2) flush_wgrads();      // bit 1: the projection's weight gradient leaves behind its data gradient
   }
   // y = LN(dropout(down(gelu(up(x)))) + x)   vilbert.py:454-471 / :585-602 / :782-786
-  // xq / site_x: the e4m3 copy of x and its scale site (the LayerNorm that produced x wrote both)
-  void ffn_fwd(const FfnP& p, const FfnA& a, size_t x, size_t xq, int site_x, int M, const Drop& dr) {
+  void ffn_fwd(const FfnP& p, const FfnA& a, const Act& x, int M, const Drop& dr) {
     Opt o; o.preact = A(a.u); o.ld_aux = p.up.out; o.act = ACT_GELU;
-    const bool q_up = f8_lin(p.up), q_dn = f8_lin(p.down);
-    if (q_up) lin_fwd_f8(A(x), xq, site_x, p.up, M, A(a.h), p.up.out, o, a.hq, q_dn ? a.site_h : -1);
-    else lin_fwd(A(x), p.up.in, p.up, M, A(a.h), p.up.out, o);
+    const Act h = lin_fwd(x, p.up.in, p.up, M, ffn_h(p, a), p.up.out, o);
     Opt o2; o2.drop = dr; residual(o2, x, p.down.out);
-    if (q_up && q_dn) lin_fwd_f8(A(a.h), a.hq, a.site_h, p.down, M, A(a.s), p.down.out, o2);
-    else lin_fwd(A(a.h), p.down.in, p.down, M, A(a.s), p.down.out, o2);
-    ln_fwd(a.s, p.ln, a.y, a.mean, a.rstd, M, p.down.out, a.yq, a.site_y);
+    lin_fwd(h, p.down.in, p.down, M, Act{a.s}, p.down.out, o2);
+    ln_fwd(a.s, p.ln, a.out(), a.mean, a.rstd, M, p.down.out);
   }
-  // in: g = grad of a.y.  out: gx = grad of x.
-  // xq / site_x: the e4m3 copy of x the forward pass read (fp8 weight gradient of the up projection)
-  void ffn_bwd(const FfnP& p, const FfnA& a, size_t x, size_t xq, int site_x, size_t g, size_t gx, const StreamScratch& sc, int M, const Drop& dr) {
+  // in: g = grad of a.y.  out: gx = grad of x (the block's input: its e4m3 copy serves the fp8 weight gradient of the up projection).
+  void ffn_bwd(const FfnP& p, const FfnA& a, const Act& x, size_t g, size_t gx, const StreamScratch& sc, int M, const Drop& dr) {
     const int H = p.down.out, I = p.up.out;
-    const size_t dl = ln_bwd(g, a.s, a.mean, a.rstd, p.ln, p.down, sc.dres_a, sc.dlin_a, sc.part_a, M, H, dr, sc.dlq_a, a.g_dl);
-    const bool q_dn = f8b_lin(p.down), q_up = f8b_lin(p.up);
-    WgQ8 w_dn, w_up;
-    if (q_dn && f8_lin(p.up) && f8_lin(p.down)) { w_dn.dyq = sc.dlq_a; w_dn.g_dy = a.g_dl; w_dn.xq = a.hq; w_dn.site_x = a.site_h; }      // hq exists when both forward GEMMs ran in fp8
-    if (q_dn && q_up && f8_lin(p.up)) { w_up.dyq = sc.duq; w_up.g_dy = a.g_du; w_up.xq = xq; w_up.site_x = site_x; }
-    lin_wgrad(A(dl), H, A(a.h), I, p.down, M, false, w_dn);
+    GradQ dlq{sc.dlq_a, a.g_dl};
+    const size_t dl = ln_bwd(g, a.s, a.mean, a.rstd, p.ln, p.down, sc.dres_a, sc.dlin_a, sc.part_a, M, H, dr, dlq);
+    lin_wgrad(A(dl), H, A(a.h), I, p.down, M, false, WgQ8{dlq, ffn_h(p, a)});
     Opt o; o.dact_src = A(a.u); o.dact = ACT_GELU; o.ld_aux = I;
-    if (q_dn) lin_dgrad_f8(sc.dlq_a, a.g_dl, A(dl), H, p.down, M, A(sc.du), I, o, sc.duq, q_up ? a.g_du : -1);
-    else lin_dgrad(A(dl), H, p.down, M, A(sc.du), I, o);
-    lin_wgrad(A(sc.du), I, A(x), H, p.up, M, true, w_up);
+    // the e5m2 copy of du is asked for where the up projection's data gradient can read it
+    const GradQ duq = lin_dgrad(A(dl), H, p.down, M, A(sc.du), I, o, dlq, GradQ{sc.duq, f8b_lin(p.up) ? a.g_du : -1});
+    lin_wgrad(A(sc.du), I, A(x.x), H, p.up, M, true, WgQ8{duq, x});
     Opt o2; o2.addend = A(sc.dres_a); o2.ld_add = H;
-    if (q_dn && q_up) lin_dgrad_f8(sc.duq, a.g_du, A(sc.du), I, p.up, M, A(gx), H, o2);
-    else lin_dgrad(A(sc.du), I, p.up, M, A(gx), H, o2);
+    lin_dgrad(A(sc.du), I, p.up, M, A(gx), H, o2, duq);
     // wgrad_flush & 1: the FFN block's two weight gradients (and the LayerNorm column pass) leave for the side stream HERE, behind
     // the FFN-up data gradient, instead of at the end of the layer with the projection's and the QKV's: the grouped launch then runs
     // beside this layer's LayerNorm backward / attention-output dgrad / attention backward / QKV dgrad -- kernels of <= 156
@@ -649,80 +687,71 @@ struct Run {
   }
 
   // ---------------------------------------------------------------- self-attention layer
-  void self_fwd(const SelfLayerP& p, const SelfLayerA& a, size_t x, size_t xq, int site_x, const uint8_t* km, int B, int T) {
+  void self_fwd(const SelfLayerP& p, const SelfLayerA& a, const Act& x, const uint8_t* km, int B, int T) {
     const int M = B * T, H = p.H, d = H / p.heads;
-    if (f8_lin(p.qkv)) lin_fwd_f8(A(x), xq, site_x, p.qkv, M, A(a.qkv), 3 * H, Opt());
-    else lin_fwd(A(x), p.qkv.in, p.qkv, M, A(a.qkv), 3 * H, Opt());
-    const bool cq = f8_lin(p.proj.dense) && attn_q_ok(T, T, d);
-    attn_fwd(A(a.qkv), 3 * H, A(a.qkv) + H, A(a.qkv) + 2 * H, 3 * H, km, A(a.ctx), H, B, p.heads, T, T, d, drop(p.p_attn, p.site),
-             cq ? a.ctxq : (size_t)-1, cq ? a.site_ctx : -1, a.lse);
-    proj_fwd(p.proj, a.proj, a.ctx, x, M, drop(p.p_hid, p.site + 1), a.ctxq, cq ? a.site_ctx : -1);
-    ffn_fwd(p.ffn, a.ffn, a.proj.a, a.proj.aq, a.proj.site_a, M, drop(p.p_hid, p.site + 2));
+    lin_fwd(x, p.qkv.in, p.qkv, M, Act{a.qkv}, 3 * H, Opt());
+    const Act ctx = ctx_act(a.ctx, a.ctxq, a.site_ctx, p.proj.dense, attn_q_ok(T, T, d));
+    attn_fwd(A(a.qkv), 3 * H, A(a.qkv) + H, A(a.qkv) + 2 * H, 3 * H, km, ctx, H, B, p.heads, T, T, d, drop(p.p_attn, p.site), a.lse);
+    proj_fwd(p.proj, a.proj, ctx, x, M, drop(p.p_hid, p.site + 1));
+    ffn_fwd(p.ffn, a.ffn, a.proj.out(), M, drop(p.p_hid, p.site + 2));
   }
-  // xq / site_x: the e4m3 copy of the layer input (fp8 weight gradient of the QKV projection)
-  void self_bwd(const SelfLayerP& p, const SelfLayerA& a, size_t x, size_t xq, int site_x, size_t g, size_t gx, const uint8_t* km, int B, int T) {
+  // x: the layer input (its e4m3 copy serves the fp8 weight gradient of the QKV projection); g: grad of the output, gx: of x
+  void self_bwd(const SelfLayerP& p, const SelfLayerA& a, const Act& x, size_t g, size_t gx, const uint8_t* km, int B, int T) {
     const int M = B * T, H = p.H, d = H / p.heads;
     const StreamScratch& sc = layer_begin();
-    ffn_bwd(p.ffn, a.ffn, a.proj.a, a.proj.aq, a.proj.site_a, g, sc.gc, sc, M, drop(p.p_hid, p.site + 2));
+    ffn_bwd(p.ffn, a.ffn, a.proj.out(), g, sc.gc, sc, M, drop(p.p_hid, p.site + 2));
     const bool aq = attn_q_ok(T, T, d);
-    const bool cq = aq && f8_lin(p.proj.dense);                 // the forward pass wrote ctxq
     const bool gq = aq && f8b_lin(p.qkv) && f8_lin(p.qkv);      // e5m2 copy of dqkv: fp8 data and weight gradient of the QKV projection
-    proj_bwd(p.proj, a.proj, a.ctx, sc.gc, sc.dres_b, sc.dlin_b, sc.dctx, sc.part_b, M, drop(p.p_hid, p.site + 1), sc.dlq_b, a.ctxq, cq ? a.site_ctx : -1);
+    const GradQ dqkvq{sc.dqkvq, gq ? a.g_dqkv : -1};
+    proj_bwd(p.proj, a.proj, ctx_act(a.ctx, a.ctxq, a.site_ctx, p.proj.dense, aq), sc.gc, sc, M, drop(p.p_hid, p.site + 1));
     uint8_t* dq8 = gq ? W<uint8_t>(sc.dqkvq) : nullptr;
     attn_bwd(A(a.qkv), 3 * H, A(a.qkv) + H, A(a.qkv) + 2 * H, 3 * H, km, A(sc.dctx), H, A(sc.dqkv), 3 * H, A(sc.dqkv) + H,
              A(sc.dqkv) + 2 * H, 3 * H, B, p.heads, T, T, d, drop(p.p_attn, p.site), dq8, a.g_dqkv, gq ? dq8 + H : nullptr,
              gq ? dq8 + 2 * H : nullptr, a.g_dqkv, a.lse, A(a.ctx), H);
-    WgQ8 w8;
-    if (gq) { w8.dyq = sc.dqkvq; w8.g_dy = a.g_dqkv; w8.xq = xq; w8.site_x = site_x; }
-    lin_wgrad(A(sc.dqkv), 3 * H, A(x), H, p.qkv, M, true, w8);
+    lin_wgrad(A(sc.dqkv), 3 * H, A(x.x), H, p.qkv, M, true, WgQ8{dqkvq, x});
     Opt o; o.addend = A(sc.dres_b); o.ld_add = H;
-    if (gq) lin_dgrad_f8(sc.dqkvq, a.g_dqkv, A(sc.dqkv), 3 * H, p.qkv, M, A(gx), H, o);
-    else lin_dgrad(A(sc.dqkv), 3 * H, p.qkv, M, A(gx), H, o);
+    lin_dgrad(A(sc.dqkv), 3 * H, p.qkv, M, A(gx), H, o, dqkvq);
     layer_end();
   }
 
   // ---------------------------------------------------------------- connection layer (vilbert.py:774-788)
   // `this` drives the TEXT stream, `V` the VISUAL stream (they may share one HIP stream).
-  void conn_fwd(Run& V, const ConnLayerP& p, const ConnLayerA& a, size_t xv, size_t xvq, int site_v, size_t xt, size_t xtq, int site_t) {
+  void conn_fwd(Run& V, const ConnLayerP& p, const ConnLayerA& a, const StepIn& x) {
     const CrctModelDims& D = e->d;
     const int B = b->B, Mv = B * b->V, Mt = B * b->T, Hb = D.Hb, d = Hb / D.b_heads;
-    if (V.f8_lin(p.qkv1)) V.lin_fwd_f8(V.A(xv), xvq, site_v, p.qkv1, Mv, V.A(a.qkv1), 3 * Hb, Opt());
-    else V.lin_fwd(V.A(xv), p.qkv1.in, p.qkv1, Mv, V.A(a.qkv1), 3 * Hb, Opt());  // query1/key1/value1  :662-664
-    if (f8_lin(p.qkv2)) lin_fwd_f8(A(xt), xtq, site_t, p.qkv2, Mt, A(a.qkv2), 3 * Hb, Opt());
-    else lin_fwd(A(xt), p.qkv2.in, p.qkv2, Mt, A(a.qkv2), 3 * Hb, Opt());      // query2/key2/value2  :673-675
+    V.lin_fwd(x.v, p.qkv1.in, p.qkv1, Mv, Act{a.qkv1}, 3 * Hb, Opt());      // query1/key1/value1  :662-664
+    lin_fwd(x.t, p.qkv2.in, p.qkv2, Mt, Act{a.qkv2}, 3 * Hb, Opt());        // query2/key2/value2  :673-675
     cross_sync(V);                                    // text needs k1, v1; visual needs k2, v2
-    // text queries over visual keys/values -> ctx1 [B,T,Hb]  :684-701 (dropout1 = v_attention prob)
     const bool aq = attn_q_ok(b->T, b->V, d) && attn_q_ok(b->V, b->T, d);
-    const bool cq1 = aq && f8_lin(p.proj_t.dense), cq2 = aq && V.f8_lin(p.proj_v.dense);
-    attn_fwd(A(a.qkv2), 3 * Hb, A(a.qkv1) + Hb, A(a.qkv1) + 2 * Hb, 3 * Hb, b->image_keymask, A(a.ctx1), Hb, B, D.b_heads,
-             b->T, b->V, d, drop(D.p_v_attn, p.site), cq1 ? a.ctx1q : (size_t)-1, cq1 ? a.site_ctx1 : -1, a.lse1);
+    const Act ctx1 = ctx_act(a.ctx1, a.ctx1q, a.site_ctx1, p.proj_t.dense, aq), ctx2 = V.ctx_act(a.ctx2, a.ctx2q, a.site_ctx2, p.proj_v.dense, aq);
+    // text queries over visual keys/values -> ctx1 [B,T,Hb]  :684-701 (dropout1 = v_attention prob)
+    attn_fwd(A(a.qkv2), 3 * Hb, A(a.qkv1) + Hb, A(a.qkv1) + 2 * Hb, 3 * Hb, b->image_keymask, ctx1, Hb, B, D.b_heads,
+             b->T, b->V, d, drop(D.p_v_attn, p.site), a.lse1);
     // visual queries over text keys/values -> ctx2 [B,V,Hb]  :704-723
-    V.attn_fwd(A(a.qkv1), 3 * Hb, A(a.qkv2) + Hb, A(a.qkv2) + 2 * Hb, 3 * Hb, b->text_keymask, A(a.ctx2), Hb, B, D.b_heads,
-               b->V, b->T, d, drop(D.p_attn, p.site + 1), cq2 ? a.ctx2q : (size_t)-1, cq2 ? a.site_ctx2 : -1, a.lse2);
+    V.attn_fwd(A(a.qkv1), 3 * Hb, A(a.qkv2) + Hb, A(a.qkv2) + 2 * Hb, 3 * Hb, b->text_keymask, ctx2, Hb, B, D.b_heads,
+               b->V, b->T, d, drop(D.p_attn, p.site + 1), a.lse2);
     // cross wiring :780 -- visual stream takes ctx2, text stream takes ctx1
-    V.proj_fwd(p.proj_v, a.proj_v, a.ctx2, xv, Mv, drop(D.p_v_hidden, p.site + 2), a.ctx2q, cq2 ? a.site_ctx2 : -1);
-    proj_fwd(p.proj_t, a.proj_t, a.ctx1, xt, Mt, drop(D.p_hidden, p.site + 3), a.ctx1q, cq1 ? a.site_ctx1 : -1);
-    V.ffn_fwd(p.ffn_v, a.ffn_v, a.proj_v.a, a.proj_v.aq, a.proj_v.site_a, Mv, drop(D.p_v_hidden, p.site + 4));
-    ffn_fwd(p.ffn_t, a.ffn_t, a.proj_t.a, a.proj_t.aq, a.proj_t.site_a, Mt, drop(D.p_hidden, p.site + 5));
+    V.proj_fwd(p.proj_v, a.proj_v, ctx2, x.v, Mv, drop(D.p_v_hidden, p.site + 2));
+    proj_fwd(p.proj_t, a.proj_t, ctx1, x.t, Mt, drop(D.p_hidden, p.site + 3));
+    V.ffn_fwd(p.ffn_v, a.ffn_v, a.proj_v.out(), Mv, drop(D.p_v_hidden, p.site + 4));
+    ffn_fwd(p.ffn_t, a.ffn_t, a.proj_t.out(), Mt, drop(D.p_hidden, p.site + 5));
   }
-  // x*q / site_*: the e4m3 copies of the two layer inputs (fp8 weight gradients of the QKV projections)
-  void conn_bwd(Run& V, const ConnLayerP& p, const ConnLayerA& a, size_t xv, size_t xvq, int site_v, size_t xt, size_t xtq, int site_t, size_t gv,
-                size_t gt, size_t gxv, size_t gxt) {
+  // x: the two layer inputs (their e4m3 copies serve the fp8 weight gradients of the QKV projections); gv / gt: grads of the two
+  // outputs, gxv / gxt: of the inputs
+  void conn_bwd(Run& V, const ConnLayerP& p, const ConnLayerA& a, const StepIn& x, size_t gv, size_t gt, size_t gxv, size_t gxt) {
     const CrctModelDims& D = e->d;
     hipEvent_t free_v = V.set_free[V.parity], free_t = set_free[parity];      // "the last readers of this scratch set are done"
     const StreamScratch& sv = V.layer_begin(); const StreamScratch& st = layer_begin();
     const int B = b->B, Mv = B * b->V, Mt = B * b->T, Hb = D.Hb, d = Hb / D.b_heads;
-    V.ffn_bwd(p.ffn_v, a.ffn_v, a.proj_v.a, a.proj_v.aq, a.proj_v.site_a, gv, sv.gc, sv, Mv, drop(D.p_v_hidden, p.site + 4));
-    ffn_bwd(p.ffn_t, a.ffn_t, a.proj_t.a, a.proj_t.aq, a.proj_t.site_a, gt, st.gc, st, Mt, drop(D.p_hidden, p.site + 5));
+    V.ffn_bwd(p.ffn_v, a.ffn_v, a.proj_v.out(), gv, sv.gc, sv, Mv, drop(D.p_v_hidden, p.site + 4));
+    ffn_bwd(p.ffn_t, a.ffn_t, a.proj_t.out(), gt, st.gc, st, Mt, drop(D.p_hidden, p.site + 5));
     const bool aq = attn_q_ok(b->T, b->V, d) && attn_q_ok(b->V, b->T, d);
-    const bool cq1 = aq && f8_lin(p.proj_t.dense), cq2 = aq && V.f8_lin(p.proj_v.dense);
     // e5m2 copies of the two fused dqkv buffers: only when BOTH QKV projections run their gradients in fp8 (each buffer is written by
     // both attention kernels)
     const bool gq = aq && f8b_lin(p.qkv1) && f8b_lin(p.qkv2) && f8_lin(p.qkv1) && f8_lin(p.qkv2);
-    V.proj_bwd(p.proj_v, a.proj_v, a.ctx2, sv.gc, sv.dres_b, sv.dlin_b, sv.dctx, sv.part_b, Mv, drop(D.p_v_hidden, p.site + 2), sv.dlq_b, a.ctx2q,
-               cq2 ? a.site_ctx2 : -1);   // dctx2 [Mv,Hb]
-    proj_bwd(p.proj_t, a.proj_t, a.ctx1, st.gc, st.dres_b, st.dlin_b, st.dctx, st.part_b, Mt, drop(D.p_hidden, p.site + 3), st.dlq_b, a.ctx1q,
-             cq1 ? a.site_ctx1 : -1);       // dctx1 [Mt,Hb]
+    const GradQ dqkvq_v{sv.dqkvq, gq ? a.g_dqkv1 : -1}, dqkvq_t{st.dqkvq, gq ? a.g_dqkv2 : -1};
+    V.proj_bwd(p.proj_v, a.proj_v, V.ctx_act(a.ctx2, a.ctx2q, a.site_ctx2, p.proj_v.dense, aq), sv.gc, sv, Mv, drop(D.p_v_hidden, p.site + 2));   // dctx2 [Mv,Hb]
+    proj_bwd(p.proj_t, a.proj_t, ctx_act(a.ctx1, a.ctx1q, a.site_ctx1, p.proj_t.dense, aq), st.gc, st, Mt, drop(D.p_hidden, p.site + 3));         // dctx1 [Mt,Hb]
     // each attention backward also writes into the OTHER stream's dqkv scratch, which the layer that used this scratch set
     // last (its dgrad, and its weight-gradient GEMMs on the side stream) may still be reading.  With side streams that
     // layer's end is marked by the set's free event (recorded on the side stream behind everything the layer enqueued):
@@ -744,16 +773,12 @@ struct Run {
                vq8, a.g_dqkv1, gq ? tq8 + Hb : nullptr, gq ? tq8 + 2 * Hb : nullptr, a.g_dqkv2, a.lse2, A(a.ctx2), Hb);
     // each stream's dqkv buffer has been written by BOTH attention backward kernels
     cross_sync(V);
-    WgQ8 wv, wt;
-    if (gq) { wv.dyq = sv.dqkvq; wv.g_dy = a.g_dqkv1; wv.xq = xvq; wv.site_x = site_v; wt.dyq = st.dqkvq; wt.g_dy = a.g_dqkv2; wt.xq = xtq; wt.site_x = site_t; }
-    V.lin_wgrad(A(sv.dqkv), 3 * Hb, A(xv), D.Hv, p.qkv1, Mv, true, wv);
+    V.lin_wgrad(A(sv.dqkv), 3 * Hb, A(x.v.x), D.Hv, p.qkv1, Mv, true, WgQ8{dqkvq_v, x.v});
     Opt ov; ov.addend = A(sv.dres_b); ov.ld_add = D.Hv;
-    if (gq) V.lin_dgrad_f8(sv.dqkvq, a.g_dqkv1, A(sv.dqkv), 3 * Hb, p.qkv1, Mv, A(gxv), D.Hv, ov);
-    else V.lin_dgrad(A(sv.dqkv), 3 * Hb, p.qkv1, Mv, A(gxv), D.Hv, ov);
-    lin_wgrad(A(st.dqkv), 3 * Hb, A(xt), D.H, p.qkv2, Mt, true, wt);
+    V.lin_dgrad(A(sv.dqkv), 3 * Hb, p.qkv1, Mv, A(gxv), D.Hv, ov, dqkvq_v);
+    lin_wgrad(A(st.dqkv), 3 * Hb, A(x.t.x), D.H, p.qkv2, Mt, true, WgQ8{dqkvq_t, x.t});
     Opt ot; ot.addend = A(st.dres_b); ot.ld_add = D.H;
-    if (gq) lin_dgrad_f8(st.dqkvq, a.g_dqkv2, A(st.dqkv), 3 * Hb, p.qkv2, Mt, A(gxt), D.H, ot);
-    else lin_dgrad(A(st.dqkv), 3 * Hb, p.qkv2, Mt, A(gxt), D.H, ot);
+    lin_dgrad(A(st.dqkv), 3 * Hb, p.qkv2, Mt, A(gxt), D.H, ot, dqkvq_t);
     V.layer_end();
     layer_end();
   }
@@ -765,8 +790,8 @@ struct Run {
     if (!rc) fail(crct_embed_text_fwd(b->tokens, b->segments, b->loc, P(e->et.word), P(e->et.pos), P(e->et.type), P(e->et.wloc),
                                       P(e->et.bloc), P(e->et.ln.g), P(e->et.ln.b), A(e->eta.sum), A(e->eta.y), F(e->eta.mean),
                                       F(e->eta.rstd), b->B, b->T, D.H, D.n_pos, 1e-12f, dt.thr, dt.scale, dt.site, c->seed, s));
-    if (!rc && f8()) fail(crct_fp8_quantize_bf16(A(e->eta.y), W<uint8_t>(e->eta.yq), c->fp8_act_scale + e->eta.site,
-                                                 c->fp8_act_amax + (int64_t)e->eta.site * CRCT_FP8_AMAX_LANES, (int64_t)b->B * b->T * D.H, s));
+    if (!rc && f8()) fail(crct_fp8_quantize_bf16(A(e->eta.y), W<uint8_t>(e->eta.yq), ascale(e->eta.site), aamax(e->eta.site),
+                                                 (int64_t)b->B * b->T * D.H, s));
   }
   void embed_image_fwd() {
     const CrctModelDims& D = e->d;
@@ -782,12 +807,12 @@ struct Run {
     }
     if (!rc) fail(b->image_feat_bf16 ? crct_softmax_rows_bf16_bf16(b->image_feat, A(e->eva.soft), Mv, D.Fv, s)
                                      : crct_softmax_rows_f32_bf16((const float*)b->image_feat, A(e->eva.soft), Mv, D.Fv, s));
-    lin_fwd(A(e->eva.soft), D.Fv, e->ev.img, Mv, A(e->eva.lin), D.Hv, Opt());
+    lin_fwd(Act{e->eva.soft}, D.Fv, e->ev.img, Mv, Act{e->eva.lin}, D.Hv, Opt());
     if (!rc) fail(crct_embed_image_fwd(A(e->eva.lin), b->image_loc, b->image_target, P(e->ev.wloc), P(e->ev.bloc), P(e->ev.color),
                                        P(e->ev.ln.g), P(e->ev.ln.b), A(e->eva.sum), A(e->eva.y), F(e->eva.mean), F(e->eva.rstd),
                                        Mv, D.Hv, 1e-12f, dv.thr, dv.scale, dv.site, c->seed, s));
-    if (!rc && f8()) fail(crct_fp8_quantize_bf16(A(e->eva.y), W<uint8_t>(e->eva.yq), c->fp8_act_scale + e->eva.site,
-                                                 c->fp8_act_amax + (int64_t)e->eva.site * CRCT_FP8_AMAX_LANES, (int64_t)Mv * D.Hv, s));
+    if (!rc && f8()) fail(crct_fp8_quantize_bf16(A(e->eva.y), W<uint8_t>(e->eva.yq), ascale(e->eva.site), aamax(e->eva.site),
+                                                 (int64_t)Mv * D.Hv, s));
   }
   void embed_text_bwd(size_t gt) {
     const CrctModelDims& D = e->d;
@@ -822,13 +847,13 @@ struct Run {
   }
 
   // ---------------------------------------------------------------- heads
-  void pipe_fwd(const LinearP* l, const bf16_t* x0, int64_t ldx0, const size_t* acts, bf16_t* out_last, int64_t ld_last, int B) {
+  void pipe_fwd(const LinearP* l, size_t x0, int64_t ldx0, const size_t* acts, size_t out_last, int64_t ld_last, int B) {
     // Linear+LeakyReLU x3, then a plain Linear into `out_last` (regressor.py:8-28)
     Opt o; o.act = ACT_LEAKY;
-    lin_fwd(x0, ldx0, l[0], B, A(acts[0]), l[0].out, o);
-    lin_fwd(A(acts[0]), l[0].out, l[1], B, A(acts[1]), l[1].out, o);
-    lin_fwd(A(acts[1]), l[1].out, l[2], B, A(acts[2]), l[2].out, o);
-    lin_fwd(A(acts[2]), l[2].out, l[3], B, out_last, ld_last, Opt());
+    lin_fwd(Act{x0}, ldx0, l[0], B, Act{acts[0]}, l[0].out, o);
+    lin_fwd(Act{acts[0]}, l[0].out, l[1], B, Act{acts[1]}, l[1].out, o);
+    lin_fwd(Act{acts[1]}, l[1].out, l[2], B, Act{acts[2]}, l[2].out, o);
+    lin_fwd(Act{acts[2]}, l[2].out, l[3], B, Act{out_last}, ld_last, Opt());
   }
   // backward of a pipe: du3 = grad of the last Linear's output (ld = ld3); writes dx0 (+= if acc).  gb = three gradient
   // buffers of this pipe alone (nothing is recycled: the weight-gradient GEMMs that read them run later, on the side stream)
@@ -859,12 +884,12 @@ struct Run {
     const int64_t ld = visual ? (int64_t)b->V * D.Hv : (int64_t)b->T * D.H;  // CLS / IMG rows: hidden_states[:, 0]
     Opt orelu; orelu.act = ACT_RELU;
     if (visual) {
-      lin_fwd(A(seq), ld, e->v_pool, B, A(e->ha.pooled_v), D.Hb, orelu);     // vilbert.py:970-976
+      lin_fwd(Act{seq}, ld, e->v_pool, B, Act{e->ha.pooled_v}, D.Hb, orelu);   // vilbert.py:970-976
       if (has_regressor())
-        pipe_fwd(e->vp, A(seq), ld, e->ha.v, A(e->ha.cat), 512, B);          // regressor on the raw IMG state; cat = (hv, hw): regressor.py:39-41
+        pipe_fwd(e->vp, seq, ld, e->ha.v, e->ha.cat, 512, B);                // regressor on the raw IMG state; cat = (hv, hw): regressor.py:39-41
     } else {
-      lin_fwd(A(seq), ld, e->t_pool, B, A(e->ha.pooled_t), D.Hb, orelu);     // vilbert.py:955-961
-      if (has_regressor()) pipe_fwd(e->tp, A(seq), ld, e->ha.t, A(e->ha.cat) + 256, 512, B);
+      lin_fwd(Act{seq}, ld, e->t_pool, B, Act{e->ha.pooled_t}, D.Hb, orelu);   // vilbert.py:955-961
+      if (has_regressor()) pipe_fwd(e->tp, seq, ld, e->ha.t, e->ha.cat + 256 * sizeof(bf16_t), 512, B);
     }
   }
   bool has_regressor() const { return e->var.regressor != CRCT_REGRESSOR_NONE; }
@@ -901,9 +926,9 @@ struct Run {
     const int B = b->B;
     Opt o; o.act = ACT_LEAKY;
     if (has_regressor()) {
-      lin_fwd(A(e->ha.cat), 512, e->fu[0], B, A(e->ha.f[0]), 512, o);
-      lin_fwd(A(e->ha.f[0]), 512, e->fu[1], B, A(e->ha.f[1]), 256, o);
-      lin_fwd(A(e->ha.f[1]), 256, e->fu[2], B, A(e->ha.f[2]), 256, o);
+      lin_fwd(Act{e->ha.cat}, 512, e->fu[0], B, Act{e->ha.f[0]}, 512, o);
+      lin_fwd(Act{e->ha.f[0]}, 512, e->fu[1], B, Act{e->ha.f[1]}, 256, o);
+      lin_fwd(Act{e->ha.f[1]}, 256, e->fu[2], B, Act{e->ha.f[2]}, 256, o);
     }
     if (rc) return;
     CrctHeadArgs h;
@@ -977,8 +1002,9 @@ int check_batch(const crct_engine* e, const CrctBatch* b) {
 }  // namespace
 
 // =================================================================================== C ABI
-static crct_engine_t* engine_create_impl(const CrctModelDims* dims, const char* names, const int64_t* offsets, const int64_t* sizes,
-                                         int n_params, int max_B, int max_T, int max_V, const CrctVariant* variant) {
+extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, const char* names, const int64_t* offsets,
+                                                     const int64_t* sizes, int n_params, int max_B, int max_T, int max_V,
+                                                     const CrctVariant* variant) {
   if (!dims || !names || !offsets || !sizes) { crct_set_error("engine_create: null argument"); return nullptr; }
   if (variant && (variant->dataset < CRCT_DATASET_PLOTQA || variant->dataset > CRCT_DATASET_FIGUREQA ||
                   variant->regressor < CRCT_REGRESSOR_PLOTQA || variant->regressor > CRCT_REGRESSOR_CE ||
@@ -1026,31 +1052,13 @@ static crct_engine_t* engine_create_impl(const CrctModelDims* dims, const char* 
   // ---- parameters
   char buf[256];
   uint32_t site = 16;
-  for (int i = 0; i < D.L; ++i) {
+  for (int i = 0; i < D.L; ++i, site += 4) {
     snprintf(buf, sizeof(buf), "bert.encoder.layer.%d.", i);
-    std::string p(buf);
-    SelfLayerP l;
-    l.H = D.H; l.heads = D.heads; l.p_attn = D.p_attn; l.p_hid = D.p_hidden; l.site = site; site += 4;
-    l.qkv = fused3(e, p + "attention.self.query", p + "attention.self.key", p + "attention.self.value", D.H, D.H, CRCT_SITE_T_QKV);
-    l.proj.dense = linear_p(e, p + "attention.output.dense", D.H, D.H, CRCT_SITE_T_OUT);
-    l.proj.ln = ln_p(e, p + "attention.output.LayerNorm");
-    l.ffn.up = linear_p(e, p + "intermediate.dense", D.H, D.I, CRCT_SITE_T_FFN_UP);
-    l.ffn.down = linear_p(e, p + "output.dense", D.I, D.H, CRCT_SITE_T_FFN_DN);
-    l.ffn.ln = ln_p(e, p + "output.LayerNorm");
-    e->tl.push_back(l);
+    e->tl.push_back(self_layer_p(e, buf, D.H, D.I, D.heads, D.p_attn, D.p_hidden, site, CRCT_SITE_T_QKV));
   }
-  for (int i = 0; i < D.Lv; ++i) {
+  for (int i = 0; i < D.Lv; ++i, site += 4) {
     snprintf(buf, sizeof(buf), "bert.encoder.v_layer.%d.", i);
-    std::string p(buf);
-    SelfLayerP l;
-    l.H = D.Hv; l.heads = D.v_heads; l.p_attn = D.p_v_attn; l.p_hid = D.p_v_hidden; l.site = site; site += 4;
-    l.qkv = fused3(e, p + "attention.self.query", p + "attention.self.key", p + "attention.self.value", D.Hv, D.Hv, CRCT_SITE_V_QKV);
-    l.proj.dense = linear_p(e, p + "attention.output.dense", D.Hv, D.Hv, CRCT_SITE_V_OUT);
-    l.proj.ln = ln_p(e, p + "attention.output.LayerNorm");
-    l.ffn.up = linear_p(e, p + "intermediate.dense", D.Hv, D.Iv, CRCT_SITE_V_FFN_UP);
-    l.ffn.down = linear_p(e, p + "output.dense", D.Iv, D.Hv, CRCT_SITE_V_FFN_DN);
-    l.ffn.ln = ln_p(e, p + "output.LayerNorm");
-    e->vl.push_back(l);
+    e->vl.push_back(self_layer_p(e, buf, D.Hv, D.Iv, D.v_heads, D.p_v_attn, D.p_v_hidden, site, CRCT_SITE_V_QKV));
   }
   for (int i = 0; i < D.n_conn; ++i) {
     snprintf(buf, sizeof(buf), "bert.encoder.c_layer.%d.", i);
@@ -1096,12 +1104,7 @@ static crct_engine_t* engine_create_impl(const CrctModelDims* dims, const char* 
   if (e->bad) return fail(nullptr);
   {
     auto own = [&](const LinearP& l) { e->wgrad_owned[l.w] = (int64_t)l.in * l.out; };
-    for (const SelfLayerP& l : e->tl) { own(l.qkv); own(l.proj.dense); own(l.ffn.up); own(l.ffn.down); }
-    for (const SelfLayerP& l : e->vl) { own(l.qkv); own(l.proj.dense); own(l.ffn.up); own(l.ffn.down); }
-    for (const ConnLayerP& l : e->cl) {
-      own(l.qkv1); own(l.qkv2); own(l.proj_v.dense); own(l.proj_t.dense);
-      own(l.ffn_v.up); own(l.ffn_v.down); own(l.ffn_t.up); own(l.ffn_t.down);
-    }
+    each_encoder_linear(e, own);
     if (e->feat) own(e->ev.img);                   // (areas_emp: produced by the embedding kernel, accumulate-only)
     own(e->t_pool); own(e->v_pool);
     if (e->var.regressor != CRCT_REGRESSOR_NONE) {
@@ -1117,12 +1120,7 @@ static crct_engine_t* engine_create_impl(const CrctModelDims* dims, const char* 
       e->wq_slot[l.w] = (int)e->wq_list.size();
       e->wq_list.push_back({l.w, (int64_t)l.in * l.out});
     };
-    for (const SelfLayerP& l : e->tl) { slot(l.qkv); slot(l.ffn.up); slot(l.ffn.down); slot(l.proj.dense); }
-    for (const SelfLayerP& l : e->vl) { slot(l.qkv); slot(l.ffn.up); slot(l.ffn.down); slot(l.proj.dense); }
-    for (const ConnLayerP& l : e->cl) {
-      slot(l.qkv1); slot(l.qkv2); slot(l.ffn_v.up); slot(l.ffn_v.down); slot(l.ffn_t.up); slot(l.ffn_t.down);
-      slot(l.proj_v.dense); slot(l.proj_t.dense);
-    }
+    each_encoder_linear(e, slot);
   }
 
   // ---- workspace
@@ -1135,15 +1133,9 @@ static crct_engine_t* engine_create_impl(const CrctModelDims* dims, const char* 
   e->eta.site = e->n_sites++; e->eva.site = e->n_sites++;
   e->taps.push_back({"emb.t", e->eta.y, 't'});
   e->taps.push_back({"emb.v", e->eva.y, 'v'});
-  e->tla.resize(D.L); e->vla.resize(D.Lv); e->cla.resize(D.n_conn);
-  for (int i = 0; i < D.L; ++i) {
-    SelfLayerA& a = e->tla[i];
-    a.qkv = ar.take(Mt * 3 * D.H * 2); a.ctx = ar.take(Mt * D.H * 2); a.ctxq = ar.take(Mt * D.H); a.lse = ar.take(Mt * D.heads * 4); a.site_ctx = e->n_sites++; a.g_dqkv = e->n_gsites++; a.proj = proj_a(ar, Mt, D.H, e->n_sites, e->n_gsites); a.ffn = ffn_a(ar, Mt, D.H, D.I, e->n_sites, e->n_gsites);
-  }
-  for (int i = 0; i < D.Lv; ++i) {
-    SelfLayerA& a = e->vla[i];
-    a.qkv = ar.take(Mv * 3 * D.Hv * 2); a.ctx = ar.take(Mv * D.Hv * 2); a.ctxq = ar.take(Mv * D.Hv); a.lse = ar.take(Mv * D.v_heads * 4); a.site_ctx = e->n_sites++; a.g_dqkv = e->n_gsites++; a.proj = proj_a(ar, Mv, D.Hv, e->n_sites, e->n_gsites); a.ffn = ffn_a(ar, Mv, D.Hv, D.Iv, e->n_sites, e->n_gsites);
-  }
+  for (int i = 0; i < D.L; ++i) e->tla.push_back(self_layer_a(ar, Mt, D.H, D.I, D.heads, e->n_sites, e->n_gsites));
+  for (int i = 0; i < D.Lv; ++i) e->vla.push_back(self_layer_a(ar, Mv, D.Hv, D.Iv, D.v_heads, e->n_sites, e->n_gsites));
+  e->cla.resize(D.n_conn);
   for (int i = 0; i < D.n_conn; ++i) {
     ConnLayerA& a = e->cla[i];
     a.qkv1 = ar.take(Mv * 3 * D.Hb * 2); a.qkv2 = ar.take(Mt * 3 * D.Hb * 2);
@@ -1200,28 +1192,22 @@ static crct_engine_t* engine_create_impl(const CrctModelDims* dims, const char* 
     e->sk_cnt[0] = ar.take((size_t)2 * e->sk_tickets * 4);      // [text | visual] in one block: one memset per call
     e->sk_cnt[1] = e->sk_cnt[0] + (size_t)e->sk_tickets * 4;
   }
-  {
-    auto reg_ffn = [&](const FfnA& a) { e->res32[a.y] = a.y32; };
-    auto reg_proj = [&](const ProjA& a) { e->res32[a.a] = a.a32; };
-    for (const SelfLayerA& a : e->tla) { reg_proj(a.proj); reg_ffn(a.ffn); }
-    for (const SelfLayerA& a : e->vla) { reg_proj(a.proj); reg_ffn(a.ffn); }
-    for (const ConnLayerA& a : e->cla) { reg_proj(a.proj_v); reg_proj(a.proj_t); reg_ffn(a.ffn_v); reg_ffn(a.ffn_t); }
-  }
   e->ws_bytes = ar.top;
 
-  // ---- taps + final outputs, following the schedule
+  // ---- the hidden states every schedule step starts from (the last entry: the encoder's outputs), and the taps on them
   {
-    size_t xt = e->eta.y, xv = e->eva.y;
+    StepIn x = {Act{e->eta.y, e->eta.yq, e->eta.site}, Act{e->eva.y, e->eva.yq, e->eva.site}};
     for (const Step& st : e->sched) {
-      if (st.kind == 't') xt = e->tla[st.idx].ffn.y;
-      else if (st.kind == 'v') xv = e->vla[st.idx].ffn.y;
-      else { xv = e->cla[st.idx].ffn_v.y; xt = e->cla[st.idx].ffn_t.y; }
-      snprintf(buf, sizeof(buf), "%c%d.t", st.kind, st.idx); e->taps.push_back({buf, xt, 't'});
-      snprintf(buf, sizeof(buf), "%c%d.v", st.kind, st.idx); e->taps.push_back({buf, xv, 'v'});
+      e->in.push_back(x);
+      if (st.kind == 't') x.t = e->tla[st.idx].ffn.out();
+      else if (st.kind == 'v') x.v = e->vla[st.idx].ffn.out();
+      else { x.v = e->cla[st.idx].ffn_v.out(); x.t = e->cla[st.idx].ffn_t.out(); }
+      snprintf(buf, sizeof(buf), "%c%d.t", st.kind, st.idx); e->taps.push_back({buf, x.t.x, 't'});
+      snprintf(buf, sizeof(buf), "%c%d.v", st.kind, st.idx); e->taps.push_back({buf, x.v.x, 'v'});
     }
-    e->final_t = xt; e->final_v = xv;
-    e->taps.push_back({"seq_t", xt, 't'});
-    e->taps.push_back({"seq_v", xv, 'v'});
+    e->in.push_back(x);
+    e->taps.push_back({"seq_t", x.t.x, 't'});
+    e->taps.push_back({"seq_v", x.v.x, 'v'});
   }
 
   // ---- gradient segments in backward order: heads, schedule reversed, embeddings
@@ -1249,12 +1235,7 @@ static crct_engine_t* engine_create_impl(const CrctModelDims* dims, const char* 
 
 extern "C" crct_engine_t* crct_engine_create(const CrctModelDims* dims, const char* names, const int64_t* offsets,
                                              const int64_t* sizes, int n_params, int max_B, int max_T, int max_V) {
-  return engine_create_impl(dims, names, offsets, sizes, n_params, max_B, max_T, max_V, nullptr);
-}
-extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, const char* names, const int64_t* offsets,
-                                                     const int64_t* sizes, int n_params, int max_B, int max_T, int max_V,
-                                                     const CrctVariant* variant) {
-  return engine_create_impl(dims, names, offsets, sizes, n_params, max_B, max_T, max_V, variant);
+  return crct_engine_create_variant(dims, names, offsets, sizes, n_params, max_B, max_T, max_V, nullptr);
 }
 extern "C" int crct_engine_set_areas(crct_engine_t* e, const float* areas) {
   CRCT_REQUIRE(e, "engine_set_areas: null engine");
@@ -1339,9 +1320,9 @@ int reset_tickets(crct_engine* e, void* ws, hipStream_t s) {
 
 }  // namespace
 
-static int engine_forward_impl(crct_engine_t* e, const float* params_f32, const void* params_bf16, const CrctBatch* batch,
-                               const CrctStepCfg* cfg, void* workspace, float* logits, float* reg, float* stats,
-                               crct_stream_t stream) {
+extern "C" int crct_engine_forward(crct_engine_t* e, const float* params_f32, const void* params_bf16, const CrctBatch* batch,
+                                   const CrctStepCfg* cfg, void* workspace, float* logits, float* reg, float* stats,
+                                   crct_stream_t stream) {
   CRCT_REQUIRE(e && params_f32 && params_bf16 && cfg && workspace && logits && reg && stats, "engine_forward: null argument");
   if (int r = check_batch(e, batch)) return r;
   CRCT_REQUIRE(!cfg->fp8 || (e->feat && e->var.regressor == CRCT_REGRESSOR_PLOTQA),
@@ -1378,45 +1359,30 @@ static int engine_forward_impl(crct_engine_t* e, const float* params_f32, const 
   wait_params(Rv, nseg - 1);
   Rt.embed_text_fwd();
   Rv.embed_image_fwd();
-  size_t xt = e->eta.y, xv = e->eva.y;
-  size_t xtq = e->eta.yq, xvq = e->eva.yq;               // e4m3 copies of the running hidden states and their scale sites (fp8 forward)
-  int site_t = e->eta.site, site_v = e->eva.site;
-  int step_i = 0;
-  for (const Step& st : e->sched) {
-    const int seg = (int)e->sched.size() - step_i;       // backward segment of this schedule step
-    Rt.phase = (e->first_conn < 0 || step_i < e->first_conn) ? 0 : 1;      // text-only prefix: nothing else on the data path
-    ++step_i;
-    if (st.kind == 't') wait_params(Rt, seg);
-    else if (st.kind == 'v') wait_params(Rv, seg);
-    else { wait_params(Rt, seg); wait_params(Rv, seg); }
-    if (st.kind == 't') {
-      const SelfLayerA& a = e->tla[st.idx];
-      Rt.self_fwd(e->tl[st.idx], a, xt, xtq, site_t, batch->text_keymask, batch->B, batch->T);
-      xt = a.ffn.y; xtq = a.ffn.yq; site_t = a.ffn.site_y;
-    } else if (st.kind == 'v') {
-      const SelfLayerA& a = e->vla[st.idx];
-      Rv.self_fwd(e->vl[st.idx], a, xv, xvq, site_v, batch->image_keymask, batch->B, batch->V);
-      xv = a.ffn.y; xvq = a.ffn.yq; site_v = a.ffn.site_y;
-    } else {
-      const ConnLayerA& a = e->cla[st.idx];
-      Rt.conn_fwd(Rv, e->cl[st.idx], a, xv, xvq, site_v, xt, xtq, site_t);
-      xv = a.ffn_v.y; xvq = a.ffn_v.yq; site_v = a.ffn_v.site_y;
-      xt = a.ffn_t.y; xtq = a.ffn_t.yq; site_t = a.ffn_t.site_y;
-    }
+  for (size_t i = 0; i < e->sched.size(); ++i) {
+    const Step& st = e->sched[i];
+    const StepIn& x = e->in[i];
+    const int seg = (int)(e->sched.size() - i);          // backward segment of this schedule step
+    Rt.phase = (e->first_conn < 0 || (int)i < e->first_conn) ? 0 : 1;      // text-only prefix: nothing else on the data path
+    if (st.kind != 'v') wait_params(Rt, seg);
+    if (st.kind != 't') wait_params(Rv, seg);
+    if (st.kind == 't') Rt.self_fwd(e->tl[st.idx], e->tla[st.idx], x.t, batch->text_keymask, batch->B, batch->T);
+    else if (st.kind == 'v') Rv.self_fwd(e->vl[st.idx], e->vla[st.idx], x.v, batch->image_keymask, batch->B, batch->V);
+    else Rt.conn_fwd(Rv, e->cl[st.idx], e->cla[st.idx], x);
   }
   Rt.phase = 1;
   wait_params(Rt, 0);
   wait_params(Rv, 0);
-  Rt.heads_branch_fwd(false, xt);
-  Rv.heads_branch_fwd(true, xv);
+  Rt.heads_branch_fwd(false, e->in.back().t.x);
+  Rv.heads_branch_fwd(true, e->in.back().v.x);
   Rt.fail(order_streams(e, Rv.s, Rt.s));                 // join
   Rt.heads_tail_fwd(logits, reg, stats);
   return Rt.rc ? Rt.rc : Rv.rc;
 }
 
-static int engine_backward_impl(crct_engine_t* e, const float* params_f32, const void* params_bf16, const CrctBatch* batch,
-                                const CrctStepCfg* cfg, void* workspace, float* grads_f32, float* logits, float* reg,
-                                float* stats, int seg, crct_stream_t stream) {
+extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, const void* params_bf16, const CrctBatch* batch,
+                                    const CrctStepCfg* cfg, void* workspace, float* grads_f32, float* logits, float* reg,
+                                    float* stats, int seg, crct_stream_t stream) {
   CRCT_REQUIRE(e && params_f32 && params_bf16 && cfg && workspace && grads_f32 && logits && reg && stats, "engine_backward: null argument");
   CRCT_REQUIRE(batch && batch->labels, "engine_backward: labels are required (training step)");
   if (int r = check_batch(e, batch)) return r;
@@ -1432,24 +1398,6 @@ static int engine_backward_impl(crct_engine_t* e, const float* params_f32, const
   const int s0 = seg < 0 ? 0 : seg, s1 = seg < 0 ? nseg : seg + 1;
   CRCT_REQUIRE(s1 <= nseg, "engine_backward: bad segment %d", seg);
   if (s0 == 0) e->wgrad_pass_begin();
-  // inputs of every schedule step (outputs of the previous step of that stream)
-  // ... with their e4m3 copies and activation scale sites (fp8 weight gradients of the QKV projections)
-  std::vector<size_t> in_t(e->sched.size()), in_v(e->sched.size()), inq_t(e->sched.size()), inq_v(e->sched.size());
-  std::vector<int> ins_t(e->sched.size()), ins_v(e->sched.size());
-  {
-    size_t xt = e->eta.y, xv = e->eva.y, xtq = e->eta.yq, xvq = e->eva.yq;
-    int site_t = e->eta.site, site_v = e->eva.site;
-    for (size_t i = 0; i < e->sched.size(); ++i) {
-      in_t[i] = xt; in_v[i] = xv; inq_t[i] = xtq; inq_v[i] = xvq; ins_t[i] = site_t; ins_v[i] = site_v;
-      const Step& st = e->sched[i];
-      if (st.kind == 't') { const FfnA& f = e->tla[st.idx].ffn; xt = f.y; xtq = f.yq; site_t = f.site_y; }
-      else if (st.kind == 'v') { const FfnA& f = e->vla[st.idx].ffn; xv = f.y; xvq = f.yq; site_v = f.site_y; }
-      else {
-        const FfnA& fv = e->cla[st.idx].ffn_v; const FfnA& ft = e->cla[st.idx].ffn_t;
-        xv = fv.y; xvq = fv.yq; site_v = fv.site_y; xt = ft.y; xtq = ft.yq; site_t = ft.site_y;
-      }
-    }
-  }
   if (int r = reset_tickets(e, workspace, (hipStream_t)stream)) return r;
   // fork: every internal stream starts after the caller's prior work (previous segment, optimizer, ...)
   Rv.fail(order_streams(e, Rt.s, Rv.s));
@@ -1460,23 +1408,19 @@ static int engine_backward_impl(crct_engine_t* e, const float* params_f32, const
     Rt.phase = (in_sched && (e->first_conn < 0 || (int)si < e->first_conn)) ? 0 : 1;      // backward tail through the text-only layers
     if (sgi == 0) {
       e->cur_t = 0; e->cur_v = 0;
-      Rt.heads_bwd(Rv, e->final_t, e->final_v, e->st.dy[0], e->sv.dy[0], logits, reg, stats);
+      Rt.heads_bwd(Rv, e->in.back().t.x, e->in.back().v.x, e->st.dy[0], e->sv.dy[0], logits, reg, stats);
     } else if (sgi == nseg - 1) {
       Rt.embed_text_bwd(e->st.dy[e->cur_t]);
       Rv.embed_image_bwd(e->sv.dy[e->cur_v]);
     } else {
-      const size_t i = e->sched.size() - (size_t)sgi;
-      const Step& st = e->sched[i];
-      if (st.kind == 't') {
-        Rt.self_bwd(e->tl[st.idx], e->tla[st.idx], in_t[i], inq_t[i], ins_t[i], e->st.dy[e->cur_t], e->st.dy[e->cur_t ^ 1], batch->text_keymask, batch->B, batch->T);
-        e->cur_t ^= 1;
-      } else if (st.kind == 'v') {
-        Rv.self_bwd(e->vl[st.idx], e->vla[st.idx], in_v[i], inq_v[i], ins_v[i], e->sv.dy[e->cur_v], e->sv.dy[e->cur_v ^ 1], batch->image_keymask, batch->B, batch->V);
-        e->cur_v ^= 1;
-      } else {
-        Rt.conn_bwd(Rv, e->cl[st.idx], e->cla[st.idx], in_v[i], inq_v[i], ins_v[i], in_t[i], inq_t[i], ins_t[i], e->sv.dy[e->cur_v], e->st.dy[e->cur_t], e->sv.dy[e->cur_v ^ 1], e->st.dy[e->cur_t ^ 1]);
-        e->cur_t ^= 1; e->cur_v ^= 1;
-      }
+      const Step& st = e->sched[si];
+      const StepIn& x = e->in[si];
+      const size_t gt = e->st.dy[e->cur_t], gxt = e->st.dy[e->cur_t ^ 1], gv = e->sv.dy[e->cur_v], gxv = e->sv.dy[e->cur_v ^ 1];
+      if (st.kind == 't') Rt.self_bwd(e->tl[st.idx], e->tla[st.idx], x.t, gt, gxt, batch->text_keymask, batch->B, batch->T);
+      else if (st.kind == 'v') Rv.self_bwd(e->vl[st.idx], e->vla[st.idx], x.v, gv, gxv, batch->image_keymask, batch->B, batch->V);
+      else Rt.conn_bwd(Rv, e->cl[st.idx], e->cla[st.idx], x, gv, gt, gxv, gxt);
+      if (st.kind != 'v') e->cur_t ^= 1;
+      if (st.kind != 't') e->cur_v ^= 1;
     }
     if (seg < 0 && cfg->seg_done_events && !Rt.rc && !Rv.rc) {
       // segments ev_from .. sgi are completely enqueued: mark that point on every internal stream for the data-parallel caller
@@ -1500,18 +1444,6 @@ static int engine_backward_impl(crct_engine_t* e, const float* params_f32, const
   Rv.main_after_wgrad();
   Rt.fail(order_streams(e, Rv.s, Rt.s));
   return Rt.rc ? Rt.rc : Rv.rc;
-}
-
-extern "C" int crct_engine_forward(crct_engine_t* e, const float* params_f32, const void* params_bf16, const CrctBatch* batch,
-                                   const CrctStepCfg* cfg, void* workspace, float* logits, float* reg, float* stats,
-                                   crct_stream_t stream) {
-  return engine_forward_impl(e, params_f32, params_bf16, batch, cfg, workspace, logits, reg, stats, stream);
-}
-
-extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, const void* params_bf16, const CrctBatch* batch,
-                                    const CrctStepCfg* cfg, void* workspace, float* grads_f32, float* logits, float* reg,
-                                    float* stats, int seg, crct_stream_t stream) {
-  return engine_backward_impl(e, params_f32, params_bf16, batch, cfg, workspace, grads_f32, logits, reg, stats, seg, stream);
 }
 
 extern "C" int crct_engine_wgrad_owned(crct_engine_t* e, int64_t* offsets, int64_t* numels, int cap) {
