@@ -229,55 +229,80 @@ def cast_bf16(x, out=None):
     return out
 
 
-def attention_fwd(q, k, v, keymask, heads, d, p_drop=0.0, site=0, seed=0, row_lse=None):
+def _attn_out(t, B, T, Hh, like, what):
+    """A caller-supplied attention output: a bf16 [B, T, heads * d] view whose rows (stride(1), the leading dimension the kernel gets)
+    may lie in a wider buffer -- batches follow one another (stride(0) = T * stride(1)), columns are contiguous.  None: a fresh
+    contiguous tensor."""
+    if t is None:
+        return torch.empty(B, T, Hh, device=like.device, dtype=torch.bfloat16)
+    _chk(t, torch.bfloat16)
+    if tuple(t.shape) != (B, T, Hh) or t.stride(2) != 1 or t.stride(1) < Hh or (B > 1 and t.stride(0) != T * t.stride(1)):
+        raise RuntimeError("%s: expected a [%d, %d, %d] view with unit column stride and batch stride T * stride(1); got shape %s strides %s"
+                           % (what, B, T, Hh, tuple(t.shape), tuple(t.stride())))
+    return t
+
+
+def _attn_outs(outs, B, Tq, Tk, Hh, like, what):
+    dq, dk, dv = outs if outs is not None else (None, None, None)
+    return (_attn_out(dq, B, Tq, Hh, like, what + ": outs[0] (dq)"), _attn_out(dk, B, Tk, Hh, like, what + ": outs[1] (dk)"),
+            _attn_out(dv, B, Tk, Hh, like, what + ": outs[2] (dv)"))
+
+
+def _q_twin(t):
+    """Zeroed uint8 tensor with t's shape and element strides: the fp8 copy shares its bf16 twin's leading dimension (in bytes)."""
+    B, T, Hh = t.shape
+    return torch.zeros(B * T * t.stride(1), device=t.device, dtype=torch.uint8).as_strided((B, T, Hh), (T * t.stride(1), t.stride(1), 1))
+
+
+def attention_fwd(q, k, v, keymask, heads, d, p_drop=0.0, site=0, seed=0, row_lse=None, out=None):
     """q [B,Tq,ldq] / k,v [B,Tk,ld*] bf16 (may be column slices of a wider buffer: pass the *slice*).
     row_lse: fp32 [B, heads, Tq] that the long-sequence kernels fill with the softmax row statistics (CrctAttnQuant.row_lse; the
-    other kernels leave it untouched) -- hand it, with the returned ctx, to ``attention_bwd``."""
+    other kernels leave it untouched) -- hand it, with the returned ctx, to ``attention_bwd``.
+    out: ctx goes there, a [B, Tq, heads * d] view that may be a column slice of a wider buffer (its stride(1) is the kernel's ldo)."""
     lib = L.load()
     B, Tq = q.shape[0], q.shape[1]
     Tk = k.shape[1]
-    ctx = torch.empty(B, Tq, heads * d, device=q.device, dtype=torch.bfloat16)
+    ctx = _attn_out(out, B, Tq, heads * d, q, "attention_fwd: out")
     thr, sc, st = _drop(p_drop, site)
     if row_lse is not None:
         assert tuple(row_lse.shape) == (B, heads, Tq)
         qz = L.AttnQuant()
         qz.row_lse = L.ptr(_chk(row_lse, torch.float32))
         L.check(lib.crct_attention_fwd_q(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(_chk(keymask, torch.uint8)), L.ptr(ctx), B, heads, Tq, Tk, d,
-                                         q.stride(1), k.stride(1), v.stride(1), heads * d, thr, sc, st, seed, C.byref(qz), L.current_stream()),
+                                         q.stride(1), k.stride(1), v.stride(1), ctx.stride(1), thr, sc, st, seed, C.byref(qz), L.current_stream()),
                 "attention_fwd")
         return ctx
     L.check(lib.crct_attention_fwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(_chk(keymask, torch.uint8)), L.ptr(ctx), B, heads, Tq, Tk, d,
-                                   q.stride(1), k.stride(1), v.stride(1), heads * d, thr, sc, st, seed, L.current_stream()),
+                                   q.stride(1), k.stride(1), v.stride(1), ctx.stride(1), thr, sc, st, seed, L.current_stream()),
             "attention_fwd")
     return ctx
 
 
-def attention_fwd_q(q, k, v, keymask, heads, d, q_scale, q_amax, p_drop=0.0, site=0, seed=0):
-    """attention_fwd that also returns the e4m3 copy of ctx (uint8, same shape), quantised with the device scalar q_scale."""
+def attention_fwd_q(q, k, v, keymask, heads, d, q_scale, q_amax, p_drop=0.0, site=0, seed=0, out=None):
+    """attention_fwd that also returns the e4m3 copy of ctx (uint8, same shape and strides), quantised with the device scalar q_scale."""
     lib = L.load()
     B, Tq = q.shape[0], q.shape[1]
     Tk = k.shape[1]
-    ctx = torch.empty(B, Tq, heads * d, device=q.device, dtype=torch.bfloat16)
-    ctx_q = torch.zeros(B, Tq, heads * d, device=q.device, dtype=torch.uint8)
+    ctx = _attn_out(out, B, Tq, heads * d, q, "attention_fwd_q: out")
+    ctx_q = _q_twin(ctx)
     qz = L.AttnQuant()
     qz.ctx_q, qz.ctx_scale, qz.ctx_amax = L.ptr(ctx_q), L.ptr(q_scale), L.ptr(q_amax)
     thr, sc, st = _drop(p_drop, site)
     L.check(lib.crct_attention_fwd_q(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(_chk(keymask, torch.uint8)), L.ptr(ctx), B, heads, Tq, Tk, d,
-                                     q.stride(1), k.stride(1), v.stride(1), heads * d, thr, sc, st, seed, C.byref(qz), L.current_stream()),
+                                     q.stride(1), k.stride(1), v.stride(1), ctx.stride(1), thr, sc, st, seed, C.byref(qz), L.current_stream()),
             "attention_fwd_q")
     return ctx, ctx_q
 
 
 def attention_bwd_q(q, k, v, keymask, dctx, heads, d, dq_scale, dq_amax, dkv_scale, dkv_amax, p_drop=0.0, site=0, seed=0, row_lse=None,
-                    ctx=None):
-    """attention_bwd that also returns the e5m2 copies of dq, dk, dv (uint8); row_lse / ctx as in ``attention_bwd``."""
+                    ctx=None, outs=None):
+    """attention_bwd that also returns the e5m2 copies of dq, dk, dv (uint8, each with the strides of its bf16 twin); row_lse / ctx / outs
+    as in ``attention_bwd``."""
     lib = L.load()
     B, Tq = q.shape[0], q.shape[1]
     Tk = k.shape[1]
-    dq = torch.empty(B, Tq, heads * d, device=q.device, dtype=torch.bfloat16)
-    dk = torch.empty(B, Tk, heads * d, device=q.device, dtype=torch.bfloat16)
-    dv = torch.empty_like(dk)
-    dq8, dk8, dv8 = (torch.zeros(t.shape, device=q.device, dtype=torch.uint8) for t in (dq, dk, dv))
+    dq, dk, dv = _attn_outs(outs, B, Tq, Tk, heads * d, q, "attention_bwd_q")
+    dq8, dk8, dv8 = (_q_twin(t) for t in (dq, dk, dv))
     qz = L.AttnQuant()
     qz.dq_q, qz.dk_q, qz.dv_q = L.ptr(dq8), L.ptr(dk8), L.ptr(dv8)
     qz.dq_scale, qz.dq_amax, qz.dkv_scale, qz.dkv_amax = L.ptr(dq_scale), L.ptr(dq_amax), L.ptr(dkv_scale), L.ptr(dkv_amax)
@@ -286,30 +311,30 @@ def attention_bwd_q(q, k, v, keymask, dctx, heads, d, dq_scale, dq_amax, dkv_sca
     thr, sc, st = _drop(p_drop, site)
     L.check(lib.crct_attention_bwd_q(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(keymask), L.ptr(_chk(dctx, torch.bfloat16)), L.ptr(dq), L.ptr(dk), L.ptr(dv),
                                      B, heads, Tq, Tk, d, q.stride(1), k.stride(1), v.stride(1), dctx.stride(1),
-                                     heads * d, heads * d, heads * d, thr, sc, st, seed, C.byref(qz), L.current_stream()), "attention_bwd_q")
+                                     dq.stride(1), dk.stride(1), dv.stride(1), thr, sc, st, seed, C.byref(qz), L.current_stream()), "attention_bwd_q")
     return (dq, dk, dv), (dq8, dk8, dv8)
 
 
-def attention_bwd(q, k, v, keymask, dctx, heads, d, p_drop=0.0, site=0, seed=0, row_lse=None, ctx=None):
+def attention_bwd(q, k, v, keymask, dctx, heads, d, p_drop=0.0, site=0, seed=0, row_lse=None, ctx=None, outs=None):
     """row_lse / ctx: what ``attention_fwd(..., row_lse=)`` of the same operands produced -- the long-sequence kernels then skip
-    their statistics sweep (the other kernels ignore both)."""
+    their statistics sweep (the other kernels ignore both).
+    outs: (dq, dk, dv) to write into, [B, Tq | Tk, heads * d] views that may be column slices of wider buffers, as the step engine's
+    fused dqkv buffers are (their stride(1) are the kernel's lddq / lddk / lddv)."""
     lib = L.load()
     B, Tq = q.shape[0], q.shape[1]
     Tk = k.shape[1]
-    dq = torch.empty(B, Tq, heads * d, device=q.device, dtype=torch.bfloat16)
-    dk = torch.empty(B, Tk, heads * d, device=q.device, dtype=torch.bfloat16)
-    dv = torch.empty_like(dk)
+    dq, dk, dv = _attn_outs(outs, B, Tq, Tk, heads * d, q, "attention_bwd")
     thr, sc, st = _drop(p_drop, site)
     if row_lse is not None or ctx is not None:
         qz = L.AttnQuant()
         qz.row_lse, qz.ctx, qz.ld_ctx = L.ptr(_chk(row_lse, torch.float32)), L.ptr(_chk(ctx, torch.bfloat16)), (ctx.stride(1) if ctx is not None else 0)
         L.check(lib.crct_attention_bwd_q(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(keymask), L.ptr(_chk(dctx, torch.bfloat16)), L.ptr(dq), L.ptr(dk),
                                          L.ptr(dv), B, heads, Tq, Tk, d, q.stride(1), k.stride(1), v.stride(1), dctx.stride(1),
-                                         heads * d, heads * d, heads * d, thr, sc, st, seed, C.byref(qz), L.current_stream()), "attention_bwd")
+                                         dq.stride(1), dk.stride(1), dv.stride(1), thr, sc, st, seed, C.byref(qz), L.current_stream()), "attention_bwd")
         return dq, dk, dv
     L.check(lib.crct_attention_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(keymask), L.ptr(_chk(dctx, torch.bfloat16)), L.ptr(dq), L.ptr(dk), L.ptr(dv),
                                    B, heads, Tq, Tk, d, q.stride(1), k.stride(1), v.stride(1), dctx.stride(1),
-                                   heads * d, heads * d, heads * d, thr, sc, st, seed, L.current_stream()), "attention_bwd")
+                                   dq.stride(1), dk.stride(1), dv.stride(1), thr, sc, st, seed, L.current_stream()), "attention_bwd")
     return dq, dk, dv
 
 

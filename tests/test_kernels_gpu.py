@@ -6,7 +6,9 @@ fp32 reference evaluated on the SAME bf16-rounded operands the only differences 
 order and the final bf16 rounding of the output: |err| <= 1e-2 * max|ref| for bf16 outputs,
 <= 2e-3 * max|ref| for fp32 outputs.  That bound is normalised by the whole output and cannot see a local error: the sections
 "against fp64" below check per element -- the GEMMs bit for bit on exact operands (tests/gemm_ref.py), the row kernels within one
-rounding of fp64.
+rounding of fp64.  The attention kernels have their per-element check in a file of their own, tests/test_attention_gpu.py: every
+instantiation of the three implementations against fp64 under the budget that tests/attention_ref.py derives from the kernels'
+roundings, with strided outputs in sentinel-filled buffers; the attention tests in this file keep the whole-output bound.
 """
 import ctypes as C
 import math
