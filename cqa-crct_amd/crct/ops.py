@@ -382,3 +382,114 @@ def scale_runs(grads, coef, seg_off, seg_len, blk_seg, blk_off, max_workgroups=0
                                      seg_len.data_ptr(), blk_seg.data_ptr(), blk_off.data_ptr(), blk_seg.numel(), int(max_workgroups),
                                      L.current_stream()), "scale_runs")
     return grads
+
+
+def _amp_state(amp):
+    """dict(grad_scale=, found_inf=, step=) of device tensors (each optional) -> (CrctAmpState, byref) or (None, None)"""
+    if amp is None:
+        return None, None
+    st = L.AmpState()
+    st.grad_scale = L.ptr(_chk(amp.get("grad_scale"), torch.float32))
+    st.found_inf = L.ptr(_chk(amp.get("found_inf"), torch.float32))
+    st.step = L.ptr(_chk(amp.get("step"), torch.int32))
+    return st, C.byref(st)
+
+
+def _fp8_shadow(fp8):
+    """dict(q=, seg_slot=, scale=, amax=[, qt=, seg_in=, seg_t_base=, seg_t_ld=]) of device tensors -> (CrctFp8Shadow, byref)"""
+    if fp8 is None:
+        return None, None
+    sh = L.Fp8Shadow()
+    sh.q, sh.qt = L.ptr(_chk(fp8.get("q"))), L.ptr(_chk(fp8.get("qt")))
+    sh.seg_slot, sh.seg_in, sh.seg_t_ld = (L.ptr(_chk(fp8.get(k), torch.int32)) for k in ("seg_slot", "seg_in", "seg_t_ld"))
+    sh.scale, sh.amax = L.ptr(_chk(fp8.get("scale"), torch.float32)), L.ptr(_chk(fp8.get("amax"), torch.float32))
+    sh.seg_t_base = L.ptr(_chk(fp8.get("seg_t_base"), torch.int64))
+    return sh, C.byref(sh)
+
+
+def adamw_step(p, g, m, v, seg_off, seg_len, seg_lr, seg_wd, blk_seg, blk_off, step=1, betas=(0.9, 0.999), eps=1e-8, p_bf16=None,
+               inv_scale=None, amp=None, fp8=None, max_workgroups=0, zero_grads=False, g_bf16=None):
+    """crct_adamw_step in place on the flat fp32 buffers p, g, m, v over the device tables (seg_*, blk_* from ``adamw_plan``).
+    inv_scale: device fp32 scalar; amp / fp8: dicts of device tensors named after the fields of CrctAmpState / CrctFp8Shadow."""
+    amp_keep, amp_arg = _amp_state(amp)
+    f8_keep, f8_arg = _fp8_shadow(fp8)
+    L.check(L.load().crct_adamw_step(L.ptr(_chk(p, torch.float32)), L.ptr(_chk(g, torch.float32)), L.ptr(_chk(m, torch.float32)),
+                                     L.ptr(_chk(v, torch.float32)), L.ptr(_chk(p_bf16, torch.bfloat16)), L.ptr(_chk(seg_off, torch.int64)),
+                                     L.ptr(_chk(seg_len, torch.int64)), L.ptr(_chk(seg_lr, torch.float32)), L.ptr(_chk(seg_wd, torch.float32)),
+                                     L.ptr(_chk(blk_seg, torch.int32)), L.ptr(_chk(blk_off, torch.int64)), blk_seg.numel(),
+                                     float(betas[0]), float(betas[1]), float(eps), int(step), L.ptr(_chk(inv_scale, torch.float32)),
+                                     amp_arg, f8_arg, int(max_workgroups), int(bool(zero_grads)), L.ptr(_chk(g_bf16, torch.bfloat16)),
+                                     L.current_stream()), "adamw_step")
+
+
+def adamw_advance(step_dev, found_inf=None):
+    """crct_adamw_advance: the device step counter (int32 [1]) += 1 unless found_inf (device fp32 [1], optional) is set."""
+    L.check(L.load().crct_adamw_advance(L.ptr(_chk(step_dev, torch.int32)), L.ptr(_chk(found_inf, torch.float32)), L.current_stream()),
+            "adamw_advance")
+
+
+def fp8_update_scales(scale, amax, n=None, reset=False, skip_if=None, fmax=448.0):
+    """crct_fp8_update_scales over the first n entries (default: all of ``scale``); amax holds FP8_AMAX_LANES words per entry."""
+    n = scale.numel() if n is None else int(n)
+    L.check(L.load().crct_fp8_update_scales(L.ptr(_chk(scale, torch.float32)), L.ptr(_chk(amax, torch.float32)), n, int(bool(reset)),
+                                            L.ptr(_chk(skip_if, torch.float32)), float(fmax), L.current_stream()), "fp8_update_scales")
+
+
+def fp8_quantize_bf16(x, q, scale, amax=None):
+    """crct_fp8_quantize_bf16: q (uint8, x.numel() bytes) = e4m3(x * *scale); max |x| max-ed into amax when given."""
+    L.check(L.load().crct_fp8_quantize_bf16(L.ptr(_chk(x, torch.bfloat16)), L.ptr(_chk(q, torch.uint8)), L.ptr(_chk(scale, torch.float32)),
+                                            L.ptr(_chk(amax, torch.float32)), x.numel(), L.current_stream()), "fp8_quantize_bf16")
+    return q
+
+
+def fp8_quantize_weights(p, q, seg_off, seg_len, seg_slot, blk_seg, blk_off, scale, amax):
+    """crct_fp8_quantize_weights: the exact per-tensor quantisation of the segments with seg_slot >= 0 into the flat byte buffer q."""
+    L.check(L.load().crct_fp8_quantize_weights(L.ptr(_chk(p, torch.float32)), L.ptr(_chk(q, torch.uint8)), L.ptr(_chk(seg_off, torch.int64)),
+                                               L.ptr(_chk(seg_len, torch.int64)), L.ptr(_chk(seg_slot, torch.int32)),
+                                               L.ptr(_chk(blk_seg, torch.int32)), L.ptr(_chk(blk_off, torch.int64)), blk_seg.numel(),
+                                               L.ptr(_chk(scale, torch.float32)), L.ptr(_chk(amax, torch.float32)), scale.numel(),
+                                               L.current_stream()), "fp8_quantize_weights")
+    return q
+
+
+def fp8_transpose_weights(q, qt, w_off, w_out, w_in, max_workgroups=0):
+    """crct_fp8_transpose_weights of the weights (byte offset, out, in) given as host sequences; builds the tile table."""
+    tiles = [((o + 63) // 64) * ((i + 63) // 64) for o, i in zip(w_out, w_in)]
+    begin = [sum(tiles[:k]) for k in range(len(tiles))]
+    dev = q.device
+    t = (torch.tensor(list(w_off), dtype=torch.int64, device=dev), torch.tensor(list(w_out), dtype=torch.int32, device=dev),
+         torch.tensor(list(w_in), dtype=torch.int32, device=dev), torch.tensor(begin, dtype=torch.int64, device=dev))
+    L.check(L.load().crct_fp8_transpose_weights(L.ptr(_chk(q, torch.uint8)), L.ptr(_chk(qt, torch.uint8)), t[0].data_ptr(), t[1].data_ptr(),
+                                                t[2].data_ptr(), t[3].data_ptr(), len(tiles), sum(tiles), int(max_workgroups),
+                                                L.current_stream()), "fp8_transpose_weights")
+    torch.cuda.current_stream().synchronize()        # the tables above must outlive the launch
+    return qt
+
+
+def cast_f32(x, out=None):
+    """crct_cast_bf16_f32: bf16 -> fp32"""
+    out = torch.empty(x.shape, device=x.device, dtype=torch.float32) if out is None else out
+    L.check(L.load().crct_cast_bf16_f32(L.ptr(_chk(x, torch.bfloat16)), L.ptr(_chk(out, torch.float32)), x.numel(), L.current_stream()), "cast")
+    return out
+
+
+def cast_runs(x, y, run_off, run_len, blk_seg, blk_off):
+    """y[off[r] + i] = cast(x[off[r] + i]) over the runs of an ``adamw_plan`` table: fp32 -> bf16 or bf16 -> fp32 by the dtypes."""
+    lib = L.load()
+    if x.dtype == torch.float32 and y.dtype == torch.bfloat16:
+        fn = lib.crct_cast_runs_f32_bf16
+    elif x.dtype == torch.bfloat16 and y.dtype == torch.float32:
+        fn = lib.crct_cast_runs_bf16_f32
+    else:
+        raise TypeError("cast_runs: fp32 -> bf16 or bf16 -> fp32 (got %s -> %s)" % (x.dtype, y.dtype))
+    L.check(fn(L.ptr(_chk(x)), L.ptr(_chk(y)), L.ptr(_chk(run_off, torch.int64)), L.ptr(_chk(run_len, torch.int64)),
+               L.ptr(_chk(blk_seg, torch.int32)), L.ptr(_chk(blk_off, torch.int64)), blk_seg.numel(), L.current_stream()), "cast_runs")
+    return y
+
+
+def zero_runs(g, run_off, run_len, blk_seg, blk_off):
+    """crct_zero_runs: g[off[r] .. off[r] + len[r]) = 0 over the runs of an ``adamw_plan`` table."""
+    L.check(L.load().crct_zero_runs(L.ptr(_chk(g, torch.float32)), L.ptr(_chk(run_off, torch.int64)), L.ptr(_chk(run_len, torch.int64)),
+                                    L.ptr(_chk(blk_seg, torch.int32)), L.ptr(_chk(blk_off, torch.int64)), blk_seg.numel(),
+                                    L.current_stream()), "zero_runs")
+    return g

@@ -1460,9 +1460,13 @@ __global__ void fp8_update_scales_kernel(float* __restrict__ scale, float* __res
   const int i = blockIdx.x * (blockDim.x / CRCT_FP8_AMAX_LANES) + threadIdx.x / CRCT_FP8_AMAX_LANES, l = threadIdx.x % CRCT_FP8_AMAX_LANES;
   if (i < n) {          // one wave (64 lanes = LANES) per entry
     float* w = amax + (long)i * CRCT_FP8_AMAX_LANES + l;
-    const float a = wave_max(*w);
-    if (reset) *w = 0.f;
-    if (l == 0 && a > 0.f) scale[i] = fmax / a;
+    const float x = *w;
+    // an inf / NaN word (an overflowed gradient under GradScaler) says nothing about the tensor's range: fmax / inf would set the scale
+    // to 0 and the running maximum would pin it there until the window resets.  The scale stays, the words are cleared at once.
+    const bool bad = __ballot(!(fabsf(x) <= 3.4028234663852886e38f)) != 0;
+    const float a = wave_max(x);
+    if (reset || bad) *w = 0.f;
+    if (l == 0 && a > 0.f && !bad) scale[i] = fmax / a;
   }
 }
 

@@ -213,7 +213,8 @@ int crct_layernorm_fwd_args(const CrctLnFwdArgs* a, crct_stream_t stream);
  *                           may be NULL) != 0 leaves everything untouched (GradScaler's found_inf: a skipped optimizer step
  *                           does not requantise the weight shadow, so its scales must stay too).  The amax values are
  *                           RUNNING maxima: call it once per step with reset = 0 and every few hundred steps with reset = 1
- *                           (a history window); clearing every step makes every wave of every producer issue an atomic
+ *                           (a history window); clearing every step makes every wave of every producer issue an atomic.
+ *                           An entry whose maximum is inf or NaN keeps its scale and has its words cleared whatever reset says
  *  crct_fp8_quantize_weights  exact per-tensor scaling of fp32 weights into the flat e4m3 shadow (same element offsets as
  *                           the fp32 buffer): tensors (seg_off, seg_len) with scale slot seg_slot[s] >= 0, chunk table
  *                           (blk_seg, blk_off) from crct_adamw_plan; writes scale[slot] = 448 / max |w|.  Used at start-up
