@@ -86,6 +86,9 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, fl
   const float target = Rb[0] / Rb[3];
   const float raw = r;
   if (MODE == HEAD_SNAP && needs) {       // nearest table value of r * scale (first on a tie), divided back
+    // x is the ROUNDED product for every entry: contracted into the subtraction (fma(-r, scale, v[0])), entry 0 alone was measured
+    // from the unrounded product and lost or won exact ties against the others by that rounding
+#pragma clang fp contract(off)
     const float x = r * Rb[3];
     float best = hv.v[0], bd = fabsf(hv.v[0] - x);
     for (int k = 1; k < hv.n; ++k) {
@@ -349,7 +352,8 @@ __global__ __launch_bounds__(256) void head_ce_wgrad_kernel(const CrctHeadArgs a
 // One wave per question.  Question q owns the candidate rows [off_q, off_q + num_ans[q]) with off_q = sum of the
 // earlier counts (recomputed by every wave: Q is a few hundred at most).  p0 = softmax(logits)[0] in fp32; the
 // answer is the FIRST row with the largest p0 (torch.argmax), or forced[q] when given; the regressed value and its
-// two error measures are gathered from the chosen row.
+// two error measures are gathered from the chosen row.  A NaN p0 is the maximum, as it is for torch.argmax: the first
+// NaN row of a question wins over every number and over every later NaN.
 __global__ __launch_bounds__(64) void eval_select_kernel(const float* __restrict__ logits, const float* __restrict__ reg_out,
                                                          const float* __restrict__ reg_err, const float* __restrict__ reg_terr,
                                                          const int64_t* __restrict__ num_ans, const int64_t* __restrict__ forced,
@@ -373,13 +377,16 @@ __global__ __launch_bounds__(64) void eval_select_kernel(const float* __restrict
       p = e0 / (e0 + e1);
       if (prob0) prob0[r] = p;
     }
-    if (p > best) { best = p; best_i = j; }       // strictly greater: the earliest row of this lane wins ties
+    // strictly greater: the earliest row of this lane wins ties; a NaN replaces any number and is never replaced
+    if (p > best || (p != p && best == best)) { best = p; best_i = j; }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ob = __shfl_xor(best, o, 64);
     const long oi = __shfl_xor(best_i, o, 64);
-    if (ob > best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
+    const bool on = ob != ob, bn = best != best;
+    const bool take = on ? (!bn || oi < best_i) : (!bn && (ob > best || (ob == best && oi < best_i)));
+    if (take) { best = ob; best_i = oi; }
   }
   if (lane == 0) {
     long a = forced ? forced[q] : (n > 0 ? best_i : 0);

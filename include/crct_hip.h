@@ -485,7 +485,9 @@ int crct_head_loss_variant(const CrctHeadVariantArgs* args, crct_stream_t stream
  * prob0 = softmax(logits [N][2])[:, 0] (:249), answers[q] = argmax of prob0 over its rows (first maximum), or
  * forced_answers[q] when given ('_REGS' question files, :283-284); sel_out / sel_err / sel_terr [Q] gather the regressed
  * value, its relative error and its tick error (regression[0] / [4] / [2], :255-257) from the chosen row.
- * prob0 [N] is optional.  Integer results are exact; an out-of-range forced answer selects +inf errors. */
+ * prob0 [N] is optional.  Integer results are exact; an out-of-range forced answer selects +inf errors.
+ * A NaN prob0 counts as the maximum, as torch.argmax and np.argmax count it: a question with NaN rows answers its first NaN
+ * row.  A row at or beyond N never wins over one below N; a question with no row below N answers 0 with sel_out 0, +inf errors. */
 int crct_eval_select(const float* logits, const float* reg_out, const float* reg_err, const float* reg_terr,
                      const int64_t* num_ans, const int64_t* forced_answers, int Q, int64_t N, float* prob0,
                      int64_t* answers, float* sel_out, float* sel_err, float* sel_terr, crct_stream_t stream);

@@ -1745,13 +1745,11 @@ def test_a_build_with_a_perturbed_gelu_derivative_is_told_apart(gemm_path):
 # ------------------------------------------------------------------------------------------- classification head + joint loss
 # crct_head_loss (heads.hip: head_rows_kernel + head_reduce_kernel) against an fp64 restatement of oracle.heads_and_losses from the
 # poolers' post-ReLU outputs and the fusion.4 post-LeakyReLU rows on, with the host's cls dropout mask.
-HEAD_SITE = 3                                     # the engine's cls dropout site
-HEAD_NSP_COEFF, HEAD_REG_COEFF = 1.0, 0.7        # CrctHeadArgs.nsp_coeff / reg_coeff of every launch below
+import heads_ref as HR       # noqa: E402
 
-
-def _head_cfg(p=0.0, seed=0, fusion_sum=0, use_l1=False, kind_l1=False, tol=0.01):
-    """The scalar settings one crct_head_loss launch and its fp64 restatement share (_head_launch, _head_ref64)."""
-    return dict(p=p, seed=seed, fusion_sum=bool(fusion_sum), use_l1=bool(use_l1), kind_l1=bool(kind_l1), tol=tol)
+HEAD_SITE = HR.HEAD_SITE                          # the engine's cls dropout site
+HEAD_NSP_COEFF, HEAD_REG_COEFF = HR.HEAD_NSP_COEFF, HR.HEAD_REG_COEFF        # CrctHeadArgs.nsp_coeff / reg_coeff of every launch below
+_head_cfg = HR.head_cfg
 _HEAD_NORMAL, _HEAD_NONE, _HEAD_BIG, _HEAD_ONE, _HEAD_HALF, _HEAD_ZERO, _HEAD_D5, _HEAD_CLOSE, _HEAD_BOTH0, _HEAD_NONE_R = range(10)
 
 
@@ -1856,79 +1854,27 @@ def _head_targets(inp, r_k, tol):
     return R, own
 
 
-def _head_ref64(inp, R, labels, keep, hc, *, g_nsp, g_reg, r_k, own):
-    """oracle.heads_and_losses from the poolers' outputs on, fp64, cls dropout = the host mask: (outputs, gradients, magnitudes).
-    hc: _head_cfg; g_nsp / g_reg: the upstream gradients of the NSP mean and of each row's reg loss; r_k: the kernel's fp32 r, used for
-    the rows in `own` (placed on a comparison boundary)."""
-    p, fusion_sum, use_l1, kind_l1, tol = hc["p"], hc["fusion_sum"], hc["use_l1"], hc["kind_l1"], hc["tol"]
-    nsp_c, reg_c = HEAD_NSP_COEFF, HEAD_REG_COEFF
-    pt, pv = (inp[k].double().requires_grad_(True) for k in ("pt", "pv"))
-    fh = inp["fh"].double().requires_grad_(True)
-    W, bc, w6, b6 = (inp[k].double().requires_grad_(True) for k in ("w_cls", "b_cls", "w6", "b6"))
-    f = pt + pv if fusion_sum else pt * pv
-    fd = f * keep.double() / (1.0 - p)
-    logits = fd @ W.t() + bc
-    z = fh @ w6 + b6
-    r = torch.tanh(z)
-    r_use = torch.where(own, r_k.double() + (r - r.detach()), r)       # boundary rows: the kernel's own fp32 r, fp64 r's gradient
-    R64 = R.double()
-    needs = R64[:, 1] == 1
-    target = R64[:, 0] / torch.where(needs, R64[:, 3], torch.ones_like(R64[:, 3]))
-    diff = r_use - target
-    l1v = diff.abs()
-    rl = l1v if use_l1 else torch.where(l1v < 0.5, diff * diff, l1v - 0.25)     # SmoothL1, beta 0.5
-    if not kind_l1:
-        rl = torch.where(target.abs() > 1, torch.zeros_like(rl), rl)
-    rl = torch.where(needs, rl, torch.zeros_like(rl))
-    both0 = (r_use == 0) & (target == 0)
-    d5 = torch.where(target == 0, torch.ones_like(l1v), l1v.detach() / target.abs())
-    d5 = torch.where(both0, torch.zeros_like(d5), d5)
-    ok5 = ((d5 <= 0.05) | both0) & needs
-    # the boundary rows' d5 flag as the kernel decides it: fp32 division of the kernel's own fp32 values
-    with np.errstate(divide="ignore", invalid="ignore"):
-        d5_32 = np.abs(r_k.numpy() - R[:, 0].numpy()) / np.abs(R[:, 0].numpy())
-    ok5 = torch.where(own, torch.from_numpy(d5_32 <= np.float32(0.05)) & needs, ok5)
-    okt = (l1v <= tol) & needs
-    B = R.shape[0]
-    nvalid = int((labels != -1).sum()) if labels is not None else 0
-    if labels is not None:
-        lab = labels.clamp_min(0)
-        ce = torch.logsumexp(logits, 1) - logits.gather(1, lab[:, None]).squeeze(1)
-        nsp = torch.where(labels != -1, ce, torch.zeros_like(ce)).sum() / max(nvalid, 1)
-    else:
-        nsp = torch.zeros((), dtype=torch.float64)
-    (g_nsp * nsp + (g_reg * rl).sum()).backward()
-    needs_n = int(needs.sum())
-    d5v = torch.where(needs, d5, torch.zeros_like(d5)).detach()
-    reg_mean = float(rl.detach().sum()) / B
-    loss = nsp_c * float(nsp.detach()) + reg_c * reg_mean if labels is not None else 0.0
-    stats = torch.tensor([loss, float(nsp.detach()), reg_mean, needs_n, int(ok5.sum()), int(okt.sum()), nvalid, 0, loss, 0, float(nsp.detach()),
-                          float(rl.detach().sum()) / needs_n if needs_n else 0.0, float(d5v.sum()) / needs_n if needs_n else 0.0, 0,
-                          needs_n, int(ok5.sum()), int(okt.sum())], dtype=torch.float64)
-    zero = torch.zeros_like(r)
-    reg = torch.stack([torch.where(needs, r_use * R64[:, 3], zero), rl, torch.where(needs, l1v, zero), r, d5v]).detach()
-    zmag = (inp["fh"].double().abs() @ inp["w6"].double().abs() + inp["b6"].double().abs())
-    tmag = torch.where(target != 0, target.abs(), torch.ones_like(target))
-    reg_mag = torch.stack([zmag * R64[:, 3].abs(), zmag * (1 + 2 * l1v.detach()), zmag, zmag, zmag / tmag]).detach()
-    out = dict(logits=logits.detach(), reg=reg, stats=stats, r=r.detach(),
-               logit_mag=(fd.abs() @ W.abs().t() + bc.abs()).detach())
-    gr = lambda t: t.grad if t.grad is not None else torch.zeros_like(t)       # noqa: E731  (no labels: no path to the NSP inputs)
-    grads = dict(d_pt=gr(pt) * (pt.detach() > 0), d_pv=gr(pv) * (pv.detach() > 0),
-                 d_fh=gr(fh) * torch.where(fh.detach() > 0, 1.0, 0.01), d_w_cls=gr(W), d_b_cls=gr(bc), d_w6=gr(w6), d_b6=gr(b6))
-    return out, grads, reg_mag
+_head_ref64 = HR.head_ref64      # the fp64 restatement lives in tests/heads_ref.py, shared with tests/test_heads_gpu.py
 
 
-def _head_launch(inp, R, labels, hc, *, grads=True, g_loss=None, g_nsp=None, g_reg=None, grad_scale=1.0, prefill=0.0):
+def _head_launch(inp, R, labels, hc, *, grads=True, g_loss=None, g_nsp=None, g_reg=None, grad_scale=1.0, prefill=0.0, variant=None):
     """One crct_head_loss launch with the settings hc (_head_cfg); outputs start NaN, the parameter gradients pre-filled with
-    prefill * randn.  Returns every buffer on the host."""
+    prefill * randn.  Returns every buffer on the host.
+    variant: None, or a dict for crct_head_loss_variant: regressor (L.REGRESSOR_KINDS name), values (the table), snap, and the options
+    no_ce_scratch (CE without its scratch), null_reg (fus_h / w_f6 / b_f6 and their gradient pointers NULL), sentinel (a value that
+    fills those gradient buffers instead: d_w6 / d_b6 as prefill, d_fh whole).  inp['w6'] / inp['b6'] give fusion.6's shape."""
     B, Hb = inp["pt"].shape
+    v = variant or {}
+    null_reg = bool(v.get("null_reg"))
     d = lambda t: t.to(DEV).contiguous()         # noqa: E731
     t = dict(pt=d(inp["pt"]), pv=d(inp["pv"]), fh=d(inp["fh"]), w_cls=d(inp["w_cls"]), b_cls=d(inp["b_cls"]), w6=d(inp["w6"]),
              b6=d(inp["b6"]), R=d(R), logits=torch.full((B, 2), float("nan"), device=DEV), reg=torch.full((5, B), float("nan"), device=DEV),
              stats=torch.full((24,), float("nan"), device=DEV), scratch=torch.full((B, 8), float("nan"), device=DEV))
     a = L.HeadArgs()
-    a.pooled_t, a.pooled_v, a.fus_h = t["pt"].data_ptr(), t["pv"].data_ptr(), t["fh"].data_ptr()
-    a.w_cls, a.b_cls, a.w_f6, a.b_f6 = t["w_cls"].data_ptr(), t["b_cls"].data_ptr(), t["w6"].data_ptr(), t["b6"].data_ptr()
+    a.pooled_t, a.pooled_v = t["pt"].data_ptr(), t["pv"].data_ptr()
+    a.w_cls, a.b_cls = t["w_cls"].data_ptr(), t["b_cls"].data_ptr()
+    if not null_reg:
+        a.fus_h, a.w_f6, a.b_f6 = t["fh"].data_ptr(), t["w6"].data_ptr(), t["b6"].data_ptr()
     a.R = t["R"].data_ptr()
     if labels is not None:
         t["labels"] = d(labels)
@@ -1939,21 +1885,40 @@ def _head_launch(inp, R, labels, hc, *, grads=True, g_loss=None, g_nsp=None, g_r
         t.update(d_pt=torch.full((B, Hb), float("nan"), device=DEV, dtype=torch.bfloat16), d_pv=torch.full((B, Hb), float("nan"), device=DEV, dtype=torch.bfloat16),
                  d_fh=torch.full((B, 256), float("nan"), device=DEV, dtype=torch.bfloat16),
                  d_w_cls=d(torch.randn(2, Hb, generator=g) * prefill), d_b_cls=d(torch.randn(2, generator=g) * prefill),
-                 d_w6=d(torch.randn(256, generator=g) * prefill), d_b6=d(torch.randn(1, generator=g) * prefill))
+                 d_w6=d(torch.randn(*inp["w6"].shape, generator=g) * prefill), d_b6=d(torch.randn(*inp["b6"].shape, generator=g) * prefill))
+        if "sentinel" in v:
+            for k in ("d_fh", "d_w6", "d_b6"):
+                t[k].fill_(v["sentinel"])
         t["prefill"] = {k: t[k].cpu() for k in ("d_w_cls", "d_b_cls", "d_w6", "d_b6")}
-        a.d_pooled_t, a.d_pooled_v, a.d_fus_h = t["d_pt"].data_ptr(), t["d_pv"].data_ptr(), t["d_fh"].data_ptr()
-        a.d_w_cls, a.d_b_cls, a.d_w_f6, a.d_b_f6 = t["d_w_cls"].data_ptr(), t["d_b_cls"].data_ptr(), t["d_w6"].data_ptr(), t["d_b6"].data_ptr()
-    for k, v in (("g_loss_dev", g_loss), ("g_nsp_dev", g_nsp), ("g_reg_dev", g_reg)):
-        if v is not None:
-            t[k] = d(v.float().reshape(-1))
+        a.d_pooled_t, a.d_pooled_v = t["d_pt"].data_ptr(), t["d_pv"].data_ptr()
+        a.d_w_cls, a.d_b_cls = t["d_w_cls"].data_ptr(), t["d_b_cls"].data_ptr()
+        if not null_reg:
+            a.d_fus_h, a.d_w_f6, a.d_b_f6 = t["d_fh"].data_ptr(), t["d_w6"].data_ptr(), t["d_b6"].data_ptr()
+    for k, x in (("g_loss_dev", g_loss), ("g_nsp_dev", g_nsp), ("g_reg_dev", g_reg)):
+        if x is not None:
+            t[k] = d(x.float().reshape(-1))
             setattr(a, k, t[k].data_ptr())
     a.B, a.Hb, a.fusion_sum, a.use_l1, a.kind_l1 = B, Hb, int(hc["fusion_sum"]), int(hc["use_l1"]), int(hc["kind_l1"])
     a.tol_margin, a.nsp_coeff, a.reg_coeff, a.grad_scale = hc["tol"], HEAD_NSP_COEFF, HEAD_REG_COEFF, grad_scale
     a.drop_thr, a.drop_scale, a.drop_site = ops._drop(hc["p"], HEAD_SITE)
     a.seed = hc["seed"]
-    L.check(L.load().crct_head_loss(C.byref(a), L.current_stream()), "head_loss")
+    if variant is None:
+        L.check(L.load().crct_head_loss(C.byref(a), L.current_stream()), "head_loss")
+    else:
+        va = L.HeadVariantArgs()
+        va.h = a
+        va.variant.dataset, va.variant.regressor = L.DATASET_KINDS["dvqa"], L.REGRESSOR_KINDS[v["regressor"]]
+        values = v.get("values", ())
+        va.variant.n_values = v.get("n_values", len(values))
+        for i, x in enumerate(values):
+            va.variant.values[i] = x
+        va.snap = int(v.get("snap", 0))
+        if v["regressor"] == "ce" and not v.get("no_ce_scratch"):
+            t["ce"] = torch.full((B, L.CE_CLASSES), float("nan"), device=DEV)
+            va.ce_scratch = t["ce"].data_ptr()
+        L.check(L.load().crct_head_loss_variant(C.byref(va), L.current_stream()), "head_loss_variant")
     torch.cuda.synchronize()
-    return {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in t.items()}
+    return {k: (x.cpu() if torch.is_tensor(x) else x) for k, x in t.items()}
 
 
 def _assert_bf16_grad(got, ref, scale, what):
