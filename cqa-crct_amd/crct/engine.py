@@ -218,6 +218,30 @@ class StepEngine(object):
                                              self.stats.data_ptr(), L.current_stream()), "engine_forward")
         return self.outputs_of(self.out, B)
 
+    def attention_probs(self, kind, index, direction=0):
+        """Attention map of the LAST forward of this engine (crct_engine_attention_probs), a fresh fp32 tensor: kind 0 / "text" layer
+        ``index`` -> [B, heads, T, T]; 1 / "visual" -> [B, v_heads, V, V]; 2 / "conn" connection layer ``index``, direction 0 =
+        attention_probs1 [B, bi_heads, T, V] (text queries over visual keys), 1 = attention_probs2 [B, bi_heads, V, T].  Computed
+        from the layer's bf16 q / k that the forward left in the workspace, with that forward's key masks and dropout stream."""
+        if self._keep is None:
+            raise RuntimeError("attention_probs: run a forward pass on this engine first")
+        tensors, step = self._keep
+        kind = {"text": 0, "visual": 1, "conn": 2}.get(kind, kind)
+        B, T = tensors["tokens"].shape
+        V = tensors["image_feat"].shape[1]
+        cfg = self.cfg
+        shape = {0: (B, cfg.num_attention_heads, T, T), 1: (B, cfg.v_num_attention_heads, V, V),
+                 2: (B, cfg.bi_num_attention_heads, V, T) if direction else (B, cfg.bi_num_attention_heads, T, V)}.get(kind)
+        if shape is None:
+            raise ValueError("attention_probs: kind must be 0 / 'text', 1 / 'visual' or 2 / 'conn'; got %r" % (kind,))
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        b, c = self._batch(tensors), self._cfg(dict(step, seg_events=None))
+        n = self.lib.crct_engine_attention_probs(self.handle, C.byref(b), C.byref(c), self.workspace.data_ptr(), int(kind), int(index),
+                                                 int(direction), out.data_ptr(), out.numel(), L.current_stream())
+        if n != out.numel():
+            raise RuntimeError("attention_probs(%r, %d, %d): %s" % (kind, index, direction, self.lib.crct_last_error().decode()))
+        return out
+
     def outputs_of(self, out, B):
         """(logits [B,2], reg [5,B], stats [24]) views of an output buffer (``self.out`` or a snapshot of it)."""
         o = self.NS + 5 * self.max[0]

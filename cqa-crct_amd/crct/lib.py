@@ -168,6 +168,7 @@ PROTOTYPES = {
     "crct_cast_runs_f32_bf16": (C.c_int, [vp, vp, vp, vp, vp, vp, c_i64, vp]),
     "crct_cast_runs_bf16_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, c_i64, vp]),
     "crct_attention_fwd": (C.c_int, [vp] * 5 + [C.c_int] * 5 + [c_i64] * 4 + _u8 + [vp]),
+    "crct_attention_probs": (C.c_int, [vp] * 4 + [C.c_int] * 5 + [c_i64] * 2 + _u8 + [vp]),
     "crct_attention_bwd": (C.c_int, [vp] * 8 + [C.c_int] * 5 + [c_i64] * 7 + _u8 + [vp]),
     "crct_attention_fwd_q": (C.c_int, [vp] * 5 + [C.c_int] * 5 + [c_i64] * 4 + _u8 + [vp, vp]),
     "crct_attention_bwd_q": (C.c_int, [vp] * 8 + [C.c_int] * 5 + [c_i64] * 7 + _u8 + [vp, vp]),
@@ -212,6 +213,7 @@ PROTOTYPES = {
     "crct_engine_fp8_grad_sites": (C.c_int, [vp]),
     "crct_engine_fp8_weights": (C.c_int, [vp, vp, vp, C.c_int]),
     "crct_zero_runs": (C.c_int, [vp, vp, vp, vp, vp, c_i64, vp]),
+    "crct_engine_attention_probs": (c_i64, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, c_i64, vp]),
     "crct_engine_tap": (c_i64, [vp, vp, C.c_char_p, C.c_int, C.c_int, C.c_int, vp, c_i64, vp]),
 }
 

@@ -626,12 +626,15 @@ class CrctModel(nn.Module):
                 self._fp8["scaled"] = True
             if not self.fp8_forward:
                 step["fp8_mode"] = 2                   # bf16 forward GEMMs; the e4m3 copies / maxima for the fp8 backward are still written
+        attention_maps = None
         if train_branch and torch.is_grad_enabled():
             loss, nsp, reg_loss, logits, reg, stats = _StepFn.apply(self._anchor, self, tensors, step)
         else:
             eng.forward(self._flat_p, self._flat_b16, tensors, step)
             logits, reg, stats = eng.snapshot(B)
             loss, nsp, reg_loss = stats[0], stats[1:2], reg[1]
+            if output_all_attention_masks and not train_branch:
+                attention_maps = self._attention_maps(eng)
         # the combined training loss as the head kernel computed it (differentiable); the step adapter returns it instead
         # of re-deriving it from nsp_loss / reg_loss with five more torch kernels and their autograd nodes
         self.last_loss = loss if train_branch else None
@@ -649,7 +652,22 @@ class CrctModel(nn.Module):
         lm_zero, img_zero, legend_loss = self._const_zeros
         if train_branch:
             return lm_zero, img_zero, nsp, None, None, logits, reg_out, legend_loss        # vilbert.py:1659
-        return None, None, logits, None, None, reg_out, legend_loss                         # vilbert.py:1661
+        return None, None, logits, None, attention_maps, reg_out, legend_loss               # vilbert.py:1661
+
+    def _attention_maps(self, eng):
+        """``output_all_attention_masks=True`` (vilbert.py:842-946, :1562): (text maps, visual maps, co-attention maps) of the forward
+        that just ran -- one fp32 tensor per text layer [B, heads, T, T] and per visual layer [B, v_heads, V, V] in layer order, one
+        (attention_probs1 [B, bi_heads, T, V], attention_probs2 [B, bi_heads, V, T]) pair per connection layer (:725).  Every tensor
+        owns its memory.  No forward kernel stores probabilities: each map is computed here by one launch of its own
+        (csrc/attention_probs.hip) from the layer's fused q / k / v buffer, which the step engine writes as bf16 in EVERY mode -- the
+        fp8 modes quantise the inputs and weights of the projection GEMM, its output stays bf16 (engine.cpp self_fwd / conn_fwd:
+        ``Act{a.qkv}`` carries no e4m3 copy) -- so the maps exist for the DVQA / FigureQA variants and all fp8 modes alike.  In
+        ``train()`` without labels the maps carry the forward's dropout mask (same seed and sites), as the reference's do."""
+        cfg = self.config
+        maps_t = [eng.attention_probs(0, i) for i in range(cfg.num_hidden_layers)]
+        maps_v = [eng.attention_probs(1, i) for i in range(cfg.v_num_hidden_layers)]
+        maps_c = [(eng.attention_probs(2, i, 0), eng.attention_probs(2, i, 1)) for i in range(len(cfg.v_biattention_id))] if cfg.with_coattention else []
+        return maps_t, maps_v, maps_c
 
 
 class VisualDialogEncoder(nn.Module):

@@ -278,6 +278,36 @@ def attention_fwd(q, k, v, keymask, heads, d, p_drop=0.0, site=0, seed=0, row_ls
     return ctx
 
 
+def attention_probs(q, k, keymask, heads, d, p_drop=0.0, site=0, seed=0, out=None):
+    """The attention probabilities of ``attention_fwd`` on the same q / k / keymask, fp32 [B, heads, Tq, Tk] (crct_attention_probs):
+    keep / (1 - p) * softmax(q k^T / sqrt(d) + (1 - keymask) * -10000).  q [B,Tq,ldq] / k [B,Tk,ldk] bf16, column slices of wider
+    buffers included; with the forward's (p_drop, site, seed) the map carries the dropout mask that forward applied.
+    out: a contiguous fp32 tensor of that shape to write into."""
+    lib = L.load()
+    _chk(q, torch.bfloat16), _chk(k, torch.bfloat16)
+    if q.dim() != 3 or k.dim() != 3 or q.shape[0] != k.shape[0] or q.shape[2] != heads * d or k.shape[2] != heads * d:
+        raise RuntimeError("attention_probs: q [B, Tq, heads * d] and k [B, Tk, heads * d] expected with heads * d = %d; got %s and %s"
+                           % (heads * d, tuple(q.shape), tuple(k.shape)))
+    B, Tq, Tk = q.shape[0], q.shape[1], k.shape[1]
+    for t, T, what in ((q, Tq, "q"), (k, Tk, "k")):
+        if t.stride(2) != 1 or (B > 1 and t.stride(0) != T * t.stride(1)):
+            raise RuntimeError("attention_probs: %s needs unit column stride and batch stride T * stride(1); got strides %s" % (what, tuple(t.stride())))
+    _chk(keymask, torch.uint8)
+    if tuple(keymask.shape) != (B, Tk) or not keymask.is_contiguous():
+        raise RuntimeError("attention_probs: keymask must be a contiguous uint8 [%d, %d]; got %s" % (B, Tk, tuple(keymask.shape)))
+    if out is None:
+        out = torch.empty(B, heads, Tq, Tk, device=q.device, dtype=torch.float32)
+    else:
+        _chk(out, torch.float32)
+        if tuple(out.shape) != (B, heads, Tq, Tk) or not out.is_contiguous():
+            raise RuntimeError("attention_probs: out must be a contiguous fp32 [%d, %d, %d, %d]; got shape %s strides %s"
+                               % (B, heads, Tq, Tk, tuple(out.shape), tuple(out.stride())))
+    thr, sc, st = _drop(p_drop, site)
+    L.check(lib.crct_attention_probs(L.ptr(q), L.ptr(k), L.ptr(keymask), L.ptr(out), B, heads, Tq, Tk, d, q.stride(1), k.stride(1),
+                                     thr, sc, st, seed, L.current_stream()), "attention_probs")
+    return out
+
+
 def attention_fwd_q(q, k, v, keymask, heads, d, q_scale, q_amax, p_drop=0.0, site=0, seed=0, out=None):
     """attention_fwd that also returns the e4m3 copy of ctx (uint8, same shape and strides), quantised with the device scalar q_scale."""
     lib = L.load()

@@ -1558,3 +1558,49 @@ extern "C" int64_t crct_engine_tap(crct_engine_t* e, const void* workspace, cons
   crct_set_error("tap: unknown activation '%s'", name);
   return -1;
 }
+
+extern "C" int64_t crct_engine_attention_probs(crct_engine_t* e, const CrctBatch* batch, const CrctStepCfg* cfg, const void* workspace, int kind,
+                                               int index, int direction, float* out, int64_t cap, crct_stream_t stream) {
+  if (!e || !cfg || !workspace || !out) { crct_set_error("engine_attention_probs: null argument"); return -1; }
+  if (check_batch(e, batch)) return -1;
+  const CrctModelDims& D = e->d;
+  const char* ws = (const char*)workspace;
+  // the key masks as crct_engine_backward resolves them: the caller's, else the ones the forward built in the workspace
+  const uint8_t* km_t = batch->text_keymask ? batch->text_keymask : (const uint8_t*)ws + e->km_t;
+  const uint8_t* km_v = batch->image_keymask ? batch->image_keymask : (const uint8_t*)ws + e->km_v;
+  const int B = batch->B, T = batch->T, V = batch->V;
+  const bf16_t* q = nullptr;
+  const bf16_t* k = nullptr;
+  const uint8_t* km = nullptr;
+  int heads = 0, Tq = 0, Tk = 0, H = 0;
+  float p = 0.f;
+  uint32_t site = 0;
+  if (kind == 0 || kind == 1) {
+    const std::vector<SelfLayerP>& lp = kind == 0 ? e->tl : e->vl;
+    const std::vector<SelfLayerA>& la = kind == 0 ? e->tla : e->vla;
+    if (index < 0 || index >= (int)lp.size()) { crct_set_error("engine_attention_probs: %s layer %d out of range [0,%d)", kind == 0 ? "text" : "visual", index, (int)lp.size()); return -1; }
+    if (direction != 0) { crct_set_error("engine_attention_probs: direction %d belongs to connection layers (kind 2)", direction); return -1; }
+    H = lp[index].H; heads = lp[index].heads; Tq = Tk = kind == 0 ? T : V;
+    q = (const bf16_t*)(ws + la[index].qkv); k = q + H;
+    km = kind == 0 ? km_t : km_v;
+    p = lp[index].p_attn; site = lp[index].site;
+  } else if (kind == 2) {
+    if (index < 0 || index >= (int)e->cl.size() || !D.with_coattention) { crct_set_error("engine_attention_probs: connection layer %d out of range [0,%d)", index, D.with_coattention ? (int)e->cl.size() : 0); return -1; }
+    if (direction != 0 && direction != 1) { crct_set_error("engine_attention_probs: direction %d must be 0 (text over visual) or 1 (visual over text)", direction); return -1; }
+    const ConnLayerA& a = e->cla[index];
+    H = D.Hb; heads = D.b_heads;
+    const bf16_t* qkv1 = (const bf16_t*)(ws + a.qkv1);      // visual stream
+    const bf16_t* qkv2 = (const bf16_t*)(ws + a.qkv2);      // text stream
+    if (direction == 0) { q = qkv2; k = qkv1 + H; km = km_v; Tq = T; Tk = V; p = D.p_v_attn; site = e->cl[index].site; }
+    else { q = qkv1; k = qkv2 + H; km = km_t; Tq = V; Tk = T; p = D.p_attn; site = e->cl[index].site + 1; }
+  } else {
+    crct_set_error("engine_attention_probs: unknown kind %d (0 text, 1 visual, 2 connection layer)", kind);
+    return -1;
+  }
+  const int64_t n = (int64_t)B * heads * Tq * Tk;
+  if (n > cap) { crct_set_error("engine_attention_probs: %lld elements do not fit the buffer of %lld", (long long)n, (long long)cap); return -1; }
+  Drop dr;
+  if (cfg->training && p > 0.f) { dr.thr = thr_of(p); dr.scale = 1.0f / (1.0f - p); }
+  if (crct_attention_probs(q, k, km, out, B, heads, Tq, Tk, H / heads, 3 * H, 3 * H, dr.thr, dr.scale, site, cfg->seed, stream)) return -1;
+  return n;
+}

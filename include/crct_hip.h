@@ -344,6 +344,18 @@ int crct_attention_bwd(const void* q, const void* k, const void* v, const uint8_
                        uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
                        crct_stream_t stream);
 
+/* The attention probabilities themselves (csrc/attention_probs.hip) -- what the reference returns under output_all_attention_masks
+ * (vilbert.py:392-412, :522-543, :684-723); no forward or backward kernel stores them:
+ *   probs[b][h][i][j] = keep_ij / (1 - p) * softmax_j(q_i . k_j / sqrt(d) + (1 - keymask[b][j]) * -10000)      fp32 [B][heads][Tq][Tk], contiguous
+ * q, k, keymask, the dropout arguments and the Philox numbering are crct_attention_fwd's: with the same (drop_thr, drop_scale,
+ * drop_site, seed) a map carries the mask that forward applied; drop_thr = 0: no dropout.  One kernel for every Tq, Tk <=
+ * CRCT_ATTN_MAX_LEN and every head size d % 8 == 0, d <= 64; ldq, ldk multiples of 8, q and k 16-byte aligned.  Anything else is
+ * refused with an error before any launch. */
+int crct_attention_probs(const void* q, const void* k, const uint8_t* keymask, float* probs,
+                         int B, int heads, int Tq, int Tk, int d, int64_t ldq, int64_t ldk,
+                         uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
+                         crct_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Text embeddings: BertEmbeddingLocation.forward, vilbert.py:320-358.
  *  sum = word[ids] + pos[posid]*(qa) + type[seg']*(seg != 0) + (W_loc loc + b_loc)*(|loc|_1 != 0)
@@ -771,6 +783,18 @@ int crct_event_query(void* ev);      /* 1 = complete, 0 = not yet, < 0 = error *
  * forward (batch B, T, V) into `out` (device, bf16); returns the element count or -1. */
 int64_t crct_engine_tap(crct_engine_t*, const void* workspace, const char* name, int B, int T, int V,
                         void* out, int64_t cap, crct_stream_t stream);
+
+/* Attention maps of the last crct_engine_forward on this workspace (same batch and cfg), computed on request from what that forward
+ * left there: the layer's fused bf16 qkv buffer (kept in every mode, fp8 included; an evaluation forward overwrites none of them) and
+ * the key masks -- the batch's own, else the ones that forward built.  kind 0: text layer `index` -> [B][heads][T][T]; kind 1: visual
+ * layer `index` -> [B][v_heads][V][V]; kind 2: connection layer `index`, direction 0 = attention_probs1 (text queries over visual keys,
+ * [B][b_heads][T][V], vilbert.py:684-696), direction 1 = attention_probs2 ([B][b_heads][V][T], :704-718).  Dropout as that forward
+ * derived it: off unless cfg->training and the layer's probability > 0, the same seed and per-layer site.  fp32 into `out` (device,
+ * room for `cap` elements); returns the element count, or -1 (crct_last_error) for an unknown kind / index / direction or a cap too
+ * small.  Adds no engine state and changes no forward launch. */
+int64_t crct_engine_attention_probs(crct_engine_t*, const CrctBatch* batch, const CrctStepCfg* cfg,
+                                    const void* workspace, int kind, int index, int direction,
+                                    float* out, int64_t cap, crct_stream_t stream);
 
 #ifdef __cplusplus
 }
