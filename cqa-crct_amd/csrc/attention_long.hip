@@ -433,12 +433,8 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_long(ATTN_HOT_PARAMS) {
 template <bool BWD, int ND, int NW, bool SHARE, bool LSE>
 hipError_t launch_nw(const AttnArgs& a, size_t lds, hipStream_t s) {
   auto kern = BWD ? attn_bwd_long<ND, NW, SHARE, LSE> : attn_fwd_long<ND, NW>;
-  static bool raised = false;             // first call is eager (outside any stream capture)
-  if (lds > 64 * 1024 && !raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
-    if (e != hipSuccess) return e;
-    raised = true;
-  }
+  const hipError_t e = crct_lds_limit(kern, lds > 64 * 1024 ? LDS_CAP : lds);
+  if (e != hipSuccess) return e;
   if (a.ldq > 0x7fffffffL || a.ldk > 0x7fffffffL || a.ldv > 0x7fffffffL) return hipErrorInvalidValue;      // preloaded as 32-bit scalars
   crct_launch(kern, dim3(a.B * a.heads), dim3(64 * NW), lds, s, ATTN_HOT_ARGS(a) a);
   return hipGetLastError();

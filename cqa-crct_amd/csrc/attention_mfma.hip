@@ -503,12 +503,8 @@ hipError_t launch_sp(const AttnArgs& a, hipStream_t s) {
   constexpr int W = BYTES > 48 * 1024 ? 1 : (W0 * SP > 8 ? 8 / SP : W0);
   static_assert(BYTES % 16 == 0 && BYTES * W <= 160 * 1024, "LDS slice");
   auto kern = BWD ? attn_bwd_mfma<NQ, NK, ND, W, SP> : attn_fwd_mfma<NQ, NK, ND, W, SP>;
-  static bool raised = false;           // first call is eager (outside any stream capture)
-  if (BYTES * W > 64 * 1024 && !raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, BYTES * W);
-    if (e != hipSuccess) return e;
-    raised = true;
-  }
+  const hipError_t e = crct_lds_limit(kern, BYTES * W);
+  if (e != hipSuccess) return e;
   const int total = a.B * a.heads;
   if (a.ldq > 0x7fffffffL || a.ldk > 0x7fffffffL || a.ldv > 0x7fffffffL) return hipErrorInvalidValue;      // preloaded as 32-bit scalars (ATTN_HOT_ARGS)
   crct_launch(kern, dim3((total + W - 1) / W), dim3(64 * W * SP), BYTES * W, s, ATTN_HOT_ARGS(a) a);

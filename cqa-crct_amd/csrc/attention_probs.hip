@@ -158,12 +158,8 @@ hipError_t launch_probs(const bf16_t* q, const bf16_t* k, const uint8_t* km, int
                         hipStream_t s) {
   const size_t lds = probs_lds(Tk, ND);
   auto kern = attn_probs_kernel<ND>;
-  static bool raised = false;             // first call is eager (outside any stream capture)
-  if (lds > 64 * 1024 && !raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)probs_lds(CRCT_ATTN_MAX_LEN, ND));
-    if (e != hipSuccess) return e;
-    raised = true;
-  }
+  const hipError_t e = crct_lds_limit(kern, lds > 64 * 1024 ? probs_lds(CRCT_ATTN_MAX_LEN, ND) : lds);
+  if (e != hipSuccess) return e;
   // few (batch, head) pairs with many query tiles: the tiles of a pair are spread over up to `split` workgroups (each loads K itself)
   const int NQ = (Tq + 15) >> 4, groups = (NQ + NW - 1) / NW;
   const long pairs = (long)B * heads;

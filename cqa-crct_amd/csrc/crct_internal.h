@@ -47,6 +47,26 @@ void crct_stamp_reset(void);
 // wrong results, timing only: what the step gains when a class of kernels costs nothing (tools/lab/step_sensitivity.sh).
 bool crct_lab_skip(const void* kern, hipStream_t s);
 #endif
+// Before a launch with more than 64 KB of dynamic LDS: `bytes` = the most `kern` is ever launched with.  Raises the kernel's limit on
+// the CURRENT device unless it already stands at least there (lds_limit.h: per kernel and device, from any host thread).  The launch
+// stream must belong to the current device, as it does under PyTorch's device guard: the runtime sets the attribute there and nowhere
+// else.  Up to 64 KB: no runtime call; above: hipGetDevice, and hipFuncSetAttribute the first time per device.
+hipError_t crct_lds_limit_raise(const void* kern, size_t bytes);      // streams.hip
+// One hipGetDevice for a whole forward / backward instead of one per launch above 64 KB (several hundred per step, ~0.1 us each):
+// while a scope lives, crct_lds_limit on THIS thread takes the device from it.  Only around code that never calls hipSetDevice.
+class CrctDeviceScope {
+ public:
+  CrctDeviceScope();
+  ~CrctDeviceScope();
+  CrctDeviceScope(const CrctDeviceScope&) = delete;
+  CrctDeviceScope& operator=(const CrctDeviceScope&) = delete;
+ private:
+  int outer_;
+};
+template <class K>
+inline hipError_t crct_lds_limit(K kern, size_t bytes) {
+  return bytes <= 64 * 1024 ? hipSuccess : crct_lds_limit_raise(reinterpret_cast<const void*>(kern), bytes);
+}
 template <class K, class... A>
 inline void crct_launch(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... a) {
 #ifdef CRCT_GEMM_LAB

@@ -1329,6 +1329,7 @@ extern "C" int crct_engine_forward(crct_engine_t* e, const float* params_f32, co
                "engine_forward: the fp8 step is built for the PlotQA model only, not for the dvqa / figure_qa variants");
   if (int r = ensure_streams(e, (hipStream_t)stream)) return r;
   e->evnext = 0;
+  CrctDeviceScope on_device;                              // every launch below runs on this thread and the device stays
   // key masks the caller did not supply are built here (one launch) and kept in the workspace for the backward pass
   CrctBatch bl = *batch;
   if (!bl.text_keymask || !bl.image_keymask) {
@@ -1388,6 +1389,7 @@ extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, c
   if (int r = check_batch(e, batch)) return r;
   if (int r = ensure_streams(e, (hipStream_t)stream)) return r;
   e->evnext = 0;
+  CrctDeviceScope on_device;                              // every launch below runs on this thread and the device stays
   CrctBatch bl = *batch;                                 // masks built by the forward pass of this batch live in the workspace
   if (!bl.text_keymask) bl.text_keymask = (const uint8_t*)workspace + e->km_t;
   if (!bl.image_keymask) bl.image_keymask = (const uint8_t*)workspace + e->km_v;

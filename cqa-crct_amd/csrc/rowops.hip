@@ -1616,24 +1616,15 @@ extern "C" int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved
                          rows_scratch, idx_scratch, (int)M, H, d_pos, used_pos, idx_scratch + M, d_type);
       CRCT_CHECK_HIP(hipGetLastError());
       DISPATCH_NCH(H, {
-        static bool big_lds_w = false;
-        if (word_lds > 64 * 1024 && !big_lds_w) {
-          CRCT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&word_scatter_kernel<NCH>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-          big_lds_w = true;
-        }
+        CRCT_CHECK_HIP(crct_lds_limit(&word_scatter_kernel<NCH>, word_lds > 64 * 1024 ? 152 * 1024 : word_lds));
         crct_launch((word_scatter_kernel<NCH>), dim3((int)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), word_lds, s,
                            (const float*)rows_scratch, ids, (int)M, H, d_word, w_first, w_last);
       });
       CRCT_CHECK_HIP(hipGetLastError());
     } else
     DISPATCH_NCH(H, {
-      static bool big_lds = false;                         // a heavy id's match list (M ints) + 4 partial rows: above 64 KiB from ~12 300 rows on at H = 1024
-      if (word_lds > 64 * 1024 && !big_lds) {
-        CRCT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&embed_scatter_kernel<NCH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        big_lds = true;
-      }
+      // a heavy id's match list (M ints) + 4 partial rows: above 64 KiB from ~12 300 rows on at H = 1024
+      CRCT_CHECK_HIP(crct_lds_limit(&embed_scatter_kernel<NCH>, word_lds > 64 * 1024 ? 152 * 1024 : word_lds));
       crct_launch((embed_scatter_kernel<NCH>), dim3(n_gather + (int)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), word_lds, s,
                          (const float*)rows_scratch, idx_scratch, (int)M, H, d_pos, used_pos, idx_scratch + M, d_type, n_gather, ids, d_word,
                          w_first, w_last);

@@ -15,6 +15,7 @@
 
 #include "common.hip.h"
 #include "crct_internal.h"
+#include "lds_limit.h"
 
 namespace {
 
@@ -128,6 +129,25 @@ extern "C" int crct_prof_stamp_read(int i, void** stream, double* t0_ms, double*
   CRCT_CHECK_HIP(hipEventElapsedTime(&d, st.a, st.b));
   *stream = (void*)st.s; *t0_ms = (double)a; *t1_ms = (double)a + (double)d;
   return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- dynamic-LDS limits
+namespace {
+crct::LdsLimits g_lds_limits;
+std::mutex g_lds_mu;                  // setting the attribute and recording it are one step: a lower request never lands after a higher one
+thread_local int t_device = -1;       // the current device while a CrctDeviceScope lives on this thread, else -1
+}  // namespace
+CrctDeviceScope::CrctDeviceScope() : outer_(t_device) { if (t_device < 0 && hipGetDevice(&t_device) != hipSuccess) t_device = -1; }
+CrctDeviceScope::~CrctDeviceScope() { t_device = outer_; }
+hipError_t crct_lds_limit_raise(const void* kern, size_t bytes) {
+  int dev = t_device;
+  hipError_t e = dev >= 0 ? hipSuccess : hipGetDevice(&dev);
+  if (e != hipSuccess || !g_lds_limits.needs_raise(kern, dev, bytes)) return e;
+  std::lock_guard<std::mutex> lk(g_lds_mu);
+  if (!g_lds_limits.needs_raise(kern, dev, bytes)) return hipSuccess;
+  e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) g_lds_limits.record(kern, dev, bytes);
+  return e;
 }
 
 // out[0..2]: streams of three queue classes other than main's (nullptr where fewer classes exist), out[3]: a second stream of

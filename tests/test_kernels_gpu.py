@@ -2410,6 +2410,68 @@ def test_gemm_grouped_bit_for_bit(mode, tile, gemm_path):
                 assert bool((rs[M:] == SENT).all()), what + ": rowsum_out written past M"
 
 
+def _stamped_cases():
+    """(name, force_generic, run, [(canvas, M, N, exact result)]) of the four launch forms: single LDS-DMA, split-K, grouped, register-staged."""
+    def single(name, K, generic, **kw_extra):
+        A, B, kw, ref = _operands("nt", 128, 128, K, 48, 48, seed=K)
+        buf = _canvas(128, 128, 128 + 24, torch.float32)
+        return (name, generic, lambda: ops.gemm(A, B, 128, 128, K, out=buf, ldc=128 + 24, **dict(kw, **kw_extra)), [(buf, 128, 128, GR.f32(ref))])
+    probs, outs = [], []
+    for i in range(2):
+        A, B, kw, ref = _operands("tt", 128, 128, 128, 32, 32, seed=31 + i)
+        buf = _canvas(128, 128, 128 + 8, torch.float32)
+        probs.append(dict(A=A, B=B, M=128, N=128, K=128, out=buf, ldc=128 + 8, **kw))
+        outs.append((buf, 128, 128, GR.f32(ref)))
+    return [single("lds-dma", 128, 0), single("split-k", 256, 0, tile=4, split_k=2), ("grouped", 0, lambda: ops.gemm_grouped(probs), outs),
+            single("register-staged", 72, 1)]
+
+
+@pytest.mark.parametrize("gemm_path", ["pipelined"], indirect=True)      # the cases choose the kernel themselves
+def test_gemm_stamped_launch_path_same_bits_one_timed_launch(gemm_path):
+    """crct_prof_enable(1) sends every GEMM launch through hipExtLaunchKernelGGL with an event pair (only bench.py arms it).  Each launch
+    form -- single, split-K on configuration 4 (96 KB of LDS), grouped weight gradients, register-staged -- writes the same bits stamped
+    as plain (the exact ones, inside its sentinel canvas), and crct_prof_read then holds exactly one launch: under the variant the
+    launch log names (cfg * 3 + kind), with a time above zero."""
+    lib = L.load()
+    try:
+        for name, generic, run, outs in _stamped_cases():
+            lib.crct_gemm_force_generic(generic)
+            lib.crct_prof_enable(0)
+            run()
+            plain = [buf.clone() for buf, *_ in outs]
+            for buf, *_ in outs:
+                buf.fill_(SENT)
+            lib.crct_prof_reset()
+            lib.crct_prof_enable(1)
+            lib.crct_launch_log_enable(1)
+            run()
+            lib.crct_prof_enable(0)
+            assert lib.crct_launch_log_count() == 1, (name, lib.crct_launch_log_count())
+            rec = L.LaunchRec()
+            assert lib.crct_launch_log_read(0, C.byref(rec)) == 0
+            lib.crct_launch_log_enable(0)
+            assert (rec.split_k, rec.n_problems) == ((2 if name == "split-k" else 1), len(outs)), (name, rec.cfg, rec.split_k, rec.n_problems)
+            assert (rec.cfg >= 16) == bool(generic) and (name != "split-k" or rec.cfg == 4), (name, rec.cfg)
+            for (buf, M, N, ref), before in zip(outs, plain):
+                assert torch.equal(buf, before), name + ": stamped and plain launches differ"
+                _assert_bits(buf[:M, :N], ref, name)
+                _assert_canary(buf, M, N, name)
+            seen = {}
+            for v in range(225):
+                cnt, fl, ms = C.c_long(0), C.c_double(0), C.c_double(0)
+                assert lib.crct_prof_read(v, C.byref(cnt), C.byref(fl), C.byref(ms)) == 0
+                if cnt.value:
+                    seen[v] = (cnt.value, ms.value)
+            print("%s: launch log cfg %d kind %d, profile %r" % (name, rec.cfg, rec.kind, seen))
+            assert list(seen) == [rec.cfg * 3 + rec.kind] and seen[rec.cfg * 3 + rec.kind][0] == 1, (name, rec.cfg, rec.kind, seen)
+            assert seen[rec.cfg * 3 + rec.kind][1] > 0, (name, seen)
+    finally:
+        lib.crct_launch_log_enable(0)
+        lib.crct_prof_enable(0)
+        lib.crct_prof_reset()
+        lib.crct_gemm_force_generic(0)
+
+
 def test_gemm_refuses_c_cached_with_accumulate(gemm_path):
     """c_cached is a plain fp32 store: the LDS-DMA epilogue writes it without reading the old value, the register-staged one added it.
     The combination is refused by crct_gemm_bf16 and crct_gemm_bf16_grouped on both kernel paths, and nothing is written."""
