@@ -68,8 +68,9 @@ class BertConfig(object):
         for flag in ("fast_mode", "in_batch_pairs", "predict_feature", "intra_gate"):
             if getattr(self, flag):
                 raise NotImplementedError("%s is off on the CRCT hot path (SURVEY.md 3.2)" % flag)
-        if self.fixed_t_layer or self.fixed_v_layer:
-            raise NotImplementedError("fixed_*_layer is off on the CRCT hot path (SURVEY.md 3.2)")
+        # vilbert.py:857-858: the frozen layers run before the first co-attention layer (crct.layout.frozen_tensors)
+        assert 0 <= self.fixed_t_layer <= (self.t_biattention_id[0] if len(self.t_biattention_id) else self.num_hidden_layers)
+        assert 0 <= self.fixed_v_layer <= (self.v_biattention_id[0] if len(self.v_biattention_id) else self.v_num_hidden_layers)
         if self.hidden_act != "gelu" or self.v_hidden_act != "gelu":
             raise NotImplementedError("only erf-GELU is built (vilbert.json:3,24)")
 

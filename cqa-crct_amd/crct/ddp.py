@@ -182,6 +182,7 @@ class FlatGradDDP(torch.nn.Module):
         self.materialize_grads = None if materialize_grads is None else bool(materialize_grads)      # None: see materializes()
         self._poisoned_at = None     # full-clear count of the gradient buffer at which the owned fp32 views were last filled with NaN
         self._buckets = None
+        self._plan_ver = 0
         self._events = self._comm = self._bucket_done = None
         self._comm_buf = None
         self._seg_bucket = None
@@ -282,7 +283,7 @@ class FlatGradDDP(torch.nn.Module):
     def _pack_plans(self, core, eng):
         """Per bucket: device tables (run offsets, run lengths, chunk table) of the gradient elements the engine does NOT own, i.e.
         what still has to be cast into the bf16 communication buffer when the weight-gradient GEMMs write there themselves."""
-        key = eng.wgrad_owned_key()
+        key = (eng.wgrad_owned_key(), self._plan_ver)
         if getattr(self, "_pack_plans_key", None) == key:
             return self._pack_plans_cache
         runs = core.non_owned_grad_runs()
@@ -307,7 +308,15 @@ class FlatGradDDP(torch.nn.Module):
         return plans
 
     def _plan(self, eng):
-        self._buckets = plan_buckets(eng.segments, self.bucket_elems)
+        """Buckets over the ranges a backward pass produces: with tensors without gradient (``CrctModel.tensors_without_grad``) a
+        segment counts with the hull of its tensors that have one, and a segment the engine does not run with nothing -- a frozen
+        prefix of the layout is neither packed nor sent.  Events and the callback still come at bucket ends; the engine records
+        them for segments that do not run as well."""
+        nograd = getattr(self.core, "tensors_without_grad", ())
+        self._plan_ver = getattr(self.core, "_nograd_version", 0)
+        segments = eng.grad_segments(nograd) if nograd else eng.segments
+        self._buckets = plan_buckets(segments, self.bucket_elems)
+        self._bucket_done = None
         self._seg_bucket, b = [], 0
         for i in range(len(eng.segments)):
             while b < len(self._buckets) - 1 and self._buckets[b][0] < i:
@@ -340,8 +349,10 @@ class FlatGradDDP(torch.nn.Module):
             self._place_wgrad_streams(core, eng, False)
             eng.backward(core.flat_params, core.flat_shadow, core.flat_grads, tensors, step, -1)
             return
-        if self._buckets is None:
+        if self._buckets is None or self._plan_ver != getattr(core, "_nograd_version", 0):
             self._plan(eng)
+        if not self._buckets:
+            raise RuntimeError("FlatGradDDP: no tensor has a gradient in this pass, there is nothing to exchange")
         self._place_wgrad_streams(core, eng, True)
         if not (self.event_mode and core.flat_grads.is_cuda):
             self.last_exchange = None
@@ -367,8 +378,11 @@ class FlatGradDDP(torch.nn.Module):
             # visible by that same protocol before the RCCL kernel ends; consumers on other streams wait for `bucket_done`, a
             # stock torch event (system-scope fence in its record) recorded behind each bucket.
             self._events = [DeviceEvent() for _ in range(4 * len(eng.segments))]
+            for ev in self._events:                              # created / recorded once so that a wait before the first record is legal
+                ev.record()
+        if self._bucket_done is None:
             self._bucket_done = [torch.cuda.Event() for _ in self._buckets]
-            for ev in self._events + self._bucket_done:          # created / recorded once so that a wait before the first record is legal
+            for ev in self._bucket_done:
                 ev.record()
         if self.grad_dtype == torch.bfloat16 and self._comm_buf is None:
             self._comm_buf = torch.zeros(core.flat_grads.numel(), dtype=torch.bfloat16, device=dev)

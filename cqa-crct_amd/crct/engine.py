@@ -168,6 +168,36 @@ class StepEngine(object):
             assert self.lib.crct_engine_fp8_weights(self.handle, off, num, n) == n
         return self.lib.crct_engine_fp8_sites(self.handle), list(zip(off[:n], num[:n]))
 
+    def set_trainable(self, flags):
+        """One flag per table entry (crct_engine_set_trainable); None = every tensor has a gradient."""
+        key = None if flags is None or all(flags) else tuple(bool(f) for f in flags)
+        if key == getattr(self, "_trainable_key", None):
+            return
+        arr = None if key is None else (C.c_uint8 * len(key))(*[int(f) for f in key])
+        L.check(self.lib.crct_engine_set_trainable(self.handle, arr, len(self.table)), "engine_set_trainable")
+        self._trainable_key = key
+
+    def backward_plan(self):
+        """Per backward segment (runs, text input gradient, visual input gradient, weight-gradient GEMMs left out) under the current
+        flags (crct_engine_backward_plan)."""
+        out = (C.c_int32 * (4 * self.n_segments))()
+        n = self.lib.crct_engine_backward_plan(self.handle, out, self.n_segments)
+        assert n == self.n_segments
+        return [(bool(out[4 * i]), bool(out[4 * i + 1]), bool(out[4 * i + 2]), int(out[4 * i + 3])) for i in range(n)]
+
+    def grad_segments(self, without_grad=()):
+        """``segments`` narrowed to what a pass under the current flags produces: per segment the hull of its tensors with gradient,
+        an empty range for a segment that does not run or has none (``without_grad``: names of the tensors without gradient)."""
+        if not without_grad:
+            return list(self.segments)
+        plan = self.backward_plan()
+        ents = sorted((e for e in self.table if e.used and e.name not in without_grad), key=lambda e: e.offset)
+        out = []
+        for (lo, hi), pl in zip(self.segments, plan):
+            mine = [e for e in ents if lo <= e.offset < hi] if pl[0] else []
+            out.append((mine[0].offset, mine[-1].offset + mine[-1].numel) if mine else (lo, lo))
+        return out
+
     def wgrad_owned(self):
         """(offsets, numels) of the weight gradients the engine overwrites under CrctStepCfg.wgrad_overwrite: fixed by the
         layout at engine creation (every Linear weight produced by exactly one weight-gradient GEMM per pass)."""

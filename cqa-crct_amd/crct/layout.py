@@ -39,6 +39,36 @@ def encoder_schedule(cfg):
     return steps
 
 
+def frozen_tensors(cfg):
+    """Name prefixes of the parameters that ``fixed_t_layer`` / ``fixed_v_layer`` leave without a gradient (vilbert.py:857-881):
+    text layers ``0 .. fixed_t_layer-1`` and visual layers ``0 .. fixed_v_layer-1`` run under ``no_grad`` -- a prefix of
+    ``encoder_schedule(cfg)`` on their stream -- which also cuts that stream's embeddings off the graph: every
+    ``bert.embeddings.*`` tensor (the tied ``cls.predictions.decoder.weight`` is the word table) resp. every
+    ``bert.v_embeddings.*`` tensor.  Returns the name prefixes; ``is_frozen(prefixes, name)`` tests one name and
+    ``frozen_names(cfg, params)`` lists the tensors."""
+    prefixes = []
+    if cfg.fixed_t_layer > 0:
+        prefixes.append("bert.embeddings.")
+        prefixes += ["bert.encoder.layer.%d." % i for i in range(cfg.fixed_t_layer)]
+    if cfg.fixed_v_layer > 0:
+        prefixes.append("bert.v_embeddings.")
+        prefixes += ["bert.encoder.v_layer.%d." % i for i in range(cfg.fixed_v_layer)]
+    return tuple(prefixes)
+
+
+def is_frozen(prefixes, name):
+    if name == "cls.predictions.decoder.weight":          # tied to the word table (vilbert.py:1029)
+        name = "bert.embeddings.word_embeddings.weight"
+    return name.startswith(prefixes) if prefixes else False
+
+
+def frozen_names(cfg, params):
+    """The parameters (``named_parameters()`` order) the reference leaves at ``.grad is None`` after a training step under
+    ``cfg``: the tensors the two fields freeze and the ones that never receive a gradient on this path (``is_unused``)."""
+    pre = frozen_tensors(cfg)
+    return [e.name for e in parameter_table(cfg, params)[0] if not e.used or is_frozen(pre, e.name)]
+
+
 def is_language_weight(name):
     """Membership rule of the reference's config/language_weights.json (BERT-base tensors get
     params['lr'], everything else params['image_lr']; utils.py:231-241).  The JSON lists the text

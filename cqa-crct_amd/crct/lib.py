@@ -194,6 +194,8 @@ PROTOTYPES = {
     "crct_engine_create": (vp, [C.POINTER(ModelDims), C.c_char_p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "crct_engine_create_variant": (vp, [C.POINTER(ModelDims), C.c_char_p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Variant)]),
     "crct_engine_set_areas": (C.c_int, [vp, vp]),
+    "crct_engine_set_trainable": (C.c_int, [vp, vp, C.c_int]),
+    "crct_engine_backward_plan": (C.c_int, [vp, vp, C.c_int]),
     "crct_engine_destroy": (None, [vp]),
     "crct_engine_workspace_bytes": (C.c_size_t, [vp]),
     "crct_engine_num_segments": (C.c_int, [vp]),

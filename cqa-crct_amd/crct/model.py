@@ -22,7 +22,7 @@ from . import lib as L
 from . import ops
 from .config import BertConfig
 from .engine import StepEngine
-from .layout import model_variant, optional_grad, parameter_table
+from .layout import frozen_tensors, is_frozen, model_variant, optional_grad, parameter_table
 
 
 class _Node(nn.Module):
@@ -103,6 +103,13 @@ class CrctModel(nn.Module):
         # areas_emp (dvqa / figure_qa): its .grad exists only once a pass with `areas` has run since the last clear, as in torch
         self._optional = [e for e in self.table if e.used and optional_grad(e.name)]
         self._optional_live = False
+        # tensors WITHOUT gradient in a training pass: frozen by config.fixed_t_layer / fixed_v_layer (vilbert.py:857-881) or by
+        # requires_grad_(False).  Their .grad is None, their range of the flat gradient buffer is unspecified and nobody reads it
+        # (_sync_trainable, before every training forward; the engine then runs less of its backward)
+        self._nograd = frozenset()
+        self._nograd_version = 0
+        self._trainable_key = None
+        self._flags = None
         self._flat_p = torch.zeros(self.total, device=device)
         self._flat_g = torch.zeros(self.total, device=device)
         self._flat_b16 = torch.zeros(self.total, device=device, dtype=torch.bfloat16)
@@ -330,7 +337,7 @@ class CrctModel(nn.Module):
         for e in self.table:
             p = byname[e.name]
             p.data = self._flat_p[e.offset:e.offset + e.numel].view(e.shape)
-            if e.used and (self._optional_live or not optional_grad(e.name)):
+            if e.used and e.name not in self._nograd and (self._optional_live or not optional_grad(e.name)):
                 p.grad = self._flat_g[e.offset:e.offset + e.numel].view(e.shape)
         self._rebound = list(byname.values())
         self._invalidate_shadow()
@@ -379,7 +386,7 @@ class CrctModel(nn.Module):
             byname = self._params_by_name()
             self._optional_params = [byname[e.name] for e in self._optional]
         for e, p in zip(self._optional, self._optional_params):
-            p.grad = self._flat_g[e.offset:e.offset + e.numel].view(e.shape) if live else None
+            p.grad = self._flat_g[e.offset:e.offset + e.numel].view(e.shape) if live and e.name not in self._nograd else None
 
     @property
     def optional_grads_live(self):
@@ -434,12 +441,52 @@ class CrctModel(nn.Module):
         self._lazy_plan_key, self._lazy_plan = key, plan
         return plan
 
+    # ------------------------------------------------------------------ tensors without gradient
+    @property
+    def tensors_without_grad(self):
+        """Names of the gradient-receiving tensors that the last training forward found frozen (config or ``requires_grad``)."""
+        return self._nograd
+
+    def _sync_trainable(self, eng):
+        """Before a training forward: which tensors have a gradient in this pass.  Cached on (fixed_t_layer, fixed_v_layer, every
+        ``requires_grad``), so an unchanged model costs one tuple comparison; on a change the ``.grad`` views are set / cleared (a
+        tensor that gets its gradient back gets a zeroed view of the flat buffer) and the engine is told."""
+        if getattr(self, "_used_params", None) is None:
+            byname = self._params_by_name()
+            self._used_params = [(e, byname[e.name]) for e in self.table if e.used]
+            self._used_only = [p for _, p in self._used_params]
+        cfg = self.config
+        key = (int(cfg.fixed_t_layer), int(cfg.fixed_v_layer), tuple([p.requires_grad for p in self._used_only]))
+        if key != self._trainable_key:
+            pre = frozen_tensors(cfg)
+            new = frozenset(e.name for e, p in self._used_params if not p.requires_grad or is_frozen(pre, e.name))
+            if self.fp8 and new:
+                # the fused optimizer keeps the e4m3 shadow and its scales current for every shadowed weight it updates: not built
+                _, shadowed = eng.fp8_layout()
+                for e, _ in self._used_params:
+                    if e.name in new and any(o <= e.offset < o + n for o, n in shadowed):
+                        raise NotImplementedError("params['fp8'] with '%s' without gradient (fixed_t_layer / fixed_v_layer / requires_grad_(False)): "
+                                                  "freezing a weight that has an e4m3 shadow is not supported; train in bf16" % e.name)
+            old = self._nograd
+            self._nograd = new
+            for e, p in self._used_params:
+                if e.name in new:
+                    p.grad = None
+                elif e.name in old and (self._optional_live or not optional_grad(e.name)):
+                    self._flat_g[e.offset:e.offset + e.numel].zero_()          # its range held anything while it had no gradient
+                    p.grad = self._flat_g[e.offset:e.offset + e.numel].view(e.shape)
+            self._flags = [e.name not in new for e in self.table] if new else None
+            self._trainable_key = key
+            self._nograd_version += 1
+        eng.set_trainable(self._flags)
+
     def _ensure_grad_views(self):
-        """``optimizer.zero_grad()`` of stock torch sets ``.grad = None``: re-attach the views and clear."""
+        """``optimizer.zero_grad()`` of stock torch sets ``.grad = None``: re-attach the views and clear.  A tensor without gradient
+        (``_sync_trainable``) has ``.grad = None`` on purpose and is not a sign of that."""
         missing = False
         byname = None
         for e in self.table:
-            if not e.used or optional_grad(e.name):
+            if not e.used or optional_grad(e.name) or e.name in self._nograd:
                 continue
             if byname is None:
                 byname = self._params_by_name()
@@ -450,7 +497,7 @@ class CrctModel(nn.Module):
             self._flat_g.zero_()
             self._wgrad_overwrite_next = False
             for e in self.table:
-                if e.used and not optional_grad(e.name):
+                if e.used and not optional_grad(e.name) and e.name not in self._nograd:
                     byname[e.name].grad = self._flat_g[e.offset:e.offset + e.numel].view(e.shape)
             self._set_optional_grads(False)
 
@@ -600,6 +647,8 @@ class CrctModel(nn.Module):
         B, T = tensors["tokens"].shape
         V = tensors["image_feat"].shape[1]
         eng = self._get_engine(B, T, V)
+        if train_branch and torch.is_grad_enabled():
+            self._sync_trainable(eng)          # which tensors have a gradient in this pass (before any launch: it may refuse)
         self._refresh_shadow()
         self._calls += 1
         p = self.params

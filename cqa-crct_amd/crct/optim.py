@@ -47,6 +47,14 @@ def _crct_core(model):
     return core
 
 
+def active_blocks(blk_seg, blk_off, active):
+    """The chunk table (``ops.adamw_plan``: per block its segment and its offset inside it, blocks in segment order) cut down to
+    the segments with ``active[segment]``: the blocks of the others are dropped, segment numbers stay -- the per-segment arrays
+    (offsets, lengths, lr, weight decay) are indexed as before.  Host tensors in, host tensors out."""
+    keep = torch.as_tensor(active, dtype=torch.bool)[blk_seg.long()]
+    return blk_seg[keep].contiguous(), blk_off[keep].contiguous()
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics, one launch.  ``param_groups`` keep the caller's layout."""
 
@@ -74,14 +82,14 @@ class FusedAdamW(torch.optim.Optimizer):
         self._seg_len = to_dev([e.numel for e in self._segs], torch.int64)
         blk_seg, blk_off = ops.adamw_plan([e.numel for e in self._segs])
         self._blk_seg, self._blk_off = blk_seg.to(dev), blk_off.to(dev)
+        # tensors without gradient (CrctModel.tensors_without_grad: frozen by the config or by requires_grad_(False)) are skipped as
+        # torch.optim.AdamW skips ``grad is None``: the full table is kept on the host and the device table rebuilt without their
+        # blocks whenever that set changes (_sync_active) -- weights, moments, step counters and bf16 shadow stay untouched
+        self._blk_full = (blk_seg, blk_off)
+        self._active_ver = 0
         # areas_emp (dvqa / figure_qa): block range of each of its segments -- a step after passes without `areas` leaves its weights
         # and moments untouched, as torch.optim.AdamW does for a None gradient
-        opt_names = {e.name for e in getattr(core, "optional_entries", ())}
-        self._opt_blocks = []
-        for i, e in enumerate(self._segs):
-            if e.name in opt_names:
-                idx = (blk_seg == i).nonzero().flatten()
-                self._opt_blocks.append((int(idx.min()), int(idx.max()) + 1, e))
+        self._index_optional(blk_seg)
         self._lr_host = torch.empty(len(self._segs), dtype=torch.float32).pin_memory()
         self._wd_host = torch.empty(len(self._segs), dtype=torch.float32).pin_memory()
         self._lr_dev = torch.empty(len(self._segs), dtype=torch.float32, device=dev)
@@ -128,10 +136,38 @@ class FusedAdamW(torch.optim.Optimizer):
                                  exp_avg_sq=self._v[e.offset:e.offset + e.numel].view(e.shape))
         self._byname = byname
 
+    def _index_optional(self, blk_seg):
+        opt_names = {e.name for e in getattr(self.core, "optional_entries", ())}
+        self._opt_blocks = []
+        for i, e in enumerate(self._segs):
+            if e.name in opt_names:
+                idx = (blk_seg == i).nonzero().flatten()
+                if idx.numel():
+                    self._opt_blocks.append((int(idx.min()), int(idx.max()) + 1, e))
+
+    def _sync_active(self):
+        """Follow the model's set of tensors without gradient: the block table on the device then holds exactly the segments whose
+        Parameter has a gradient.  Host work only, and only when the set has changed."""
+        core = self.core
+        ver = getattr(core, "_nograd_version", 0)
+        if ver == self._active_ver:
+            return
+        self._active_ver = ver
+        nograd = core.tensors_without_grad
+        dev = core.flat_params.device
+        blk_seg, blk_off = active_blocks(self._blk_full[0], self._blk_full[1], [e.name not in nograd for e in self._segs])
+        self._blk_prev = (self._blk_seg, self._blk_off)      # an overlapped update of the last step may still be reading them
+        self._blk_seg, self._blk_off = blk_seg.to(dev), blk_off.to(dev)
+        self._index_optional(blk_seg)
+        self._seg_blocks = None                      # the overlap plan and launch groups are cut from the block table
+        self._groups_key = None
+        self._clip = None
+
     def covers_every_gradient(self):
         """Does this optimizer update every tensor that receives a gradient?  (One built over a parameter subset leaves the rest to
         somebody who reads ``.grad``.)"""
-        return len(self._segs) == len(self._used)
+        nograd = getattr(self.core, "tensors_without_grad", ())
+        return all(e.name in self._group_of or e.name in nograd for e in self._used)
 
     def set_early(self, on=True):
         """Overlap the update with the rest of backward (needs ``overlap``); see ``early`` above."""
@@ -157,6 +193,8 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _launch(self, b0, b1, inv_scale, stream, max_workgroups=0):
         core, g0 = self.core, self.param_groups[0]
+        if b1 <= b0:                 # nothing in this range has a gradient
+            return
         frozen = [] if getattr(core, "optional_grads_live", True) else [e for lo, hi, e in self._opt_blocks if lo < b1 and hi > b0]
         if frozen:               # areas_emp without a gradient: its weights, moments and shadow are put back behind the update
             side = torch.cuda.ExternalStream(stream, device=core.flat_params.device)
@@ -296,16 +334,12 @@ class FusedAdamW(torch.optim.Optimizer):
             return False
         import bisect
         blk_seg = self._blk_seg.cpu().tolist()
-        first_blk = {}
-        for i, sgi in enumerate(blk_seg):
-            first_blk.setdefault(sgi, i)
         offs = [e.offset for e in self._segs]
         self._seg_blocks = []
         for lo, hi in eng.segments:
             s0, s1 = bisect.bisect_left(offs, lo), bisect.bisect_left(offs, hi)
-            b0 = first_blk[s0] if s0 < len(offs) and s0 in first_blk else len(blk_seg)
-            b1 = first_blk[s1] if s1 < len(offs) and s1 in first_blk else len(blk_seg)
-            self._seg_blocks.append((b0, b1))
+            # blocks are in segment order: the first block of the first segment >= s that has any (segments without gradient have none)
+            self._seg_blocks.append((bisect.bisect_left(blk_seg, s0), bisect.bisect_left(blk_seg, s1)))
         covered = sum(b1 - b0 for b0, b1 in self._seg_blocks)
         if covered != len(blk_seg):
             raise RuntimeError("optimizer overlap plan does not cover every block (%d of %d)" % (covered, len(blk_seg)))
@@ -339,6 +373,7 @@ class FusedAdamW(torch.optim.Optimizer):
         loss = closure() if closure is not None else None
         core = self.core
         self._follow_device()
+        self._sync_active()
         amp = self._amp_begin()
         if not amp:
             self._step += 1
@@ -455,6 +490,7 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("clip_grad_norm_: in early mode the update of a segment starts before the last gradient exists, so a "
                                "global norm cannot be applied; call set_early(False)")
         self._follow_device()
+        self._sync_active()
         core = self.core
         src = self._grad_buffer()
         if in_place and src is not core.flat_grads:

@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <functional>
 #include <vector>
 
@@ -71,11 +72,13 @@ extern "C" int crct_gemm_bf16(const CrctGemmArgs* a, crct_stream_t stream) {
 }
 
 // target_wgs < 0: the library's default (crct_gemm_group_target_workgroups)
-static int gemm_grouped_checked(const CrctGemmArgs* a, int n, crct_stream_t stream, int target_wgs) {
+// keep: NULL, or one flag per problem -- only the flagged ones are launched, as members of the group all n would have formed
+static int gemm_grouped_checked(const CrctGemmArgs* a, int n, crct_stream_t stream, int target_wgs, const uint8_t* keep = nullptr) {
   CRCT_REQUIRE(a != nullptr && n >= 1, "gemm_grouped: bad arguments");
   for (int i = 0; i < n; ++i)
     if (int r = gemm_check(a[i], "gemm_grouped", i)) return r;
-  if (target_wgs < 0) CRCT_CHECK_HIP(crct_gemm_launch_grouped(a, n, (hipStream_t)stream));
+  if (keep) CRCT_CHECK_HIP(crct_gemm_launch_grouped_keep(a, n, keep, (hipStream_t)stream, target_wgs < 0 ? 0 : target_wgs));
+  else if (target_wgs < 0) CRCT_CHECK_HIP(crct_gemm_launch_grouped(a, n, (hipStream_t)stream));
   else CRCT_CHECK_HIP(crct_gemm_launch_grouped_wgs(a, n, (hipStream_t)stream, target_wgs));
   return 0;
 }
@@ -99,7 +102,7 @@ struct Arena {
 struct Drop { uint32_t thr = 0; float scale = 1.f; uint32_t site = 0; };
 
 // ---- parameter offsets (elements into the flat buffers)
-struct LinearP { int64_t w = -1, b = -1; int in = 0, out = 0; int site = 0; };
+struct LinearP { int64_t w = -1, b = -1; int in = 0, out = 0; int site = 0; int parts = 1; };      // parts: 3 for a fused QKV (three tensors back to back)
 struct LnP { int64_t g = -1, b = -1; };
 struct FfnP { LinearP up, down; LnP ln; };
 struct ProjP { LinearP dense; LnP ln; };      // LN(dropout(dense(ctx)) + residual)
@@ -133,6 +136,9 @@ struct StreamScratch { size_t dy[2], dres_a, dlin_a, dres_b, dlin_b, gc, du, dct
 struct Step { char kind; int idx; };
 struct StepIn { Act t, v; };      // the two hidden states a schedule step starts from
 struct Tap { std::string name; size_t off; char stream; };
+// What one backward segment does (crct_engine_backward_plan): whether it runs, whether the gradients of its text / visual
+// input are produced (the embedding segment: whether that stream's half runs), how many weight-gradient GEMMs it leaves out
+struct SegPlan { bool runs = true, dx_t = true, dx_v = true; int dropped = 0; };
 
 }  // namespace
 
@@ -200,6 +206,23 @@ struct crct_engine {
   std::unordered_map<int64_t, int64_t> wgrad_owned;
   std::unordered_map<int64_t, int> wgrad_pass;
   void wgrad_pass_begin() { wgrad_pass.clear(); }
+  // tensors without gradient (crct_engine_set_trainable): their flat offsets, and what backward leaves out because of them.  Empty
+  // set = every tensor has a gradient: the plan is all-true and no launch or event differs.
+  std::vector<int64_t> param_off;      // offsets in the order given to crct_engine_create*
+  std::unordered_set<int64_t> nograd;
+  std::vector<SegPlan> plan;           // per backward segment
+  bool grad_at(int64_t o) const { return nograd.empty() || !nograd.count(o); }
+  bool w_grad(const LinearP& l) const {
+    for (int k = 0; k < l.parts; ++k) if (grad_at(l.w + k * ((int64_t)l.in * l.out / l.parts))) return true;
+    return false;
+  }
+  bool b_grad(const LinearP& l) const {
+    for (int k = 0; k < l.parts; ++k) if (grad_at(l.b + k * (l.out / l.parts))) return true;
+    return false;
+  }
+  // The Linear rule: the weight-gradient GEMM of a Linear inside a running step is left out only when its weight has no gradient and
+  // no bias gradient rides on that GEMM (with_bias: QKV and FFN-up, whose bias sums come out of the GEMM's rowsum_out)
+  bool drops_wgrad(const LinearP& l, bool with_bias) const { return !nograd.empty() && !w_grad(l) && !(with_bias && b_grad(l)); }
   std::vector<Tap> taps;
   std::vector<StepIn> in;            // in[i]: the hidden states schedule step i starts from; in[sched.size()]: the encoder's outputs
   int cur_t = 0, cur_v = 0;          // ping-pong index of the running activation gradients
@@ -224,6 +247,7 @@ LnP ln_p(crct_engine* e, const std::string& name) {
 // three Linear(in, out) stored back to back -> one Linear(in, 3*out)
 LinearP fused3(crct_engine* e, const std::string& a, const std::string& b, const std::string& c, int in, int out, int site) {
   LinearP l = linear_p(e, a, in, 3 * out, site);
+  l.parts = 3;
   const int64_t wsz = (int64_t)in * out;
   if (e->P(b + ".weight") != l.w + wsz || e->P(c + ".weight") != l.w + 2 * wsz || e->P(b + ".bias") != l.b + out ||
       e->P(c + ".bias") != l.b + 2 * out) {
@@ -506,14 +530,16 @@ struct Run {
   // the bf16 dy.
   void lin_wgrad(const void* dy, int64_t lddy, const void* x, int64_t ldx, const LinearP& l, int M, bool with_bias = false, const WgQ8& w8 = WgQ8()) {
     if (rc) return;
+    const bool keep = !e->drops_wgrad(l, with_bias);      // a dropped GEMM keeps its place in the layer's group (flush_wgrads)
+    if (!keep && !defer_wgrad) return;
     const bool f8w = f8b() == 1 && c->fp8_wgrad && defer_wgrad && f8_lin(l) && w8.dy.site >= 0 && w8.x.site >= 0 &&
                      l.in % 16 == 0 && l.out % 16 == 0 && lddy % 16 == 0 && ldx % 16 == 0;
     const bool fold = !f8w && with_bias && M % 64 == 0 && l.in % 8 == 0 && l.out % 8 == 0 && lddy % 8 == 0 && ldx % 8 == 0;
-    if (with_bias && !fold) bias_grad(dy, lddy, l, M);
+    if (with_bias && !fold && keep) bias_grad(dy, lddy, l, M);
     if (rc) return;
     Opt o; o.f32 = true; o.acc = true;
     CrctGemmArgs g = gemm_args(WGRAD, l, M, dy, lddy, x, ldx, G(l.w), l.in, o, f8w ? q8(w8.dy) : Q8(), f8w ? q8(w8.x) : Q8());
-    if (c->wgrad_overwrite && e->wgrad_owned.count(l.w)) {
+    if (keep && c->wgrad_overwrite && e->wgrad_owned.count(l.w)) {
       if (++e->wgrad_pass[l.w] > 1) { rc = 1; crct_set_error("engine_backward: weight gradient at offset %lld is produced twice in one pass but is listed as owned", (long long)l.w); return; }
       g.accumulate = 0;               // the only producer of this gradient: write it, whatever the buffer held
       if (c->grads_bf16) {            // ... straight into the exchange's bf16 buffer (CrctStepCfg.grads_bf16): the caller packs none of the owned gradients
@@ -523,6 +549,7 @@ struct Run {
     }
     if (fold) g.rowsum_out = G(l.b);
     if (f8w) {
+      if (!keep) return;                                  // (a weight with an e4m3 shadow and no gradient is refused by the caller)
       if (g.tile != 36) g.tile = 37;                      // 2 stages (two workgroups per CU) unless the site policy asks for 3
       pending_f8.push_back(g);
       return;
@@ -531,11 +558,16 @@ struct Run {
     // queued also without a side stream (sw == s): the same groups, hence the same kernels and summation orders,
     // in every stream mode -- results stay bit-identical across modes
     pending.push_back(g);
+    pending_keep.push_back(keep);
     if (pending.size() == 8) flush_wgrads();
   }
   // launch the queued weight-gradient GEMMs on the side stream, ordered after everything enqueued on s so far
   std::vector<CrctGemmArgs> pending_f8;      // the layer's fp8 weight gradients: one grouped launch of their own
+  // pending[i] is launched iff pending_keep[i]: a GEMM the Linear rule drops stays in the list, so that the groups are cut at the
+  // same places and take the configuration and the kernel they would have had with it (crct_gemm_launch_grouped_keep)
+  std::vector<uint8_t> pending_keep;
   void flush_wgrads() {
+    if (!pending.empty() && std::find(pending_keep.begin(), pending_keep.end(), 1) == pending_keep.end()) { pending.clear(); pending_keep.clear(); }
     if (rc || (pending.empty() && pending_f8.empty() && pending_fin.empty() && pending_bias.empty())) return;
     if (sw == s) ++tick;
     wgrad_after_main();
@@ -552,9 +584,11 @@ struct Run {
     const int target = (sw != s && !pending.empty() && pending[0].K <= e->wgrad_target_rows && !e->one_wgrad_stream) ? e->wgrad_target : 0;
     for (size_t i = 0; i < pending.size() && !rc; i += 8) {
       const int ng = (int)std::min<size_t>(8, pending.size() - i);
-      fail(gemm_grouped_checked(pending.data() + i, ng, sw, target));
+      const uint8_t* kp = pending_keep.data() + i;
+      fail(gemm_grouped_checked(pending.data() + i, ng, sw, target, std::find(kp, kp + ng, 0) == kp + ng ? nullptr : kp));
     }
     pending.clear();
+    pending_keep.clear();
     for (size_t i = 0; i < pending_f8.size() && !rc; i += 8)
       fail(crct_gemm_bf16_grouped(pending_f8.data() + i, (int)std::min<size_t>(8, pending_f8.size() - i), sw));
     pending_f8.clear();
@@ -696,7 +730,8 @@ struct Run {
     ffn_fwd(p.ffn, a.ffn, a.proj.out(), M, drop(p.p_hid, p.site + 2));
   }
   // x: the layer input (its e4m3 copy serves the fp8 weight gradient of the QKV projection); g: grad of the output, gx: of x
-  void self_bwd(const SelfLayerP& p, const SelfLayerA& a, const Act& x, size_t g, size_t gx, const uint8_t* km, int B, int T) {
+  // dx = false (the lowest running step of its stream, SegPlan): gx has no reader and the launch that only produces it is not issued
+  void self_bwd(const SelfLayerP& p, const SelfLayerA& a, const Act& x, size_t g, size_t gx, const uint8_t* km, int B, int T, bool dx = true) {
     const int M = B * T, H = p.H, d = H / p.heads;
     const StreamScratch& sc = layer_begin();
     ffn_bwd(p.ffn, a.ffn, a.proj.out(), g, sc.gc, sc, M, drop(p.p_hid, p.site + 2));
@@ -710,7 +745,7 @@ struct Run {
              gq ? dq8 + 2 * H : nullptr, a.g_dqkv, a.lse, A(a.ctx), H);
     lin_wgrad(A(sc.dqkv), 3 * H, A(x.x), H, p.qkv, M, true, WgQ8{dqkvq, x});
     Opt o; o.addend = A(sc.dres_b); o.ld_add = H;
-    lin_dgrad(A(sc.dqkv), 3 * H, p.qkv, M, A(gx), H, o, dqkvq);
+    if (dx) lin_dgrad(A(sc.dqkv), 3 * H, p.qkv, M, A(gx), H, o, dqkvq);
     layer_end();
   }
 
@@ -737,8 +772,9 @@ struct Run {
     ffn_fwd(p.ffn_t, a.ffn_t, a.proj_t.out(), Mt, drop(D.p_hidden, p.site + 5));
   }
   // x: the two layer inputs (their e4m3 copies serve the fp8 weight gradients of the QKV projections); gv / gt: grads of the two
-  // outputs, gxv / gxt: of the inputs
-  void conn_bwd(Run& V, const ConnLayerP& p, const ConnLayerA& a, const StepIn& x, size_t gv, size_t gt, size_t gxv, size_t gxt) {
+  // outputs, gxv / gxt: of the inputs (dxv / dxt = false: not produced, as in self_bwd)
+  void conn_bwd(Run& V, const ConnLayerP& p, const ConnLayerA& a, const StepIn& x, size_t gv, size_t gt, size_t gxv, size_t gxt,
+                bool dxv = true, bool dxt = true) {
     const CrctModelDims& D = e->d;
     hipEvent_t free_v = V.set_free[V.parity], free_t = set_free[parity];      // "the last readers of this scratch set are done"
     const StreamScratch& sv = V.layer_begin(); const StreamScratch& st = layer_begin();
@@ -775,10 +811,10 @@ struct Run {
     cross_sync(V);
     V.lin_wgrad(A(sv.dqkv), 3 * Hb, A(x.v.x), D.Hv, p.qkv1, Mv, true, WgQ8{dqkvq_v, x.v});
     Opt ov; ov.addend = A(sv.dres_b); ov.ld_add = D.Hv;
-    V.lin_dgrad(A(sv.dqkv), 3 * Hb, p.qkv1, Mv, A(gxv), D.Hv, ov, dqkvq_v);
+    if (dxv) V.lin_dgrad(A(sv.dqkv), 3 * Hb, p.qkv1, Mv, A(gxv), D.Hv, ov, dqkvq_v);
     lin_wgrad(A(st.dqkv), 3 * Hb, A(x.t.x), D.H, p.qkv2, Mt, true, WgQ8{dqkvq_t, x.t});
     Opt ot; ot.addend = A(st.dres_b); ot.ld_add = D.H;
-    lin_dgrad(A(st.dqkv), 3 * Hb, p.qkv2, Mt, A(gxt), D.H, ot, dqkvq_t);
+    if (dxt) lin_dgrad(A(st.dqkv), 3 * Hb, p.qkv2, Mt, A(gxt), D.H, ot, dqkvq_t);
     V.layer_end();
     layer_end();
   }
@@ -820,7 +856,7 @@ struct Run {
     layer_begin();
     ++tick;
     if (!rc) fail(crct_embed_text_bwd_indexed(A(gt), A(e->eta.sum), F(e->eta.mean), F(e->eta.rstd), b->tokens, b->segments, b->loc,
-                                              P(e->et.ln.g), G(e->et.word), G(e->et.pos), G(e->et.type), G(e->et.wloc), G(e->et.bloc),
+                                              P(e->et.ln.g), e->grad_at(e->et.word) ? G(e->et.word) : nullptr, G(e->et.pos), G(e->et.type), G(e->et.wloc), G(e->et.bloc),
                                               G(e->et.ln.g), G(e->et.ln.b), F(partials), b->B, b->T, D.H, D.n_pos, dt.thr, dt.scale,
                                               dt.site, c->seed, F(e->embed_rows[0]), W<int32_t>(e->embed_idx[0]), D.n_types, e->word_index,
                                               D.vocab, s));
@@ -999,6 +1035,62 @@ int check_batch(const crct_engine* e, const CrctBatch* b) {
   return 0;
 }
 
+// The backward plan, derived from the schedule and the set of tensors without gradient -- the one place the rules live:
+//  * a schedule step runs iff a tensor with gradient lies in it or below it in the forward graph on a stream it touches (a
+//    co-attention step touches both; the embeddings are the bottom step of their stream);
+//  * the gradient of a step's text / visual input is produced iff something with gradient lies below that input;
+//  * the last segment holds both embeddings: each half follows its own stream;
+//  * `dropped`: the weight-gradient GEMMs a running segment leaves out (crct_engine::drops_wgrad).
+void replan(crct_engine* e) {
+  const size_t nseg = e->sched.size() + 2;
+  e->plan.assign(nseg, SegPlan());
+  if (e->nograd.empty()) return;
+  auto lin = [&](const LinearP& l) { return e->w_grad(l) || e->b_grad(l); };
+  auto ln = [&](const LnP& l) { return e->grad_at(l.g) || e->grad_at(l.b); };
+  auto proj = [&](const ProjP& p) { return lin(p.dense) || ln(p.ln); };
+  auto ffn = [&](const FfnP& p) { return lin(p.up) || lin(p.down) || ln(p.ln); };
+  auto drops = [&](const LinearP& l, bool with_bias) { return e->drops_wgrad(l, with_bias) ? 1 : 0; };
+  auto self_drops = [&](const SelfLayerP& l) { return drops(l.qkv, true) + drops(l.proj.dense, false) + drops(l.ffn.up, true) + drops(l.ffn.down, false); };
+  bool below_t = e->grad_at(e->et.word) || e->grad_at(e->et.pos) || e->grad_at(e->et.type) || e->grad_at(e->et.wloc) ||
+                 e->grad_at(e->et.bloc) || ln(e->et.ln);
+  bool below_v = (e->feat ? lin(e->ev.img) : lin(e->ev.areas)) || e->grad_at(e->ev.color) || e->grad_at(e->ev.wloc) ||
+                 e->grad_at(e->ev.bloc) || ln(e->ev.ln);
+  SegPlan& emb = e->plan[nseg - 1];
+  emb.runs = below_t || below_v; emb.dx_t = below_t; emb.dx_v = below_v;
+  emb.dropped = (e->feat && below_v) ? drops(e->ev.img, false) : 0;
+  for (size_t i = 0; i < e->sched.size(); ++i) {
+    const Step& st = e->sched[i];
+    SegPlan& pl = e->plan[e->sched.size() - i];
+    pl.dx_t = below_t; pl.dx_v = below_v;
+    if (st.kind == 't' || st.kind == 'v') {
+      const SelfLayerP& l = st.kind == 't' ? e->tl[st.idx] : e->vl[st.idx];
+      bool& below = st.kind == 't' ? below_t : below_v;
+      pl.runs = below || lin(l.qkv) || proj(l.proj) || ffn(l.ffn);
+      pl.dropped = pl.runs ? self_drops(l) : 0;
+      below = pl.runs;
+    } else {
+      const ConnLayerP& l = e->cl[st.idx];
+      pl.runs = below_t || below_v || lin(l.qkv1) || lin(l.qkv2) || proj(l.proj_v) || proj(l.proj_t) || ffn(l.ffn_v) || ffn(l.ffn_t);
+      pl.dropped = !pl.runs ? 0 : drops(l.qkv1, true) + drops(l.qkv2, true) + drops(l.proj_v.dense, false) + drops(l.proj_t.dense, false) +
+                                    drops(l.ffn_v.up, true) + drops(l.ffn_v.down, false) + drops(l.ffn_t.up, true) + drops(l.ffn_t.down, false);
+      below_t = below_v = pl.runs;
+    }
+    if (!pl.runs) pl.dx_t = pl.dx_v = false;
+  }
+  // heads: both input gradients are the running activation gradients the encoder's backward starts from
+  SegPlan& hd = e->plan[0];
+  const bool reg = e->var.regressor != CRCT_REGRESSOR_NONE;
+  bool own = lin(e->t_pool) || lin(e->v_pool) || lin(e->cls);
+  int dropped = drops(e->t_pool, false) + drops(e->v_pool, false);
+  for (int j = 0; j < 4 && reg; ++j) {
+    own = own || lin(e->tp[j]) || lin(e->vp[j]) || lin(e->fu[j]);
+    dropped += drops(e->tp[j], false) + drops(e->vp[j], false) + (j < 3 ? drops(e->fu[j], false) : 0);      // fusion.6: the head kernel's
+  }
+  hd.runs = own || below_t || below_v;
+  hd.dx_t = hd.runs && below_t; hd.dx_v = hd.runs && below_v;
+  hd.dropped = hd.runs ? dropped : 0;
+}
+
 }  // namespace
 
 // =================================================================================== C ABI
@@ -1027,6 +1119,7 @@ extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, 
       const char* q = strchr(p, '\n');
       std::string k = q ? std::string(p, q - p) : std::string(p);
       e->off[k] = offsets[i]; e->size[k] = sizes[i];
+      e->param_off.push_back(offsets[i]);
       if (!q) break;
       p = q + 1;
     }
@@ -1230,6 +1323,7 @@ extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, 
     e->seg_range.push_back(range_of({std::string(buf)}));
   }
   e->seg_range.push_back(range_of({"bert.embeddings.", "bert.v_embeddings."}));
+  replan(e);
   return e;
 }
 
@@ -1242,6 +1336,25 @@ extern "C" int crct_engine_set_areas(crct_engine_t* e, const float* areas) {
   CRCT_REQUIRE(!areas || !e->feat, "engine_set_areas: the 'plotqa' image embeddings have no areas term (vilbert.py:1463-1465)");
   e->areas = areas;
   return 0;
+}
+
+extern "C" int crct_engine_set_trainable(crct_engine_t* e, const uint8_t* flags, int n) {
+  CRCT_REQUIRE(e, "engine_set_trainable: null engine");
+  CRCT_REQUIRE(!flags || n == (int)e->param_off.size(), "engine_set_trainable: %d flags for %d parameters", n, (int)e->param_off.size());
+  e->nograd.clear();
+  for (int i = 0; flags && i < n; ++i)
+    if (!flags[i]) e->nograd.insert(e->param_off[i]);
+  replan(e);
+  return 0;
+}
+extern "C" int crct_engine_backward_plan(const crct_engine_t* e, int32_t* plan, int cap_segments) {
+  if (!e) return -1;
+  const int n = (int)e->plan.size();
+  for (int i = 0; plan && i < n && i < cap_segments; ++i) {
+    const SegPlan& p = e->plan[i];
+    plan[4 * i] = p.runs; plan[4 * i + 1] = p.dx_t; plan[4 * i + 2] = p.dx_v; plan[4 * i + 3] = p.dropped;
+  }
+  return n;
 }
 
 extern "C" void crct_engine_destroy(crct_engine_t* e) {
@@ -1400,6 +1513,7 @@ extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, c
   const int s0 = seg < 0 ? 0 : seg, s1 = seg < 0 ? nseg : seg + 1;
   CRCT_REQUIRE(s1 <= nseg, "engine_backward: bad segment %d", seg);
   if (s0 == 0) e->wgrad_pass_begin();
+  if (seg >= 0 && !e->plan[seg].runs) return 0;          // nothing in or below this segment has a gradient: no launch, no event
   if (int r = reset_tickets(e, workspace, (hipStream_t)stream)) return r;
   // fork: every internal stream starts after the caller's prior work (previous segment, optimizer, ...)
   Rv.fail(order_streams(e, Rt.s, Rv.s));
@@ -1408,19 +1522,22 @@ extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, c
     const bool in_sched = sgi != 0 && sgi != nseg - 1;
     const size_t si = in_sched ? e->sched.size() - (size_t)sgi : 0;
     Rt.phase = (in_sched && (e->first_conn < 0 || (int)si < e->first_conn)) ? 0 : 1;      // backward tail through the text-only layers
-    if (sgi == 0) {
+    const SegPlan& pl = e->plan[sgi];
+    if (!pl.runs) {
+      // not run; its events below are still recorded, so a caller waiting on them never sees the previous pass's
+    } else if (sgi == 0) {
       e->cur_t = 0; e->cur_v = 0;
       Rt.heads_bwd(Rv, e->in.back().t.x, e->in.back().v.x, e->st.dy[0], e->sv.dy[0], logits, reg, stats);
     } else if (sgi == nseg - 1) {
-      Rt.embed_text_bwd(e->st.dy[e->cur_t]);
-      Rv.embed_image_bwd(e->sv.dy[e->cur_v]);
+      if (pl.dx_t) Rt.embed_text_bwd(e->st.dy[e->cur_t]);
+      if (pl.dx_v) Rv.embed_image_bwd(e->sv.dy[e->cur_v]);
     } else {
       const Step& st = e->sched[si];
       const StepIn& x = e->in[si];
       const size_t gt = e->st.dy[e->cur_t], gxt = e->st.dy[e->cur_t ^ 1], gv = e->sv.dy[e->cur_v], gxv = e->sv.dy[e->cur_v ^ 1];
-      if (st.kind == 't') Rt.self_bwd(e->tl[st.idx], e->tla[st.idx], x.t, gt, gxt, batch->text_keymask, batch->B, batch->T);
-      else if (st.kind == 'v') Rv.self_bwd(e->vl[st.idx], e->vla[st.idx], x.v, gv, gxv, batch->image_keymask, batch->B, batch->V);
-      else Rt.conn_bwd(Rv, e->cl[st.idx], e->cla[st.idx], x, gv, gt, gxv, gxt);
+      if (st.kind == 't') Rt.self_bwd(e->tl[st.idx], e->tla[st.idx], x.t, gt, gxt, batch->text_keymask, batch->B, batch->T, pl.dx_t);
+      else if (st.kind == 'v') Rv.self_bwd(e->vl[st.idx], e->vla[st.idx], x.v, gv, gxv, batch->image_keymask, batch->B, batch->V, pl.dx_v);
+      else Rt.conn_bwd(Rv, e->cl[st.idx], e->cla[st.idx], x, gv, gt, gxv, gxt, pl.dx_v, pl.dx_t);
       if (st.kind != 'v') e->cur_t ^= 1;
       if (st.kind != 't') e->cur_v ^= 1;
     }

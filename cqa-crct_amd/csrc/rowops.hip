@@ -1021,7 +1021,7 @@ __global__ __launch_bounds__(256) void embed_text_bwd_kernel(
     row_load_bf16(x, sum_p + row * H, H, lane);
     row_apply_dropmask(dy, H, lane, row, thr, scale, site, seed);
     row_ln_bwd(dy, x, gamma, H, lane, mean_p[row], rstd_p[row], adg, adb);
-    if (!rows_scratch) row_atomic_add(dy, d_word + ids[row] * (long)H, H, lane);     // fall-back only: see word_scatter_indexed_body
+    if (!rows_scratch && d_word) row_atomic_add(dy, d_word + ids[row] * (long)H, H, lane);     // fall-back only: see word_scatter_indexed_body
     int pid = -1;
     if (qa) {
       const int fq = first_qa_index(segs + (long)b * T, T, lane);
@@ -1598,8 +1598,9 @@ extern "C" int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved
   hipStream_t s = (hipStream_t)stream;
   if (!idx_scratch || M > GATHER_MAX_ROWS || n_types <= 0) rows_scratch = nullptr;      // atomics fall-back
   const int nb = embed_bwd_blocks(M);
-  int* w_first = rows_scratch ? word_index : nullptr;     // first / last row per id, zero on entry and on exit
-  int* w_last = rows_scratch ? word_index + n_vocab : nullptr;
+  // d_word == NULL (the word table has no gradient): no index fill, no word workgroups; every other output keeps its bits
+  int* w_first = rows_scratch && d_word ? word_index : nullptr;     // first / last row per id, zero on entry and on exit
+  int* w_last = rows_scratch && d_word ? word_index + n_vocab : nullptr;
   const int type_partials = rows_scratch && n_types >= 2 && d_type;     // partials then hold 9 row sets
   DISPATCH_NCH(H, crct_launch((embed_text_bwd_kernel<NCH>), dim3(nb), dim3(256), 0, s, (const bf16_t*)dy,
                                      (const bf16_t*)sum_saved, mean, rstd, ids, segs, loc, gamma, d_word, d_pos, d_type,
@@ -1615,7 +1616,7 @@ extern "C" int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved
       crct_launch(gather_sum_kernel, dim3(n_gather), dim3(256), (size_t)M * sizeof(int), s,
                          rows_scratch, idx_scratch, (int)M, H, d_pos, used_pos, idx_scratch + M, d_type);
       CRCT_CHECK_HIP(hipGetLastError());
-      DISPATCH_NCH(H, {
+      if (d_word) DISPATCH_NCH(H, {
         CRCT_CHECK_HIP(crct_lds_limit(&word_scatter_kernel<NCH>, word_lds > 64 * 1024 ? 152 * 1024 : word_lds));
         crct_launch((word_scatter_kernel<NCH>), dim3((int)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), word_lds, s,
                            (const float*)rows_scratch, ids, (int)M, H, d_word, w_first, w_last);
@@ -1625,7 +1626,7 @@ extern "C" int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved
     DISPATCH_NCH(H, {
       // a heavy id's match list (M ints) + 4 partial rows: above 64 KiB from ~12 300 rows on at H = 1024
       CRCT_CHECK_HIP(crct_lds_limit(&embed_scatter_kernel<NCH>, word_lds > 64 * 1024 ? 152 * 1024 : word_lds));
-      crct_launch((embed_scatter_kernel<NCH>), dim3(n_gather + (int)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), word_lds, s,
+      crct_launch((embed_scatter_kernel<NCH>), dim3(n_gather + (d_word ? (int)((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK) : 0)), dim3(256), word_lds, s,
                          (const float*)rows_scratch, idx_scratch, (int)M, H, d_pos, used_pos, idx_scratch + M, d_type, n_gather, ids, d_word,
                          w_first, w_last);
     });

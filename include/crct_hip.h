@@ -377,7 +377,8 @@ int crct_embed_text_fwd(const int64_t* ids, const int64_t* segs, const float* lo
  * word_index = int32 [2][n_vocab] in device memory, ALL ZERO on entry and all zero again on exit (the kernels clean up what they set);
  * required (non-NULL, n_vocab > 0) with rows_scratch and idx_scratch, or the call fails before any launch.  The row kernel leaves the
  * first and last token row of every id there; the word-table sums then let every wave that is not its id's first row return at once
- * and scan only [first, last] for the others. */
+ * and scan only [first, last] for the others.
+ * d_word == NULL: the word table has no gradient -- no index fill and no word-table sums; all other outputs keep their bits. */
 int crct_embed_text_bwd_indexed(const void* dy, const void* sum_saved, const float* mean, const float* rstd,
                                 const int64_t* ids, const int64_t* segs, const float* loc, const float* gamma,
                                 float* d_word, float* d_pos, float* d_type, float* d_wloc, float* d_bloc,
@@ -625,6 +626,19 @@ crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, const char*
 /* areas (fp32 [B][V], device) of the batch the next forward / backward calls run on; NULL = no areas term.  Forward and backward
  * of one batch must see the same value.  Variants DVQA / FIGUREQA only. */
 int crct_engine_set_areas(crct_engine_t*, const float* areas);
+/* Which parameters have a gradient in the backward passes that follow: one flag per parameter, in the order given to
+ * crct_engine_create* (n = n_params); 0 = the tensor is WITHOUT gradient.  NULL, or all flags set, is the behaviour without this
+ * call: not one launch or event differs.  Backward then runs less of itself (crct_engine_backward_plan); the forward is untouched.
+ * The ranges of tensors without gradient in grads_f32 are unspecified after a pass (mostly not written at all). */
+int crct_engine_set_trainable(crct_engine_t*, const uint8_t* flags, int n);
+/* What crct_engine_backward does per segment under the current flags: plan[4 * s + 0] = the segment runs (a segment that does not
+ * run issues no launch; its seg_done_events are still recorded and seg_enqueued still called); [1] / [2] = the gradient of its text /
+ * visual input is produced (last segment: the text / image embedding's half runs); [3] = how many weight-gradient GEMMs it leaves
+ * out.  A step runs iff a tensor with gradient lies in it or below it in the forward graph on a stream it touches; a Linear's
+ * weight-gradient GEMM is left out only when its weight has no gradient and no bias gradient is summed by that GEMM (the QKV and
+ * FFN-up biases are); every other gradient keeps its kernel, its group's configuration and its bits.  Returns the number of
+ * segments; fills at most cap_segments of them (plan may be NULL). */
+int crct_engine_backward_plan(const crct_engine_t*, int32_t* plan, int cap_segments);
 void crct_engine_destroy(crct_engine_t*);
 size_t crct_engine_workspace_bytes(const crct_engine_t*);
 int crct_engine_num_segments(const crct_engine_t*);
