@@ -1667,13 +1667,17 @@ extern "C" int crct_engine_set_site_policy(crct_engine_t* e, int site, int kind,
 extern "C" int64_t crct_engine_tap(crct_engine_t* e, const void* workspace, const char* name, int B, int T, int V, void* out,
                                    int64_t cap, crct_stream_t stream) {
   if (!e || !name) return -1;
+  auto copy = [&](const Tap& t) -> int64_t {
+    const int64_t n = t.stream == 't' ? (int64_t)B * T * e->d.H : (int64_t)B * V * e->d.Hv;
+    if (n > cap) { crct_set_error("tap: buffer too small"); return -1; }
+    if (hipMemcpyAsync(out, (const char*)workspace + t.off, (size_t)n * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return -1;
+    return n;
+  };
+  // the running hidden gradients, resolved at call time: the buffers the next backward segment reads
+  if (!strcmp(name, "grad.t")) return copy(Tap{name, e->st.dy[e->cur_t], 't'});
+  if (!strcmp(name, "grad.v")) return copy(Tap{name, e->sv.dy[e->cur_v], 'v'});
   for (const Tap& t : e->taps)
-    if (t.name == name) {
-      const int64_t n = t.stream == 't' ? (int64_t)B * T * e->d.H : (int64_t)B * V * e->d.Hv;
-      if (n > cap) { crct_set_error("tap: buffer too small"); return -1; }
-      if (hipMemcpyAsync(out, (const char*)workspace + t.off, (size_t)n * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return -1;
-      return n;
-    }
+    if (t.name == name) return copy(t);
   crct_set_error("tap: unknown activation '%s'", name);
   return -1;
 }

@@ -794,7 +794,11 @@ int crct_event_synchronize(void* ev);
 int crct_event_query(void* ev);      /* 1 = complete, 0 = not yet, < 0 = error */
 
 /* Debug taps: copy a named bf16 activation ("emb.t", "t3.t", "c0.v", "seq_t" ...) of the last
- * forward (batch B, T, V) into `out` (device, bf16); returns the element count or -1. */
+ * forward (batch B, T, V) into `out` (device, bf16); returns the element count or -1.
+ * "grad.t" / "grad.v": the running hidden gradients, shaped like "seq_t" / "seq_v" -- the bf16 buffers the NEXT backward segment
+ * reads, resolved at call time.  After segment 0 they hold the heads' gradient of seq_t / seq_v, after a layer's segment that
+ * layer's input gradient on the stream(s) it touched.  Valid only between the crct_engine_backward(seg >= 0) calls of one pass,
+ * and only where the segment's plan produced that gradient (crct_engine_backward_plan: dx_t / dx_v); anything else is stale. */
 int64_t crct_engine_tap(crct_engine_t*, const void* workspace, const char* name, int B, int T, int V,
                         void* out, int64_t cap, crct_stream_t stream);
 
