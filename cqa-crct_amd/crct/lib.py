@@ -126,6 +126,7 @@ PROTOTYPES = {
     "crct_gemm_group_target_workgroups": (C.c_int, [C.c_int]),
     "crct_gemm_group_concat": (C.c_int, [C.c_int]),
     "crct_embed_scatter_split": (None, [C.c_int]),
+    # 0 = off, 1 = every GEMM on the register-staged kernel, 2 = the LDS-DMA kernels with the generic epilogue instead of the epilogue classes
     "crct_gemm_force_generic": (C.c_int, [C.c_int]),
     "crct_prof_enable": (C.c_int, [C.c_int]),
     "crct_prof_reset": (C.c_int, []),

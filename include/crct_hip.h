@@ -140,8 +140,10 @@ int crct_gemm_fp8_scaled_mfma(int on);
 /* Tile the launcher would pick for an M x N output (0..3, see CrctGemmArgs.tile). */
 int crct_gemm_pick_tile(int M, int N);
 
-/* Test hook: on != 0 routes every GEMM through the register-staged kernel (any K % 8 == 0) instead of
- * the LDS-DMA pipelined kernel (K % 64 == 0), so the parity tests can cover both code paths. */
+/* Test hook.  on = 1 (or any value but 0 and 2) routes every GEMM through the register-staged kernel (any K % 8 == 0) instead of
+ * the LDS-DMA pipelined kernel (K % 64 == 0), so the parity tests can cover both code paths.  on = 2 keeps the LDS-DMA kernels --
+ * same configurations, split-K and grouping -- and runs every one of them with the generic epilogue instead of its epilogue class
+ * (gemm.hip, epilogue_class): the class kernels are bitwise checked against it.  on = 0: neither. */
 int crct_gemm_force_generic(int on);
 
 /* Live measurement for bench.py: when enabled, every GEMM launch is bracketed by HIP events on its
