@@ -10,8 +10,12 @@ value is within 5 % (or within the chart's tick tolerance).
 What is different from the reference is only HOW: the reference walks the questions in a Python loop with one
 ``.item()`` host sync each (:281-292) and moves every intermediate to the CPU; here the selection is one HIP launch
 (``crct_eval_select``, one wave per question) and all flags / tables stay on the device until the caller reads them.
+``evaluate`` is the loop for every dataset (PlotQA, DVQA, and FigureQA's ``binary_answers`` branch :280-285): there the
+selection, the flags and the three tables of a batch are one launch together (``crct_eval_score``).
 Logging, CSV dumps and plots of the reference are not rebuilt.
 """
+import ctypes
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -151,34 +155,112 @@ def reduce_breakdown_table(get_ans_type, group, params, breakdown_tensor, batch,
     return breakdown_tensor
 
 
-def plotqa_evaluate(dataloader, dataset, params, eval_batch_size, dialog_encoder, group=None, with_histogram=True):
-    """The evaluation loop (evaluation.py:199-386 without logging / CSV / plots).
-    ``dataset`` needs ``get_ans_type(qa_id)`` (fig_dataloader.py:704-…) and may provide ``cut_batch_padding``.
-    Returns (total_correct_tensor [6, 2], breakdown_tensor [5, 4, 3, 3], histogram [13]) on the device."""
+def question_categories(batch, get_ans_type):
+    """The breakdown indices of a batch's questions (evaluation.py:471-474) as one host int32 [Q, 3] tensor: figure kind 1..4
+    (FIG_INDEX), answer kind (``get_ans_type``), question category (``get_qcat_by_qid``).  Unknown figure kinds become -1 and
+    are counted by the kernel as errors."""
+    ids = batch["id"].reshape(-1).tolist()
+    rows = [[FIG_INDEX.get(t, -1), int(get_ans_type(i)), get_qcat_by_qid(q)[1]] for i, q, t in zip(ids, batch["qid"], batch["qa_type"])]
+    return torch.tensor(rows, dtype=torch.int32).reshape(len(ids), 3)
+
+
+def score_batch(nsp_scores, reg_out, reg_err, reg_terr, batch, tables, binary=False, forced=None, cats=None, with_histogram=False,
+                want_prob0=False):
+    """Selection, flags and tables of one batch as ONE launch (``crct_eval_score``; evaluation.py:280-311, :465-543).
+    ``tables`` (int64 [lib.EVAL_TABLE_WORDS], on the device) is added into in place.  ``cats``: int32 [Q, 3] from
+    ``question_categories`` (host or device; one copy) or None for no breakdown.  The regression rows may be None with
+    ``binary``.  Returns (answers [Q] int64, sel_out, sel_err, sel_terr [Q] fp32, flags [Q] uint8, prob0 [N] or None)."""
+    dev = nsp_scores.device
+    if dev.type != "cuda":
+        raise RuntimeError("score_batch runs on an MI355X only (no CPU fallback)")
+    if tables.device != dev or tables.dtype != torch.int64 or tables.numel() != L.EVAL_TABLE_WORDS or not tables.is_contiguous():
+        raise ValueError("score_batch: tables must be a contiguous int64 [%d] tensor on %s" % (L.EVAL_TABLE_WORDS, dev))
+    i64 = lambda t: None if t is None else t.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()      # noqa: E731
+    f32 = lambda t: None if t is None else t.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()    # noqa: E731
+    logits = nsp_scores.to(torch.float32).contiguous()
+    N = logits.shape[0]
+    gt_id = i64(batch["gt_id"])
+    Q = gt_id.numel()
+    keep = [logits, gt_id, f32(reg_out), f32(reg_err), f32(reg_terr),
+            i64(batch["next_sentence_labels"]) if binary else None, None if binary else i64(batch["num_ans"]), i64(forced),
+            batch["needs_reg"].reshape(-1).to(device=dev, dtype=torch.uint8).contiguous(), f32(batch["tolerance_margin"]),
+            None if cats is None else cats.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()]
+    answers = torch.empty(Q, dtype=torch.int64, device=dev)
+    so, se, st = (torch.empty(Q, device=dev) for _ in range(3))
+    flags = torch.empty(Q, dtype=torch.uint8, device=dev)
+    p0 = torch.empty(N, device=dev) if want_prob0 else None
+    a = L.EvalScoreArgs()
+    (a.logits, a.gt_id, a.reg_out, a.reg_err, a.reg_terr, a.labels, a.num_ans, a.forced, a.needs_reg, a.tolerance,
+     a.cats) = (L.ptr(t) for t in keep)
+    a.answers, a.sel_out, a.sel_err, a.sel_terr, a.flags, a.prob0, a.tables = (L.ptr(t) for t in (answers, so, se, st, flags, p0, tables))
+    a.N, a.Q, a.mode, a.with_histogram = N, Q, 1 if binary else 0, 1 if with_histogram else 0
+    L.check(L.load().crct_eval_score(ctypes.byref(a), L.current_stream()), "eval_score")
+    return answers, so, se, st, flags, p0
+
+
+def prediction_record(batch, answers, sel_out, sel_err, sel_terr):
+    """evaluation.py:316-321: [Q, 8] float64 rows (id, gt_id, answer, gt, regressed value, target, relative error, tick error) on the
+    device, NaN from column 3 on where the question needs no regression."""
+    dev = answers.device
+    col = lambda k: batch[k].reshape(-1).to(dev).to(torch.float64)               # noqa: E731
+    rec = torch.stack([col("id"), col("gt_id"), answers.double(), col("gt"), sel_out.double(), col("reg_target"), sel_err.double(), sel_terr.double()], 1)
+    rec[batch["needs_reg"].reshape(-1).to(dev).bool().logical_not(), 3:] = float("nan")
+    return rec
+
+
+def evaluate(dataloader, dataset, params, eval_batch_size, dialog_encoder, group=None, with_histogram=True, return_predictions=False):
+    """The evaluation loop of every dataset the model knows (evaluation.py:199-386 without logging / CSV / plots): candidate
+    rows for PlotQA and DVQA, ``params['binary_answers']`` (:280-285) for FigureQA, forced answers for '_REGS' question files;
+    the breakdown and the histogram only for PlotQA (:331).  Everything after the forwards is one launch per batch
+    (``score_batch``) into one int64 buffer, which is all-reduced ONCE after the loop when a process group is up (integer sums:
+    the same totals as the reference's per-batch reductions).
+    ``dataset`` needs ``get_ans_type(qa_id)`` for PlotQA and may provide ``cut_batch_padding``.
+    Returns (total_correct_tensor [6, 2] float64, breakdown_tensor [5, 4, 3, 3] float64, histogram [13] int64) on the device,
+    and with ``return_predictions`` a list of ``prediction_record`` tensors, one per batch, as a fourth value."""
     was_training = dialog_encoder.training
     dialog_encoder.eval()
     dev = torch.device(params["device"])
-    breakdown = torch.zeros(5, 4, 3, 3, dtype=torch.float64, device=dev)
-    total = torch.zeros(6, 2, dtype=torch.float64, device=dev)
-    histogram = torch.zeros(13, dtype=torch.int64, device=dev)
+    tables = torch.zeros(L.EVAL_TABLE_WORDS, dtype=torch.int64, device=dev)
+    binary = bool(params.get("binary_answers"))
+    plotqa = "plotqa" in params["dataset"]
     forced_mode = "_REGS" in str(params.get("qa_file", ""))
-    with torch.no_grad():
-        for batch in dataloader:
-            (dataset.cut_batch_padding if hasattr(dataset, "cut_batch_padding") else cut_batch_padding)(batch)
-            if batch["id"].shape[0] == 0:
-                continue
-            scores, out, err, terr = score_rows(dialog_encoder, batch, params, eval_batch_size)
-            assert batch["tokens"].shape[0] == scores.shape[0] == out.shape[0] == err.shape[0] == terr.shape[0]   # :269
-            forced = batch["gt_id"] if forced_mode else None
-            answers, sel_out, sel_err, sel_terr, _ = select_answers(scores, out, err, terr, batch["num_ans"], forced)
-            nsp_right, reg_right, reg_t_right, needs = correctness(answers, sel_err, sel_terr, batch)
-            reduce_total_acc(total, needs, nsp_right, reg_right, reg_t_right, group)
-            if "plotqa" in params["dataset"]:
-                correct = nsp_right & (needs.logical_not() | reg_right)
-                correct_t = nsp_right & (needs.logical_not() | reg_t_right)
-                reduce_breakdown_table(dataset.get_ans_type, group, params, breakdown, batch, correct, correct_t, needs)
-                if with_histogram:
-                    reduce_histogram(histogram, sel_err[needs].view(-1), group)
-    if was_training:
-        dialog_encoder.train()
+    records = []
+    try:
+        with torch.no_grad():
+            for batch in dataloader:
+                (dataset.cut_batch_padding if hasattr(dataset, "cut_batch_padding") else cut_batch_padding)(batch)
+                if batch["id"].shape[0] == 0:
+                    continue
+                scores, out, err, terr = score_rows(dialog_encoder, batch, params, eval_batch_size)
+                assert batch["tokens"].shape[0] == scores.shape[0] == out.shape[0] == err.shape[0] == terr.shape[0]   # :269
+                cats = question_categories(batch, dataset.get_ans_type) if plotqa else None
+                forced = batch["gt_id"] if forced_mode and not binary else None
+                answers, so, se, st, _, _ = score_batch(scores, out, err, terr, batch, tables, binary=binary, forced=forced, cats=cats,
+                                                        with_histogram=plotqa and with_histogram)
+                if return_predictions:
+                    records.append(prediction_record(batch, answers, so, se, st))
+    finally:
+        if was_training:
+            dialog_encoder.train()
+    if dist.is_available() and dist.is_initialized():
+        if dist.get_backend(group) == "gloo":              # 1.6 KB, once per evaluation: through the host where the backend has no device path
+            host = tables.cpu()
+            dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+            tables.copy_(host)
+        else:
+            dist.all_reduce(tables, op=dist.ReduceOp.SUM, group=group)
+    if int(tables[L.EVAL_ERRORS]) != 0:
+        raise ValueError("evaluate: %d questions with a category outside figure kind 1..4 (%s) / answer kind 0..2 / question category "
+                         "0..2" % (int(tables[L.EVAL_ERRORS]), ", ".join(k for k in FIG_INDEX if k != "Total")))
+    total = tables[L.EVAL_TOTAL:L.EVAL_TOTAL + 12].to(torch.float64).reshape(6, 2)
+    breakdown = tables[L.EVAL_BREAKDOWN:L.EVAL_BREAKDOWN + 180].to(torch.float64).reshape(5, 4, 3, 3)
+    histogram = tables[L.EVAL_HISTOGRAM:L.EVAL_HISTOGRAM + 13].clone()
+    if return_predictions:
+        return total, breakdown, histogram, records
     return total, breakdown, histogram
+
+
+def plotqa_evaluate(dataloader, dataset, params, eval_batch_size, dialog_encoder, group=None, with_histogram=True):
+    """The PlotQA evaluation loop under its earlier name: ``evaluate``.
+    Returns (total_correct_tensor [6, 2], breakdown_tensor [5, 4, 3, 3], histogram [13]) on the device."""
+    return evaluate(dataloader, dataset, params, eval_batch_size, dialog_encoder, group=group, with_histogram=with_histogram)

@@ -59,6 +59,16 @@ class HeadVariantArgs(C.Structure):
     _fields_ = [("h", HeadArgs), ("variant", Variant), ("snap", c_i32), ("ce_scratch", vp)]
 
 
+EVAL_TOTAL, EVAL_BREAKDOWN, EVAL_HISTOGRAM, EVAL_ERRORS, EVAL_TABLE_WORDS = 0, 12, 192, 205, 206      # CRCT_EVAL_* of include/crct_hip.h
+
+
+class EvalScoreArgs(C.Structure):
+    _fields_ = [("logits", vp), ("reg_out", vp), ("reg_err", vp), ("reg_terr", vp), ("num_ans", vp), ("forced", vp), ("labels", vp),
+                ("gt_id", vp), ("needs_reg", vp), ("tolerance", vp), ("cats", vp), ("answers", vp), ("sel_out", vp), ("sel_err", vp),
+                ("sel_terr", vp), ("flags", vp), ("prob0", vp), ("tables", vp), ("N", c_i64), ("Q", c_i32), ("mode", c_i32),
+                ("with_histogram", c_i32)]
+
+
 class ModelDims(C.Structure):
     _fields_ = [("vocab", c_i32), ("n_pos", c_i32), ("n_types", c_i32), ("H", c_i32), ("L", c_i32), ("heads", c_i32), ("I", c_i32),
                 ("Fv", c_i32), ("Hv", c_i32), ("Lv", c_i32), ("v_heads", c_i32), ("Iv", c_i32), ("Hb", c_i32), ("b_heads", c_i32),
@@ -186,6 +196,7 @@ PROTOTYPES = {
     "crct_head_loss": (C.c_int, [C.POINTER(HeadArgs), vp]),
     "crct_head_loss_variant": (C.c_int, [C.POINTER(HeadVariantArgs), vp]),
     "crct_eval_select": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, c_i64, vp, vp, vp, vp, vp, vp]),
+    "crct_eval_score": (C.c_int, [C.POINTER(EvalScoreArgs), vp]),
     "crct_adamw_plan": (c_i64, [vp, C.c_int, vp, vp, c_i64]),
     "crct_adamw_step": (C.c_int, [vp] * 11 + [c_i64, c_f32, c_f32, c_f32, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "crct_adamw_advance": (C.c_int, [vp, vp, vp]),

@@ -354,13 +354,20 @@ __global__ __launch_bounds__(256) void head_ce_wgrad_kernel(const CrctHeadArgs a
 // answer is the FIRST row with the largest p0 (torch.argmax), or forced[q] when given; the regressed value and its
 // two error measures are gathered from the chosen row.  A NaN p0 is the maximum, as it is for torch.argmax: the first
 // NaN row of a question wins over every number and over every later NaN.
-__global__ __launch_bounds__(64) void eval_select_kernel(const float* __restrict__ logits, const float* __restrict__ reg_out,
-                                                         const float* __restrict__ reg_err, const float* __restrict__ reg_terr,
-                                                         const int64_t* __restrict__ num_ans, const int64_t* __restrict__ forced,
-                                                         int Q, long N, float* __restrict__ prob0, int64_t* __restrict__ answers,
-                                                         float* __restrict__ sel_out, float* __restrict__ sel_err,
-                                                         float* __restrict__ sel_terr) {
-  const int q = blockIdx.x, lane = threadIdx.x;
+// softmax(l0, l1)[0] in fp32: the one expression both evaluation kernels use
+__device__ __forceinline__ float eval_p0(float l0, float l1) {
+  const float m = fmaxf(l0, l1);
+  const float e0 = expf(l0 - m), e1 = expf(l1 - m);
+  return e0 / (e0 + e1);
+}
+
+// what a question's wave picked: the answer, its row, and whether that row exists (0 <= a < num_ans[q] and r < N)
+struct EvalPick { long a, r; bool ok; };
+
+// The selection of one question by its wave (all 64 lanes call it; every lane returns the same pick).
+__device__ __forceinline__ EvalPick eval_select_wave(const float* __restrict__ logits, const int64_t* __restrict__ num_ans,
+                                                     const int64_t* __restrict__ forced, int q, int lane, long N,
+                                                     float* __restrict__ prob0) {
   long off = 0;
   for (int i = lane; i < q; i += 64) off += num_ans[i];
 #pragma unroll
@@ -372,9 +379,7 @@ __global__ __launch_bounds__(64) void eval_select_kernel(const float* __restrict
     const long r = off + j;
     float p = 0.f;
     if (r < N) {
-      const float l0 = logits[2 * r], l1 = logits[2 * r + 1], m = fmaxf(l0, l1);
-      const float e0 = expf(l0 - m), e1 = expf(l1 - m);
-      p = e0 / (e0 + e1);
+      p = eval_p0(logits[2 * r], logits[2 * r + 1]);
       if (prob0) prob0[r] = p;
     }
     // strictly greater: the earliest row of this lane wins ties; a NaN replaces any number and is never replaced
@@ -388,14 +393,100 @@ __global__ __launch_bounds__(64) void eval_select_kernel(const float* __restrict
     const bool take = on ? (!bn || oi < best_i) : (!bn && (ob > best || (ob == best && oi < best_i)));
     if (take) { best = ob; best_i = oi; }
   }
+  EvalPick k;
+  k.a = forced ? forced[q] : (n > 0 ? best_i : 0);
+  k.r = off + k.a;
+  k.ok = k.a >= 0 && k.a < n && k.r < N;
+  return k;
+}
+
+__global__ __launch_bounds__(64) void eval_select_kernel(const float* __restrict__ logits, const float* __restrict__ reg_out,
+                                                         const float* __restrict__ reg_err, const float* __restrict__ reg_terr,
+                                                         const int64_t* __restrict__ num_ans, const int64_t* __restrict__ forced,
+                                                         int Q, long N, float* __restrict__ prob0, int64_t* __restrict__ answers,
+                                                         float* __restrict__ sel_out, float* __restrict__ sel_err,
+                                                         float* __restrict__ sel_terr) {
+  const int q = blockIdx.x, lane = threadIdx.x;
+  const EvalPick k = eval_select_wave(logits, num_ans, forced, q, lane, N, prob0);
   if (lane == 0) {
-    long a = forced ? forced[q] : (n > 0 ? best_i : 0);
-    answers[q] = a;
-    const long r = off + a;
-    const bool ok = a >= 0 && a < n && r < N;
-    sel_out[q] = ok ? reg_out[r] : 0.f;
-    sel_err[q] = ok ? reg_err[r] : INFINITY;
-    sel_terr[q] = ok ? reg_terr[r] : INFINITY;
+    answers[q] = k.a;
+    sel_out[q] = k.ok ? reg_out[k.r] : 0.f;
+    sel_err[q] = k.ok ? reg_err[k.r] : INFINITY;
+    sel_terr[q] = k.ok ? reg_terr[k.r] : INFINITY;
+  }
+}
+
+// ------------------------------------------------------------------ evaluation: selection, flags and the accuracy tables in one launch
+// One wave per question, as above.  Mode 0 selects with eval_select_wave (the same bits as eval_select_kernel); mode 1 is the
+// reference's binary_answers branch (evaluation.py:280-285): one row per question, answer = round-half-even(p0), right when it
+// equals 1 - label.  Lane 0 then derives the flags (:303-311) and adds the question into tables (CRCT_EVAL_* offsets): 64-bit
+// integer atomics only, so the sums are exact and do not depend on the order the waves arrive in.
+__device__ __forceinline__ void eval_add(int64_t* tables, int i, bool on) {
+  if (on) atomicAdd(reinterpret_cast<unsigned long long*>(tables) + i, 1ULL);
+}
+
+__global__ __launch_bounds__(64) void eval_score_kernel(const CrctEvalScoreArgs a) {
+  const int q = blockIdx.x, lane = threadIdx.x;
+  long ans;
+  float so = 0.f, se = 0.f, st = 0.f;
+  bool nsp_right;
+  if (a.mode == 0) {
+    const EvalPick k = eval_select_wave(a.logits, a.num_ans, a.forced, q, lane, a.N, a.prob0);
+    if (lane != 0) return;
+    ans = k.a;
+    so = k.ok ? a.reg_out[k.r] : 0.f;
+    se = k.ok ? a.reg_err[k.r] : INFINITY;
+    st = k.ok ? a.reg_terr[k.r] : INFINITY;
+    nsp_right = ans == a.gt_id[q];
+  } else {
+    if (lane != 0) return;
+    const float p = eval_p0(a.logits[2 * (long)q], a.logits[2 * (long)q + 1]);
+    if (a.prob0) a.prob0[q] = p;
+    const bool nan = p != p;
+    ans = nan ? -1 : (long)rintf(p);                  // round half to even, as torch.round / np.round: p0 = 0.5 answers 0
+    nsp_right = !nan && ans == 1 - a.labels[q];
+  }
+  const bool needs = a.needs_reg[q] != 0;
+  const bool reg_right = se <= 0.05f && needs;
+  const bool reg_t_right = st <= a.tolerance[q] && needs;
+  const bool correct = nsp_right && (!needs || reg_right), correct_t = nsp_right && (!needs || reg_t_right);
+  a.answers[q] = ans;
+  if (a.sel_out) a.sel_out[q] = so;
+  if (a.sel_err) a.sel_err[q] = se;
+  if (a.sel_terr) a.sel_terr[q] = st;
+  if (a.flags) a.flags[q] = (uint8_t)((nsp_right ? 1 : 0) | (reg_right ? 2 : 0) | (reg_t_right ? 4 : 0));
+  int64_t* total = a.tables + CRCT_EVAL_TOTAL;       // [6][2] (hits, count), evaluation.py:492-519
+  eval_add(total, 0, nsp_right);            eval_add(total, 1, true);
+  eval_add(total, 2, nsp_right && needs);   eval_add(total, 3, needs);
+  eval_add(total, 4, reg_right);            eval_add(total, 5, needs);
+  eval_add(total, 6, reg_t_right);          eval_add(total, 7, needs);
+  eval_add(total, 8, correct);              eval_add(total, 9, true);
+  eval_add(total, 10, correct_t);           eval_add(total, 11, true);
+  if (a.with_histogram && needs) {                   // :528-543: (lo, hi] bins of the relative error; 0 and NaN fall in none
+    const float edge[13] = {0.f, (float)(1.0 / 20), (float)(2.0 / 20), (float)(3.0 / 20), (float)(4.0 / 20), (float)(3.0 / 10), (float)(4.0 / 10),
+                            (float)(5.0 / 10), (float)(6.0 / 10), (float)(7.0 / 10), (float)(8.0 / 10), (float)(9.0 / 10), (float)(10.0 / 10)};
+    int bin = -1;
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+      if (edge[k] < se && se <= edge[k + 1]) bin = k;
+    if (1.f < se) bin = 12;
+    if (bin >= 0) eval_add(a.tables + CRCT_EVAL_HISTOGRAM, bin, true);
+  }
+  if (a.cats) {                                      // :465-484: [figure 0 and own][answer kind, and 3 when regressed][category][hit5, hitT, n]
+    const int fig = a.cats[3 * q], kind = a.cats[3 * q + 1], qc = a.cats[3 * q + 2];
+    if (fig < 1 || fig > 4 || kind < 0 || kind > 2 || qc < 0 || qc > 2) {
+      eval_add(a.tables, CRCT_EVAL_ERRORS, true);    // nothing is stored at a bad index
+    } else {
+      int64_t* bd = a.tables + CRCT_EVAL_BREAKDOWN;
+      for (int f = 0; f < 2; ++f) {
+        const int row = (f ? fig : 0) * 4;
+        for (int r = 0; r < 2; ++r) {
+          if (r && !needs) break;
+          const int base = ((row + (r ? 3 : kind)) * 3 + qc) * 3;
+          eval_add(bd, base, correct); eval_add(bd, base + 1, correct_t); eval_add(bd, base + 2, true);
+        }
+      }
+    }
   }
 }
 
@@ -410,6 +501,25 @@ extern "C" int crct_eval_select(const float* logits, const float* reg_out, const
   if (Q == 0) return 0;
   crct_launch(eval_select_kernel, dim3(Q), dim3(64), 0, (hipStream_t)stream, logits, reg_out, reg_err, reg_terr, num_ans,
                      forced_answers, Q, (long)N, prob0, answers, sel_out, sel_err, sel_terr);
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int crct_eval_score(const CrctEvalScoreArgs* args, crct_stream_t stream) {
+  CRCT_REQUIRE(args, "eval_score: null argument struct");
+  const CrctEvalScoreArgs& a = *args;
+  CRCT_REQUIRE(a.mode == 0 || a.mode == 1, "eval_score: mode %d (0 = candidate rows, 1 = binary answers)", a.mode);
+  CRCT_REQUIRE(a.Q >= 0 && a.N >= 0, "eval_score: bad sizes");
+  CRCT_REQUIRE(a.logits && a.gt_id && a.needs_reg && a.tolerance && a.answers && a.tables, "eval_score: null argument");
+  if (a.mode == 1) {
+    CRCT_REQUIRE(a.N == a.Q, "eval_score: binary answers score one row per question, got N %lld for Q %d", (long long)a.N, a.Q);
+    CRCT_REQUIRE(a.labels, "eval_score: binary answers need labels");
+  } else {
+    CRCT_REQUIRE(a.num_ans, "eval_score: candidate rows need num_ans");
+    CRCT_REQUIRE(a.reg_out && a.reg_err && a.reg_terr, "eval_score: candidate rows need reg_out, reg_err, reg_terr");
+  }
+  if (a.Q == 0) return 0;
+  crct_launch(eval_score_kernel, dim3(a.Q), dim3(64), 0, (hipStream_t)stream, a);
   CRCT_CHECK_HIP(hipGetLastError());
   return 0;
 }

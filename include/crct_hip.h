@@ -507,6 +507,38 @@ int crct_eval_select(const float* logits, const float* reg_out, const float* reg
                      const int64_t* num_ans, const int64_t* forced_answers, int Q, int64_t N, float* prob0,
                      int64_t* answers, float* sel_out, float* sel_err, float* sel_terr, crct_stream_t stream);
 
+/* Evaluation scoring of one batch in ONE launch (evaluation.py:280-311 and the tables of :465-484, :492-519, :528-543): the
+ * selection of crct_eval_select, the correctness flags and the accuracy tables, one wave per question.
+ * mode 0: candidate rows -- prob0 / answers / sel_* are those of crct_eval_select bit for bit; nsp_right = answers == gt_id.
+ * mode 1: binary answers (:280-285, FigureQA) -- N == Q, one row per question, answers = p0 rounded half to even (p0 = 0.5
+ *   answers 0), nsp_right = answers == 1 - labels; a NaN p0 answers -1 and is never right; sel_* = 0 (reg_* are not read).
+ * flags [Q]: bit 0 nsp_right, bit 1 reg_right = sel_err <= 0.05f && needs, bit 2 reg_t_right = sel_terr <= tolerance && needs.
+ * tables: int64 [CRCT_EVAL_TABLE_WORDS], ADDED into (64-bit integer atomics: exact, order-independent):
+ *   total [6][2] at CRCT_EVAL_TOTAL, breakdown [5][4][3][3] at CRCT_EVAL_BREAKDOWN (only with cats), histogram [13] at
+ *   CRCT_EVAL_HISTOGRAM (only with_histogram, questions with needs; bins (lo, hi] with fp32 edges i/20, i/10; 0 falls in none),
+ *   and at CRCT_EVAL_ERRORS the number of questions whose cats entry is out of range (they add nothing to the breakdown).
+ * cats [Q][3]: figure kind 1..4, answer kind 0..2, question category 0..2.  Every per-question output but answers may be NULL. */
+enum { CRCT_EVAL_TOTAL = 0, CRCT_EVAL_BREAKDOWN = 12, CRCT_EVAL_HISTOGRAM = 192, CRCT_EVAL_ERRORS = 205, CRCT_EVAL_TABLE_WORDS = 206 };
+typedef struct CrctEvalScoreArgs {
+  const float* logits;                  /* [N][2] */
+  const float* reg_out; const float* reg_err; const float* reg_terr;      /* [N]; mode 0 */
+  const int64_t* num_ans;               /* [Q]; mode 0 */
+  const int64_t* forced;                /* [Q] or NULL; mode 0 */
+  const int64_t* labels;                /* [N]; mode 1 */
+  const int64_t* gt_id;                 /* [Q] */
+  const uint8_t* needs_reg;             /* [Q] */
+  const float* tolerance;               /* [Q] */
+  const int32_t* cats;                  /* [Q][3] or NULL */
+  int64_t* answers;                     /* [Q] */
+  float* sel_out; float* sel_err; float* sel_terr;     /* [Q] or NULL */
+  uint8_t* flags;                       /* [Q] or NULL */
+  float* prob0;                         /* [N] or NULL */
+  int64_t* tables;                      /* [CRCT_EVAL_TABLE_WORDS], added into */
+  int64_t N;
+  int32_t Q, mode, with_histogram;
+} CrctEvalScoreArgs;
+int crct_eval_score(const CrctEvalScoreArgs* args, crct_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused multi-tensor AdamW (torch.optim.AdamW semantics as constructed by utils.py:228-249) over
  * the flat fp32 parameter / gradient / moment buffers, refreshing the bf16 weight shadow.
