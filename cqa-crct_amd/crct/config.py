@@ -106,6 +106,15 @@ def vilbert_config(**overrides):
     return c
 
 
+def vilbert_original_config(**overrides):
+    """The original ViLBERT 6-layer / 6-connection model (settings of reference
+    config/bert_base_6layer_6conect_original.json): ``vilbert_config`` with 12 text heads (head size 64) and
+    8 visual / co-attention heads on 1024 (head size 128), 2048-wide region features."""
+    d = dict(num_attention_heads=12, v_num_attention_heads=8, bi_num_attention_heads=8, v_feature_size=2048)
+    d.update(overrides)
+    return vilbert_config(**d)
+
+
 def tiny_config(**overrides):
     """Small config used by the parity fixtures (SURVEY.md 8c 'Tiny config')."""
     d = dict(

@@ -1,5 +1,6 @@
 // Scaled-dot-product attention: the entry points of all three implementations (see pick_path below) and the fp32 VALU kernels
-// for the short CRCT sequences (<= 112 visual elements, <= 112 text tokens, any head size that is a multiple of 8 up to 64):
+// for the short CRCT sequences (<= 112 visual elements, <= 112 text tokens, any head size that is a multiple of 8 up to 64; head size
+// 128 is accepted by the entry points and runs on attention_long.hip's blocked MFMA kernels at every length, never here):
 // one 256-thread workgroup per (batch, head); q, k, v, the score
 // matrix and the probabilities live in LDS in fp32, all arithmetic is fp32 VALU (the score / PV
 // products are < 1 % of the step's FLOPs -- SURVEY.md 8a -- so they do not go to MFMA).
@@ -379,14 +380,14 @@ hipError_t dispatch(const AttnArgs& a, size_t lds, hipStream_t s) {
 
 // Three implementations behind one pair of entry points:
 //   attention_mfma.hip  register-resident MFMA kernels: Tq, Tk <= 112, d in {32, 48, 64}            (the default where it applies)
-//   attention_long.hip  key-tile loop, online softmax:  Tq, Tk <= CRCT_ATTN_MAX_LEN, d in {32, 48, 64} (beyond 112; everywhere it
-//                       applies after crct_attention_force_long(1))
+//   attention_long.hip  key-tile loop, online softmax:  Tq, Tk <= CRCT_ATTN_MAX_LEN, d in {32, 48, 64, 128} (beyond 112, and every
+//                       length at d = 128; everywhere it applies after crct_attention_force_long(1))
 //   this file           fp32 VALU, everything in LDS:   Tq, Tk <= 112, any d % 8 == 0 up to 64        (other head sizes; everything
-//                       it can take after crct_attention_force_valu(1))
+//                       it can take after crct_attention_force_valu(1) -- d = 128 is not among it and keeps its MFMA kernel)
 int g_force_valu = 0, g_force_long = 0;
 enum { PATH_NONE = 0, PATH_MFMA, PATH_LONG, PATH_VALU };
 int pick_path(int Tq, int Tk, int d) {
-  const bool valu_ok = Tq <= 112 && Tk <= 112;
+  const bool valu_ok = Tq <= 112 && Tk <= 112 && d <= 64;      // head size 128 has no VALU kernel: it stays on the MFMA paths whatever is forced
   if (g_force_valu && valu_ok) return PATH_VALU;
   if (g_force_long && crct_attention_long_ok(Tq, Tk, d)) return PATH_LONG;
   if (crct_attention_mfma_ok(Tq, Tk, d)) return PATH_MFMA;
@@ -396,8 +397,8 @@ int pick_path(int Tq, int Tk, int d) {
 int check_args(int Tq, int Tk, int d) {
   CRCT_REQUIRE(Tq >= 1 && Tk >= 1 && Tq <= CRCT_ATTN_MAX_LEN && Tk <= CRCT_ATTN_MAX_LEN, "attention: Tq=%d Tk=%d must be in [1,%d]", Tq, Tk,
                CRCT_ATTN_MAX_LEN);
-  CRCT_REQUIRE(d % 8 == 0 && d >= 8 && d <= 64, "attention: head size %d must be a multiple of 8 in [8,64]", d);
-  CRCT_REQUIRE(pick_path(Tq, Tk, d) != PATH_NONE, "attention: Tq=%d Tk=%d beyond 112 needs a head size of 32, 48 or 64 (got %d)", Tq, Tk, d);
+  CRCT_REQUIRE((d % 8 == 0 && d >= 8 && d <= 64) || d == 128, "attention: head size %d must be a multiple of 8 in [8,64], or 128", d);
+  CRCT_REQUIRE(pick_path(Tq, Tk, d) != PATH_NONE, "attention: Tq=%d Tk=%d beyond 112 needs a head size of 32, 48, 64 or 128 (got %d)", Tq, Tk, d);
   return 0;
 }
 bool use_mfma(int Tq, int Tk, int d) { const int p = pick_path(Tq, Tk, d); return p == PATH_MFMA || p == PATH_LONG; }

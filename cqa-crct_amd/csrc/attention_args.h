@@ -1,6 +1,7 @@
 // Arguments shared by the three attention implementations (attention.hip: fp32 VALU, any length up to 112;
 // attention_mfma.hip: register-resident MFMA kernels, lengths up to 112, head sizes 32 / 48 / 64; attention_long.hip: key-tile loop
-// with online softmax, lengths up to CRCT_ATTN_MAX_LEN, head sizes 32 / 48 / 64).
+// with online softmax, lengths up to CRCT_ATTN_MAX_LEN, head sizes 32 / 48 / 64, and head size 128 at every length from 1 on -- there
+// over image blocks of 256 rows, a row of an image being 32 ND + 16 = 272 B).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

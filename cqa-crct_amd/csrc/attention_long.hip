@@ -1,6 +1,8 @@
 // MFMA attention for sequences beyond the 112 x 112 register-resident kernels of attention_mfma.hip: the reference's own PlotQA
 // shape (config/plotqa.json:5-6: 124 text tokens x 44 visual elements; options.py:27 defaults to 256 tokens), up to
-// CRCT_ATTN_MAX_LEN = 512 queries x 512 keys (the text position table of config/vilbert.json) at head sizes 32 / 48 / 64.  Same math, same -10000 additive key mask, same
+// CRCT_ATTN_MAX_LEN = 512 queries x 512 keys (the text position table of config/vilbert.json) at head sizes 32 / 48 / 64, and at head size 128 (the original
+// ViLBERT config's visual stream and co-attention: 8 heads on 1024) for EVERY length 1 .. 512 -- the blocked kernels attn_fwd_blk /
+// attn_bwd_blk further down ("head size 128"), the same phases over image blocks of 256 rows.  Same math, same -10000 additive key mask, same
 // Philox element numbering (and therefore the same dropout masks) as attention.hip / attention_mfma.hip:
 //   P = softmax(q k^T / sqrt(d) + (1 - keymask) * -10000) ; ctx = dropout(P) v
 // Reference: BertSelfAttention.forward vilbert.py:392-412, BertImageSelfAttention :522-543, BertBiAttention :684-723.
@@ -430,6 +432,345 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_long(ATTN_HOT_PARAMS) {
   if (a.dv_q || a.dk_q) wave_amax(a.dkv_qamax, am_kv, lane);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- head size 128
+// At d = 128 a row of an image is 272 B: the K and V images of 512 keys are 278 528 B against 163 840 B of LDS, so the resident images
+// become BLOCKS of BLK_T = 16 tiles (256 rows; two images of a block: 139 264 B).  One pair of image slots serves the whole kernel (K, V
+// blocks in the forward and in phase A, Q, dO blocks in phase B); a wave's OWN tile always comes straight from global memory, as in the
+// SHARE form above.  The work is handed out in ROUNDS of NW tiles (round rd: wave wv owns tile rd NW + wv) and every round sweeps the blocks,
+// its state in registers: the online-softmax m, l and the ctx^T accumulator in the forward; m, l, delta, then dq^T in phase A; dv^T, dk^T in
+// phase B.  A block that is already resident is not loaded again, and successive sweeps run over the blocks in alternating directions, so
+// with one block per side (up to 256 x 256) every image is loaded once and with two a sweep loads one block.  The order in which a tile's
+// blocks are accumulated is a function of the shape alone: still one wave per output element, a fixed order, no atomics.
+constexpr int BLK_T = 16;
+static_assert(CRCT_ATTN_MAX_LEN <= 2 * 16 * BLK_T, "phase A keeps the dropout bits of at most two key blocks (kw0, kw1)");
+
+// LDS bytes: two image slots of min(tiles, BLK_T) tiles + key bias (forward: NK rounded up to a tile pair) [+ backward: row statistics,
+// one transposition tile per wave]
+inline size_t fwd_blk_lds(int NK, int ND) {
+  const int NKP = (NK + 1) & ~1, RT = NKP < BLK_T ? NKP : BLK_T;
+  return (size_t)32 * RT * (32 * ND + 16) + 64 * NKP;
+}
+inline size_t bwd_blk_lds(int NQ, int NK, int ND, int NW) {
+  const int NX = NQ > NK ? NQ : NK, RT = NX < BLK_T ? NX : BLK_T;
+  return (size_t)32 * RT * (32 * ND + 16) + 256 * NQ + 64 * NK + (size_t)NW * 16 * SCR_STB;
+}
+
+// the block `blk` of BLK_T tiles of two matrices (rows 256 blk .. of T; `tiles` tiles in all) becomes resident in the two image slots;
+// every wave of the workgroup calls this at the same point (the barriers), `resident` is uniform
+template <int ND>
+__device__ __forceinline__ void load_block(char* img0, char* img1, const bf16_t* __restrict__ s0, long ld0, const bf16_t* __restrict__ s1, long ld1,
+                                           int T, int tiles, int blk, int& resident, int tid, int nthr) {
+  if (blk == resident) return;
+  __syncthreads();                          // every wave is done with the block that leaves
+  const int r0 = 16 * BLK_T * blk, rows = 16 * min(tiles - BLK_T * blk, BLK_T);
+  load_image<ND>(img0, s0 + (long)r0 * ld0, ld0, T - r0, rows, tid, nthr);
+  load_image<ND>(img1, s1 + (long)r0 * ld1, ld1, T - r0, rows, tid, nthr);
+  __syncthreads();
+  resident = blk;
+}
+
+template <int ND, int NW>
+__global__ __launch_bounds__(64 * NW) void attn_fwd_blk(ATTN_HOT_PARAMS) {
+  ATTN_HOT_UNPACK
+  constexpr int STB = 32 * ND + 16, d = 16 * ND;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, g = lane >> 4, wv = tid >> 6;
+  const int NQ = (a.Tq + 15) >> 4, NK = (a.Tk + 15) >> 4, NKP = (NK + 1) & ~1;
+  const int NB = (NKP + BLK_T - 1) / BLK_T, RT = min(NKP, BLK_T);
+  const long bh = blockIdx.x;
+  const int b = (int)(bh / a.heads), h = (int)(bh % a.heads);
+  char* Ks = smem;
+  char* Vs = Ks + 16 * RT * STB;
+  float* kbias = reinterpret_cast<float*>(Vs + 16 * RT * STB);
+  load_keybias(kbias, a.keymask + (long)b * a.Tk, a.Tk, 16 * NKP, tid, 64 * NW);      // visible after load_block's barriers
+  const float sc = a.scale * LOG2E, ds = a.thr ? a.dscale : 1.0f;
+  const bf16_t* qg = a.q + (long)b * a.Tq * a.ldq + h * d;
+  const bf16_t* kg = a.k + (long)b * a.Tk * a.ldk + h * d;
+  const bf16_t* vg = a.v + (long)b * a.Tk * a.ldv + h * d;
+  float am = 0.f;
+  int resident = -1;
+  const int rounds = (NQ + NW - 1) / NW;
+#pragma unroll 1
+  for (int rd = 0; rd < rounds; ++rd) {
+    const int it = rd * NW + wv, i = 16 * it + n;
+    const bool active = it < NQ;               // wave-uniform; an idle wave of the last round still meets the barriers
+    s4_t qf[ND];
+#pragma unroll
+    for (int ks = 0; ks < ND; ++ks) qf[ks] = frag_rows_global(qg, a.ldq, a.Tq, active ? 16 * it : 0, 16 * ks, lane);
+    float m = -INFINITY, l = 0.f;
+    f4_t o[ND];
+#pragma unroll
+    for (int ct = 0; ct < ND; ++ct) o[ct] = f4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int kk = 0; kk < NB; ++kk) {
+      const int blk = (rd & 1) ? NB - 1 - kk : kk;
+      load_block<ND>(Ks, Vs, kg, a.ldk, vg, a.ldv, a.Tk, NKP, blk, resident, tid, 64 * NW);
+      if (!active) continue;
+      const int je = min(NKP - BLK_T * blk, BLK_T);      // even
+#pragma unroll 1
+      for (int jl = 0; jl < je; jl += 2) {
+        const int jt = BLK_T * blk + jl;
+        f4_t s[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          s[u] = f4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ks = 0; ks < ND; ++ks) s[u] = mma16(frag_rows(Ks, STB, 16 * (jl + u), 16 * ks, lane), qf[ks], s[u]);      // S^T[j][i]
+        }
+        float cm = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const f4_t kb = *reinterpret_cast<const f4_t*>(kbias + 16 * (jt + u) + 4 * g);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { s[u][r] = fmaf(s[u][r], sc, kb[r]); cm = fmaxf(cm, s[u][r]); }
+        }
+        const float mn = fmaxf(m, xmax2(cm));          // finite: key 16 jt exists
+        const float alpha = __builtin_amdgcn_exp2f(m - mn);
+        float ps = 0.f;
+        s4_t pb[2];
+        const uint32_t kb8 = keep_byte(a, bh, i, jt >> 1, g);          // jt is even: one call for the pair
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const uint32_t nib = (kb8 >> (4 * u)) & 0xfu;
+          f4_t p;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float e = __builtin_amdgcn_exp2f(s[u][r] - mn);
+            ps += e;
+            p[r] = ((nib >> r) & 1u) ? e * ds : 0.f;
+          }
+          pb[u] = pack4(p);
+        }
+        l = fmaf(l, alpha, ps);
+        m = mn;
+#pragma unroll
+        for (int ct = 0; ct < ND; ++ct) {
+          o[ct] = o[ct] * alpha;
+#pragma unroll
+          for (int u = 0; u < 2; ++u) o[ct] = mma16(frag_cols(Vs, STB, 16 * (jl + u), 16 * ct, lane), pb[u], o[ct]);        // ctx^T[c][i]
+        }
+      }
+    }
+    if (active) {
+      const float lsum = xsum2(l);
+      const float inv = 1.0f / lsum;
+      if (i < a.Tq) {
+#pragma unroll
+        for (int ct = 0; ct < ND; ++ct)
+          store_tile_t<true>(a.ctx, a.ctx_q, a.ldo, (long)b * a.Tq + i, h * d + 16 * ct + 4 * g, o[ct] * inv, a.ctx_qscale, am);
+        if (a.lse && g == 0) a.lse[bh * a.Tq + i] = m + __builtin_amdgcn_logf(lsum);      // v_log_f32: log2
+      }
+    }
+  }
+  if (a.ctx_q) wave_amax(a.ctx_qamax, am, lane);
+}
+
+template <int ND, int NW, bool LSE>
+__global__ __launch_bounds__(64 * NW) void attn_bwd_blk(ATTN_HOT_PARAMS) {
+  ATTN_HOT_UNPACK
+  constexpr int STB = 32 * ND + 16, d = 16 * ND;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, g = lane >> 4, wv = tid >> 6;
+  const int NQ = (a.Tq + 15) >> 4, NK = (a.Tk + 15) >> 4;
+  const int NX = NQ > NK ? NQ : NK, RT = min(NX, BLK_T);
+  const int NKB = (NK + BLK_T - 1) / BLK_T, NQB = (NQ + BLK_T - 1) / BLK_T;
+  const long bh = blockIdx.x;
+  const int b = (int)(bh / a.heads), h = (int)(bh % a.heads);
+  char* I0 = smem;                          // K block (phase A), Q block (phase B)
+  char* I1 = I0 + 16 * RT * STB;            // V block (phase A), dO block (phase B)
+  float4* stats = reinterpret_cast<float4*>(I1 + 16 * RT * STB);      // per query: m, 1 / l, delta
+  float* kbias = reinterpret_cast<float*>(stats + 16 * NQ);
+  char* scr = reinterpret_cast<char*>(kbias + 16 * NK) + wv * 16 * SCR_STB;
+  uint8_t* keepc = reinterpret_cast<uint8_t*>(kbias + 16 * NK) + NW * 16 * SCR_STB;      // as in attn_bwd_long
+  const bool cached = a.keep_cache != 0;
+  const bf16_t* qg = a.q + (long)b * a.Tq * a.ldq + h * d;
+  const bf16_t* og = a.dctx + (long)b * a.Tq * a.ldo + h * d;
+  const bf16_t* kg = a.k + (long)b * a.Tk * a.ldk + h * d;
+  const bf16_t* vg = a.v + (long)b * a.Tk * a.ldv + h * d;
+  load_keybias(kbias, a.keymask + (long)b * a.Tk, a.Tk, 16 * NK, tid, 64 * NW);      // visible after load_block's barriers
+  const float sc = a.scale * LOG2E, ds = a.thr ? a.dscale : 1.0f;
+  float am_q = 0.f, am_kv = 0.f;
+  int resident = -1, sweep = 0;
+  // ---------------------------------------------------------------- phase A: statistics and dq of the wave's query tile of the round
+  const int rounds_q = (NQ + NW - 1) / NW;
+#pragma unroll 1
+  for (int rd = 0; rd < rounds_q; ++rd) {
+    const int it = rd * NW + wv, i = 16 * it + n;
+    const bool active = it < NQ;
+    s4_t qf[ND], of[ND];
+#pragma unroll
+    for (int ks = 0; ks < ND; ++ks) {
+      qf[ks] = frag_rows_global(qg, a.ldq, a.Tq, active ? 16 * it : 0, 16 * ks, lane);
+      of[ks] = frag_rows_global(og, a.ldo, a.Tq, active ? 16 * it : 0, 16 * ks, lane);
+    }
+    float m = -INFINITY, l = 0.f, dl = 0.f;
+    uint64_t kw0 = ~0ull, kw1 = ~0ull;      // keep bits of sweep 1 for sweep 2: 4 per key tile, one word per key block
+    if constexpr (LSE) {
+      // the forward's statistics: m <- lse (then exp2(s - m) IS the probability: l = 1), delta from the forward's output
+      const bf16_t* cg = a.ctx + ((long)b * a.Tq + min(i, a.Tq - 1)) * a.ldc + h * d + 4 * g;
+#pragma unroll
+      for (int ks = 0; ks < ND; ++ks) {
+        const uint2 ov = *reinterpret_cast<const uint2*>(cg + 16 * ks);
+        dl = fmaf(bf2f((bf16_t)(ov.x & 0xffff)), bf2f((bf16_t)of[ks][0]), dl);
+        dl = fmaf(bf2f((bf16_t)(ov.x >> 16)), bf2f((bf16_t)of[ks][1]), dl);
+        dl = fmaf(bf2f((bf16_t)(ov.y & 0xffff)), bf2f((bf16_t)of[ks][2]), dl);
+        dl = fmaf(bf2f((bf16_t)(ov.y >> 16)), bf2f((bf16_t)of[ks][3]), dl);
+      }
+      // a query past Tq (padding of the last tile: q and dO rows are zero) gets m = +inf: its probabilities are exactly 0 whatever its scores
+      m = i < a.Tq ? a.lse[bh * a.Tq + i] : INFINITY;
+      l = 0.25f;                                   // xsum2 over the four lane groups below: 1
+    } else {
+#pragma unroll 1
+      for (int kk = 0; kk < NKB; ++kk) {
+        const int blk = (sweep & 1) ? NKB - 1 - kk : kk;
+        load_block<ND>(I0, I1, kg, a.ldk, vg, a.ldv, a.Tk, NK, blk, resident, tid, 64 * NW);
+        if (!active) continue;
+        const int je = min(NK - BLK_T * blk, BLK_T);
+        uint64_t w = 0ull;
+        uint32_t kb8 = 0xffu;
+#pragma unroll 1
+        for (int jl = 0; jl < je; ++jl) {
+          const int jt = BLK_T * blk + jl;
+          f4_t s, gp;
+          score_tiles<ND>(s, gp, I0, I1, kbias + 16 * BLK_T * blk, qf, of, jl, sc, lane);
+          const float cm = xmax2(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
+          const float mn = fmaxf(m, cm);
+          const float alpha = __builtin_amdgcn_exp2f(m - mn);
+          if (!(jl & 1)) kb8 = keep_byte(a, bh, i, jt >> 1, g);      // BLK_T is even: even jl = first tile of a pair
+          const uint32_t nib = (kb8 >> (4 * (jl & 1))) & 0xfu;
+          w |= (uint64_t)nib << (4 * jl);
+          if (cached) keepc[(it * NK + jt) * 64 + lane] = (uint8_t)nib;
+          float ps = 0.f, pd = 0.f;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float e = __builtin_amdgcn_exp2f(s[r] - mn);
+            ps += e;
+            pd = fmaf(e, ((nib >> r) & 1u) ? gp[r] * ds : 0.f, pd);
+          }
+          l = fmaf(l, alpha, ps);
+          dl = fmaf(dl, alpha, pd);
+          m = mn;
+        }
+        if (blk == 0) kw0 = w; else kw1 = w;
+      }
+      ++sweep;
+    }
+    const float inv = 1.0f / xsum2(l);
+    const float delta = xsum2(dl) * inv;
+    if (active && g == 0) stats[i] = make_float4(m, inv, delta, 0.f);
+    f4_t dq[ND];
+#pragma unroll
+    for (int ct = 0; ct < ND; ++ct) dq[ct] = f4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int kk = 0; kk < NKB; ++kk) {
+      const int blk = (sweep & 1) ? NKB - 1 - kk : kk;
+      load_block<ND>(I0, I1, kg, a.ldk, vg, a.ldv, a.Tk, NK, blk, resident, tid, 64 * NW);
+      if (!active) continue;
+      const int je = min(NK - BLK_T * blk, BLK_T);
+      const uint64_t w = blk == 0 ? kw0 : kw1;
+      uint32_t kb8 = 0xffu;
+#pragma unroll 1
+      for (int jl = 0; jl < je; ++jl) {
+        const int jt = BLK_T * blk + jl;
+        f4_t s, gp;
+        score_tiles<ND>(s, gp, I0, I1, kbias + 16 * BLK_T * blk, qf, of, jl, sc, lane);
+        uint32_t nib;
+        if constexpr (LSE) {                     // no sweep 1: the dropout bits are made (and parked for phase B) here
+          if (!(jl & 1)) kb8 = keep_byte(a, bh, i, jt >> 1, g);
+          nib = (kb8 >> (4 * (jl & 1))) & 0xfu;
+          if (cached) keepc[(it * NK + jt) * 64 + lane] = (uint8_t)nib;
+        } else {
+          nib = (uint32_t)(w >> (4 * jl)) & 0xfu;
+        }
+        f4_t dsv;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(s[r] - m) * inv;
+          dsv[r] = p * ((((nib >> r) & 1u) ? gp[r] * ds : 0.f) - delta);
+        }
+        const s4_t dsb = pack4(dsv);
+#pragma unroll
+        for (int ct = 0; ct < ND; ++ct) dq[ct] = mma16(frag_cols(I0, STB, 16 * jl, 16 * ct, lane), dsb, dq[ct]);      // dq^T[c][i]
+      }
+    }
+    ++sweep;
+    if (active && i < a.Tq) {
+#pragma unroll
+      for (int ct = 0; ct < ND; ++ct)
+        store_tile_t<false>(a.dq, a.dq_q, a.lddq, (long)b * a.Tq + i, h * d + 16 * ct + 4 * g, dq[ct] * a.scale, a.dq_qscale, am_q);
+    }
+  }
+  if (a.dq_q) wave_amax(a.dq_qamax, am_q, lane);
+  // ---------------------------------------------------------------- phase B: dv and dk of the wave's key tile of the round
+  // (load_block's first barrier: the statistics of every query tile are in LDS and every wave is done with the K, V block)
+  resident = -1;
+  const int rounds_k = (NK + NW - 1) / NW;
+#pragma unroll 1
+  for (int rd = 0; rd < rounds_k; ++rd) {
+    const int jt = rd * NW + wv, j = 16 * jt + n;
+    const bool active = jt < NK;
+    s4_t kf[ND], vf[ND];
+#pragma unroll
+    for (int ks = 0; ks < ND; ++ks) {
+      kf[ks] = frag_rows_global(kg, a.ldk, a.Tk, active ? 16 * jt : 0, 16 * ks, lane);
+      vf[ks] = frag_rows_global(vg, a.ldv, a.Tk, active ? 16 * jt : 0, 16 * ks, lane);
+    }
+    f4_t dv[ND], dk[ND];
+#pragma unroll
+    for (int ct = 0; ct < ND; ++ct) { dv[ct] = f4_t{0.f, 0.f, 0.f, 0.f}; dk[ct] = f4_t{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll 1
+    for (int kk = 0; kk < NQB; ++kk) {
+      const int blk = (rd & 1) ? NQB - 1 - kk : kk;
+      load_block<ND>(I0, I1, qg, a.ldq, og, a.ldo, a.Tq, NQ, blk, resident, tid, 64 * NW);
+      if (!active) continue;
+      const f4_t kb = *reinterpret_cast<const f4_t*>(kbias + 16 * jt + 4 * g);
+      const int ie = min(NQ - BLK_T * blk, BLK_T);
+#pragma unroll 1
+      for (int il = 0; il < ie; ++il) {
+        const int it = BLK_T * blk + il, i = 16 * it + n;
+        f4_t s = f4_t{0.f, 0.f, 0.f, 0.f}, gp = f4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < ND; ++ks) {
+          s = mma16(kf[ks], frag_rows(I0, STB, 16 * il, 16 * ks, lane), s);
+          gp = mma16(vf[ks], frag_rows(I1, STB, 16 * il, 16 * ks, lane), gp);
+        }
+        const float4 st = stats[i];
+        const uint32_t nib = cached ? keepc[(it * NK + jt) * 64 + lane] : (keep_byte(a, bh, i, jt >> 1, g) >> (4 * (jt & 1))) & 0xfu;
+        f4_t pdv, dsv;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(fmaf(s[r], sc, kb[r]) - st.x) * st.y;
+          const bool kp = (nib >> r) & 1u;
+          pdv[r] = kp ? p * ds : 0.f;
+          dsv[r] = p * ((kp ? gp[r] * ds : 0.f) - st.z);
+        }
+        // accumulator layout (query = column) -> [query][key] tile in LDS -> B operand of the products that contract over the queries
+        put_tile_t(scr, SCR_STB, 0, 0, pdv, lane);
+        wave_sync();
+        const s4_t pf = frag_cols(scr, SCR_STB, 0, 0, lane);
+        wave_sync();
+        put_tile_t(scr, SCR_STB, 0, 0, dsv, lane);
+        wave_sync();
+        const s4_t sf = frag_cols(scr, SCR_STB, 0, 0, lane);
+        wave_sync();
+#pragma unroll
+        for (int ct = 0; ct < ND; ++ct) {
+          dv[ct] = mma16(frag_cols(I1, STB, 16 * il, 16 * ct, lane), pf, dv[ct]);       // dv^T[c][j] += dO[i][c] Pd[i][j]
+          dk[ct] = mma16(frag_cols(I0, STB, 16 * il, 16 * ct, lane), sf, dk[ct]);       // dk^T[c][j] += q[i][c] dS[i][j]
+        }
+      }
+    }
+    if (active && j < a.Tk) {
+#pragma unroll
+      for (int ct = 0; ct < ND; ++ct) {
+        store_tile_t<false>(a.dv, a.dv_q, a.lddv, (long)b * a.Tk + j, h * d + 16 * ct + 4 * g, dv[ct], a.dkv_qscale, am_kv);
+        store_tile_t<false>(a.dk, a.dk_q, a.lddk, (long)b * a.Tk + j, h * d + 16 * ct + 4 * g, dk[ct] * a.scale, a.dkv_qscale, am_kv);
+      }
+    }
+  }
+  if (a.dv_q || a.dk_q) wave_amax(a.dkv_qamax, am_kv, lane);
+}
+
 template <bool BWD, int ND, int NW, bool SHARE, bool LSE>
 hipError_t launch_nw(const AttnArgs& a, size_t lds, hipStream_t s) {
   auto kern = BWD ? attn_bwd_long<ND, NW, SHARE, LSE> : attn_fwd_long<ND, NW>;
@@ -468,24 +809,55 @@ hipError_t launch_d(const AttnArgs& a_in, hipStream_t s) {
   if (share) return NW == 8 ? launch_nw<BWD, ND, 8, true, false>(a, lds, s) : launch_nw<BWD, ND, 4, true, false>(a, lds, s);
   return NW == 8 ? launch_nw<BWD, ND, 8, false, false>(a, lds, s) : launch_nw<BWD, ND, 4, false, false>(a, lds, s);
 }
+// head size 128: the blocked kernels, same wave counts and the same rule for the dropout-bit cache
+template <bool BWD, int ND, int NW, bool LSE>
+hipError_t launch_blk_nw(const AttnArgs& a, size_t lds, hipStream_t s) {
+  auto kern = BWD ? attn_bwd_blk<ND, NW, LSE> : attn_fwd_blk<ND, NW>;
+  const hipError_t e = crct_lds_limit(kern, lds > 64 * 1024 ? LDS_CAP : lds);
+  if (e != hipSuccess) return e;
+  if (a.ldq > 0x7fffffffL || a.ldk > 0x7fffffffL || a.ldv > 0x7fffffffL) return hipErrorInvalidValue;      // preloaded as 32-bit scalars
+  crct_launch(kern, dim3(a.B * a.heads), dim3(64 * NW), lds, s, ATTN_HOT_ARGS(a) a);
+  return hipGetLastError();
+}
+template <bool BWD, int ND>
+hipError_t launch_blk(const AttnArgs& a_in, hipStream_t s) {
+  AttnArgs a = a_in;
+  const int NQ = (a.Tq + 15) >> 4, NK = (a.Tk + 15) >> 4;
+  const int NW = waves_for(BWD, NQ, NK);
+  size_t lds = BWD ? bwd_blk_lds(NQ, NK, ND, NW) : fwd_blk_lds(NK, ND);
+  if (lds > (size_t)LDS_CAP) return hipErrorInvalidValue;
+  a.keep_cache = 0;
+  if (BWD && a.thr && lds + keep_cache_bytes(NQ, NK) <= (size_t)LDS_CAP && LDS_CAP / (lds + keep_cache_bytes(NQ, NK)) == LDS_CAP / lds) {
+    a.keep_cache = 1;
+    lds += keep_cache_bytes(NQ, NK);
+  }
+  if constexpr (BWD) {
+    if (a.lse && a.ctx) return NW == 8 ? launch_blk_nw<true, ND, 8, true>(a, lds, s) : launch_blk_nw<true, ND, 4, true>(a, lds, s);
+  }
+  return NW == 8 ? launch_blk_nw<BWD, ND, 8, false>(a, lds, s) : launch_blk_nw<BWD, ND, 4, false>(a, lds, s);
+}
 template <bool BWD>
 hipError_t launch(const AttnArgs& a, hipStream_t s) {
   switch (a.d) {
     case 32: return launch_d<BWD, 2>(a, s);
     case 48: return launch_d<BWD, 3>(a, s);
     case 64: return launch_d<BWD, 4>(a, s);
+    case 128: return launch_blk<BWD, 8>(a, s);
   }
   return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-// Both directions must fit (the forward of a shape the backward cannot take is of no use to the step): head size 32 / 48 / 64
+// Both directions must fit (the forward of a shape the backward cannot take is of no use to the step): head size 32 / 48 / 64 / 128
 // and at most CRCT_ATTN_MAX_LEN queries and keys -- 512 x 512 x 64: forward 146 KB for the K, V images, backward exactly the 160 KB
-// (two images + statistics + key bias + eight transposition tiles).
+// (two images + statistics + key bias + eight transposition tiles).  512 x 512 x 128 (row stride 272 B, blocks of 256 rows): forward
+// 2 x 256 x 272 = 139 264 B of image slots + 2 048 B of key bias = 141 312 B; backward 139 264 + 8 192 (statistics) + 2 048 (key bias) +
+// 8 x 768 (transposition tiles) = 155 648 B of the 163 840 -- every length 1 .. 512 fits, in both directions.
 bool crct_attention_long_ok(int Tq, int Tk, int d) {
-  if (!(d == 32 || d == 48 || d == 64) || Tq < 1 || Tk < 1 || Tq > CRCT_ATTN_MAX_LEN || Tk > CRCT_ATTN_MAX_LEN) return false;
+  if (!(d == 32 || d == 48 || d == 64 || d == 128) || Tq < 1 || Tk < 1 || Tq > CRCT_ATTN_MAX_LEN || Tk > CRCT_ATTN_MAX_LEN) return false;
   const int NQ = (Tq + 15) >> 4, NK = (Tk + 15) >> 4, ND = d / 16;
+  if (d == 128) return bwd_blk_lds(NQ, NK, ND, waves_for(true, NQ, NK)) <= (size_t)LDS_CAP && fwd_blk_lds(NK, ND) <= (size_t)LDS_CAP;
   return bwd_lds(NQ, NK, ND, waves_for(true, NQ, NK), true) <= (size_t)LDS_CAP && fwd_lds(NK, ND) <= (size_t)LDS_CAP;
 }
 hipError_t crct_attention_long_fwd(const AttnArgs& a, hipStream_t s) { return launch<false>(a, s); }

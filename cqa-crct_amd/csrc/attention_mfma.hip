@@ -1,6 +1,10 @@
 // MFMA attention for the short CRCT sequences: one, two or four waves per (batch, head) (see launch()), sequences up to 112 queries x
 // 112 keys (1-4 or 7 tiles of 16 per side), head size 32 / 48 / 64.  Same math and the same dropout stream as attention.hip (which stays
-// the path for longer sequences):
+// the path for longer sequences).  Head size 128 (ND = 8) is NOT instantiated here: with one wave per pair the ctx^T / dq^T accumulators of
+// a 7 x 7-tile case alone are ND NQ = 56 f4 tiles = 224 VGPRs, and the four backward images of 112 rows are 4 x 112 x 272 B = 122 KB before
+// the P image; pick_path (attention.hip) sends every d = 128 shape to attention_long.hip's blocked kernels, whose register footprint does
+// not grow with the tile counts.  crct_attention_force_split(n) therefore has no effect at d = 128: every count falls back to the wave
+// counts of attention_long.hip (waves_for: 4 or 8 per pair), and the bits are the same for every n:
 //   P = softmax(q k^T / sqrt(d) + (1 - keymask) * -10000) ; ctx = dropout(P) v
 // Reference: BertSelfAttention.forward vilbert.py:392-412, BertImageSelfAttention :522-543,
 // BertBiAttention :684-723.

@@ -6,8 +6,9 @@
 // constants (scale log2e folded into one fma, the mask offset -10000.f * log2e), the same Philox numbering (attention_args.h attn_keep8):
 // a map carries the very dropout mask its forward applied.
 //
-// ONE rule for every length up to CRCT_ATTN_MAX_LEN and every head size d % 8 == 0 up to 64 (ND = ceil(d / 16) contraction slices; the
-// tail of a head size that is no multiple of 16 is zero-filled):
+// ONE rule for every length up to CRCT_ATTN_MAX_LEN and every head size d % 8 == 0 up to 64, and 128 (ND = ceil(d / 16) contraction slices; the
+// tail of a head size that is no multiple of 16 is zero-filled).  LDS is the K image and the key term: at d = 128 (row stride 272 B) and 512
+// keys 512 x 272 + 2 048 = 141 312 B of the 163 840, so K stays one resident image at every length:
 //   * a workgroup of NW = 4 waves belongs to one (batch, head): K as a row-major LDS image (rows beyond Tk and columns beyond d zero),
 //     the additive key term as fp32 (0 attended, -10000 log2e masked, -inf ABSENT: the padding keys of the last tile pair are no keys);
 //   * a wave owns 16 queries at a time (Q fragments straight from global memory) and computes S^T = K Q^T per 16-key tile, the forward's
@@ -177,7 +178,7 @@ extern "C" int crct_attention_probs(const void* q, const void* k, const uint8_t*
                                     crct_stream_t stream) {
   CRCT_REQUIRE(Tq >= 1 && Tk >= 1 && Tq <= CRCT_ATTN_MAX_LEN && Tk <= CRCT_ATTN_MAX_LEN, "attention_probs: Tq=%d Tk=%d must be in [1,%d]", Tq, Tk,
                CRCT_ATTN_MAX_LEN);
-  CRCT_REQUIRE(d % 8 == 0 && d >= 8 && d <= 64, "attention_probs: head size %d must be a multiple of 8 in [8,64]", d);
+  CRCT_REQUIRE((d % 8 == 0 && d >= 8 && d <= 64) || d == 128, "attention_probs: head size %d must be a multiple of 8 in [8,64], or 128", d);
   CRCT_REQUIRE(B >= 0 && heads >= 0 && (int64_t)B * heads <= 0x7fffffffLL, "attention_probs: bad B=%d heads=%d", B, heads);
   CRCT_REQUIRE(probs, "attention_probs: null output");
   CRCT_REQUIRE(q && k && keymask, "attention_probs: null q / k / keymask");
@@ -197,6 +198,7 @@ extern "C" int crct_attention_probs(const void* q, const void* k, const uint8_t*
     case 1: CRCT_CHECK_HIP(launch_probs<1>(qb, kb, keymask, B, heads, Tq, Tk, (int)ldq, (int)ldk, a, s)); break;
     case 2: CRCT_CHECK_HIP(launch_probs<2>(qb, kb, keymask, B, heads, Tq, Tk, (int)ldq, (int)ldk, a, s)); break;
     case 3: CRCT_CHECK_HIP(launch_probs<3>(qb, kb, keymask, B, heads, Tq, Tk, (int)ldq, (int)ldk, a, s)); break;
+    case 8: CRCT_CHECK_HIP(launch_probs<8>(qb, kb, keymask, B, heads, Tq, Tk, (int)ldq, (int)ldk, a, s)); break;
     default: CRCT_CHECK_HIP(launch_probs<4>(qb, kb, keymask, B, heads, Tq, Tk, (int)ldq, (int)ldk, a, s)); break;
   }
   return 0;

@@ -135,7 +135,7 @@ struct StreamScratch { size_t dy[2], dres_a, dlin_a, dres_b, dlin_b, gc, du, dct
 
 struct Step { char kind; int idx; };
 struct StepIn { Act t, v; };      // the two hidden states a schedule step starts from
-struct Tap { std::string name; size_t off; char stream; };
+struct Tap { std::string name; size_t off; char stream; int width = 0; };      // width: elements per row where it is not the stream's hidden size (the fused qkv buffers)
 // What one backward segment does (crct_engine_backward_plan): whether it runs, whether the gradients of its text / visual
 // input are produced (the embedding segment: whether that stream's half runs), how many weight-gradient GEMMs it leaves out
 struct SegPlan { bool runs = true, dx_t = true, dx_v = true; int dropped = 0; };
@@ -1301,6 +1301,14 @@ extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, 
     e->in.push_back(x);
     e->taps.push_back({"seq_t", x.t.x, 't'});
     e->taps.push_back({"seq_v", x.v.x, 'v'});
+    // the fused [rows, 3 H] q | k | v buffers the attention kernels (and crct_engine_attention_probs) read: "t<i>.qkv", "v<i>.qkv", and per
+    // connection layer "c<i>.qkv1" (visual rows) / "c<i>.qkv2" (text rows)
+    for (int i = 0; i < D.L; ++i) { snprintf(buf, sizeof(buf), "t%d.qkv", i); e->taps.push_back({buf, e->tla[i].qkv, 't', 3 * D.H}); }
+    for (int i = 0; i < D.Lv; ++i) { snprintf(buf, sizeof(buf), "v%d.qkv", i); e->taps.push_back({buf, e->vla[i].qkv, 'v', 3 * D.Hv}); }
+    for (int i = 0; i < D.n_conn; ++i) {
+      snprintf(buf, sizeof(buf), "c%d.qkv1", i); e->taps.push_back({buf, e->cla[i].qkv1, 'v', 3 * D.Hb});
+      snprintf(buf, sizeof(buf), "c%d.qkv2", i); e->taps.push_back({buf, e->cla[i].qkv2, 't', 3 * D.Hb});
+    }
   }
 
   // ---- gradient segments in backward order: heads, schedule reversed, embeddings
@@ -1668,7 +1676,7 @@ extern "C" int64_t crct_engine_tap(crct_engine_t* e, const void* workspace, cons
                                    int64_t cap, crct_stream_t stream) {
   if (!e || !name) return -1;
   auto copy = [&](const Tap& t) -> int64_t {
-    const int64_t n = t.stream == 't' ? (int64_t)B * T * e->d.H : (int64_t)B * V * e->d.Hv;
+    const int64_t n = t.stream == 't' ? (int64_t)B * T * (t.width ? t.width : e->d.H) : (int64_t)B * V * (t.width ? t.width : e->d.Hv);
     if (n > cap) { crct_set_error("tap: buffer too small"); return -1; }
     if (hipMemcpyAsync(out, (const char*)workspace + t.off, (size_t)n * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return -1;
     return n;

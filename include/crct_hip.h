@@ -317,8 +317,9 @@ int crct_cast_runs_bf16_f32(const void* x, float* y, const int64_t* off, const i
  * (1 = attend); ctx bf16 [B][Tq][ldo].
  * Lengths: Tq, Tk <= CRCT_ATTN_MAX_LEN (512: the text position table of config/vilbert.json, i.e. every length the reference model can
  * embed; CRCT/options.py:27's default max_seq_len is 256, config/plotqa.json:5-6 trains at 124 text tokens x 44 visual elements) for
- * head sizes 32 / 48 / 64 -- the three of config/vilbert.json; any other head size (d <= 64,
- * d % 8 == 0) only up to 112 x 112.  Anything else is refused with an error, never truncated.
+ * head sizes 32 / 48 / 64 -- the three of config/vilbert.json -- and 128 -- the visual stream and co-attention of the original ViLBERT
+ * config (8 heads on 1024); any other head size (d <= 64, d % 8 == 0) only up to 112 x 112.  Anything else (80, 96, 112 among it) is
+ * refused with an error, never truncated.
  */
 #define CRCT_ATTN_MAX_LEN 512
 int crct_attention_fwd(const void* q, const void* k, const void* v, const uint8_t* keymask, void* ctx,
@@ -327,11 +328,11 @@ int crct_attention_fwd(const void* q, const void* k, const void* v, const uint8_
                        uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
                        crct_stream_t stream);
 /* Three implementations share these entry points: Tq, Tk <= 112 with d in {32, 48, 64} run register-resident MFMA kernels
- * (attention_mfma.hip); longer sequences with those head sizes a key-tile loop with online softmax on MFMA (attention_long.hip);
- * other head sizes up to 112 x 112 (and everything up to 112 x 112 after crct_attention_force_valu(1)) the fp32 VALU kernels.
- * Same dropout stream in all three. */
+ * (attention_mfma.hip); longer sequences with those head sizes, and d = 128 at every length, a key-tile loop with online softmax on MFMA
+ * (attention_long.hip; at d = 128 over image blocks of 256 rows); other head sizes up to 112 x 112 (and everything with d <= 64 up to
+ * 112 x 112 after crct_attention_force_valu(1); d = 128 keeps its MFMA kernels) the fp32 VALU kernels.  Same dropout stream in all three. */
 void crct_attention_force_valu(int on);
-/* Test hook: on != 0 sends every shape the long-sequence kernels can take (d in {32, 48, 64}) through them, short ones included. */
+/* Test hook: on != 0 sends every shape the long-sequence kernels can take (d in {32, 48, 64, 128}) through them, short ones included. */
 void crct_attention_force_long(int on);
 /* Test hook of the MFMA kernels: n = 1 / 2 / 4 waves per (batch, head) where the tile counts allow it, 0 = automatic.  Every
  * count computes the same bits (tests/test_kernels_gpu.py). */
@@ -351,7 +352,7 @@ int crct_attention_bwd(const void* q, const void* k, const void* v, const uint8_
  *   probs[b][h][i][j] = keep_ij / (1 - p) * softmax_j(q_i . k_j / sqrt(d) + (1 - keymask[b][j]) * -10000)      fp32 [B][heads][Tq][Tk], contiguous
  * q, k, keymask, the dropout arguments and the Philox numbering are crct_attention_fwd's: with the same (drop_thr, drop_scale,
  * drop_site, seed) a map carries the mask that forward applied; drop_thr = 0: no dropout.  One kernel for every Tq, Tk <=
- * CRCT_ATTN_MAX_LEN and every head size d % 8 == 0, d <= 64; ldq, ldk multiples of 8, q and k 16-byte aligned.  Anything else is
+ * CRCT_ATTN_MAX_LEN and every head size d % 8 == 0, d <= 64, and d = 128; ldq, ldk multiples of 8, q and k 16-byte aligned.  Anything else is
  * refused with an error before any launch. */
 int crct_attention_probs(const void* q, const void* k, const uint8_t* keymask, float* probs,
                          int B, int heads, int Tq, int Tk, int d, int64_t ldq, int64_t ldk,
@@ -829,6 +830,8 @@ int crct_event_query(void* ev);      /* 1 = complete, 0 = not yet, < 0 = error *
 
 /* Debug taps: copy a named bf16 activation ("emb.t", "t3.t", "c0.v", "seq_t" ...) of the last
  * forward (batch B, T, V) into `out` (device, bf16); returns the element count or -1.
+ * "t<i>.qkv" / "v<i>.qkv": the fused [rows][3 H] q | k | v buffer of a self layer; "c<i>.qkv1" (visual rows) / "c<i>.qkv2" (text rows):
+ * the two [rows][3 bi_hidden] buffers of a connection layer -- what the attention kernels and crct_engine_attention_probs read.
  * "grad.t" / "grad.v": the running hidden gradients, shaped like "seq_t" / "seq_v" -- the bf16 buffers the NEXT backward segment
  * reads, resolved at call time.  After segment 0 they hold the heads' gradient of seq_t / seq_v, after a layer's segment that
  * layer's input gradient on the stream(s) it touched.  Valid only between the crct_engine_backward(seg >= 0) calls of one pass,
