@@ -2,7 +2,7 @@
 // shape (config/plotqa.json:5-6: 124 text tokens x 44 visual elements; options.py:27 defaults to 256 tokens), up to
 // CRCT_ATTN_MAX_LEN = 512 queries x 512 keys (the text position table of config/vilbert.json) at head sizes 32 / 48 / 64, and at head size 128 (the original
 // ViLBERT config's visual stream and co-attention: 8 heads on 1024) for EVERY length 1 .. 512 -- the blocked kernels attn_fwd_blk /
-// attn_bwd_blk further down ("head size 128"), the same phases over image blocks of 256 rows.  Same math, same -10000 additive key mask, same
+// attn_bwd_blk further down ("head size 128"), the same tile steps over image blocks of 256 rows.  Same math, same -10000 additive key mask, same
 // Philox element numbering (and therefore the same dropout masks) as attention.hip / attention_mfma.hip:
 //   P = softmax(q k^T / sqrt(d) + (1 - keymask) * -10000) ; ctx = dropout(P) v
 // Reference: BertSelfAttention.forward vilbert.py:392-412, BertImageSelfAttention :522-543, BertBiAttention :684-723.
@@ -30,6 +30,16 @@
 //            too: O = (mask o P / (1 - p)) V) is a d-element dot product per query.  A quarter of the kernel's instructions.
 // Every output element is accumulated by ONE wave in a fixed order: no atomics, bit-reproducible.  The price is 9 d / 16 MFMAs
 // per tile pair instead of the minimal 5 d / 16 -- on < 3 % of the step's arithmetic.
+//
+// Every TILE STEP of the backward's loops is written once, as a __device__ function on ND that attn_bwd_long and attn_bwd_blk call with the
+// two resident images, the row offset of the tile within them (16 jt in the whole-image kernel, 16 jl within a block) and the GLOBAL tile
+// indices (Philox, key bias, keep cache): stats_tile (sweep 1), dq_tile (sweep 2), store_dq; kv_tile (phase B), store_dkv.  None of them
+// holds a workgroup barrier.  The kernels keep what differs: the LDS carve-up, load_image / load_block with every __syncthreads, the SHARE
+// fragment sources, the rounds, the sweep direction and where the keep words of sweep 1 live.  On the host: one launcher (launch_kern), one
+// rule for the dropout-bit cache (add_keep_cache).  STILL WRITTEN TWICE, change both: the forward's tile-pair step and epilogue
+// (attn_fwd_long, attn_fwd_blk) -- as functions they cost attn_fwd_long<4, 8> 5 % at 512 x 512 -- and phase A's kept statistics (the
+// `if constexpr (LSE)` blocks of the two backward kernels) -- as a function it moved h * d of attn_bwd_blk<8, 8, true> into 64-bit scalar
+// arithmetic with more SGPR spills, 0.7 % at 512 x 512 (profiles/attention_long_refactor.txt).
 #include "common.hip.h"
 #include "crct_internal.h"
 #include "attention_args.h"
@@ -37,7 +47,6 @@
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int SCR_STB = 48;                  // row stride of a wave's 16 x 16 bf16 transposition tile (32 B of data + 16)
 constexpr int LDS_CAP = 160 * 1024;
 
@@ -63,10 +72,6 @@ __device__ __forceinline__ void load_image(char* img, const bf16_t* __restrict__
     }
   }
 }
-// additive key term in the exp2 domain: 0 (attended), -10000 log2 e (masked), -inf (no such key: padding of the last tile)
-__device__ __forceinline__ void load_keybias(float* kb, const uint8_t* km, int Tk, int n, int tid, int nthr) {
-  for (int j = tid; j < n; j += nthr) kb[j] = j < Tk ? (km[j] ? 0.f : -10000.f * LOG2E) : -INFINITY;
-}
 // the lane's 8 keep bits of the key-tile PAIR jp for query i (bit 4 u + r: key 16 (2 jp + u) + 4 g + r is kept): one Philox call, the
 // numbering all three implementations share (attention_args.h, attn_keep8)
 __device__ __forceinline__ uint32_t keep_byte(const AttnArgs& a, long bh, int i, int jp, int g) {
@@ -82,26 +87,9 @@ __device__ __forceinline__ void store_tile_t(bf16_t* dst, uint8_t* qdst, long ld
   const uint2 pk = make_uint2(pack2bf(t[0], t[1]), pack2bf(t[2], t[3]));
   *reinterpret_cast<uint2*>(dst + row * ld + col0) = pk;
   if (qdst) {
-    constexpr float LIM = E4M3 ? 448.f : 57344.f;
-    const float qs = qscale[0];
-    float f[4] = {bf2f((bf16_t)(pk.x & 0xffff)), bf2f((bf16_t)(pk.x >> 16)), bf2f((bf16_t)(pk.y & 0xffff)), bf2f((bf16_t)(pk.y >> 16))};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { am = fmaxf(am, fabsf(f[r])); f[r] = fminf(fmaxf(f[r] * qs, -LIM), LIM); }
-    uint32_t o = 0u;
-    if constexpr (E4M3) {
-      o = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], o, false);
-      o = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], o, true);
-    } else {
-      o = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], o, false);
-      o = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], o, true);
-    }
-    *reinterpret_cast<uint32_t*>(qdst + row * ld + col0) = o;
+    const float f[4] = {bf2f((bf16_t)(pk.x & 0xffff)), bf2f((bf16_t)(pk.x >> 16)), bf2f((bf16_t)(pk.y & 0xffff)), bf2f((bf16_t)(pk.y >> 16))};
+    *reinterpret_cast<uint32_t*>(qdst + row * ld + col0) = sat_cvt4<E4M3>(f, qscale[0], am);
   }
-}
-__device__ __forceinline__ void wave_amax(float* dst, float am, int lane) {
-  am = fmaxf(am, __shfl_xor(am, 32, 64)); am = fmaxf(am, __shfl_xor(am, 16, 64)); am = fmaxf(am, __shfl_xor(am, 8, 64));
-  am = fmaxf(am, __shfl_xor(am, 4, 64)); am = fmaxf(am, __shfl_xor(am, 2, 64)); am = fmaxf(am, __shfl_xor(am, 1, 64));
-  if (lane == 0) amax_update(dst, am);
 }
 
 // LDS bytes: forward = K, V images of NKP = NK rounded up to 2 key tiles + the key bias; backward = Q, dO, K, V images (or, SHARE, one
@@ -115,6 +103,141 @@ inline size_t bwd_lds(int NQ, int NK, int ND, int NW, bool share) {
 // + the dropout bits of the whole score matrix, one byte per lane and tile pair (phase A writes, phase B reads): where it fits
 inline size_t keep_cache_bytes(int NQ, int NK) { return (size_t)64 * NQ * NK; }
 
+// ---------------------------------------------------------------------------------------------------------------- the tile steps
+// Tile indices passed to the steps (it: query tile, jt: key tile) are GLOBAL (Philox, key bias of every key of the pair in `kbias`, keep cache);
+// r0 is the row of the tile within the two images it is read from.  sc = scale log2 e; ds = 1 / (1 - p), 1 without dropout; bh = the (batch,
+// head) pair of the workgroup.  Backward, where `cached`: keepc holds the dropout bits phase A parks for phase B, [NQ][NK][64 lanes].
+// S^T and dP^T tiles of (key tile jt at row r0 of the K, V images, the wave's query fragments): s <- scores in the exp2 domain (scaled, key
+// bias added), gp <- (dO v^T)^T, unscaled and before the dropout mask
+template <int ND>
+__device__ __forceinline__ void score_tiles(f4_t& s, f4_t& gp, int lane, float sc, const float* kbias, const char* Ks, const char* Vs, int r0,
+                                            int jt, const s4_t (&qf)[ND], const s4_t (&of)[ND]) {
+  constexpr int STB = 32 * ND + 16;
+  s = f4_t{0.f, 0.f, 0.f, 0.f};
+  gp = f4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < ND; ++ks) {
+    s = mma16(frag_rows(Ks, STB, r0, 16 * ks, lane), qf[ks], s);
+    gp = mma16(frag_rows(Vs, STB, r0, 16 * ks, lane), of[ks], gp);
+  }
+  const f4_t kb = *reinterpret_cast<const f4_t*>(kbias + 16 * jt + 4 * (lane >> 4));
+#pragma unroll
+  for (int r = 0; r < 4; ++r) s[r] = fmaf(s[r], sc, kb[r]);
+}
+// The lane's 4 keep bits of (query tile it, key tile jt) where phase A makes them: one Philox call per tile PAIR (kb8 carries the pair's
+// byte from the even tile to the odd one; the caller walks the key tiles upwards from an even one), parked for phase B where `cached`
+__device__ __forceinline__ uint32_t make_keep_nibble(const AttnArgs& a, long bh, int lane, uint8_t* keepc, bool cached, int NK, int it, int jt,
+                                                     uint32_t& kb8) {
+  if (!(jt & 1)) kb8 = keep_byte(a, bh, 16 * it + (lane & 15), jt >> 1, lane >> 4);
+  const uint32_t nib = (kb8 >> (4 * (jt & 1))) & 0xfu;
+  if (cached) keepc[(it * NK + jt) * 64 + lane] = (uint8_t)nib;
+  return nib;
+}
+// Phase A sweep 1: row-statistics step of key tile jt -- m, l and dl = sum_j e_ij dP_ij accumulated online; returns the keep bits it made
+template <int ND>
+__device__ __forceinline__ uint32_t stats_tile(const AttnArgs& a, long bh, int lane, float sc, float ds, const float* kbias, uint8_t* keepc, bool cached,
+                                               int NK, const char* Ks, const char* Vs, int r0, int it, int jt, const s4_t (&qf)[ND],
+                                               const s4_t (&of)[ND], uint32_t& kb8, float& m, float& l, float& dl) {
+  f4_t s, gp;
+  score_tiles<ND>(s, gp, lane, sc, kbias, Ks, Vs, r0, jt, qf, of);
+  const float cm = xmax2(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
+  const float mn = fmaxf(m, cm);
+  const float alpha = __builtin_amdgcn_exp2f(m - mn);
+  const uint32_t nib = make_keep_nibble(a, bh, lane, keepc, cached, NK, it, jt, kb8);
+  float ps = 0.f, pd = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float e = __builtin_amdgcn_exp2f(s[r] - mn);
+    ps += e;
+    pd = fmaf(e, ((nib >> r) & 1u) ? gp[r] * ds : 0.f, pd);
+  }
+  l = fmaf(l, alpha, ps);
+  dl = fmaf(dl, alpha, pd);
+  m = mn;
+  return nib;
+}
+// Phase A sweep 2: dS^T = P^T (dP^T - delta) of key tile jt and dq^T += K^T dS^T.  The keep bits are sweep 1's (nib1) or, LSE (no sweep 1),
+// made and parked here
+template <int ND, bool LSE>
+__device__ __forceinline__ void dq_tile(const AttnArgs& a, long bh, int lane, float sc, float ds, const float* kbias, uint8_t* keepc, bool cached, int NK,
+                                        const char* Ks, const char* Vs, int r0, int it, int jt, const s4_t (&qf)[ND], const s4_t (&of)[ND],
+                                        uint32_t nib1, uint32_t& kb8, float m, float inv, float delta, f4_t (&dq)[ND]) {
+  constexpr int STB = 32 * ND + 16;
+  f4_t s, gp;
+  score_tiles<ND>(s, gp, lane, sc, kbias, Ks, Vs, r0, jt, qf, of);
+  uint32_t nib = nib1;
+  if constexpr (LSE) nib = make_keep_nibble(a, bh, lane, keepc, cached, NK, it, jt, kb8);
+  f4_t dsv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float p = __builtin_amdgcn_exp2f(s[r] - m) * inv;
+    dsv[r] = p * ((((nib >> r) & 1u) ? gp[r] * ds : 0.f) - delta);
+  }
+  const s4_t dsb = pack4(dsv);
+#pragma unroll
+  for (int ct = 0; ct < ND; ++ct) dq[ct] = mma16(frag_cols(Ks, STB, r0, 16 * ct, lane), dsb, dq[ct]);      // dq^T[c][i]
+}
+// Output stores of phase A (row i < Tq: dq, scaled) and, below, phase B (row j < Tk: dv, dk scaled), with their e5m2 copies
+template <int ND>
+__device__ __forceinline__ void store_dq(const AttnArgs& a, int b, int h, int lane, int i, const f4_t (&dq)[ND], float& am) {
+  constexpr int d = 16 * ND;
+  const int g = lane >> 4;
+#pragma unroll
+  for (int ct = 0; ct < ND; ++ct)
+    store_tile_t<false>(a.dq, a.dq_q, a.lddq, (long)b * a.Tq + i, h * d + 16 * ct + 4 * g, dq[ct] * a.scale, a.dq_qscale, am);
+}
+// Phase B: query tile `it` (at row r0 of the Q, dO images) for the wave's key tile jt (fragments kf, vf, key bias kb): S^T, dP^T, P and dS
+// from the row statistics, the two transpositions through the wave's LDS tile, dv^T += dO^T Pd and dk^T += Q^T dS
+template <int ND>
+__device__ __forceinline__ void kv_tile(const AttnArgs& a, long bh, int lane, float sc, float ds, uint8_t* keepc, bool cached, int NK,
+                                        const char* Qs, const char* Os, int r0, int it, int jt, const s4_t (&kf)[ND], const s4_t (&vf)[ND], f4_t kb,
+                                        const float4* stats, char* scr, f4_t (&dv)[ND], f4_t (&dk)[ND]) {
+  constexpr int STB = 32 * ND + 16;
+  const int g = lane >> 4, i = 16 * it + (lane & 15);
+  f4_t s = f4_t{0.f, 0.f, 0.f, 0.f}, gp = f4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < ND; ++ks) {
+    s = mma16(kf[ks], frag_rows(Qs, STB, r0, 16 * ks, lane), s);
+    gp = mma16(vf[ks], frag_rows(Os, STB, r0, 16 * ks, lane), gp);
+  }
+  const float4 st = stats[i];
+  const uint32_t nib = cached ? keepc[(it * NK + jt) * 64 + lane] : (keep_byte(a, bh, i, jt >> 1, g) >> (4 * (jt & 1))) & 0xfu;
+  f4_t pdv, dsv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float p = __builtin_amdgcn_exp2f(fmaf(s[r], sc, kb[r]) - st.x) * st.y;
+    const bool kp = (nib >> r) & 1u;
+    pdv[r] = kp ? p * ds : 0.f;
+    dsv[r] = p * ((kp ? gp[r] * ds : 0.f) - st.z);
+  }
+  // accumulator layout (query = column) -> [query][key] tile in LDS -> B operand of the products that contract over the queries
+  put_tile_t(scr, SCR_STB, 0, 0, pdv, lane);
+  wave_sync();
+  const s4_t pf = frag_cols(scr, SCR_STB, 0, 0, lane);
+  wave_sync();
+  put_tile_t(scr, SCR_STB, 0, 0, dsv, lane);
+  wave_sync();
+  const s4_t sf = frag_cols(scr, SCR_STB, 0, 0, lane);
+  wave_sync();
+#pragma unroll
+  for (int ct = 0; ct < ND; ++ct) {
+    dv[ct] = mma16(frag_cols(Os, STB, r0, 16 * ct, lane), pf, dv[ct]);       // dv^T[c][j] += dO[i][c] Pd[i][j]
+    dk[ct] = mma16(frag_cols(Qs, STB, r0, 16 * ct, lane), sf, dk[ct]);       // dk^T[c][j] += q[i][c] dS[i][j]
+  }
+}
+template <int ND>
+__device__ __forceinline__ void store_dkv(const AttnArgs& a, int b, int h, int lane, int j, const f4_t (&dv)[ND], const f4_t (&dk)[ND],
+                                          float& am) {
+  constexpr int d = 16 * ND;
+  const int g = lane >> 4;
+#pragma unroll
+  for (int ct = 0; ct < ND; ++ct) {
+    store_tile_t<false>(a.dv, a.dv_q, a.lddv, (long)b * a.Tk + j, h * d + 16 * ct + 4 * g, dv[ct], a.dkv_qscale, am);
+    store_tile_t<false>(a.dk, a.dk_q, a.lddk, (long)b * a.Tk + j, h * d + 16 * ct + 4 * g, dk[ct] * a.scale, a.dkv_qscale, am);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- whole images resident
 template <int ND, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_long(ATTN_HOT_PARAMS) {
   ATTN_HOT_UNPACK
@@ -197,24 +320,6 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long(ATTN_HOT_PARAMS) {
   if (a.ctx_q) wave_amax(a.ctx_qamax, am, lane);
 }
 
-// S^T and dP^T tiles of (key tile jt, the wave's query fragments): s <- scores in the exp2 domain (scaled, key bias added),
-// gp <- (dO v^T)^T, unscaled and before the dropout mask
-template <int ND>
-__device__ __forceinline__ void score_tiles(f4_t& s, f4_t& gp, const char* Ks, const char* Vs, const float* kbias, const s4_t (&qf)[ND],
-                                            const s4_t (&of)[ND], int jt, float sc, int lane) {
-  constexpr int STB = 32 * ND + 16;
-  s = f4_t{0.f, 0.f, 0.f, 0.f};
-  gp = f4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < ND; ++ks) {
-    s = mma16(frag_rows(Ks, STB, 16 * jt, 16 * ks, lane), qf[ks], s);
-    gp = mma16(frag_rows(Vs, STB, 16 * jt, 16 * ks, lane), of[ks], gp);
-  }
-  const f4_t kb = *reinterpret_cast<const f4_t*>(kbias + 16 * jt + 4 * (lane >> 4));
-#pragma unroll
-  for (int r = 0; r < 4; ++r) s[r] = fmaf(s[r], sc, kb[r]);
-}
-
 // SHARE = false: all four images resident (up to 256 x 256 x 64) -- every fragment out of LDS.  SHARE = true (beyond that, up to 512 x 512 x 64):
 // the images of the two phases share one space and a wave's OWN tile (q / dO in phase A, k / v in phase B) comes straight from global
 // memory; costs the PlotQA-shaped step 0.27 ms (18.95 against 18.68) where both fit, hence only where it must.
@@ -242,7 +347,6 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_long(ATTN_HOT_PARAMS) {
   // 16 jt + 4 g ..): one Philox call per lane and tile pair instead of two (~140 SIMD cycles a wave-call at 7 rounds:
   // tools/lab/philox_rate.hip; a fifth of this issue-bound kernel's instructions with dropout on)
   uint8_t* keepc = reinterpret_cast<uint8_t*>(kbias + 16 * NK) + NW * 16 * SCR_STB;
-  const bool cached = a.keep_cache != 0;
   const bf16_t* qg = a.q + (long)b * a.Tq * a.ldq + h * d;
   const bf16_t* og = a.dctx + (long)b * a.Tq * a.ldo + h * d;
   const bf16_t* kg = a.k + (long)b * a.Tk * a.ldk + h * d;
@@ -255,6 +359,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_long(ATTN_HOT_PARAMS) {
   load_image<ND>(Vs, vg, a.ldv, a.Tk, 16 * NK, tid, 64 * NW);
   load_keybias(kbias, a.keymask + (long)b * a.Tk, a.Tk, 16 * NK, tid, 64 * NW);
   __syncthreads();
+  const bool cached = a.keep_cache != 0;
   const float sc = a.scale * LOG2E, ds = a.thr ? a.dscale : 1.0f;
   float am_q = 0.f, am_kv = 0.f;
   // ---------------------------------------------------------------- phase A: statistics and dq of the wave's query tiles
@@ -291,32 +396,14 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_long(ATTN_HOT_PARAMS) {
 #pragma unroll
     for (int jo = 0; jo < 4; ++jo) {
       if (!LSE && 8 * jo < NK) {
-        uint32_t w = 0u, kb8 = 0xffu;
+        uint32_t kwo = 0u, kb8 = 0xffu;
         const int je = min(8, NK - 8 * jo);
 #pragma unroll 1
         for (int ji = 0; ji < je; ++ji) {
           const int jt = 8 * jo + ji;
-          f4_t s, gp;
-          score_tiles<ND>(s, gp, Ks, Vs, kbias, qf, of, jt, sc, lane);
-          const float cm = xmax2(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
-          const float mn = fmaxf(m, cm);
-          const float alpha = __builtin_amdgcn_exp2f(m - mn);
-          if (!(ji & 1)) kb8 = keep_byte(a, bh, i, jt >> 1, g);      // jt = 8 jo + ji: even ji = first tile of a pair
-          const uint32_t nib = (kb8 >> (4 * (ji & 1))) & 0xfu;
-          w |= nib << (4 * ji);
-          if (cached) keepc[(it * NK + jt) * 64 + lane] = (uint8_t)nib;
-          float ps = 0.f, pd = 0.f;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float e = __builtin_amdgcn_exp2f(s[r] - mn);
-            ps += e;
-            pd = fmaf(e, ((nib >> r) & 1u) ? gp[r] * ds : 0.f, pd);
-          }
-          l = fmaf(l, alpha, ps);
-          dl = fmaf(dl, alpha, pd);
-          m = mn;
+          kwo |= stats_tile<ND>(a, bh, lane, sc, ds, kbias, keepc, cached, NK, Ks, Vs, 16 * jt, it, jt, qf, of, kb8, m, l, dl) << (4 * ji);
         }
-        kw[jo] = w;
+        kw[jo] = kwo;
       }
     }
     const float inv = 1.0f / xsum2(l);
@@ -328,39 +415,18 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_long(ATTN_HOT_PARAMS) {
 #pragma unroll
     for (int jo = 0; jo < 4; ++jo) {
       if (8 * jo < NK) {
-        const uint32_t w = kw[jo];
+        const uint32_t kwo = kw[jo];
         uint32_t kb8 = 0xffu;
         const int je = min(8, NK - 8 * jo);
 #pragma unroll 1
         for (int ji = 0; ji < je; ++ji) {
           const int jt = 8 * jo + ji;
-          f4_t s, gp;
-          score_tiles<ND>(s, gp, Ks, Vs, kbias, qf, of, jt, sc, lane);
-          uint32_t nib;
-          if constexpr (LSE) {                     // no sweep 1: the dropout bits are made (and parked for phase B) here
-            if (!(ji & 1)) kb8 = keep_byte(a, bh, i, jt >> 1, g);
-            nib = (kb8 >> (4 * (ji & 1))) & 0xfu;
-            if (cached) keepc[(it * NK + jt) * 64 + lane] = (uint8_t)nib;
-          } else {
-            nib = (w >> (4 * ji)) & 0xfu;
-          }
-          f4_t dsv;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float p = __builtin_amdgcn_exp2f(s[r] - m) * inv;
-            dsv[r] = p * ((((nib >> r) & 1u) ? gp[r] * ds : 0.f) - delta);
-          }
-          const s4_t dsb = pack4(dsv);
-#pragma unroll
-          for (int ct = 0; ct < ND; ++ct) dq[ct] = mma16(frag_cols(Ks, STB, 16 * jt, 16 * ct, lane), dsb, dq[ct]);      // dq^T[c][i]
+          dq_tile<ND, LSE>(a, bh, lane, sc, ds, kbias, keepc, cached, NK, Ks, Vs, 16 * jt, it, jt, qf, of, (kwo >> (4 * ji)) & 0xfu, kb8, m, inv,
+                           delta, dq);
         }
       }
     }
-    if (i < a.Tq) {
-#pragma unroll
-      for (int ct = 0; ct < ND; ++ct)
-        store_tile_t<false>(a.dq, a.dq_q, a.lddq, (long)b * a.Tq + i, h * d + 16 * ct + 4 * g, dq[ct] * a.scale, a.dq_qscale, am_q);
-    }
+    if (i < a.Tq) store_dq<ND>(a, b, h, lane, i, dq, am_q);
   }
   if (a.dq_q) wave_amax(a.dq_qamax, am_q, lane);
   __syncthreads();                          // the statistics of every query tile are in LDS; every wave is done with the K, V images
@@ -388,46 +454,8 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_long(ATTN_HOT_PARAMS) {
 #pragma unroll
     for (int ct = 0; ct < ND; ++ct) { dv[ct] = f4_t{0.f, 0.f, 0.f, 0.f}; dk[ct] = f4_t{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll 1
-    for (int it = 0; it < NQ; ++it) {
-      const int i = 16 * it + n;
-      f4_t s = f4_t{0.f, 0.f, 0.f, 0.f}, gp = f4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < ND; ++ks) {
-        s = mma16(kf[ks], frag_rows(Qs, STB, 16 * it, 16 * ks, lane), s);
-        gp = mma16(vf[ks], frag_rows(Os, STB, 16 * it, 16 * ks, lane), gp);
-      }
-      const float4 st = stats[i];
-      const uint32_t nib = cached ? keepc[(it * NK + jt) * 64 + lane] : (keep_byte(a, bh, i, jt >> 1, g) >> (4 * (jt & 1))) & 0xfu;
-      f4_t pdv, dsv;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f(fmaf(s[r], sc, kb[r]) - st.x) * st.y;
-        const bool kp = (nib >> r) & 1u;
-        pdv[r] = kp ? p * ds : 0.f;
-        dsv[r] = p * ((kp ? gp[r] * ds : 0.f) - st.z);
-      }
-      // accumulator layout (query = column) -> [query][key] tile in LDS -> B operand of the products that contract over the queries
-      put_tile_t(scr, SCR_STB, 0, 0, pdv, lane);
-      wave_sync();
-      const s4_t pf = frag_cols(scr, SCR_STB, 0, 0, lane);
-      wave_sync();
-      put_tile_t(scr, SCR_STB, 0, 0, dsv, lane);
-      wave_sync();
-      const s4_t sf = frag_cols(scr, SCR_STB, 0, 0, lane);
-      wave_sync();
-#pragma unroll
-      for (int ct = 0; ct < ND; ++ct) {
-        dv[ct] = mma16(frag_cols(Os, STB, 16 * it, 16 * ct, lane), pf, dv[ct]);       // dv^T[c][j] += dO[i][c] Pd[i][j]
-        dk[ct] = mma16(frag_cols(Qs, STB, 16 * it, 16 * ct, lane), sf, dk[ct]);       // dk^T[c][j] += q[i][c] dS[i][j]
-      }
-    }
-    if (j < a.Tk) {
-#pragma unroll
-      for (int ct = 0; ct < ND; ++ct) {
-        store_tile_t<false>(a.dv, a.dv_q, a.lddv, (long)b * a.Tk + j, h * d + 16 * ct + 4 * g, dv[ct], a.dkv_qscale, am_kv);
-        store_tile_t<false>(a.dk, a.dk_q, a.lddk, (long)b * a.Tk + j, h * d + 16 * ct + 4 * g, dk[ct] * a.scale, a.dkv_qscale, am_kv);
-      }
-    }
+    for (int it = 0; it < NQ; ++it) kv_tile<ND>(a, bh, lane, sc, ds, keepc, cached, NK, Qs, Os, 16 * it, it, jt, kf, vf, kb, stats, scr, dv, dk);
+    if (j < a.Tk) store_dkv<ND>(a, b, h, lane, j, dv, dk, am_kv);
   }
   if (a.dv_q || a.dk_q) wave_amax(a.dkv_qamax, am_kv, lane);
 }
@@ -441,7 +469,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_long(ATTN_HOT_PARAMS) {
 // phase B.  A block that is already resident is not loaded again, and successive sweeps run over the blocks in alternating directions, so
 // with one block per side (up to 256 x 256) every image is loaded once and with two a sweep loads one block.  The order in which a tile's
 // blocks are accumulated is a function of the shape alone: still one wave per output element, a fixed order, no atomics.
-constexpr int BLK_T = 16;
+constexpr int BLK_T = 16;          // even: a key-tile pair never straddles two blocks
 static_assert(CRCT_ATTN_MAX_LEN <= 2 * 16 * BLK_T, "phase A keeps the dropout bits of at most two key blocks (kw0, kw1)");
 
 // LDS bytes: two image slots of min(tiles, BLK_T) tiles + key bias (forward: NK rounded up to a tile pair) [+ backward: row statistics,
@@ -565,8 +593,10 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_blk(ATTN_HOT_PARAMS) {
   if (a.ctx_q) wave_amax(a.ctx_qamax, am, lane);
 }
 
+// (the second launch bound is the least number of waves per SIMD the kernel is compiled for: 2 at 4 waves, where two workgroups share a CU
+// wherever their LDS fits, so a wave gets at most 256 registers; 1, the default, at 8 waves)
 template <int ND, int NW, bool LSE>
-__global__ __launch_bounds__(64 * NW) void attn_bwd_blk(ATTN_HOT_PARAMS) {
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_blk(ATTN_HOT_PARAMS) {
   ATTN_HOT_UNPACK
   constexpr int STB = 32 * ND + 16, d = 16 * ND;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -582,12 +612,12 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_blk(ATTN_HOT_PARAMS) {
   float* kbias = reinterpret_cast<float*>(stats + 16 * NQ);
   char* scr = reinterpret_cast<char*>(kbias + 16 * NK) + wv * 16 * SCR_STB;
   uint8_t* keepc = reinterpret_cast<uint8_t*>(kbias + 16 * NK) + NW * 16 * SCR_STB;      // as in attn_bwd_long
-  const bool cached = a.keep_cache != 0;
   const bf16_t* qg = a.q + (long)b * a.Tq * a.ldq + h * d;
   const bf16_t* og = a.dctx + (long)b * a.Tq * a.ldo + h * d;
   const bf16_t* kg = a.k + (long)b * a.Tk * a.ldk + h * d;
   const bf16_t* vg = a.v + (long)b * a.Tk * a.ldv + h * d;
   load_keybias(kbias, a.keymask + (long)b * a.Tk, a.Tk, 16 * NK, tid, 64 * NW);      // visible after load_block's barriers
+  const bool cached = a.keep_cache != 0;
   const float sc = a.scale * LOG2E, ds = a.thr ? a.dscale : 1.0f;
   float am_q = 0.f, am_kv = 0.f;
   int resident = -1, sweep = 0;
@@ -626,32 +656,13 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_blk(ATTN_HOT_PARAMS) {
         load_block<ND>(I0, I1, kg, a.ldk, vg, a.ldv, a.Tk, NK, blk, resident, tid, 64 * NW);
         if (!active) continue;
         const int je = min(NK - BLK_T * blk, BLK_T);
-        uint64_t w = 0ull;
+        uint64_t kwb = 0ull;
         uint32_t kb8 = 0xffu;
 #pragma unroll 1
-        for (int jl = 0; jl < je; ++jl) {
-          const int jt = BLK_T * blk + jl;
-          f4_t s, gp;
-          score_tiles<ND>(s, gp, I0, I1, kbias + 16 * BLK_T * blk, qf, of, jl, sc, lane);
-          const float cm = xmax2(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
-          const float mn = fmaxf(m, cm);
-          const float alpha = __builtin_amdgcn_exp2f(m - mn);
-          if (!(jl & 1)) kb8 = keep_byte(a, bh, i, jt >> 1, g);      // BLK_T is even: even jl = first tile of a pair
-          const uint32_t nib = (kb8 >> (4 * (jl & 1))) & 0xfu;
-          w |= (uint64_t)nib << (4 * jl);
-          if (cached) keepc[(it * NK + jt) * 64 + lane] = (uint8_t)nib;
-          float ps = 0.f, pd = 0.f;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float e = __builtin_amdgcn_exp2f(s[r] - mn);
-            ps += e;
-            pd = fmaf(e, ((nib >> r) & 1u) ? gp[r] * ds : 0.f, pd);
-          }
-          l = fmaf(l, alpha, ps);
-          dl = fmaf(dl, alpha, pd);
-          m = mn;
-        }
-        if (blk == 0) kw0 = w; else kw1 = w;
+        for (int jl = 0; jl < je; ++jl)
+          kwb |= (uint64_t)stats_tile<ND>(a, bh, lane, sc, ds, kbias, keepc, cached, NK, I0, I1, 16 * jl, it, BLK_T * blk + jl, qf, of, kb8, m, l,
+                                          dl) << (4 * jl);
+        if (blk == 0) kw0 = kwb; else kw1 = kwb;
       }
       ++sweep;
     }
@@ -667,38 +678,15 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_blk(ATTN_HOT_PARAMS) {
       load_block<ND>(I0, I1, kg, a.ldk, vg, a.ldv, a.Tk, NK, blk, resident, tid, 64 * NW);
       if (!active) continue;
       const int je = min(NK - BLK_T * blk, BLK_T);
-      const uint64_t w = blk == 0 ? kw0 : kw1;
+      const uint64_t kwb = blk == 0 ? kw0 : kw1;
       uint32_t kb8 = 0xffu;
 #pragma unroll 1
-      for (int jl = 0; jl < je; ++jl) {
-        const int jt = BLK_T * blk + jl;
-        f4_t s, gp;
-        score_tiles<ND>(s, gp, I0, I1, kbias + 16 * BLK_T * blk, qf, of, jl, sc, lane);
-        uint32_t nib;
-        if constexpr (LSE) {                     // no sweep 1: the dropout bits are made (and parked for phase B) here
-          if (!(jl & 1)) kb8 = keep_byte(a, bh, i, jt >> 1, g);
-          nib = (kb8 >> (4 * (jl & 1))) & 0xfu;
-          if (cached) keepc[(it * NK + jt) * 64 + lane] = (uint8_t)nib;
-        } else {
-          nib = (uint32_t)(w >> (4 * jl)) & 0xfu;
-        }
-        f4_t dsv;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = __builtin_amdgcn_exp2f(s[r] - m) * inv;
-          dsv[r] = p * ((((nib >> r) & 1u) ? gp[r] * ds : 0.f) - delta);
-        }
-        const s4_t dsb = pack4(dsv);
-#pragma unroll
-        for (int ct = 0; ct < ND; ++ct) dq[ct] = mma16(frag_cols(I0, STB, 16 * jl, 16 * ct, lane), dsb, dq[ct]);      // dq^T[c][i]
-      }
+      for (int jl = 0; jl < je; ++jl)
+        dq_tile<ND, LSE>(a, bh, lane, sc, ds, kbias, keepc, cached, NK, I0, I1, 16 * jl, it, BLK_T * blk + jl, qf, of,
+                         (uint32_t)(kwb >> (4 * jl)) & 0xfu, kb8, m, inv, delta, dq);
     }
     ++sweep;
-    if (active && i < a.Tq) {
-#pragma unroll
-      for (int ct = 0; ct < ND; ++ct)
-        store_tile_t<false>(a.dq, a.dq_q, a.lddq, (long)b * a.Tq + i, h * d + 16 * ct + 4 * g, dq[ct] * a.scale, a.dq_qscale, am_q);
-    }
+    if (active && i < a.Tq) store_dq<ND>(a, b, h, lane, i, dq, am_q);
   }
   if (a.dq_q) wave_amax(a.dq_qamax, am_q, lane);
   // ---------------------------------------------------------------- phase B: dv and dk of the wave's key tile of the round
@@ -726,59 +714,32 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_blk(ATTN_HOT_PARAMS) {
       const f4_t kb = *reinterpret_cast<const f4_t*>(kbias + 16 * jt + 4 * g);
       const int ie = min(NQ - BLK_T * blk, BLK_T);
 #pragma unroll 1
-      for (int il = 0; il < ie; ++il) {
-        const int it = BLK_T * blk + il, i = 16 * it + n;
-        f4_t s = f4_t{0.f, 0.f, 0.f, 0.f}, gp = f4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < ND; ++ks) {
-          s = mma16(kf[ks], frag_rows(I0, STB, 16 * il, 16 * ks, lane), s);
-          gp = mma16(vf[ks], frag_rows(I1, STB, 16 * il, 16 * ks, lane), gp);
-        }
-        const float4 st = stats[i];
-        const uint32_t nib = cached ? keepc[(it * NK + jt) * 64 + lane] : (keep_byte(a, bh, i, jt >> 1, g) >> (4 * (jt & 1))) & 0xfu;
-        f4_t pdv, dsv;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = __builtin_amdgcn_exp2f(fmaf(s[r], sc, kb[r]) - st.x) * st.y;
-          const bool kp = (nib >> r) & 1u;
-          pdv[r] = kp ? p * ds : 0.f;
-          dsv[r] = p * ((kp ? gp[r] * ds : 0.f) - st.z);
-        }
-        // accumulator layout (query = column) -> [query][key] tile in LDS -> B operand of the products that contract over the queries
-        put_tile_t(scr, SCR_STB, 0, 0, pdv, lane);
-        wave_sync();
-        const s4_t pf = frag_cols(scr, SCR_STB, 0, 0, lane);
-        wave_sync();
-        put_tile_t(scr, SCR_STB, 0, 0, dsv, lane);
-        wave_sync();
-        const s4_t sf = frag_cols(scr, SCR_STB, 0, 0, lane);
-        wave_sync();
-#pragma unroll
-        for (int ct = 0; ct < ND; ++ct) {
-          dv[ct] = mma16(frag_cols(I1, STB, 16 * il, 16 * ct, lane), pf, dv[ct]);       // dv^T[c][j] += dO[i][c] Pd[i][j]
-          dk[ct] = mma16(frag_cols(I0, STB, 16 * il, 16 * ct, lane), sf, dk[ct]);       // dk^T[c][j] += q[i][c] dS[i][j]
-        }
-      }
+      for (int il = 0; il < ie; ++il)
+        kv_tile<ND>(a, bh, lane, sc, ds, keepc, cached, NK, I0, I1, 16 * il, BLK_T * blk + il, jt, kf, vf, kb, stats, scr, dv, dk);
     }
-    if (active && j < a.Tk) {
-#pragma unroll
-      for (int ct = 0; ct < ND; ++ct) {
-        store_tile_t<false>(a.dv, a.dv_q, a.lddv, (long)b * a.Tk + j, h * d + 16 * ct + 4 * g, dv[ct], a.dkv_qscale, am_kv);
-        store_tile_t<false>(a.dk, a.dk_q, a.lddk, (long)b * a.Tk + j, h * d + 16 * ct + 4 * g, dk[ct] * a.scale, a.dkv_qscale, am_kv);
-      }
-    }
+    if (active && j < a.Tk) store_dkv<ND>(a, b, h, lane, j, dv, dk, am_kv);
   }
   if (a.dv_q || a.dk_q) wave_amax(a.dkv_qamax, am_kv, lane);
 }
 
-template <bool BWD, int ND, int NW, bool SHARE, bool LSE>
-hipError_t launch_nw(const AttnArgs& a, size_t lds, hipStream_t s) {
-  auto kern = BWD ? attn_bwd_long<ND, NW, SHARE, LSE> : attn_fwd_long<ND, NW>;
+// ---------------------------------------------------------------------------------------------------------------- host
+// every kernel of this file has one signature; NW waves per (batch, head)
+using attn_kernel_t = void (*)(ATTN_HOT_PARAMS);
+hipError_t launch_kern(attn_kernel_t kern, int NW, const AttnArgs& a, size_t lds, hipStream_t s) {
   const hipError_t e = crct_lds_limit(kern, lds > 64 * 1024 ? LDS_CAP : lds);
   if (e != hipSuccess) return e;
   if (a.ldq > 0x7fffffffL || a.ldk > 0x7fffffffL || a.ldv > 0x7fffffffL) return hipErrorInvalidValue;      // preloaded as 32-bit scalars
   crct_launch(kern, dim3(a.B * a.heads), dim3(64 * NW), lds, s, ATTN_HOT_ARGS(a) a);
   return hipGetLastError();
+}
+// Backward with dropout: the dropout-bit cache (keep_cache_bytes) joins the kernel's LDS where it fits and does not lower the number of
+// workgroups a CU's 160 KB hold
+inline void add_keep_cache(AttnArgs& a, size_t& lds, bool bwd, int NQ, int NK) {
+  a.keep_cache = 0;
+  if (bwd && a.thr && lds + keep_cache_bytes(NQ, NK) <= (size_t)LDS_CAP && LDS_CAP / (lds + keep_cache_bytes(NQ, NK)) == LDS_CAP / lds) {
+    a.keep_cache = 1;
+    lds += keep_cache_bytes(NQ, NK);
+  }
 }
 // Waves per (batch, head).  Forward: 8 when there are at least 8 query tiles to hand out, else 4.  Backward: phase A hands out the query
 // tiles, phase B the key tiles, so 8 waves only when BOTH sides have 8 tiles -- the co-attention shapes (124 x 44: 8 x 3 tiles) keep
@@ -787,6 +748,11 @@ hipError_t launch_nw(const AttnArgs& a, size_t lds, hipStream_t s) {
 inline int waves_for(bool bwd, int NQ, int NK) { return (bwd ? (NQ < NK ? NQ : NK) : NQ) >= 8 ? 8 : 4; }
 // backward: four resident images where they fit, the shared image pair beyond (bwd_share)
 inline bool bwd_share(int NQ, int NK, int ND, int NW) { return bwd_lds(NQ, NK, ND, NW, false) > (size_t)LDS_CAP; }
+template <int ND, int NW>
+attn_kernel_t bwd_long_kernel(bool share, bool lse) {
+  if (lse) return share ? attn_bwd_long<ND, NW, true, true> : attn_bwd_long<ND, NW, false, true>;
+  return share ? attn_bwd_long<ND, NW, true, false> : attn_bwd_long<ND, NW, false, false>;
+}
 template <bool BWD, int ND>
 hipError_t launch_d(const AttnArgs& a_in, hipStream_t s) {
   AttnArgs a = a_in;
@@ -794,31 +760,17 @@ hipError_t launch_d(const AttnArgs& a_in, hipStream_t s) {
   const int NW = waves_for(BWD, NQ, NK);
   const bool share = BWD && bwd_share(NQ, NK, ND, NW);
   size_t lds = BWD ? bwd_lds(NQ, NK, ND, NW, share) : fwd_lds(NK, ND);
-  a.keep_cache = 0;
-  // ... where it does not lower the number of workgroups a CU's 160 KB hold
-  if (BWD && a.thr && lds + keep_cache_bytes(NQ, NK) <= (size_t)LDS_CAP && LDS_CAP / (lds + keep_cache_bytes(NQ, NK)) == LDS_CAP / lds) {
-    a.keep_cache = 1;
-    lds += keep_cache_bytes(NQ, NK);
-  }
+  add_keep_cache(a, lds, BWD, NQ, NK);
+  attn_kernel_t kern;
   if constexpr (BWD) {
-    if (a.lse && a.ctx) {     // the forward's statistics and output are at hand: no statistics sweep
-      if (share) return NW == 8 ? launch_nw<true, ND, 8, true, true>(a, lds, s) : launch_nw<true, ND, 4, true, true>(a, lds, s);
-      return NW == 8 ? launch_nw<true, ND, 8, false, true>(a, lds, s) : launch_nw<true, ND, 4, false, true>(a, lds, s);
-    }
+    const bool lse = a.lse && a.ctx;      // the forward's statistics and output are at hand: no statistics sweep
+    kern = NW == 8 ? bwd_long_kernel<ND, 8>(share, lse) : bwd_long_kernel<ND, 4>(share, lse);
+  } else {
+    kern = NW == 8 ? attn_fwd_long<ND, 8> : attn_fwd_long<ND, 4>;
   }
-  if (share) return NW == 8 ? launch_nw<BWD, ND, 8, true, false>(a, lds, s) : launch_nw<BWD, ND, 4, true, false>(a, lds, s);
-  return NW == 8 ? launch_nw<BWD, ND, 8, false, false>(a, lds, s) : launch_nw<BWD, ND, 4, false, false>(a, lds, s);
+  return launch_kern(kern, NW, a, lds, s);
 }
 // head size 128: the blocked kernels, same wave counts and the same rule for the dropout-bit cache
-template <bool BWD, int ND, int NW, bool LSE>
-hipError_t launch_blk_nw(const AttnArgs& a, size_t lds, hipStream_t s) {
-  auto kern = BWD ? attn_bwd_blk<ND, NW, LSE> : attn_fwd_blk<ND, NW>;
-  const hipError_t e = crct_lds_limit(kern, lds > 64 * 1024 ? LDS_CAP : lds);
-  if (e != hipSuccess) return e;
-  if (a.ldq > 0x7fffffffL || a.ldk > 0x7fffffffL || a.ldv > 0x7fffffffL) return hipErrorInvalidValue;      // preloaded as 32-bit scalars
-  crct_launch(kern, dim3(a.B * a.heads), dim3(64 * NW), lds, s, ATTN_HOT_ARGS(a) a);
-  return hipGetLastError();
-}
 template <bool BWD, int ND>
 hipError_t launch_blk(const AttnArgs& a_in, hipStream_t s) {
   AttnArgs a = a_in;
@@ -826,15 +778,15 @@ hipError_t launch_blk(const AttnArgs& a_in, hipStream_t s) {
   const int NW = waves_for(BWD, NQ, NK);
   size_t lds = BWD ? bwd_blk_lds(NQ, NK, ND, NW) : fwd_blk_lds(NK, ND);
   if (lds > (size_t)LDS_CAP) return hipErrorInvalidValue;
-  a.keep_cache = 0;
-  if (BWD && a.thr && lds + keep_cache_bytes(NQ, NK) <= (size_t)LDS_CAP && LDS_CAP / (lds + keep_cache_bytes(NQ, NK)) == LDS_CAP / lds) {
-    a.keep_cache = 1;
-    lds += keep_cache_bytes(NQ, NK);
-  }
+  add_keep_cache(a, lds, BWD, NQ, NK);
+  attn_kernel_t kern;
   if constexpr (BWD) {
-    if (a.lse && a.ctx) return NW == 8 ? launch_blk_nw<true, ND, 8, true>(a, lds, s) : launch_blk_nw<true, ND, 4, true>(a, lds, s);
+    if (a.lse && a.ctx) kern = NW == 8 ? attn_bwd_blk<ND, 8, true> : attn_bwd_blk<ND, 4, true>;
+    else kern = NW == 8 ? attn_bwd_blk<ND, 8, false> : attn_bwd_blk<ND, 4, false>;
+  } else {
+    kern = NW == 8 ? attn_fwd_blk<ND, 8> : attn_fwd_blk<ND, 4>;
   }
-  return NW == 8 ? launch_blk_nw<BWD, ND, 8, false>(a, lds, s) : launch_blk_nw<BWD, ND, 4, false>(a, lds, s);
+  return launch_kern(kern, NW, a, lds, s);
 }
 template <bool BWD>
 hipError_t launch(const AttnArgs& a, hipStream_t s) {

@@ -113,9 +113,7 @@ __device__ __forceinline__ void store_rows_q(bf16_t* dst, uint8_t* qdst, long ld
     }
     *reinterpret_cast<uint2*>(qdst + (long)r * ld + cc) = make_uint2(o[0], o[1]);
   }
-  am = fmaxf(am, __shfl_xor(am, 32, 64)); am = fmaxf(am, __shfl_xor(am, 16, 64)); am = fmaxf(am, __shfl_xor(am, 8, 64));
-  am = fmaxf(am, __shfl_xor(am, 4, 64)); am = fmaxf(am, __shfl_xor(am, 2, 64)); am = fmaxf(am, __shfl_xor(am, 1, 64));
-  if (lane == 0) amax_update(amax_dst, am);
+  wave_amax(amax_dst, am, lane);
 }
 // bit 4*jt + r of the result: key 16*jt + 4*g + r exists and is attended (keymask != 0); `valid`: it exists.
 // Lane l reads keymask[l] (and [l + 64] for more than 64 keys), two wave ballots give every lane all the keys.
@@ -141,7 +139,7 @@ template <int NK>
 __device__ __forceinline__ void softmax_cols(f4_t (&s)[NK], uint32_t& keep, uint32_t attend, uint32_t valid, int Tk, int Tq, int i,
                                              long bh, const AttnArgs& a, int lane) {
   const int g = lane >> 4;
-  const float sc = a.scale * 1.4426950408889634f, off = -10000.f * 1.4426950408889634f;
+  const float sc = a.scale * LOG2E, off = -10000.f * LOG2E;
   float mx = -INFINITY;
 #pragma unroll
   for (int jt = 0; jt < NK; ++jt)

@@ -26,7 +26,6 @@
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int NW = 4;
 
 #ifdef CRCT_PROBS_NT

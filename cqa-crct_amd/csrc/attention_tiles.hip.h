@@ -1,5 +1,6 @@
 // Device helpers shared by the MFMA attention kernels (attention_mfma.hip: short sequences, everything in registers;
-// attention_long.hip: key-tile loop with online softmax): v_mfma_f32_16x16x16_bf16 fragments out of row-major LDS images.
+// attention_long.hip: key-tile loop with online softmax; attention_probs.hip): v_mfma_f32_16x16x16_bf16 fragments out of row-major LDS
+// images, the wave amax reduction and the saturating fp8 convert of the fp8 copies, LOG2E and the additive key term.
 #pragma once
 #include "common.hip.h"
 #include "attention_args.h"
@@ -45,6 +46,36 @@ __device__ __forceinline__ float xmax2(float v) {
 __device__ __forceinline__ float xsum2(float v) {
   v += __shfl_xor(v, 16, 64);
   return v + __shfl_xor(v, 32, 64);
+}
+
+// wave maximum of `am` into the amax slot of the workgroup (fp8 copies: CrctAttnQuant)
+__device__ __forceinline__ void wave_amax(float* dst, float am, int lane) {
+  am = fmaxf(am, __shfl_xor(am, 32, 64)); am = fmaxf(am, __shfl_xor(am, 16, 64)); am = fmaxf(am, __shfl_xor(am, 8, 64));
+  am = fmaxf(am, __shfl_xor(am, 4, 64)); am = fmaxf(am, __shfl_xor(am, 2, 64)); am = fmaxf(am, __shfl_xor(am, 1, 64));
+  if (lane == 0) amax_update(dst, am);
+}
+// four values -> four fp8 bytes of f * qs (E4M3: OCP e4m3, else e5m2), saturated to the format's largest finite value; am <- max(am, |f|)
+template <bool E4M3>
+__device__ __forceinline__ uint32_t sat_cvt4(const float (&v)[4], float qs, float& am) {
+  constexpr float LIM = E4M3 ? 448.f : 57344.f;
+  float f[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { am = fmaxf(am, fabsf(v[r])); f[r] = fminf(fmaxf(v[r] * qs, -LIM), LIM); }
+  uint32_t o = 0u;
+  if constexpr (E4M3) {
+    o = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], o, false);
+    o = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], o, true);
+  } else {
+    o = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], o, false);
+    o = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], o, true);
+  }
+  return o;
+}
+
+constexpr float LOG2E = 1.4426950408889634f;
+// additive key term in the exp2 domain: 0 (attended), -10000 log2 e (masked), -inf (no such key: padding of the last tile)
+__device__ __forceinline__ void load_keybias(float* kb, const uint8_t* km, int Tk, int n, int tid, int nthr) {
+  for (int j = tid; j < n; j += nthr) kb[j] = j < Tk ? (km[j] ? 0.f : -10000.f * LOG2E) : -INFINITY;
 }
 
 // fragment X[r0 + (lane & 15)][c0 + 4 (lane >> 4) + e] straight from global memory (rows >= T read as zero)

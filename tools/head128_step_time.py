@@ -6,10 +6,14 @@
 (b) one attention forward and one backward launch alone, 16 heads x 64 against 8 heads x 128 -- the same H = 1024, the same FLOPs -- at
     36 x 36, 124 x 44, 44 x 124, 124 x 124 and 512 x 512 (B 80; 512 x 512 at B 8), dropout 0.1.
 
-Every figure is device-event time over `--steps` (a) / `--iters` (b) repetitions after a warm-up, the median of `--rounds` alternating
+(c) only on request (--only long; not part of --only all): one forward and one backward launch (kept statistics, dropout 0.1) of attention_long.hip at the shapes the engine runs on
+    it -- 124 x 124 at 16 x 48, 124 x 44 and 44 x 124 at 32 x 32, the four d = 128 shapes, 512 x 512 at 16 x 64 and 8 x 128 (B 8).  With
+    --lib PATH the kernels come from that build of the library: two builds are compared by alternating processes.
+
+Every figure is device-event time over `--steps` (a) / `--iters` (b, c) repetitions after a warm-up, the median of `--rounds` alternating
 rounds, with the spread (min .. max) beside it.  One JSON line per figure.
 
-    python tools/head128_step_time.py [--steps 20] [--warmup 5] [--rounds 3] [--iters 50]
+    python tools/head128_step_time.py [--steps 20] [--warmup 5] [--rounds 3] [--iters 50] [--only all|step|attention|long] [--lib PATH]
 """
 import argparse
 import json
@@ -23,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cqa-crct_amd"))
 
 from crct import config as C                       # noqa: E402
+from crct import lib as L                          # noqa: E402
 from crct import ops                               # noqa: E402
 from crct import synthetic as S                    # noqa: E402
 from crct.model import VisualDialogEncoder         # noqa: E402
@@ -31,6 +36,8 @@ from crct.step_adapter import forward as step_forward   # noqa: E402
 
 STEP_SHAPES = {"configs[1]": (80, 36, 20), "plotqa-real": (80, 44, 124)}          # (B, V, T), F = 2048
 ATTN_SHAPES = [(80, 36, 36), (80, 124, 44), (80, 44, 124), (80, 124, 124), (8, 512, 512)]      # (B, Tq, Tk)
+LONG_SHAPES = [(80, 124, 124, 16, 48), (80, 124, 44, 32, 32), (80, 44, 124, 32, 32), (80, 36, 36, 8, 128), (80, 124, 44, 8, 128),
+               (80, 44, 124, 8, 128), (80, 124, 124, 8, 128), (8, 512, 512, 16, 64), (8, 512, 512, 8, 128)]      # (B, Tq, Tk, heads, d)
 
 
 def timed(fn, n):
@@ -111,14 +118,42 @@ def attention_times(args, dev):
                         model_gflop=round(flops * (1.0 if direction == "fwd" else 2.5) / 1e9, 3)), s, unit="us")
 
 
+def long_times(args, dev):
+    for B, Tq, Tk, heads, d in LONG_SHAPES:
+        g = torch.Generator().manual_seed(Tq * 1000 + Tk)
+        H = heads * d
+        q = torch.randn(B, Tq, H, generator=g).to(dev).bfloat16()
+        k, v = (torch.randn(B, Tk, H, generator=g).to(dev).bfloat16() for _ in range(2))
+        do = torch.randn(B, Tq, H, generator=g).to(dev).bfloat16()
+        km = torch.ones(B, Tk, dtype=torch.uint8, device=dev)
+        ctx, dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(k), torch.empty_like(k)
+        lse = torch.empty(B, heads, Tq, device=dev)
+        kw = dict(p_drop=0.1, site=3, seed=9)
+        calls = {"fwd": lambda: ops.attention_fwd(q, k, v, km, heads, d, row_lse=lse, out=ctx, **kw),
+                 "bwd": lambda: ops.attention_bwd(q, k, v, km, do, heads, d, row_lse=lse, ctx=ctx, outs=(dq, dk, dv), **kw)}
+        for fn in calls.values():
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        samples = {key: [] for key in calls}
+        for _ in range(args.rounds):
+            for key, fn in calls.items():
+                samples[key].append(1e3 * timed(fn, args.iters))
+        for direction, s in samples.items():
+            report(dict(what="long_" + direction, heads=heads, d=d, B=B, Tq=Tq, Tk=Tk, iters=args.iters, lib=args.lib or "package"), s, unit="us")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--only", choices=("all", "step", "attention"), default="all")
+    ap.add_argument("--only", choices=("all", "step", "attention", "long"), default="all")
+    ap.add_argument("--lib", default=None, help="another build of libcrct_hip.so to load instead of the package's")
     args = ap.parse_args()
+    if args.lib:
+        L.LIB_PATH = os.path.abspath(args.lib)
     if not torch.cuda.is_available():
         raise SystemExit("head128_step_time.py measures on the GPU; none found")
     dev = torch.device("cuda:0")
@@ -126,6 +161,8 @@ def main():
         attention_times(args, dev)
     if args.only in ("all", "step"):
         step_times(args, dev)
+    if args.only == "long":
+        long_times(args, dev)
 
 
 if __name__ == "__main__":
