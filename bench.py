@@ -9,10 +9,19 @@ inputs, dropout ENABLED (p = 0.1), config ``config/vilbert.json`` with ``v_featu
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                # ... or under a launcher that has set RANK / WORLD_SIZE already
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # ... and write what the last timed step computed to DIR/*.npy
+    python bench.py --gpus 1 --steps K --warmup W --full               # ... and every further measurement listed below
+
+A plain run does what its headline figure needs and nothing else: set up, W warm-up steps, K timed steps, the outputs of
+--dump-outputs, the result line.  Every other leg -- the sustained and PCIe-inclusive legs, the stand-alone gradient all-reduce,
+the stamped steps behind `roofline` / config.gemm_sites / config.gemm_variants / config.critical_path, the CPU baseline -- takes
+steps or seconds of its own and runs only under --full (where --sustained-s 0, --no-h2d-leg, --profile-steps 0 and
+--no-cpu-baseline still switch single legs off).  The line of a plain run has the same fields; what was not measured is null,
+and `roofline`, `cpu_baseline` and `value_h2d_inclusive` are absent.
 
 Prints ONE JSON line on rank 0:
   value        : whole-job QA-pairs/s with the batches already resident in HBM when the timed region starts (a pool of 8
                  pre-staged batches is rotated).
+ The rest under --full only:
   config.h2d_inclusive : the same step fed from PAGEABLE HOST batches through crct.input_pipeline.DevicePrefetcher (one
                  pinned staging buffer and ONE async copy per batch on a copy stream, double-buffered; features shipped
                  as bf16 unless --host-feat fp32), measured in the same run -- the PCIe-inclusive rate.
@@ -81,23 +90,28 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every leg that takes steps or seconds of its own: "
+                    "config.sustained, config.h2d_inclusive, the stand-alone all-reduce of config.gradient_allreduce, the stamped steps behind "
+                    "`roofline` / config.gemm_sites / config.gemm_variants / config.critical_path, and `cpu_baseline` (default: none of them; "
+                    "--sustained-s 0, --no-h2d-leg, --profile-steps 0 and --no-cpu-baseline switch single legs of a --full run off)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None, help="a named shape (sets --batch / --vis / --tokens / --feat): %s"
                     % ", ".join("%s = B %d, V %d, T %d, F_v %d" % ((k,) + v) for k, v in sorted(WORKLOADS.items())))
     ap.add_argument("--batch", type=int, default=80)
     ap.add_argument("--vis", type=int, default=36)
     ap.add_argument("--tokens", type=int, default=20)
     ap.add_argument("--feat", type=int, default=2048)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU leg (cpu_baseline)")
     ap.add_argument("--cpu-batch", type=int, default=80)
-    ap.add_argument("--profile-steps", type=int, default=3)
+    ap.add_argument("--profile-steps", type=int, default=3, help="--full: extra steps with stamped GEMM launches (roofline, config.gemm_sites / "
+                    "gemm_variants) and, at most two of them, with every launch stamped (config.critical_path); 0 = skip")
     ap.add_argument("--bucket-mb", type=int, default=64)
     ap.add_argument("--input", choices=("resident", "prefetch", "sync"), default="resident",
                     help="what `value` is measured on.  resident: batches already in HBM (the contract's headline); prefetch: pageable "
                          "host batches through crct.input_pipeline.DevicePrefetcher; sync: pageable host batches moved by the step "
                          "adapter's synchronous .to(device), as the reference does")
-    ap.add_argument("--sustained-s", type=float, default=2.0, help="length in seconds of the extra sustained leg (config.sustained): the same step "
+    ap.add_argument("--sustained-s", type=float, default=2.0, help="--full: length in seconds of the extra sustained leg (config.sustained): the same step "
                     "repeated back to back for at least this long, so that an outside sampler (rocm-smi, 5 s period) sees the GPU busy; 0 = skip")
-    ap.add_argument("--no-h2d-leg", action="store_true", help="skip the PCIe-inclusive leg (config.h2d_inclusive)")
+    ap.add_argument("--no-h2d-leg", action="store_true", help="--full without the PCIe-inclusive leg (config.h2d_inclusive)")
     ap.add_argument("--host-feat", choices=("bf16", "fp32"), default="bf16", help="dtype of image_feat in the host batches of the prefetch legs")
     ap.add_argument("--fuse-zero-grad", action="store_true", help="AdamW zeroes the gradients it consumes (measured: no gain)")
     ap.add_argument("--eager-zero-grad", action="store_true", help="zero_grad() fills the whole gradient buffer and backward "
@@ -614,9 +628,11 @@ def main():
         parts = [[S.make_batch(a.batch, a.tokens, a.vis, a.feat, seed=1234 + r + 97 * i) for r in range(a.emulate_ranks)] for i in range(8)]
         host_pool = [{k: torch.cat([p[k] for p in ps], 0) for k in ps[0]} for ps in parts]
     dev_pool = [stage(b, dev) for b in host_pool]
-    host_feed = host_pool
-    if a.host_feat == "bf16":                        # the data loader ships bf16 features: half the H2D bytes of the step
-        host_feed = [dict(b, image_feat=b["image_feat"].to(torch.bfloat16)) for b in host_pool]
+
+    def host_feed():                                 # the host batches of the prefetch legs, made when one of them starts
+        if a.host_feat == "bf16":                    # the data loader ships bf16 features: half the H2D bytes of the step
+            return [dict(b, image_feat=b["image_feat"].to(torch.bfloat16)) for b in host_pool]
+        return host_pool
 
     def forever(pool):
         while True:
@@ -630,7 +646,7 @@ def main():
         nonlocal prefetcher
         if kind == "prefetch":
             if prefetcher is None:
-                prefetcher = iter(DevicePrefetcher(forever(host_feed), dev, depth=2))
+                prefetcher = iter(DevicePrefetcher(forever(host_feed()), dev, depth=2))
             return prefetcher
         return feeds[kind]
 
@@ -699,7 +715,7 @@ def main():
     qa_per_s = a.batch * a.emulate_ranks * world * a.steps / dt
 
     sustained = None
-    if a.sustained_s > 0:
+    if a.full and a.sustained_s > 0:
         # the timed region above is K steps (0.15 s at the driver's K = 20): too short for any outside observer of GPU utilisation.
         # The same step, resident batches, for >= sustained_s seconds; reported next to the headline, never instead of it.
         n_sus = max(a.steps, int(a.sustained_s / max(dt / a.steps, 1e-4)) + 1)
@@ -707,7 +723,7 @@ def main():
         sustained = {"seconds": dt_s, "steps": n_sus, "ms_per_step": dt_s / n_sus * 1e3,
                      "qa_pairs_per_s": a.batch * a.emulate_ranks * world * n_sus / dt_s}
     h2d = None
-    if a.input == "resident" and not a.no_h2d_leg:
+    if a.full and a.input == "resident" and not a.no_h2d_leg:
         cur["feed"] = feed_of("prefetch")
         for _ in range(max(5, a.warmup // 2)):       # both slots' pinned / device buffers and the worker thread exist after two batches
             run_step()
@@ -739,15 +755,17 @@ def main():
                 rc.all_reduce_(buf, aux)
             else:
                 dist.all_reduce(buf)
-        torch.cuda.synchronize()
-        for _ in range(2):
-            all_reduce()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(5):
-            all_reduce()
-        torch.cuda.synchronize()
-        ar = (time.perf_counter() - t1) / 5
+        ar = None                    # seconds per stand-alone all-reduce: 2 + 5 collectives of their own
+        if a.full:
+            torch.cuda.synchronize()
+            for _ in range(2):
+                all_reduce()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(5):
+                all_reduce()
+            torch.cuda.synchronize()
+            ar = (time.perf_counter() - t1) / 5
         from crct import rccl as RC
         comm = {"rccl": {"version": RC.version()[1], "env": RC.env_seen(), "route": "direct ncclAllReduce (crct/rccl.py)" if rc is not None else "torch.distributed",
                          "direct_route_fallback_reason": getattr(ddp, "rccl_fallback", None),
@@ -758,8 +776,8 @@ def main():
                                note="one-GPU prediction of the %d-rank step: per bucket a kernel of %d workgroups streams the payload twice through HBM and holds "
                                     "its stream for payload x 2 (N - 1) / N / bus bandwidth (crct_ghost_collective); nothing is reduced"
                                     % (ddp.ghost["ranks"], ddp.ghost["channels"])) if ddp.ghost else None),
-                "allreduce_bytes": used * 4, "allreduce_ms": ar * 1e3,
-                "bus_GBps": 2.0 * (world - 1) / world * used * 4 / ar / 1e9,
+                "allreduce_bytes": used * 4, "allreduce_ms": ar * 1e3 if ar else None,
+                "bus_GBps": 2.0 * (world - 1) / world * used * 4 / ar / 1e9 if ar else None,
                 "step_payload": {"dtype": a.grad_dtype, "bytes_per_step": used * (2 if a.grad_dtype == "bf16" else 4),
                                  "buckets": len(ddp._buckets or ()), "bucket_mb_of_fp32_gradients": a.bucket_mb,
                                  "collectives_issued_inside_the_backward_call": ddp.issued_inside_engine_call,
@@ -769,9 +787,9 @@ def main():
                                  "single_rank_forced": bool(a.force_exchange and world == 1)}}
 
     # profiled steps run on EVERY rank (they contain the collectives of a normal step); only rank 0 reads the stamps
-    rows, sites = gemm_profile(run_step, a.profile_steps) if a.profile_steps > 0 else ([], [])
+    rows, sites = gemm_profile(run_step, a.profile_steps) if a.full and a.profile_steps > 0 else ([], [])
     # ... and so do the stamped steps behind config.critical_path (every library kernel with its own begin / end stamps)
-    crit = critical_path(run_step, core, min(a.profile_steps, 2)) if a.profile_steps > 0 else None
+    crit = critical_path(run_step, core, min(a.profile_steps, 2)) if a.full and a.profile_steps > 0 else None
     # the instruction each pass of the fp8 mode issues decides the peak its GEMMs are priced against: the block-scaled fp8 MFMA
     # (v_mfma_scale_f32_16x16x128_f8f6f4, unit scales) runs at twice the bf16 rate -- 5 PFLOP/s dense (MI355X_MICROARCH.md)
     kind_peak = {}
@@ -829,7 +847,7 @@ def main():
                                                         "ms_per_step": dom["ms_per_step"]},
                                "timing": "kernel begin / end stamps (hipExtLaunchKernelGGL start / stop events), %d profiled steps, in the step "
                                          "(other streams' kernels run beside each launch)" % a.profile_steps}
-        if not a.no_cpu_baseline:      # rank 0 only, after the timed region (its peers wait at the closing barrier meanwhile)
+        if a.full and not a.no_cpu_baseline:      # rank 0 only, after the timed region (its peers wait at the closing barrier meanwhile)
             out["cpu_baseline"] = cpu_baseline(core, cfg, params, a.cpu_batch, a.tokens, a.vis, a.feat)
         print(json.dumps(out), flush=True)
     if prefetcher is not None:

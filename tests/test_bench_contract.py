@@ -1,6 +1,7 @@
-"""The committed bench line (profiles/r4_bench_n1.json, written by `python bench.py` on the GPU box) keeps the
+"""The committed bench line (profiles/r4_bench_n1.json, what `python bench.py --full` prints on an MI355X) keeps the
 contract the driver parses: metric / unit of BASELINE.json, whole-job value, and the `roofline` and `cpu_baseline`
-objects.  Runs on CPU: it checks the artifact, not the GPU."""
+objects of a --full run.  Runs on CPU: it checks the artifact, not the GPU.  Below it: the command line (plain run
+against --full), the self-launch path and the --dump-outputs writer on CPU, and the benchmark itself on the GPU."""
 import json
 import os
 
@@ -71,6 +72,24 @@ def test_driver_entry_points_are_there():
     g.build()
     for top in ("bench.py", "DESIGN.md", "INTEGRATION.md", "include/crct_hip.h", "oracle/crct_oracle.py"):
         assert os.path.getsize(os.path.join(ROOT, top)) > 1000, top
+
+
+def test_full_is_an_option_that_is_off_by_default(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` is the plain run (set-up, warm-up, timed steps, the line); --full asks for every
+    further leg, and the switches of the single legs keep their defaults, so that --full alone runs them all."""
+    import sys
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    plain = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+    monkeypatch.setattr(sys, "argv", plain)
+    a = bench.parse()
+    assert a.full is False and (a.gpus, a.steps, a.warmup) == (1, 7, 2)
+    assert a.sustained_s > 0 and a.profile_steps > 0 and not a.no_h2d_leg and not a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", plain + ["--full"])
+    b = bench.parse()
+    assert b.full is True
+    assert {k: v for k, v in vars(b).items() if k != "full"} == {k: v for k, v in vars(a).items() if k != "full"}
 
 
 def test_bench_starts_its_own_ranks():
@@ -150,7 +169,9 @@ def test_two_rank_bench_runs_end_to_end(tmp_path):
     --gpus 2 ...`), on this one-GPU box with both ranks on cuda:0 and gloo between them (CRCT_BENCH_SHARE_GPU: a developer
     switch that changes the process group only): FlatGradDDP in event mode, the stats all-reduce inside the step, the
     overlapped optimizer, max-over-ranks timing, ONE JSON line from rank 0.  (Round 2 shipped for a while with an in-place
-    all-reduce on the buffer the loss is a view of -- every N > 1 run died in backward; this test is the guard.)"""
+    all-reduce on the buffer the loss is a view of -- every N > 1 run died in backward; this test is the guard.)
+    The self-launched run is a --full one (with the legs `common` switches off): the sustained leg and the stand-alone all-reduce
+    run with the exchange on; the other three are plain runs and report neither."""
     import subprocess
     import sys
     env = dict({k: v for k, v in os.environ.items() if not k.startswith("CRCT_")},        # bench.py refuses stray CRCT_* switches
@@ -168,7 +189,7 @@ def test_two_rank_bench_runs_end_to_end(tmp_path):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grad-dtype", dtype.split("+")[0]] + extra + common
         if dtype == "bf16":      # the default payload WITHOUT a launcher: exactly `python bench.py --gpus 2 ...`, which starts its own two ranks
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grad-dtype", "bf16"] + common
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grad-dtype", "bf16", "--full"] + common
         res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
         rows = [r for r in res.stdout.strip().split("\n") if r.startswith("{")]
@@ -181,6 +202,13 @@ def test_two_rank_bench_runs_end_to_end(tmp_path):
         if dtype.startswith("bf16"):      # the weight-gradient GEMMs wrote the communication buffer themselves (lazy clears from step 2 on)
             assert pay["weight_gradients_written_as_bf16_by_the_gemms"] is True
         assert line["dtype"] == ("fp8" if dtype.endswith("fp8") else "bf16")
+        comm = line["config"]["gradient_allreduce"]
+        if dtype == "bf16":      # --full: 2 s worth of steps (at the timed steps' pace) after the timed ones, and the flat gradient buffer all-reduced on its own
+            assert line["config"]["sustained"]["steps"] >= 2.0 / (line["ms_per_step"] * 1e-3) and line["config"]["sustained"]["seconds"] > 0
+            assert comm["allreduce_ms"] > 0 and comm["bus_GBps"] > 0
+        else:
+            assert line["config"]["sustained"] is None and comm["allreduce_ms"] is None and comm["bus_GBps"] is None
+        assert comm["allreduce_bytes"] > 0 and comm["rccl"]["world"] == 2
         losses[dtype] = line["config"]["global_loss"]
     # the same four optimizer steps by ONE rank on the concatenation of the two ranks' batches: the data-parallel run must land on
     # the same mean loss (1/world folded into the gradient seeds, SUM all-reduce, every rank applying the same update)
@@ -200,3 +228,51 @@ def test_two_rank_bench_runs_end_to_end(tmp_path):
     assert abs(losses["fp32"] - ref) <= 2e-3 * abs(ref), (losses, ref)       # different batch split -> other summation orders / bf16 roundings
     assert abs(losses["bf16"] - ref) <= 5e-3 * abs(ref), (losses, ref)
     assert abs(losses["bf16+fp8"] - ref) <= 3e-2 * abs(ref), (losses, ref)   # e4m3 / e5m2 GEMMs: the loss moves by a per cent or so
+
+
+LEGS = ("sustained", "h2d_inclusive", "critical_path")      # config keys of legs with steps of their own: null in a plain line
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_full_adds_every_leg(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` reports the headline and what describes the timed steps, and none of the
+    legs that take steps of their own; --full reports them all (the CPU leg switched off here: it alone takes ~20 s) next to the
+    same headline fields.  Without dropout both runs compute the same steps, so the last timed step's loss is the same number and
+    the arrays of --dump-outputs are the same bits: --full adds work after the timed steps and changes nothing in them."""
+    import subprocess
+    import sys
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CRCT_") and k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    lines = {}
+    for kind, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--sustained-s", "0.2"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16", "--no-dropout",
+               "--dump-outputs", str(tmp_path / kind)] + extra
+        res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        rows = [r for r in res.stdout.strip().split("\n") if r.startswith("{")]
+        assert len(rows) == 1, rows
+        lines[kind] = json.loads(rows[0])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["metric"] == "QA-pairs/sec training step (whole node)" and line["unit"] == "QA-pairs/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "bf16" and line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
+        assert line["ms_per_step"] > 0 and abs(line["value"] - 16 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+        assert line["config"]["schedule"]["optimizer_overlap"] is True and line["config"]["host_enqueue_ms_per_step"] > 0
+    # the plain line: the same config keys, nothing measured outside the timed steps
+    assert set(plain["config"]) == set(full["config"])
+    for key in ("roofline", "cpu_baseline", "value_h2d_inclusive", "ms_per_step_h2d_inclusive"):
+        assert key not in plain, key
+    assert all(plain["config"][k] is None for k in LEGS) and plain["config"]["gemm_sites"] == [] and plain["config"]["gemm_variants"] == []
+    # the --full line: every leg that was asked for
+    assert "cpu_baseline" not in full                                        # --no-cpu-baseline
+    assert full["config"]["sustained"]["steps"] >= 0.2 / (full["ms_per_step"] * 1e-3) and full["config"]["sustained"]["ms_per_step"] > 0      # 0.2 s at the timed pace
+    assert full["value_h2d_inclusive"] == full["config"]["h2d_inclusive"]["qa_pairs_per_s"] > 0
+    assert full["config"]["critical_path"]["launches_per_step"] > 100 and len(full["config"]["gemm_sites"]) > 20 and full["config"]["gemm_variants"]
+    r = full["roofline"]
+    assert r["bound"] == "mfma" and abs(r["peak"] - 2500.0) < 1e-6 and 0.0 < r["frac"] < 1.0 and r["ffn"]["t.ffn_up.fwd"]["us"] > 0      # peak = FLOPs / ideal time: a quotient
+    # the timed steps are the same steps
+    assert plain["config"]["final_loss"] == full["config"]["final_loss"]
+    names = sorted(os.listdir(str(tmp_path / "plain")))
+    assert names == sorted(os.listdir(str(tmp_path / "full"))) and "params_after_step.npy" in names
+    for n in names:
+        assert np.array_equal(np.load(str(tmp_path / "plain" / n)), np.load(str(tmp_path / "full" / n))), n

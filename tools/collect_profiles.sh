@@ -72,22 +72,22 @@ python tools/lab/fp8_draws.py 2>&1 | grep -v "$F" > $O/${tag}_fp8_parity_draws.t
 ./tools/lab/tr8_probe.bin > $O/${tag}_tr8_probe.txt 2>&1
 fi
 if want bench; then
-python bench.py --steps 20 --warmup 5 2> $O/${tag}_bench_n1.err | grep '^{' > $O/${tag}_bench_n1.json
-python bench.py --steps 20 --warmup 5 --dtype fp8 --no-cpu-baseline 2> $O/${tag}_bench_n1_fp8.err | grep '^{' > $O/${tag}_bench_n1_fp8.json
-python bench.py --steps 20 --warmup 5 --dtype fp8 --fp8-bf16-wgrad --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_fp8_bf16_wgrad.json
-python bench.py --steps 20 --warmup 5 --dtype fp8 --fp8-forward-only --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_fp8_forward_only.json
-python bench.py --steps 20 --warmup 5 --dtype fp8 --fp8-bf16-forward --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_fp8_bf16_forward.json
-python bench.py --steps 20 --warmup 5 $LC --no-cpu-baseline 2> $O/${tag}_bench_n1_longctx.err | grep '^{' > $O/${tag}_bench_n1_longctx.json
-python bench.py --steps 20 --warmup 5 $LC --dtype fp8 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_longctx_fp8.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --force-exchange --exchange-pack-all 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_forced_exchange_pack_all.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --force-exchange --dtype fp8 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_forced_exchange_fp8.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --force-exchange 2> $O/${tag}_bench_n1_forced_exchange.err | grep '^{' > $O/${tag}_bench_n1_forced_exchange.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --force-exchange --grad-dtype fp32 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_forced_exchange_fp32.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --force-exchange --ghost-ranks 8 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_ghost8.json
-python bench.py --steps 20 --warmup 5 --workload plotqa-real 2> $O/${tag}_bench_n1_plotqa_real.err | grep '^{' > $O/${tag}_bench_n1_plotqa_real.json
+python bench.py --full --steps 20 --warmup 5 2> $O/${tag}_bench_n1.err | grep '^{' > $O/${tag}_bench_n1.json
+python bench.py --full --steps 20 --warmup 5 --dtype fp8 --no-cpu-baseline 2> $O/${tag}_bench_n1_fp8.err | grep '^{' > $O/${tag}_bench_n1_fp8.json
+python bench.py --full --steps 20 --warmup 5 --dtype fp8 --fp8-bf16-wgrad --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_fp8_bf16_wgrad.json
+python bench.py --full --steps 20 --warmup 5 --dtype fp8 --fp8-forward-only --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_fp8_forward_only.json
+python bench.py --full --steps 20 --warmup 5 --dtype fp8 --fp8-bf16-forward --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_fp8_bf16_forward.json
+python bench.py --full --steps 20 --warmup 5 $LC --no-cpu-baseline 2> $O/${tag}_bench_n1_longctx.err | grep '^{' > $O/${tag}_bench_n1_longctx.json
+python bench.py --full --steps 20 --warmup 5 $LC --dtype fp8 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_longctx_fp8.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --force-exchange --exchange-pack-all 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_forced_exchange_pack_all.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --force-exchange --dtype fp8 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_forced_exchange_fp8.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --force-exchange 2> $O/${tag}_bench_n1_forced_exchange.err | grep '^{' > $O/${tag}_bench_n1_forced_exchange.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --force-exchange --grad-dtype fp32 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_forced_exchange_fp32.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --force-exchange --ghost-ranks 8 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_ghost8.json
+python bench.py --full --steps 20 --warmup 5 --workload plotqa-real 2> $O/${tag}_bench_n1_plotqa_real.err | grep '^{' > $O/${tag}_bench_n1_plotqa_real.json
 # the residual stream stored as bf16 (rounds 1 - 5; params['residual_fp32'] = False): the speed the default gives up for its gradient fidelity
-python bench.py --steps 20 --warmup 5 --residual-bf16 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_residual_bf16.json
-python bench.py --steps 20 --warmup 5 --residual-bf16 --no-cpu-baseline --workload plotqa-real 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_plotqa_real_residual_bf16.json
+python bench.py --full --steps 20 --warmup 5 --residual-bf16 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_residual_bf16.json
+python bench.py --full --steps 20 --warmup 5 --residual-bf16 --no-cpu-baseline --workload plotqa-real 2>/dev/null | grep '^{' > $O/${tag}_bench_n1_plotqa_real_residual_bf16.json
 for f in bench_n1 bench_n1_fp8 bench_n1_fp8_bf16_wgrad bench_n1_fp8_forward_only bench_n1_fp8_bf16_forward bench_n1_longctx bench_n1_longctx_fp8 bench_n1_forced_exchange bench_n1_forced_exchange_pack_all bench_n1_forced_exchange_fp8 bench_n1_forced_exchange_fp32 bench_n1_ghost8 bench_n1_plotqa_real bench_n1_residual_bf16 bench_n1_plotqa_real_residual_bf16; do python -c "import json; d=json.load(open('$O/${tag}_$f.json')); print('$f', round(d['ms_per_step'],3), round(d['value']), 'ffn frac', round(d['roofline']['frac'],4), 'traffic', d['roofline']['traffic'])"; done
 fi
 head -45 $O/${tag}_pmc_sites.txt
