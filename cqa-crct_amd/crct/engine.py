@@ -153,6 +153,15 @@ class StepEngine(object):
             c.seg_enqueued = C.cast(fn, C.c_void_p)
         return c
 
+    def set_ln_addend(self, on):
+        """How the block-closing GEMMs of the fp32 residual stream get their fp32 addend (crct_engine_set_ln_addend): True (default)
+        = rebuilt in the epilogue from the producing LayerNorm's inputs, False = from an fp32 copy the LayerNorm writes.  The copies'
+        buffers are part of the workspace only on the second route: it grows here when needed.  Same bits either way."""
+        L.check(self.lib.crct_engine_set_ln_addend(self.handle, int(bool(on))), "set_ln_addend")
+        self.ws_bytes = self.lib.crct_engine_workspace_bytes(self.handle)
+        if self.workspace.numel() < self.ws_bytes:
+            self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+
     def set_site_policy(self, site, kind, cfg=-1, split_k=0, phase=-1):
         """Launch policy of one GEMM site (crct_engine_set_site_policy): ``site`` / ``kind`` by name (crct.lib.SITE_NAMES /
         KIND_NAMES) or number, ``phase`` 0 = text-only part of the schedule, 1 = beside the visual stream, -1 = both."""

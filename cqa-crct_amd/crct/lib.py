@@ -25,6 +25,10 @@ class GemmArgs(C.Structure):
                 ("site", c_i32), ("split_k", c_i32), ("splitk_ws", vp), ("splitk_cnt", vp), ("addend_f32", c_i32), ("c_cached", c_i32)]
 
 
+class GemmLnAddend(C.Structure):     # CrctGemmLnAddend: the addend of a GEMM is the LayerNorm of its fp32 `addend` rows
+    _fields_ = [("mean", vp), ("rstd", vp), ("gamma", vp), ("beta", vp)]
+
+
 class LaunchRec(C.Structure):
     _fields_ = [("site", c_i32), ("kind", c_i32), ("M", c_i32), ("N", c_i32), ("K", c_i32), ("cfg", c_i32), ("split_k", c_i32),
                 ("grid", c_i32), ("n_problems", c_i32), ("flops", C.c_double)]
@@ -131,6 +135,8 @@ PROTOTYPES = {
     "crct_abi_version": (C.c_int, []),
     "crct_gemm_bf16": (C.c_int, [C.POINTER(GemmArgs), vp]),
     "crct_gemm_bf16_grouped": (C.c_int, [C.POINTER(GemmArgs), C.c_int, vp]),
+    "crct_gemm_bf16_ln_addend": (C.c_int, [C.POINTER(GemmArgs), C.POINTER(GemmLnAddend), vp]),
+    "crct_gemm_bf16_grouped_ln_addend": (C.c_int, [C.POINTER(GemmArgs), C.POINTER(GemmLnAddend), C.c_int, vp]),
     "crct_gemm_pick_tile": (C.c_int, [C.c_int, C.c_int]),
     "crct_gemm_group_max_workgroups": (C.c_int, [C.c_int]),
     "crct_gemm_group_target_workgroups": (C.c_int, [C.c_int]),
@@ -170,6 +176,7 @@ PROTOTYPES = {
     "crct_fp8_quantize_weights": (C.c_int, [vp] * 7 + [c_i64, vp, vp, C.c_int, vp]),
     "crct_gemm_group_wgrad_config": (C.c_int, [C.c_int]),
     "crct_engine_set_wgrad_flush": (C.c_int, [vp, C.c_int]),
+    "crct_engine_set_ln_addend": (C.c_int, [vp, C.c_int]),
     "crct_engine_set_wgrad_workgroups": (C.c_int, [vp, C.c_int, C.c_int]),
     "crct_gemm_class_config": (C.c_int, [C.c_int, C.c_int]),
     "crct_gemm_fp8_scaled_mfma": (C.c_int, [C.c_int]),

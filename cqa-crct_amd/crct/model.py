@@ -515,6 +515,8 @@ class CrctModel(nn.Module):
                 L.check(self._engine.lib.crct_engine_set_wgrad_workgroups(self._engine.handle, int(self.wgrad_workgroups[0]), int(self.wgrad_workgroups[1])), "set_wgrad_workgroups")
             if getattr(self, "wgrad_flush", None) is not None:    # where a layer's weight gradients leave for the side stream (crct_engine_set_wgrad_flush)
                 L.check(self._engine.lib.crct_engine_set_wgrad_flush(self._engine.handle, int(self.wgrad_flush)), "set_wgrad_flush")
+            if getattr(self, "ln_addend", None) is not None:      # fp32 residual addend rebuilt by the GEMM (True) or written by the LayerNorm (crct_engine_set_ln_addend)
+                self._engine.set_ln_addend(self.ln_addend)
             mode = getattr(self, "stream_mode", None)             # (use_visual_stream, use_wgrad_streams) of crct_engine_set_streams
             if mode is not None:
                 L.check(self._engine.lib.crct_engine_set_streams(self._engine.handle, int(mode[0]), int(mode[1])), "set_streams")

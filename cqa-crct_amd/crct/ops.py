@@ -74,10 +74,25 @@ def _splitk_space(dev, M, N, S):
     return ws, cnt
 
 
-def gemm(A, B, M, N, K, **kw):
-    """One GEMM with its fused epilogue (keyword arguments: see ``_gemm_args``)."""
+def _ln_addend(ln, src):
+    """``src`` = (mean [M], rstd [M], gamma [N], beta [N]), fp32: CrctGemmLnAddend (None: no LayerNorm addend)."""
+    if src is not None:
+        for t in src:
+            _chk(t, torch.float32)
+        ln.mean, ln.rstd, ln.gamma, ln.beta = (L.ptr(t) for t in src)
+    return ln
+
+
+def gemm(A, B, M, N, K, ln_addend=None, **kw):
+    """One GEMM with its fused epilogue (keyword arguments: see ``_gemm_args``).  ln_addend = (mean, rstd, gamma, beta): the fp32
+    ``addend`` holds the rows a LayerNorm normalised and the epilogue adds that LayerNorm's fp32 output, rebuilt per element
+    (crct_gemm_bf16_ln_addend) -- the bits of ``layernorm_fwd(..., y_f32=True)``'s fp32 output as a plain fp32 addend."""
     g = L.GemmArgs()
     out = _gemm_args(g, A, B, M, N, K, **kw)
+    if ln_addend is not None:
+        ln = _ln_addend(L.GemmLnAddend(), ln_addend)
+        L.check(L.load().crct_gemm_bf16_ln_addend(C.byref(g), C.byref(ln), L.current_stream()), "gemm (LayerNorm addend)")
+        return out
     L.check(L.load().crct_gemm_bf16(C.byref(g), L.current_stream()), "gemm")
     return out
 
@@ -86,7 +101,14 @@ def gemm_grouped(problems):
     """``problems`` = [dict(A=, B=, M=, N=, K=, ...gemm keywords)] sharing (ta, tb): ONE grouped launch (crct_gemm_bf16_grouped),
     every problem with its own epilogue.  Returns the outputs."""
     arr = (L.GemmArgs * len(problems))()
-    outs = [_gemm_args(g, **prob) for g, prob in zip(arr, problems)]
+    lns = (L.GemmLnAddend * len(problems))()
+    srcs = [prob.get("ln_addend") for prob in problems]
+    outs = [_gemm_args(g, **{k: v for k, v in prob.items() if k != "ln_addend"}) for g, prob in zip(arr, problems)]
+    if any(src is not None for src in srcs):      # a problem's ``ln_addend``: as for ``gemm``
+        for ln, src in zip(lns, srcs):
+            _ln_addend(ln, src)
+        L.check(L.load().crct_gemm_bf16_grouped_ln_addend(arr, lns, len(problems), L.current_stream()), "gemm_grouped (LayerNorm addend)")
+        return outs
     L.check(L.load().crct_gemm_bf16_grouped(arr, len(problems), L.current_stream()), "gemm_grouped")
     return outs
 

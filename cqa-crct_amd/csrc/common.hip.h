@@ -58,6 +58,14 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(fmaxf(lane_f32(v, 0), lane_f32(v, 16)), fmaxf(lane_f32(v, 32), lane_f32(v, 48)));
 }
 
+// ------------------------------------------------------------------ LayerNorm output value
+// The one definition of y = gamma * ((x - mean) * rstd) + beta: the LayerNorm kernels (rowops.hip, row_normalize) and the GEMM epilogues
+// that rebuild a LayerNorm's fp32 output row as their residual addend (gemm.hip, CrctGemmLnAddend) must agree to the bit, so the
+// operations are spelled out -- subtract, multiply, ONE fused multiply-add -- and no translation unit's contraction setting has a say.
+__device__ __forceinline__ float ln_value(float x, float mean, float rstd, float gamma, float beta) {
+  return __builtin_fmaf(gamma, (x - mean) * rstd, beta);
+}
+
 // ------------------------------------------------------------------ Philox4x32 (counter based RNG), 7 rounds
 // Dropout masks are never stored: forward and backward regenerate them from
 // (seed, site, element index).  One call yields 4 x u32 = eight 16-bit slices for the elements 8 idx8 .. 8 idx8 + 7 (philox_keep8).

@@ -29,6 +29,10 @@ hipError_t crct_gemm_launch_grouped(const CrctGemmArgs* gs, int n, hipStream_t s
 hipError_t crct_gemm_launch_grouped_wgs(const CrctGemmArgs* gs, int n, hipStream_t s, int target_wgs);
 // only the problems with keep[i] != 0, launched as members of the group all n form (keep == NULL: all of them)
 hipError_t crct_gemm_launch_grouped_keep(const CrctGemmArgs* gs, int n, const uint8_t* keep, hipStream_t s, int target_wgs);
+// the same launches with LayerNorm addends (CrctGemmLnAddend): ln == NULL, or one entry per problem (mean == NULL: none for that problem); target_wgs < 0:
+// the library's default (crct_gemm_group_target_workgroups)
+hipError_t crct_gemm_launch_ln(const CrctGemmArgs& g, const CrctGemmLnAddend* ln, hipStream_t s);
+hipError_t crct_gemm_launch_grouped_ln(const CrctGemmArgs* gs, const CrctGemmLnAddend* ln, int n, const uint8_t* keep, hipStream_t s, int target_wgs);
 // streams.hip: three streams on hardware queues other than main's (+ a second one on the last queue), found by probing
 int crct_streams_place(hipStream_t main, hipStream_t out[4], int* n_classes);
 

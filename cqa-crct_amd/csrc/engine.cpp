@@ -71,6 +71,15 @@ extern "C" int crct_gemm_bf16(const CrctGemmArgs* a, crct_stream_t stream) {
   return 0;
 }
 
+extern "C" int crct_gemm_bf16_ln_addend(const CrctGemmArgs* a, const CrctGemmLnAddend* ln, crct_stream_t stream) {
+  CRCT_REQUIRE(a != nullptr, "gemm: null args");
+  if (int r = gemm_check(*a, "gemm", -1)) return r;
+  CRCT_REQUIRE(!ln || (a->addend && a->addend_f32 && ln->mean && ln->rstd && ln->gamma && ln->beta),
+               "gemm: a LayerNorm addend needs the fp32 addend it normalises (addend, addend_f32) and mean, rstd, gamma, beta");
+  CRCT_CHECK_HIP(crct_gemm_launch_ln(*a, ln, (hipStream_t)stream));
+  return 0;
+}
+
 // target_wgs < 0: the library's default (crct_gemm_group_target_workgroups)
 // keep: NULL, or one flag per problem -- only the flagged ones are launched, as members of the group all n would have formed
 static int gemm_grouped_checked(const CrctGemmArgs* a, int n, crct_stream_t stream, int target_wgs, const uint8_t* keep = nullptr) {
@@ -83,6 +92,17 @@ static int gemm_grouped_checked(const CrctGemmArgs* a, int n, crct_stream_t stre
   return 0;
 }
 extern "C" int crct_gemm_bf16_grouped(const CrctGemmArgs* a, int n, crct_stream_t stream) { return gemm_grouped_checked(a, n, stream, -1); }
+extern "C" int crct_gemm_bf16_grouped_ln_addend(const CrctGemmArgs* a, const CrctGemmLnAddend* ln, int n, crct_stream_t stream) {
+  if (!ln) return gemm_grouped_checked(a, n, stream, -1);
+  CRCT_REQUIRE(a != nullptr && n >= 1, "gemm_grouped: bad arguments");
+  for (int i = 0; i < n; ++i) {
+    if (int r = gemm_check(a[i], "gemm_grouped", i)) return r;
+    CRCT_REQUIRE(!ln[i].mean || (a[i].addend && a[i].addend_f32 && ln[i].rstd && ln[i].gamma && ln[i].beta),
+                 "gemm_grouped: a LayerNorm addend needs the fp32 addend it normalises and mean, rstd, gamma, beta (problem %d)", i);
+  }
+  CRCT_CHECK_HIP(crct_gemm_launch_grouped_ln(a, ln, n, nullptr, (hipStream_t)stream, -1));      // -1: the library's default grid policy
+  return 0;
+}
 
 namespace {
 
@@ -111,21 +131,24 @@ struct ConnLayerP { LinearP qkv1, qkv2; ProjP proj_v, proj_t; FfnP ffn_v, ffn_t;
 
 // ---- activation offsets (bytes into the workspace)
 constexpr size_t NONE = (size_t)-1;
-// An activation as the blocks hand it on: the bf16 tensor, its e4m3 copy with the activation scale site (site -1: no copy) and
-// the fp32 copy a LayerNorm leaves of its output for the fp32 residual stream (NONE: the embeddings' outputs, bf16 there)
-struct Act { size_t x = 0, q = NONE; int site = -1; size_t x32 = NONE; };
+// An activation as the blocks hand it on: the bf16 tensor, its e4m3 copy with the activation scale site (site -1: no copy) and, for the
+// fp32 residual stream, where the fp32 value of a LayerNorm's output comes from: s / mean / rstd / ln -- the rows the LayerNorm normalised,
+// their statistics and its parameters, from which the block-closing GEMM rebuilds it (CrctGemmLnAddend) -- and x32, the fp32 copy the
+// LayerNorm writes on the two-output route (crct_engine_set_ln_addend(e, 0)).  NONE: the embeddings' outputs, bf16 there.
+struct Act { size_t x = 0, q = NONE; int site = -1; size_t x32 = NONE; size_t s = NONE, mean = NONE, rstd = NONE; LnP ln; };
 // the e5m2 copy of a gradient and its gradient scale site (-1: no copy)
 struct GradQ { size_t q = NONE; int site = -1; };
 // s: the pre-LayerNorm sum, room for fp32 (the fp32 residual stream, CrctStepCfg.residual_fp32; bf16 in the first half otherwise);
-// y32 / a32: the fp32 copy of the LayerNorm output that the NEXT block's epilogue adds as its residual
+// y32 / a32: the fp32 copy of the LayerNorm output that the NEXT block's epilogue adds as its residual on the two-output route (planned
+// behind everything else: crct_engine_set_ln_addend)
 // hq / yq: e4m3 copies (fp8 forward), site_*: their scale slots; g_*: gradient scale sites (fp8 backward)
 struct FfnA {
   size_t u, h, s, y, y32, mean, rstd, hq, yq; int site_h, site_y; int g_dl, g_du;
-  Act out() const { return {y, yq, site_y, y32}; }
+  Act out(const LnP& ln) const { return {y, yq, site_y, y32, s, mean, rstd, ln}; }
 };
 struct ProjA {
   size_t s, a, a32, mean, rstd, aq; int site_a; int g_dl;
-  Act out() const { return {a, aq, site_a, a32}; }
+  Act out(const LnP& ln) const { return {a, aq, site_a, a32, s, mean, rstd, ln}; }
 };
 // ctxq / site_ctx: e4m3 copy of the attention context and its activation scale site; g_dqkv: gradient scale site of the fused dqkv buffer
 // lse*: softmax row statistics [B][heads][Tq] fp32 the long-sequence attention forward leaves for its backward (CrctAttnQuant.row_lse)
@@ -183,6 +206,8 @@ struct crct_engine {
   // streams, ordered against the caller's stream by events (fork / join inside every call)
   bool use_vis_stream = true, use_wgrad_stream = true, streams_forced = false;
   int wgrad_target = 96, wgrad_target_rows = 3000;      // crct_engine_set_wgrad_workgroups (Run::flush_wgrads)
+  int ln_addend = 1;                   // crct_engine_set_ln_addend: 1 = the block-closing GEMMs rebuild their fp32 addend (Run::residual), 0 = the LayerNorms write it
+  size_t ws_core = 0, ws_two_output = 0;      // workspace bytes without / with the fp32 LayerNorm outputs of the two-output route
   int wgrad_flush = 1;                 // crct_engine_set_wgrad_flush: extra flush points of a layer's queued weight gradients (Run::ffn_bwd).
                                        // 1 (round 4): FFN group 0.075 -> 0.081 of peak in the step, step -0.02 (bf16) / -0.06 (fp8) / -0.08 ms (long context)
   bool one_wgrad_stream = false;       // both data streams' weight gradients on ONE side stream (frees a hardware queue for the exchange)
@@ -285,7 +310,7 @@ template <class F> void each_encoder_linear(const crct_engine* e, F f) {
 FfnA ffn_a(Arena& ar, size_t M, int H, int I, int& sites, int& gsites) {
   FfnA a;
   a.g_dl = gsites++; a.g_du = gsites++;
-  a.u = ar.take(M * I * 2); a.h = ar.take(M * I * 2); a.s = ar.take(M * H * 4); a.y = ar.take(M * H * 2); a.y32 = ar.take(M * H * 4);
+  a.u = ar.take(M * I * 2); a.h = ar.take(M * I * 2); a.s = ar.take(M * H * 4); a.y = ar.take(M * H * 2); a.y32 = NONE;
   a.mean = ar.take(M * 4); a.rstd = ar.take(M * 4);
   a.hq = ar.take(M * I); a.yq = ar.take(M * H);
   a.site_h = sites++; a.site_y = sites++;
@@ -294,7 +319,7 @@ FfnA ffn_a(Arena& ar, size_t M, int H, int I, int& sites, int& gsites) {
 ProjA proj_a(Arena& ar, size_t M, int H, int& sites, int& gsites) {
   ProjA a;
   a.g_dl = gsites++;
-  a.s = ar.take(M * H * 4); a.a = ar.take(M * H * 2); a.a32 = ar.take(M * H * 4); a.mean = ar.take(M * 4); a.rstd = ar.take(M * 4);
+  a.s = ar.take(M * H * 4); a.a = ar.take(M * H * 2); a.a32 = NONE; a.mean = ar.take(M * 4); a.rstd = ar.take(M * 4);
   a.aq = ar.take(M * H);
   a.site_a = sites++;
   return a;
@@ -414,6 +439,7 @@ struct Run {
     void* preact = nullptr; const void* dact_src = nullptr; int dact = 0; int act = 0;
     const void* addend = nullptr; int64_t ld_aux = 0, ld_add = 0; Drop drop; bool f32 = false; bool acc = false;
     bool add_f32 = false, c_cached = false;      // the fp32 residual stream: fp32 addend; fp32 output that the next kernel reads
+    CrctGemmLnAddend ln = {nullptr, nullptr, nullptr, nullptr};      // ... the addend is the LayerNorm of those fp32 rows (forward only)
   };
   // both sides reach this point before either goes on: the two data streams are ordered against each other
   void cross_sync(Run& V) {
@@ -488,7 +514,10 @@ struct Run {
     }
     return g;
   }
-  void launch(const CrctGemmArgs& g) { ++tick; fail(crct_gemm_bf16(&g, s)); }      // on the data stream: one tick per launch
+  void launch(const CrctGemmArgs& g, const CrctGemmLnAddend* ln = nullptr) {      // on the data stream: one tick per launch
+    ++tick;
+    fail(ln && ln->mean ? crct_gemm_bf16_ln_addend(&g, ln, s) : crct_gemm_bf16(&g, s));
+  }
 
   // y[M][out] = x W^T + b (+ epilogue), in the precision the Linear itself decides.  The forward rules, all of them:
   //  * fp8 operands iff the weight has an e4m3 shadow in an fp8 forward (f8_lin) AND the input comes with an e4m3 copy
@@ -502,7 +531,7 @@ struct Run {
     const bool q = f8_lin(l) && x.site >= 0;
     if (!q) y.site = -1;
     if (rc) return y;
-    launch(gemm_args(FWD, l, M, A(x.x), ldx, nullptr, 0, A(y.x), ldy, o, q && f8() == 1 ? q8(x) : Q8(), Q8(), q8(y)));
+    launch(gemm_args(FWD, l, M, A(x.x), ldx, nullptr, 0, A(y.x), ldy, o, q && f8() == 1 ? q8(x) : Q8(), Q8(), q8(y)), &o.ln);
     return y;
   }
   // dx[M][in] = dy W (+ epilogue).  The data-gradient rules:
@@ -609,18 +638,27 @@ struct Run {
     if (rc) return;
     ++tick;
     CrctLnFwdArgs a = {A(x), P(ln.g), P(ln.b), A(y.x), F(mean), F(rstd), M, H, 1e-12f, 0, 1.f, 0, c->seed, nullptr, nullptr, nullptr, 0, nullptr};
-    if (r32()) { a.x_f32 = 1; a.y_f32 = F(y.x32); }
+    if (r32()) { a.x_f32 = 1; if (!e->ln_addend) a.y_f32 = F(y.x32); }
     if (f8()) { a.q_out = W<uint8_t>(y.q); a.q_scale = ascale(y.site); a.q_amax = aamax(y.site); }
     fail(crct_layernorm_fwd_args(&a, s));
   }
   // The fp32 residual stream (CrctStepCfg.residual_fp32): the pre-LayerNorm sums are written and read as fp32, and every block adds
-  // the fp32 copy of its input where the producing LayerNorm left one (the embeddings' outputs have none: bf16 there, one rounding)
+  // the fp32 value of its input where a LayerNorm produced it (the embeddings' outputs have none: bf16 there, one rounding).  The
+  // closing GEMM's epilogue rebuilds that value from the LayerNorm's own inputs -- s, which it reads instead of a copy (the same 4
+  // bytes per element), two floats per row and two per column -- so the LayerNorm stores its bf16 output only; the rows, statistics
+  // and parameters all outlive the block (the backward pass reads them; no buffer of the plan is recycled within a forward, evaluation
+  // included).  ln_addend == 0: the LayerNorm writes the fp32 copy x32 and the epilogue adds that (same bits).
   bool r32() const { return c->residual_fp32 != 0; }
   void residual(Opt& o, const Act& x, int64_t ld) const {
     o.ld_add = ld;
     if (r32()) {
       o.f32 = true; o.c_cached = true;
-      if (x.x32 != NONE) { o.addend = F(x.x32); o.add_f32 = true; return; }
+      if (e->ln_addend && x.s != NONE) {
+        o.addend = F(x.s); o.add_f32 = true;
+        o.ln = CrctGemmLnAddend{F(x.mean), F(x.rstd), P(x.ln.g), P(x.ln.b)};
+        return;
+      }
+      if (!e->ln_addend && x.x32 != NONE) { o.addend = F(x.x32); o.add_f32 = true; return; }
     }
     o.addend = A(x.x);
   }
@@ -683,7 +721,7 @@ struct Run {
   void proj_fwd(const ProjP& p, const ProjA& a, const Act& ctx, const Act& x, int M, const Drop& dr) {
     Opt o; o.drop = dr; residual(o, x, p.dense.out);
     lin_fwd(ctx, p.dense.in, p.dense, M, Act{a.s}, p.dense.out, o);
-    ln_fwd(a.s, p.ln, a.out(), a.mean, a.rstd, M, p.dense.out);
+    ln_fwd(a.s, p.ln, a.out(p.ln), a.mean, a.rstd, M, p.dense.out);
   }
   // in: g = grad of a.  out: sc.dres_b (residual gradient), sc.dctx.  Parameter gradients accumulated.
   void proj_bwd(const ProjP& p, const ProjA& a, const Act& ctx, size_t g, const StreamScratch& sc, int M, const Drop& dr) {
@@ -699,7 +737,7 @@ struct Run {
     const Act h = lin_fwd(x, p.up.in, p.up, M, ffn_h(p, a), p.up.out, o);
     Opt o2; o2.drop = dr; residual(o2, x, p.down.out);
     lin_fwd(h, p.down.in, p.down, M, Act{a.s}, p.down.out, o2);
-    ln_fwd(a.s, p.ln, a.out(), a.mean, a.rstd, M, p.down.out);
+    ln_fwd(a.s, p.ln, a.out(p.ln), a.mean, a.rstd, M, p.down.out);
   }
   // in: g = grad of a.y.  out: gx = grad of x (the block's input: its e4m3 copy serves the fp8 weight gradient of the up projection).
   void ffn_bwd(const FfnP& p, const FfnA& a, const Act& x, size_t g, size_t gx, const StreamScratch& sc, int M, const Drop& dr) {
@@ -727,14 +765,14 @@ struct Run {
     const Act ctx = ctx_act(a.ctx, a.ctxq, a.site_ctx, p.proj.dense, attn_q_ok(T, T, d));
     attn_fwd(A(a.qkv), 3 * H, A(a.qkv) + H, A(a.qkv) + 2 * H, 3 * H, km, ctx, H, B, p.heads, T, T, d, drop(p.p_attn, p.site), a.lse);
     proj_fwd(p.proj, a.proj, ctx, x, M, drop(p.p_hid, p.site + 1));
-    ffn_fwd(p.ffn, a.ffn, a.proj.out(), M, drop(p.p_hid, p.site + 2));
+    ffn_fwd(p.ffn, a.ffn, a.proj.out(p.proj.ln), M, drop(p.p_hid, p.site + 2));
   }
   // x: the layer input (its e4m3 copy serves the fp8 weight gradient of the QKV projection); g: grad of the output, gx: of x
   // dx = false (the lowest running step of its stream, SegPlan): gx has no reader and the launch that only produces it is not issued
   void self_bwd(const SelfLayerP& p, const SelfLayerA& a, const Act& x, size_t g, size_t gx, const uint8_t* km, int B, int T, bool dx = true) {
     const int M = B * T, H = p.H, d = H / p.heads;
     const StreamScratch& sc = layer_begin();
-    ffn_bwd(p.ffn, a.ffn, a.proj.out(), g, sc.gc, sc, M, drop(p.p_hid, p.site + 2));
+    ffn_bwd(p.ffn, a.ffn, a.proj.out(p.proj.ln), g, sc.gc, sc, M, drop(p.p_hid, p.site + 2));
     const bool aq = attn_q_ok(T, T, d);
     const bool gq = aq && f8b_lin(p.qkv) && f8_lin(p.qkv);      // e5m2 copy of dqkv: fp8 data and weight gradient of the QKV projection
     const GradQ dqkvq{sc.dqkvq, gq ? a.g_dqkv : -1};
@@ -768,8 +806,8 @@ struct Run {
     // cross wiring :780 -- visual stream takes ctx2, text stream takes ctx1
     V.proj_fwd(p.proj_v, a.proj_v, ctx2, x.v, Mv, drop(D.p_v_hidden, p.site + 2));
     proj_fwd(p.proj_t, a.proj_t, ctx1, x.t, Mt, drop(D.p_hidden, p.site + 3));
-    V.ffn_fwd(p.ffn_v, a.ffn_v, a.proj_v.out(), Mv, drop(D.p_v_hidden, p.site + 4));
-    ffn_fwd(p.ffn_t, a.ffn_t, a.proj_t.out(), Mt, drop(D.p_hidden, p.site + 5));
+    V.ffn_fwd(p.ffn_v, a.ffn_v, a.proj_v.out(p.proj_v.ln), Mv, drop(D.p_v_hidden, p.site + 4));
+    ffn_fwd(p.ffn_t, a.ffn_t, a.proj_t.out(p.proj_t.ln), Mt, drop(D.p_hidden, p.site + 5));
   }
   // x: the two layer inputs (their e4m3 copies serve the fp8 weight gradients of the QKV projections); gv / gt: grads of the two
   // outputs, gxv / gxt: of the inputs (dxv / dxt = false: not produced, as in self_bwd)
@@ -779,8 +817,8 @@ struct Run {
     hipEvent_t free_v = V.set_free[V.parity], free_t = set_free[parity];      // "the last readers of this scratch set are done"
     const StreamScratch& sv = V.layer_begin(); const StreamScratch& st = layer_begin();
     const int B = b->B, Mv = B * b->V, Mt = B * b->T, Hb = D.Hb, d = Hb / D.b_heads;
-    V.ffn_bwd(p.ffn_v, a.ffn_v, a.proj_v.out(), gv, sv.gc, sv, Mv, drop(D.p_v_hidden, p.site + 4));
-    ffn_bwd(p.ffn_t, a.ffn_t, a.proj_t.out(), gt, st.gc, st, Mt, drop(D.p_hidden, p.site + 5));
+    V.ffn_bwd(p.ffn_v, a.ffn_v, a.proj_v.out(p.proj_v.ln), gv, sv.gc, sv, Mv, drop(D.p_v_hidden, p.site + 4));
+    ffn_bwd(p.ffn_t, a.ffn_t, a.proj_t.out(p.proj_t.ln), gt, st.gc, st, Mt, drop(D.p_hidden, p.site + 5));
     const bool aq = attn_q_ok(b->T, b->V, d) && attn_q_ok(b->V, b->T, d);
     // e5m2 copies of the two fused dqkv buffers: only when BOTH QKV projections run their gradients in fp8 (each buffer is written by
     // both attention kernels)
@@ -1285,16 +1323,25 @@ extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, 
     e->sk_cnt[0] = ar.take((size_t)2 * e->sk_tickets * 4);      // [text | visual] in one block: one memset per call
     e->sk_cnt[1] = e->sk_cnt[0] + (size_t)e->sk_tickets * 4;
   }
-  e->ws_bytes = ar.top;
+  // the fp32 LayerNorm outputs of the two-output route lie behind everything else: the default route neither writes nor allocates them
+  e->ws_core = ar.top;
+  for (SelfLayerA& a : e->tla) { a.proj.a32 = ar.take(Mt * D.H * 4); a.ffn.y32 = ar.take(Mt * D.H * 4); }
+  for (SelfLayerA& a : e->vla) { a.proj.a32 = ar.take(Mv * D.Hv * 4); a.ffn.y32 = ar.take(Mv * D.Hv * 4); }
+  for (ConnLayerA& a : e->cla) {
+    a.proj_v.a32 = ar.take(Mv * D.Hv * 4); a.ffn_v.y32 = ar.take(Mv * D.Hv * 4);
+    a.proj_t.a32 = ar.take(Mt * D.H * 4); a.ffn_t.y32 = ar.take(Mt * D.H * 4);
+  }
+  e->ws_two_output = ar.top;
+  e->ws_bytes = e->ln_addend ? e->ws_core : e->ws_two_output;
 
   // ---- the hidden states every schedule step starts from (the last entry: the encoder's outputs), and the taps on them
   {
     StepIn x = {Act{e->eta.y, e->eta.yq, e->eta.site}, Act{e->eva.y, e->eva.yq, e->eva.site}};
     for (const Step& st : e->sched) {
       e->in.push_back(x);
-      if (st.kind == 't') x.t = e->tla[st.idx].ffn.out();
-      else if (st.kind == 'v') x.v = e->vla[st.idx].ffn.out();
-      else { x.v = e->cla[st.idx].ffn_v.out(); x.t = e->cla[st.idx].ffn_t.out(); }
+      if (st.kind == 't') x.t = e->tla[st.idx].ffn.out(e->tl[st.idx].ffn.ln);
+      else if (st.kind == 'v') x.v = e->vla[st.idx].ffn.out(e->vl[st.idx].ffn.ln);
+      else { x.v = e->cla[st.idx].ffn_v.out(e->cl[st.idx].ffn_v.ln); x.t = e->cla[st.idx].ffn_t.out(e->cl[st.idx].ffn_t.ln); }
       snprintf(buf, sizeof(buf), "%c%d.t", st.kind, st.idx); e->taps.push_back({buf, x.t.x, 't'});
       snprintf(buf, sizeof(buf), "%c%d.v", st.kind, st.idx); e->taps.push_back({buf, x.v.x, 'v'});
     }
@@ -1659,6 +1706,13 @@ extern "C" int crct_engine_set_wgrad_workgroups(crct_engine_t* e, int target_wgs
 extern "C" int crct_engine_set_wgrad_flush(crct_engine_t* e, int mode) {
   if (!e) return 1;
   e->wgrad_flush = mode;
+  return 0;
+}
+
+extern "C" int crct_engine_set_ln_addend(crct_engine_t* e, int on) {
+  if (!e) return 1;
+  e->ln_addend = on != 0;
+  e->ws_bytes = e->ln_addend ? e->ws_core : e->ws_two_output;
   return 0;
 }
 

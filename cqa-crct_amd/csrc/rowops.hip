@@ -226,7 +226,7 @@ __device__ __forceinline__ void row_normalize(Row<NCH>& r, const Row<NCH>& gamma
     const int c = (lane + 64 * i) * 8;
     if (c < H) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) r.v[i][j] = gamma.v[i][j] * ((r.v[i][j] - mean) * rstd) + beta.v[i][j];
+      for (int j = 0; j < 8; ++j) r.v[i][j] = ln_value(r.v[i][j], mean, rstd, gamma.v[i][j], beta.v[i][j]);
       if (thr) {
         const uint32_t kb = philox_keep8(seed, site, ((uint64_t)row * (uint64_t)H + (uint64_t)c) >> 3, thr);      // c % 8 == 0, H % 8 == 0
 #pragma unroll
@@ -249,7 +249,7 @@ __device__ __forceinline__ void row_normalize(Row<NCH>& r, const float* gamma, c
       const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
       const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
-      for (int j = 0; j < 8; ++j) r.v[i][j] = gg[j] * ((r.v[i][j] - mean) * rstd) + bb[j];
+      for (int j = 0; j < 8; ++j) r.v[i][j] = ln_value(r.v[i][j], mean, rstd, gg[j], bb[j]);
       if (thr) {
         const uint32_t kb = philox_keep8(seed, site, ((uint64_t)row * (uint64_t)H + (uint64_t)c) >> 3, thr);      // c % 8 == 0, H % 8 == 0
 #pragma unroll
@@ -1160,6 +1160,11 @@ __global__ __launch_bounds__(256) void embed_image_bwd_kernel(
 }
 
 inline int nch_for(int H) { return (H / 8 + 63) / 64; }
+// workgroups of a LayerNorm-forward launch at most (4 rows each per pass; a build-time value for A/B builds).  Re-checked in the step after the
+// kernel stopped writing the fp32 copy of its output (EXPERIMENTS.md, LayerNorm addend): 256 and 512 measured no better than 2048.
+#ifndef CRCT_LN_FWD_GRID_CAP
+#define CRCT_LN_FWD_GRID_CAP 2048
+#endif
 inline int row_grid(long M, int cap) {
   long g = (M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -1196,7 +1201,7 @@ static int ln_fwd_launch(const CrctLnFwdArgs& a, hipStream_t s) {
   if (int r = ln_fwd_check(a)) return r;
   if (a.M <= 0) return 0;
   const LnFwdP p = ln_fwd_problem(a);
-  DISPATCH_NCH(a.H, crct_launch((ln_fwd_kernel<NCH>), dim3(row_grid(a.M, 2048)), dim3(256), 0, s, LN_FWD_HOT(p) p));
+  DISPATCH_NCH(a.H, crct_launch((ln_fwd_kernel<NCH>), dim3(row_grid(a.M, CRCT_LN_FWD_GRID_CAP)), dim3(256), 0, s, LN_FWD_HOT(p) p));
   CRCT_CHECK_HIP(hipGetLastError());
   return 0;
 }

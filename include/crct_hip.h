@@ -99,6 +99,20 @@ int64_t crct_gemm_splitk_ws_elems(int M, int N, int split_k);
 int crct_gemm_splitk_tickets(int M, int N);
 
 int crct_gemm_bf16(const CrctGemmArgs* args, crct_stream_t stream);
+/* A third kind of addend, beside bf16 and fp32 (CrctGemmArgs.addend_f32): the LayerNorm of fp32 rows.  With this struct the GEMM's `addend`
+ * is s, the fp32 [M][ld_add] rows a LayerNorm normalised (addend_f32 must be set), and the epilogue adds
+ *   gamma[n] * ((s[m][n] - mean[m]) * rstd[m]) + beta[n]
+ * -- to the bit the fp32 value crct_layernorm_fwd_args writes through CrctLnFwdArgs.y_f32 from the same s, gamma and beta and the mean /
+ * rstd it returned (one definition in the kernels: common.hip.h, ln_value).  The residual stream of the step engine reads the block
+ * input this way instead of from an fp32 copy of every LayerNorm output.  mean, rstd: fp32 [M]; gamma, beta: fp32 [N]; all four non-NULL.
+ * Works on every kernel path, split-K and grouped launches included.  Kept out of CrctGemmArgs, whose layout is pinned. */
+typedef struct CrctGemmLnAddend {
+  const float* mean; const float* rstd; const float* gamma; const float* beta;
+} CrctGemmLnAddend;
+/* crct_gemm_bf16 with a LayerNorm addend (ln == NULL: exactly crct_gemm_bf16). */
+int crct_gemm_bf16_ln_addend(const CrctGemmArgs* args, const CrctGemmLnAddend* ln, crct_stream_t stream);
+/* crct_gemm_bf16_grouped with one CrctGemmLnAddend per problem (ln == NULL: none; an entry with mean == NULL: none for that problem). */
+int crct_gemm_bf16_grouped_ln_addend(const CrctGemmArgs* args, const CrctGemmLnAddend* ln, int n, crct_stream_t stream);
 /* n <= 8 independent GEMMs in ONE grid (same ta/tb, no epilogue extras besides the output type and accumulate):
  * the weight gradients of one layer.  Problems that do not qualify are launched one by one. */
 int crct_gemm_bf16_grouped(const CrctGemmArgs* args, int n, crct_stream_t stream);
@@ -198,8 +212,10 @@ typedef struct CrctLnFwdArgs {
   int32_t M, H; float eps; uint32_t drop_thr; float drop_scale; uint32_t drop_site; uint64_t seed;
   void* q_out; const float* q_scale; float* q_amax;
   /* The fp32 residual stream (CrctStepCfg.residual_fp32): x_f32 != 0 -> x is fp32 [M][H] (the pre-LayerNorm sum as the GEMM epilogue
-   * left it, CrctGemmArgs.c_cached); y_f32 != NULL -> y is ALSO written as fp32 [M][H] (the next block's residual addend,
-   * CrctGemmArgs.addend_f32).  The bf16 y stays what GEMMs read. */
+   * left it, CrctGemmArgs.c_cached); y_f32 != NULL -> y is ALSO written as fp32 [M][H] (a residual addend for CrctGemmArgs.addend_f32).
+   * The bf16 y stays what GEMMs read.  The step engine passes no y_f32 by default: its block-closing GEMMs rebuild the fp32 row from
+   * x, mean and rstd (CrctGemmLnAddend) and the LayerNorm stores 2 instead of 6 bytes per element; y_f32 remains for direct callers and
+   * for the engine's two-output route (crct_engine_set_ln_addend(e, 0)). */
   int32_t x_f32; float* y_f32;
 } CrctLnFwdArgs;
 int crct_layernorm_fwd_args(const CrctLnFwdArgs* a, crct_stream_t stream);
@@ -792,6 +808,12 @@ int crct_engine_streams(crct_engine_t*, crct_stream_t out[4]);
 // the attention-output projection's right behind its data gradient.
 // Scheduling only: the gradients are bit-identical in every mode.
 int crct_engine_set_wgrad_flush(crct_engine_t* e, int mode);
+// How the block-closing GEMMs of the fp32 residual stream get their fp32 addend (developer A/B switch; default 1).  1: they rebuild it in the
+// epilogue from the producing LayerNorm's input rows, mean, rstd, gamma and beta (CrctGemmLnAddend), and the LayerNorms write their bf16
+// output only.  0: the LayerNorms also write an fp32 copy (CrctLnFwdArgs.y_f32) and the GEMMs add that.  The copies' buffers lie behind
+// everything else in the workspace: crct_engine_workspace_bytes covers them only while the setting is 0, so a caller that switches to 0
+// asks for the size again and provides a workspace of that size.  Every output is bit-identical in both settings.
+int crct_engine_set_ln_addend(crct_engine_t* e, int on);
 // Persistent-grid policy of the engine's grouped bf16 weight-gradient launches: target_wgs workgroups (0 = one per tile) for the
 // groups of a data stream with at most max_rows token rows, and only while every data stream has a side stream of its own (a
 // shared side stream -- the mode a gradient exchange uses -- would become the critical path).  Defaults 96 / 3000.
