@@ -21,18 +21,23 @@ void crct_set_error(const char* fmt, ...);
     }                                           \
   } while (0)
 
-// whether a GEMM configuration id (CrctGemmArgs.tile) is built (gemm.hip, k_configs and the fp8 ids)
+// whether a GEMM configuration id (CrctGemmArgs.tile) is built (gemm.hip, k_configs)
 bool crct_gemm_config_built(int id);
-hipError_t crct_gemm_launch(const CrctGemmArgs& g, hipStream_t s);
-hipError_t crct_gemm_launch_grouped(const CrctGemmArgs* gs, int n, hipStream_t s);
-// target_wgs > 0: a grouped bf16 weight-gradient launch runs as a persistent grid of about that many workgroups (gemm.hip, group_grid)
-hipError_t crct_gemm_launch_grouped_wgs(const CrctGemmArgs* gs, int n, hipStream_t s, int target_wgs);
-// only the problems with keep[i] != 0, launched as members of the group all n form (keep == NULL: all of them)
-hipError_t crct_gemm_launch_grouped_keep(const CrctGemmArgs* gs, int n, const uint8_t* keep, hipStream_t s, int target_wgs);
-// the same launches with LayerNorm addends (CrctGemmLnAddend): ln == NULL, or one entry per problem (mean == NULL: none for that problem); target_wgs < 0:
-// the library's default (crct_gemm_group_target_workgroups)
-hipError_t crct_gemm_launch_ln(const CrctGemmArgs& g, const CrctGemmLnAddend* ln, hipStream_t s);
-hipError_t crct_gemm_launch_grouped_ln(const CrctGemmArgs* gs, const CrctGemmLnAddend* ln, int n, const uint8_t* keep, hipStream_t s, int target_wgs);
+// the configuration of the step engine's fp8 weight gradients, given what the site policy asks for (-1: nothing)
+int crct_gemm_fp8_wgrad_step_config(int asked);
+// The two GEMM launches (gemm.hip), behind the validation of the C entry points (engine.cpp, gemm_check).
+// One problem with its LayerNorm addend (CrctGemmLnAddend; ln == NULL or ln->mean == NULL: none).
+hipError_t crct_gemm_launch(const CrctGemmArgs& g, const CrctGemmLnAddend* ln, hipStream_t s);
+// n problems in one grid where they qualify, else one by one.
+struct CrctGemmGroup {
+  const CrctGemmArgs* gs;          // the n problems
+  const CrctGemmLnAddend* ln;      // NULL, or one entry per problem (mean == NULL: none for that problem)
+  int n;
+  const uint8_t* keep;             // NULL, or one flag per problem: only the flagged ones are launched, as members of the group all n form
+  int target_wgs;                  // > 0: a grouped bf16 weight-gradient launch runs as a persistent grid of about that many workgroups
+                                   // (gemm.hip, group_grid); 0: one workgroup per tile; < 0: the library's default (crct_gemm_group_target_workgroups)
+};
+hipError_t crct_gemm_launch_grouped(const CrctGemmGroup& grp, hipStream_t s);
 // streams.hip: three streams on hardware queues other than main's (+ a second one on the last queue), found by probing
 int crct_streams_place(hipStream_t main, hipStream_t out[4], int* n_classes);
 

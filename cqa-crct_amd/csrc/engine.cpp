@@ -46,8 +46,8 @@ extern "C" const char* crct_last_error(void) { return g_err; }
 extern "C" int crct_abi_version(void) { return 7; }
 
 // What every GEMM launch must satisfy, stated once: `who` prefixes the message ("gemm" / "gemm_grouped"), idx >= 0 names the
-// problem of a grouped launch.
-static int gemm_check(const CrctGemmArgs& a, const char* who, int idx) {
+// problem of a grouped launch.  ln: the problem's LayerNorm addend, or NULL for none.
+static int gemm_check(const CrctGemmArgs& a, const CrctGemmLnAddend* ln, const char* who, int idx) {
   char of[32] = "";
   if (idx >= 0) snprintf(of, sizeof(of), " (problem %d)", idx);
   CRCT_REQUIRE(a.A && a.B && a.C, "%s: null operand%s", who, of);
@@ -61,48 +61,32 @@ static int gemm_check(const CrctGemmArgs& a, const char* who, int idx) {
   CRCT_REQUIRE(a.tile < 0 || crct_gemm_config_built(a.tile), "%s: configuration %d is not built%s", who, a.tile, of);
   // the staged epilogue stores a c_cached output without reading it, the register-staged one adds the old value: refused on both paths
   CRCT_REQUIRE(!(a.c_cached && a.accumulate), "%s: c_cached with accumulate is not supported (c_cached is a plain fp32 store)%s", who, of);
-  return 0;
-}
-
-extern "C" int crct_gemm_bf16(const CrctGemmArgs* a, crct_stream_t stream) {
-  CRCT_REQUIRE(a != nullptr, "gemm: null args");
-  if (int r = gemm_check(*a, "gemm", -1)) return r;
-  CRCT_CHECK_HIP(crct_gemm_launch(*a, (hipStream_t)stream));
+  // a LayerNorm addend stands on the fp32 addend it normalises and needs all four of its vectors.  (An fp8 weight gradient takes no
+  // addend of any kind: gemm.hip, f8t_ok refuses a.addend, and with it this one.)
+  CRCT_REQUIRE(!ln || (a.addend && a.addend_f32 && ln->mean && ln->rstd && ln->gamma && ln->beta),
+               "%s: a LayerNorm addend needs the fp32 addend it normalises (addend, addend_f32) and mean, rstd, gamma, beta%s", who, of);
   return 0;
 }
 
 extern "C" int crct_gemm_bf16_ln_addend(const CrctGemmArgs* a, const CrctGemmLnAddend* ln, crct_stream_t stream) {
   CRCT_REQUIRE(a != nullptr, "gemm: null args");
-  if (int r = gemm_check(*a, "gemm", -1)) return r;
-  CRCT_REQUIRE(!ln || (a->addend && a->addend_f32 && ln->mean && ln->rstd && ln->gamma && ln->beta),
-               "gemm: a LayerNorm addend needs the fp32 addend it normalises (addend, addend_f32) and mean, rstd, gamma, beta");
-  CRCT_CHECK_HIP(crct_gemm_launch_ln(*a, ln, (hipStream_t)stream));
+  if (int r = gemm_check(*a, ln, "gemm", -1)) return r;
+  CRCT_CHECK_HIP(crct_gemm_launch(*a, ln, (hipStream_t)stream));
   return 0;
 }
+extern "C" int crct_gemm_bf16(const CrctGemmArgs* a, crct_stream_t stream) { return crct_gemm_bf16_ln_addend(a, nullptr, stream); }
 
-// target_wgs < 0: the library's default (crct_gemm_group_target_workgroups)
-// keep: NULL, or one flag per problem -- only the flagged ones are launched, as members of the group all n would have formed
-static int gemm_grouped_checked(const CrctGemmArgs* a, int n, crct_stream_t stream, int target_wgs, const uint8_t* keep = nullptr) {
-  CRCT_REQUIRE(a != nullptr && n >= 1, "gemm_grouped: bad arguments");
-  for (int i = 0; i < n; ++i)
-    if (int r = gemm_check(a[i], "gemm_grouped", i)) return r;
-  if (keep) CRCT_CHECK_HIP(crct_gemm_launch_grouped_keep(a, n, keep, (hipStream_t)stream, target_wgs < 0 ? 0 : target_wgs));
-  else if (target_wgs < 0) CRCT_CHECK_HIP(crct_gemm_launch_grouped(a, n, (hipStream_t)stream));
-  else CRCT_CHECK_HIP(crct_gemm_launch_grouped_wgs(a, n, (hipStream_t)stream, target_wgs));
+static int gemm_grouped_checked(const CrctGemmGroup& grp, crct_stream_t stream) {
+  CRCT_REQUIRE(grp.gs != nullptr && grp.n >= 1, "gemm_grouped: bad arguments");
+  for (int i = 0; i < grp.n; ++i)
+    if (int r = gemm_check(grp.gs[i], grp.ln && grp.ln[i].mean ? &grp.ln[i] : nullptr, "gemm_grouped", i)) return r;      // mean == NULL: none for this problem
+  CRCT_CHECK_HIP(crct_gemm_launch_grouped(grp, (hipStream_t)stream));
   return 0;
 }
-extern "C" int crct_gemm_bf16_grouped(const CrctGemmArgs* a, int n, crct_stream_t stream) { return gemm_grouped_checked(a, n, stream, -1); }
 extern "C" int crct_gemm_bf16_grouped_ln_addend(const CrctGemmArgs* a, const CrctGemmLnAddend* ln, int n, crct_stream_t stream) {
-  if (!ln) return gemm_grouped_checked(a, n, stream, -1);
-  CRCT_REQUIRE(a != nullptr && n >= 1, "gemm_grouped: bad arguments");
-  for (int i = 0; i < n; ++i) {
-    if (int r = gemm_check(a[i], "gemm_grouped", i)) return r;
-    CRCT_REQUIRE(!ln[i].mean || (a[i].addend && a[i].addend_f32 && ln[i].rstd && ln[i].gamma && ln[i].beta),
-                 "gemm_grouped: a LayerNorm addend needs the fp32 addend it normalises and mean, rstd, gamma, beta (problem %d)", i);
-  }
-  CRCT_CHECK_HIP(crct_gemm_launch_grouped_ln(a, ln, n, nullptr, (hipStream_t)stream, -1));      // -1: the library's default grid policy
-  return 0;
+  return gemm_grouped_checked(CrctGemmGroup{a, ln, n, nullptr, -1}, stream);      // -1: the library's default grid policy
 }
+extern "C" int crct_gemm_bf16_grouped(const CrctGemmArgs* a, int n, crct_stream_t stream) { return crct_gemm_bf16_grouped_ln_addend(a, nullptr, n, stream); }
 
 namespace {
 
@@ -516,7 +500,7 @@ struct Run {
   }
   void launch(const CrctGemmArgs& g, const CrctGemmLnAddend* ln = nullptr) {      // on the data stream: one tick per launch
     ++tick;
-    fail(ln && ln->mean ? crct_gemm_bf16_ln_addend(&g, ln, s) : crct_gemm_bf16(&g, s));
+    fail(crct_gemm_bf16_ln_addend(&g, ln && ln->mean ? ln : nullptr, s));
   }
 
   // y[M][out] = x W^T + b (+ epilogue), in the precision the Linear itself decides.  The forward rules, all of them:
@@ -579,7 +563,7 @@ struct Run {
     if (fold) g.rowsum_out = G(l.b);
     if (f8w) {
       if (!keep) return;                                  // (a weight with an e4m3 shadow and no gradient is refused by the caller)
-      if (g.tile != 36) g.tile = 37;                      // 2 stages (two workgroups per CU) unless the site policy asks for 3
+      g.tile = crct_gemm_fp8_wgrad_step_config(g.tile);   // 2 stages (two workgroups per CU) unless the site policy asks for 3
       pending_f8.push_back(g);
       return;
     }
@@ -593,7 +577,7 @@ struct Run {
   // launch the queued weight-gradient GEMMs on the side stream, ordered after everything enqueued on s so far
   std::vector<CrctGemmArgs> pending_f8;      // the layer's fp8 weight gradients: one grouped launch of their own
   // pending[i] is launched iff pending_keep[i]: a GEMM the Linear rule drops stays in the list, so that the groups are cut at the
-  // same places and take the configuration and the kernel they would have had with it (crct_gemm_launch_grouped_keep)
+  // same places and take the configuration and the kernel they would have had with it (CrctGemmGroup.keep)
   std::vector<uint8_t> pending_keep;
   void flush_wgrads() {
     if (!pending.empty() && std::find(pending_keep.begin(), pending_keep.end(), 1) == pending_keep.end()) { pending.clear(); pending_keep.clear(); }
@@ -614,7 +598,7 @@ struct Run {
     for (size_t i = 0; i < pending.size() && !rc; i += 8) {
       const int ng = (int)std::min<size_t>(8, pending.size() - i);
       const uint8_t* kp = pending_keep.data() + i;
-      fail(gemm_grouped_checked(pending.data() + i, ng, sw, target, std::find(kp, kp + ng, 0) == kp + ng ? nullptr : kp));
+      fail(gemm_grouped_checked(CrctGemmGroup{pending.data() + i, nullptr, ng, std::find(kp, kp + ng, 0) == kp + ng ? nullptr : kp, target}, sw));
     }
     pending.clear();
     pending_keep.clear();

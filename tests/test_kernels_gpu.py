@@ -2576,6 +2576,40 @@ def test_gemm_fp8_weight_gradient_bit_for_bit(tile):
         _assert_bits(p[4], ref, "fp8 grouped wgrad problem %d" % i)
 
 
+def test_gemm_configuration_ids_serve_their_operand_kind(gemm_path):
+    """A configuration id counts only on the operands its row of k_configs serves.  An fp8 id as CrctGemmArgs.tile of a bf16 GEMM (a
+    site policy of an fp8 step, in its bf16 calibration pass) runs configuration 12; each fp8 forward id (20, 21) on an fp8 forward
+    problem and each fp8 weight-gradient id (36, 37) on an fp8 weight gradient runs itself, whatever the shape would have chosen.
+    Every result bit for bit against the exact one."""
+    M, N, K = 129, 72, 64
+    A, B, kw, ref = _operands("nt", M, N, K, 48, 48, seed=5)
+    for tile in (20, 36):
+        expect = (12 if gemm_path == "pipelined" else _ran_cfg(gemm_path, tile, M, N, K), 1, 1)
+        _run_exact(A, B, M, N, K, dict(kw, tile=tile), ref, expect, "fp8 id %d on a bf16 GEMM" % tile, False)
+    M, N, K = 129, 72, 128                 # by shape this problem runs 20
+    qa, qb = GR.operands(M, N, K, 16, 16, seed=9, kind="e4m3")
+    sa, sb = torch.tensor([8.0], device=DEV), torch.tensor([4.0], device=DEV)
+    xa, xb = _f8(qa, "e4m3"), _f8(qb, "e4m3")
+    exact = GR.epilogue(GR.ref_nt(qa.to(DEV), qb.to(DEV)), alpha=1.0 / 32, out="f32")["y"]
+    for tile in (20, 21):
+        out = torch.full((M, N), SENT, device=DEV)
+        g = L.GemmArgs()
+        g.A, g.B, g.C, g.scale_a, g.scale_b = L.ptr(xa), L.ptr(xb), L.ptr(out), L.ptr(sa), L.ptr(sb)
+        g.lda, g.ldb, g.ldc, g.ld_aux, g.ld_add, g.ld_q = K, K, N, N, N, N
+        g.M, g.N, g.K, g.c_is_f32, g.tile, g.alpha, g.fp8 = M, N, K, 1, tile, 1.0, 1
+        _, recs = _logged(lambda: L.check(L.load().crct_gemm_bf16(C.byref(g), L.current_stream()), "gemm_fp8"))
+        assert recs == [(tile, 1, 1)], (tile, recs)
+        _assert_bits(out, exact, "fp8 forward under id %d" % tile)
+    R, N, K = 130, 48, 80
+    dq, xq = GR.ints((R, N), 8, 3, "e5m2"), GR.ints((R, K), 16, 4, "e4m3")
+    exact = GR.f32(GR.ref_tt(dq.to(DEV), xq.to(DEV)) / 32)
+    for tile in (36, 37):
+        out = torch.full((N, K), SENT, device=DEV)
+        _, recs = _logged(lambda: ops.gemm_wgrad_fp8([(_f8(dq, "e5m2"), _f8(xq, "e4m3"), sa, sb, out)], accumulate=False, tile=tile))
+        assert recs == [(tile, 1, 1)], (tile, recs)
+        _assert_bits(out, exact, "fp8 weight gradient under id %d" % tile)
+
+
 # ------------------------------------------------------------------------------------------- LayerNorm and column sums against fp64
 _LN_CASES = [(1, 64), (7, 96), (255, 520), (1600, 768), (9920, 1024), (255, 2048), (7, 2048), (1600, 520), (1, 1024), (9920, 64)]
 

@@ -146,6 +146,16 @@ def test_only_built_gemm_configurations_are_accepted():
     assert b"configuration 22 is not built" in lib.crct_last_error()
 
 
+def test_an_fp8_configuration_is_no_bf16_class_choice():
+    """Ids 20 / 21 / 36 / 37 are built (CrctGemmArgs.tile accepts them), but a shape class runs a bf16 configuration: refused, entry kept."""
+    lib = L.load()
+    cls = L.CLASS_NAMES.index("L.n")
+    old = lib.crct_gemm_class_config(cls, -1)
+    for cfg in (20, 21, 36, 37):
+        assert lib.crct_gemm_class_config(cls, cfg) == -1
+        assert lib.crct_gemm_class_config(cls, -1) == old
+
+
 def test_model_refuses_cpu():
     from crct.model import VisualDialogEncoder
     with pytest.raises(RuntimeError):

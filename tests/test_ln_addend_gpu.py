@@ -170,6 +170,37 @@ def test_ln_addend_grouped_launch():
         _assert_canary(g, M, N, "grouped %d x %d" % (M, N))
 
 
+def test_ln_addend_grouped_call_launched_one_by_one():
+    """A grouped call that does not qualify for one grid (a problem of 96 rows) runs as single launches, and each problem takes its
+    own LayerNorm addend along: the launches and the bits of the two single ``ops.gemm`` calls."""
+    shapes = [(96, 72, 64), (129, 200, 64)]
+
+    def problems():
+        probs, outs = [], []
+        for i, (M, N, K) in enumerate(shapes):
+            A, B = _operands(M, N, K)
+            c = _ln_case(M, N)
+            out = _canvas(M, N, N + 8, torch.float32)
+            p = dict(A=A, B=B, M=M, N=N, K=K, out=out, lda=K + 16, ldb=K + 8, ldc=N + 8, bias=c["bias"], ld_add=N + 16, c_cached=True,
+                     p_drop=P_DROP, site=DROP_SITE + i, seed=DROP_SEED, addend=c["y32"])
+            if i == 0:
+                p.update(addend=c["s"], ln_addend=c["ln"])
+            probs.append(p)
+            outs.append(out)
+        return probs, outs
+
+    probs, ref = problems()
+    single = _logged(lambda: [ops.gemm(**p) for p in probs])
+    probs, got = problems()
+    recs = _logged(lambda: ops.gemm_grouped(probs))
+    torch.cuda.synchronize()
+    assert len(recs) == 2 and all(r[2] == 1 for r in recs) and recs == single, (recs, single)
+    for (M, N, K), r, g in zip(shapes, ref, got):
+        assert torch.equal(_bits(g), _bits(r)), (M, N, K)
+        assert bool((g[:M, :N].double() != SENT).all()), (M, N, K)
+        _assert_canary(g, M, N, "one by one %d x %d" % (M, N))
+
+
 def test_ln_addend_is_refused_without_its_fp32_rows():
     M, N, K = 129, 72, 64
     A, B = _operands(M, N, K)
