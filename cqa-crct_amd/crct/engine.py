@@ -162,6 +162,25 @@ class StepEngine(object):
         if self.workspace.numel() < self.ws_bytes:
             self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
 
+    def set_input_grads(self, image_feat=None, image_loc=None, areas=None, txt_loc=None, text_emb=None):
+        """Where the backward passes that follow leave the gradients of the step's float inputs (crct_engine_set_input_grads): contiguous
+        fp32 device tensors -- image_feat [B, V, Fv], image_loc [B, V, 4], areas [B, V], txt_loc [B, T, 4], text_emb [B, T, H] (the summed
+        text embeddings in front of their LayerNorm) -- each written, not accumulated; None = not wanted, no argument = off.  A feature
+        gradient needs B * V * Fv fp32 more workspace: it grows here and KEEPS its bytes, since the request usually arrives between
+        the forward and the backward of a batch."""
+        req = L.InputGrads()
+        for name, t in (("d_image_feat", image_feat), ("d_image_loc", image_loc), ("d_areas", areas), ("d_txt_loc", txt_loc), ("d_text_emb", text_emb)):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError("set_input_grads: %s must be a contiguous fp32 tensor on the device" % name)
+            setattr(req, name, L.ptr(t))
+        L.check(self.lib.crct_engine_set_input_grads(self.handle, C.byref(req)), "engine_set_input_grads")
+        self._input_grads = (image_feat, image_loc, areas, txt_loc, text_emb)      # the engine holds raw pointers
+        self.ws_bytes = self.lib.crct_engine_workspace_bytes(self.handle)
+        if self.workspace.numel() < self.ws_bytes:
+            grown = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+            grown[:self.workspace.numel()].copy_(self.workspace)
+            self.workspace = grown
+
     def set_site_policy(self, site, kind, cfg=-1, split_k=0, phase=-1):
         """Launch policy of one GEMM site (crct_engine_set_site_policy): ``site`` / ``kind`` by name (crct.lib.SITE_NAMES /
         KIND_NAMES) or number, ``phase`` 0 = text-only part of the schedule, 1 = beside the visual stream, -1 = both."""

@@ -125,7 +125,11 @@ class StepCfg(C.Structure):
                 ("residual_fp32", c_i32)]
 
 
-SEG_ENQUEUED_FN = C.CFUNCTYPE(None, C.c_int, vp)      # void (*seg_enqueued)(int seg, void* user)
+class InputGrads(C.Structure):      # CrctInputGrads: fp32 device buffers for the gradients of the step's float inputs, NULL = not wanted
+    _fields_ = [("d_image_feat", vp), ("d_image_loc", vp), ("d_areas", vp), ("d_txt_loc", vp), ("d_text_emb", vp)]
+
+
+SEG_ENQUEUED_FN =C.CFUNCTYPE(None, C.c_int, vp)      # void (*seg_enqueued)(int seg, void* user)
 
 
 # name -> (restype, argtypes); every symbol include/crct_hip.h declares
@@ -213,6 +217,9 @@ PROTOTYPES = {
     "crct_engine_create": (vp, [C.POINTER(ModelDims), C.c_char_p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "crct_engine_create_variant": (vp, [C.POINTER(ModelDims), C.c_char_p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Variant)]),
     "crct_engine_set_areas": (C.c_int, [vp, vp]),
+    "crct_engine_set_input_grads": (C.c_int, [vp, C.POINTER(InputGrads)]),
+    "crct_embed_input_grad": (C.c_int, [vp] * 11 + [C.c_int] * 2 + _u8 + [vp]),
+    "crct_softmax_bwd_rows": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp]),
     "crct_engine_set_trainable": (C.c_int, [vp, vp, C.c_int]),
     "crct_engine_backward_plan": (C.c_int, [vp, vp, C.c_int]),
     "crct_engine_destroy": (None, [vp]),

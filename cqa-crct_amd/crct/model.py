@@ -37,10 +37,15 @@ class _StepFn(torch.autograd.Function):
     computed by the head kernel, encoder_decorator.py:144-153), nsp_loss [1] and the per-row regression loss [B]; backward
     hands their upstream gradients (device tensors, no sync) to the engine, which accumulates every parameter gradient
     into the flat buffer (``param.grad`` are views of it).  The usual case -- only ``loss`` is differentiated -- costs no
-    torch kernel besides autograd's own seed: the head kernel scales its built-in seeds by the upstream scalar."""
+    torch kernel besides autograd's own seed: the head kernel scales its built-in seeds by the upstream scalar.
+
+    The float inputs of the step -- the device tensors of ``image_feat``, ``image_loc``, ``loc`` (the text boxes) and ``areas``, the same
+    objects ``tensors`` holds -- are autograd inputs too: for those that need a gradient, backward hands the engine a buffer
+    (``StepEngine.set_input_grads``) for the duration of the pass and returns it with the dtype and shape of the input.  The values
+    carry whatever the upstream gradient carries (a GradScaler's loss scale), and are local: a data-parallel pass never exchanges them."""
 
     @staticmethod
-    def forward(ctx, anchor, model, tensors, step):
+    def forward(ctx, anchor, model, tensors, step, image_feat=None, image_loc=None, loc=None, areas=None):
         # (fp8 data gradients only: the forward pass is the plain bf16 one -- no fp8 state, no copies -- the backward pass gets it)
         fwd_step = {k: v for k, v in step.items() if k != "fp8"} if step.get("fp8_backward_only") else step
         model._engine.forward(model._flat_p, model._flat_b16, tensors, fwd_step)
@@ -58,7 +63,7 @@ class _StepFn(torch.autograd.Function):
         step = dict(ctx.step)
         if g_nsp is None and g_reg is None:
             if g_loss is None:
-                return None, None, None, None
+                return (None,) * 8
             step["g_loss"] = g_loss.reshape(1).float()                 # views / no-ops for the fp32 scalar autograd hands over
         else:                                                          # a caller combining nsp_loss / reg_loss itself
             B = ctx.tensors["tokens"].shape[0]
@@ -68,8 +73,8 @@ class _StepFn(torch.autograd.Function):
             gr = g_reg.reshape(B).float() if g_reg is not None else torch.zeros(B, device=dev)
             step["g_nsp"] = (gn + gl * step["nsp_coeff"]).contiguous()
             step["g_reg"] = (gr + gl * (step["reg_coeff"] / B)).contiguous()
-        model._run_backward(ctx.tensors, step)
-        return None, None, None, None
+        grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
+        return (None, None, None, None) + grads
 
 
 class SequenceMask(object):
@@ -151,6 +156,10 @@ class CrctModel(nn.Module):
         self._grad_waits = None
         self.record_segment_events = False           # set by FusedAdamW's early mode
         self._opt_stream = None
+        # token saliency: token ids cannot require grad, so True makes the next backward pass leave ``text_embedding_grad`` -- fp32
+        # [B, T, H], the gradient with respect to the summed text embeddings in front of their LayerNorm (replaced by every such pass)
+        self.keep_text_embedding_grad = False
+        self.text_embedding_grad = None
         self.init_weights(int(params.get("seed", 0)))
         self.register_load_state_dict_post_hook(lambda m, k: m._invalidate_shadow())
 
@@ -592,6 +601,38 @@ class CrctModel(nn.Module):
         else:
             self._ddp.backward(self, eng, tensors, step)
 
+    def _run_backward_with_inputs(self, tensors, step, need):
+        """``_run_backward`` with the gradients of the float inputs: ``need`` = which of (image_feat, image_loc, loc, areas) autograd wants.
+        Returns the four gradients (None where not wanted, and for the features of the dvqa / figure_qa variants, which never read them --
+        the reference computes that term and drops it), each with the dtype and shape of its tensor in ``tensors``.  With
+        ``keep_text_embedding_grad`` the pass also leaves ``text_embedding_grad``.  The request stands for this pass only."""
+        want_feat, want_iloc, want_tloc, want_areas = (bool(n) for n in need)
+        want_feat = want_feat and self.variant[0] == "plotqa"
+        want_areas = want_areas and tensors.get("areas") is not None
+        keep_emb = bool(self.keep_text_embedding_grad)
+        if not (want_feat or want_iloc or want_tloc or want_areas or keep_emb):
+            self._run_backward(tensors, step)
+            return None, None, None, None
+        dev = self._flat_p.device
+        B, T = tensors["tokens"].shape
+
+        def buf(like, on):
+            return torch.empty(like.shape, dtype=torch.float32, device=dev) if on else None
+        d_feat, d_iloc = buf(tensors["image_feat"], want_feat), buf(tensors["image_loc"], want_iloc)
+        d_tloc, d_areas = buf(tensors["loc"], want_tloc), buf(tensors.get("areas"), want_areas)
+        d_emb = torch.empty(B, T, self.config.hidden_size, dtype=torch.float32, device=dev) if keep_emb else None
+        eng = self._engine
+        eng.set_input_grads(image_feat=d_feat, image_loc=d_iloc, areas=d_areas, txt_loc=d_tloc, text_emb=d_emb)
+        try:
+            self._run_backward(tensors, step)
+        finally:
+            eng.set_input_grads()
+        if keep_emb:
+            self.text_embedding_grad = d_emb
+        if d_feat is not None and tensors["image_feat"].dtype != torch.float32:
+            d_feat = d_feat.to(tensors["image_feat"].dtype)
+        return d_feat, d_iloc, d_tloc, d_areas
+
     def _device_inputs(self, input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
                        image_attention_mask, image_target, R, labels, areas=None):
         dev = self._flat_p.device
@@ -679,7 +720,13 @@ class CrctModel(nn.Module):
                 step["fp8_mode"] = 2                   # bf16 forward GEMMs; the e4m3 copies / maxima for the fp8 backward are still written
         attention_maps = None
         if train_branch and torch.is_grad_enabled():
-            loss, nsp, reg_loss, logits, reg, stats = _StepFn.apply(self._anchor, self, tensors, step)
+            # the float inputs as autograd inputs; the engine's dict keeps detached aliases of the ones that are part of a graph
+            live = (tensors["image_feat"], tensors["image_loc"], tensors["loc"], tensors.get("areas"))
+            if any(t is not None and t.requires_grad for t in live):
+                tensors = dict(tensors, image_feat=live[0].detach(), image_loc=live[1].detach(), loc=live[2].detach())
+                if live[3] is not None:
+                    tensors["areas"] = live[3].detach()
+            loss, nsp, reg_loss, logits, reg, stats = _StepFn.apply(self._anchor, self, tensors, step, *live)
         else:
             eng.forward(self._flat_p, self._flat_b16, tensors, step)
             logits, reg, stats = eng.snapshot(B)

@@ -244,6 +244,33 @@ def softmax_rows(x):
     return y
 
 
+def softmax_bwd_rows(x, g):
+    """Gradient of the row softmax with respect to fp32 or bf16 features x [M, F] for the upstream gradient g (fp32 [M, F]) -> fp32 [M, F]."""
+    M, F = x.shape
+    dx = torch.empty(M, F, device=x.device, dtype=torch.float32)
+    _chk(x, torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32)
+    L.check(L.load().crct_softmax_bwd_rows(L.ptr(x), int(x.dtype == torch.bfloat16), L.ptr(_chk(g, torch.float32)), L.ptr(dx), M, F,
+                                           L.current_stream()), "softmax_bwd_rows")
+    return dx
+
+
+def embed_input_grad(dy, sum_saved, mean, rstd, gamma, loc=None, w_loc=None, w_areas=None, want=("d_loc", "d_areas", "d_sum"),
+                     p_drop=0.0, site=0, seed=0):
+    """Gradients of an embedding's float inputs from its LayerNorm's saved state (crct_embed_input_grad): dy, sum_saved bf16 [M, H];
+    ``want`` names the outputs -- (d_loc fp32 [M, 4], d_areas fp32 [M], d_sum fp32 [M, H]), None for the ones left out."""
+    M, H = dy.shape
+    dev = dy.device
+    d_loc = torch.empty(M, 4, device=dev) if "d_loc" in want else None
+    d_areas = torch.empty(M, device=dev) if "d_areas" in want else None
+    d_sum = torch.empty(M, H, device=dev) if "d_sum" in want else None
+    thr, scale, site = _drop(p_drop, site)
+    L.check(L.load().crct_embed_input_grad(L.ptr(_chk(dy, torch.bfloat16)), L.ptr(_chk(sum_saved, torch.bfloat16)), L.ptr(_chk(mean, torch.float32)),
+                                           L.ptr(_chk(rstd, torch.float32)), L.ptr(_chk(gamma, torch.float32)), L.ptr(_chk(loc, torch.float32)),
+                                           L.ptr(_chk(w_loc, torch.float32)), L.ptr(_chk(w_areas, torch.float32)), L.ptr(d_loc), L.ptr(d_areas),
+                                           L.ptr(d_sum), M, H, thr, scale, site, int(seed), L.current_stream()), "embed_input_grad")
+    return d_loc, d_areas, d_sum
+
+
 def cast_bf16(x, out=None):
     lib = L.load()
     out = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16) if out is None else out

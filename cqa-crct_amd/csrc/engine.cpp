@@ -164,6 +164,17 @@ struct crct_engine {
   CrctVariant var = {CRCT_DATASET_PLOTQA, CRCT_REGRESSOR_PLOTQA, 0, {}};
   bool feat = true;
   const float* areas = nullptr;        // crct_engine_set_areas: fp32 [B][V] of the running batch, or NULL
+  // crct_engine_set_input_grads: where the following backward passes leave the gradients of the float inputs (all NULL: off), the fp32
+  // [maxB * maxV][Fv] upstream gradient of the feature softmax behind everything else in the workspace (counted only while
+  // d_image_feat is requested), and whether a tensor WITH gradient sits in the text / image embedding (replan): an embedding half
+  // that runs for a requested input gradient alone leaves the parameter-gradient kernels out
+  CrctInputGrads ig = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t ws_ig = 0;
+  bool emb_own_t = true, emb_own_v = true;
+  bool ig_text() const { return ig.d_txt_loc || ig.d_text_emb; }
+  bool ig_vis() const { return ig.d_image_feat || ig.d_image_loc || ig.d_areas; }
+  size_t ws_base() const { return ln_addend ? ws_core : ws_two_output; }
+  void ws_update() { ws_bytes = ws_base() + (ig.d_image_feat ? ws_ig : 0); }
   struct { size_t sum, y, mean, rstd, yq; int site; } eta;
   struct { size_t soft, lin, sum, y, mean, rstd, yq; int site; } eva;
   LinearP t_pool, v_pool, cls, tp[4], vp[4], fu[4];
@@ -901,7 +912,36 @@ struct Run {
                                        P(e->ev.ln.g), A(sc.gc), G(e->ev.color), G(e->ev.wloc), G(e->ev.bloc), G(e->ev.img.b),
                                        G(e->ev.ln.g), G(e->ev.ln.b), F(partials), Mv, D.Hv, dv.thr, dv.scale, dv.site,
                                        c->seed, F(e->embed_rows[1]), W<int32_t>(e->embed_idx[1]), D.n_color, s));
-    lin_wgrad(A(sc.gc), D.Hv, A(e->eva.soft), D.Fv, e->ev.img, Mv);   // no dgrad: features are inputs
+    lin_wgrad(A(sc.gc), D.Hv, A(e->eva.soft), D.Fv, e->ev.img, Mv);   // the features are inputs: their gradient only on request (embed_image_input_grads)
+  }
+  // The gradients of the embeddings' float inputs (crct_engine_set_input_grads), after the half's own backward on its stream.
+  void embed_text_input_grads(size_t gt) {
+    const CrctModelDims& D = e->d;
+    const Drop dt = drop(D.p_hidden, 1);
+    ++tick;
+    if (!rc) fail(crct_embed_input_grad(A(gt), A(e->eta.sum), F(e->eta.mean), F(e->eta.rstd), P(e->et.ln.g), b->loc, P(e->et.wloc), nullptr,
+                                        e->ig.d_txt_loc, nullptr, e->ig.d_text_emb, b->B * b->T, D.H, dt.thr, dt.scale, dt.site, c->seed, s));
+  }
+  // ... image rows: d_loc and d_areas from the row kernel; the features' gradient through new_image_embeddings and the softmax:
+  // g[Mv][Fv] = d_sum W as fp32 (its bf16 rounding would sit in front of the softmax backward's cancelling difference) from the bf16
+  // d_sum in this layer's gc that the weight-gradient GEMM reads too -- always the bf16 kernel: this Linear has no e4m3 shadow
+  void embed_image_input_grads(size_t gv) {
+    const CrctModelDims& D = e->d;
+    const int Mv = b->B * b->V;
+    const Drop dv = drop(D.p_hidden, 2);
+    if (e->ig.d_image_loc || e->ig.d_areas) {
+      ++tick;
+      if (!rc) fail(crct_embed_input_grad(A(gv), A(e->eva.sum), F(e->eva.mean), F(e->eva.rstd), P(e->ev.ln.g), nullptr, P(e->ev.wloc),
+                                          e->ig.d_areas ? P(e->ev.areas.w) : nullptr, e->ig.d_image_loc, e->ig.d_areas, nullptr, Mv, D.Hv,
+                                          dv.thr, dv.scale, dv.site, c->seed, s));
+    }
+    if (!e->ig.d_image_feat) return;
+    const StreamScratch& sc = *sets[parity];               // the set embed_image_bwd has just written (layer_begin does not advance it)
+    float* g = F(e->ws_base());
+    Opt o; o.f32 = true;
+    lin_dgrad(A(sc.gc), D.Hv, e->ev.img, Mv, g, D.Fv, o);
+    ++tick;
+    if (!rc) fail(crct_softmax_bwd_rows(b->image_feat, b->image_feat_bf16, g, e->ig.d_image_feat, Mv, D.Fv, s));
   }
 
   // ---------------------------------------------------------------- heads
@@ -1061,11 +1101,13 @@ int check_batch(const crct_engine* e, const CrctBatch* b) {
 //  * a schedule step runs iff a tensor with gradient lies in it or below it in the forward graph on a stream it touches (a
 //    co-attention step touches both; the embeddings are the bottom step of their stream);
 //  * the gradient of a step's text / visual input is produced iff something with gradient lies below that input;
-//  * the last segment holds both embeddings: each half follows its own stream;
+//  * the last segment holds both embeddings: each half follows its own stream, and runs also for a requested gradient of one of its
+//    float inputs (crct_engine_set_input_grads) -- which therefore keeps every step above it on that stream running;
 //  * `dropped`: the weight-gradient GEMMs a running segment leaves out (crct_engine::drops_wgrad).
 void replan(crct_engine* e) {
   const size_t nseg = e->sched.size() + 2;
   e->plan.assign(nseg, SegPlan());
+  e->emb_own_t = e->emb_own_v = true;
   if (e->nograd.empty()) return;
   auto lin = [&](const LinearP& l) { return e->w_grad(l) || e->b_grad(l); };
   auto ln = [&](const LnP& l) { return e->grad_at(l.g) || e->grad_at(l.b); };
@@ -1077,9 +1119,13 @@ void replan(crct_engine* e) {
                  e->grad_at(e->et.bloc) || ln(e->et.ln);
   bool below_v = (e->feat ? lin(e->ev.img) : lin(e->ev.areas)) || e->grad_at(e->ev.color) || e->grad_at(e->ev.wloc) ||
                  e->grad_at(e->ev.bloc) || ln(e->ev.ln);
+  e->emb_own_t = below_t; e->emb_own_v = below_v;
+  // a requested input gradient counts as something with gradient below the embeddings of its stream (crct_engine_set_input_grads)
+  below_t = below_t || e->ig_text();
+  below_v = below_v || e->ig_vis();
   SegPlan& emb = e->plan[nseg - 1];
   emb.runs = below_t || below_v; emb.dx_t = below_t; emb.dx_v = below_v;
-  emb.dropped = (e->feat && below_v) ? drops(e->ev.img, false) : 0;
+  emb.dropped = (e->feat && below_v) ? drops(e->ev.img, false) : 0;      // (also when the half runs for an input gradient alone)
   for (size_t i = 0; i < e->sched.size(); ++i) {
     const Step& st = e->sched[i];
     SegPlan& pl = e->plan[e->sched.size() - i];
@@ -1316,7 +1362,8 @@ extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, 
     a.proj_t.a32 = ar.take(Mt * D.H * 4); a.ffn_t.y32 = ar.take(Mt * D.H * 4);
   }
   e->ws_two_output = ar.top;
-  e->ws_bytes = e->ln_addend ? e->ws_core : e->ws_two_output;
+  e->ws_ig = e->feat ? align_up(Mv * D.Fv * 4, 256) : 0;
+  e->ws_update();
 
   // ---- the hidden states every schedule step starts from (the last entry: the encoder's outputs), and the taps on them
   {
@@ -1374,6 +1421,19 @@ extern "C" int crct_engine_set_areas(crct_engine_t* e, const float* areas) {
   CRCT_REQUIRE(e, "engine_set_areas: null engine");
   CRCT_REQUIRE(!areas || !e->feat, "engine_set_areas: the 'plotqa' image embeddings have no areas term (vilbert.py:1463-1465)");
   e->areas = areas;
+  return 0;
+}
+
+extern "C" int crct_engine_set_input_grads(crct_engine_t* e, const CrctInputGrads* req) {
+  CRCT_REQUIRE(e, "engine_set_input_grads: null engine");
+  const CrctInputGrads none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  const CrctInputGrads r = req ? *req : none;
+  CRCT_REQUIRE(!r.d_image_feat || e->feat, "engine_set_input_grads: d_image_feat: the 'dvqa' / 'figure_qa' image embeddings never read the features (vilbert.py:1481-1483)");
+  CRCT_REQUIRE(!r.d_areas || !e->feat, "engine_set_input_grads: d_areas: the 'plotqa' image embeddings have no areas term (vilbert.py:1463-1465)");
+  const bool changed = (r.d_txt_loc || r.d_text_emb) != e->ig_text() || (r.d_image_feat || r.d_image_loc || r.d_areas) != e->ig_vis();
+  e->ig = r;
+  e->ws_update();
+  if (changed) replan(e);
   return 0;
 }
 
@@ -1539,6 +1599,7 @@ extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, c
   CRCT_REQUIRE(e && params_f32 && params_bf16 && cfg && workspace && grads_f32 && logits && reg && stats, "engine_backward: null argument");
   CRCT_REQUIRE(batch && batch->labels, "engine_backward: labels are required (training step)");
   if (int r = check_batch(e, batch)) return r;
+  CRCT_REQUIRE(!e->ig.d_areas || e->areas, "engine_backward: d_areas is requested (crct_engine_set_input_grads) but the batch has no areas (crct_engine_set_areas)");
   if (int r = ensure_streams(e, (hipStream_t)stream)) return r;
   e->evnext = 0;
   CrctDeviceScope on_device;                              // every launch below runs on this thread and the device stays
@@ -1568,8 +1629,12 @@ extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, c
       e->cur_t = 0; e->cur_v = 0;
       Rt.heads_bwd(Rv, e->in.back().t.x, e->in.back().v.x, e->st.dy[0], e->sv.dy[0], logits, reg, stats);
     } else if (sgi == nseg - 1) {
-      if (pl.dx_t) Rt.embed_text_bwd(e->st.dy[e->cur_t]);
-      if (pl.dx_v) Rv.embed_image_bwd(e->sv.dy[e->cur_v]);
+      // each half: the parameter gradients where a tensor of the embedding has one -- the image half of 'plotqa' also for a requested
+      // feature gradient, whose GEMM reads the bf16 d_sum that kernel stores -- then the requested input gradients on the same stream
+      if (pl.dx_t && e->emb_own_t) Rt.embed_text_bwd(e->st.dy[e->cur_t]);
+      if (pl.dx_t && e->ig_text()) Rt.embed_text_input_grads(e->st.dy[e->cur_t]);
+      if (pl.dx_v && (e->emb_own_v || e->ig.d_image_feat)) Rv.embed_image_bwd(e->sv.dy[e->cur_v]);
+      if (pl.dx_v && e->ig_vis()) Rv.embed_image_input_grads(e->sv.dy[e->cur_v]);
     } else {
       const Step& st = e->sched[si];
       const StepIn& x = e->in[si];
@@ -1696,7 +1761,7 @@ extern "C" int crct_engine_set_wgrad_flush(crct_engine_t* e, int mode) {
 extern "C" int crct_engine_set_ln_addend(crct_engine_t* e, int on) {
   if (!e) return 1;
   e->ln_addend = on != 0;
-  e->ws_bytes = e->ln_addend ? e->ws_core : e->ws_two_output;
+  e->ws_update();
   return 0;
 }
 

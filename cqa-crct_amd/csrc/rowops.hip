@@ -1159,6 +1159,148 @@ __global__ __launch_bounds__(256) void embed_image_bwd_kernel(
   if (SRC == IMG_AREAS) row_store_f32(awa, partials + (7 * nr + pr) * H, H, lane);
 }
 
+// ------------------------------------------------------------------------------ gradients of the embeddings' float inputs
+// The LayerNorm-backward row d_sum of an embedding, rebuilt exactly as embed_text_bwd_kernel / embed_image_bwd_kernel build it (same
+// loads, same mask bits, row_ln_bwd itself: its column accumulators are dead here), and what the float inputs of that row get from it:
+//   d_loc[row][k] = sum_c d_sum[c] W_loc[c][k]      (Linear(4, H); a text row without a box -- |loc|_1 == 0, vilbert.py:346-347 -- gets 0)
+//   d_areas[row]  = sum_c d_sum[c] w_areas[c]       (areas_emp = Linear(1, H))
+//   d_sum_out[row][:] = d_sum                        (the gradient of the summed embeddings in front of the LayerNorm)
+// Every output is optional.  A lane sums its columns in ascending order, wave_sum combines the lanes: one fixed order, no atomics.
+template <int NCH>
+__global__ __launch_bounds__(256) void embed_input_grad_kernel(
+    const bf16_t* __restrict__ dy_p, const bf16_t* __restrict__ sum_p, const float* __restrict__ mean_p,
+    const float* __restrict__ rstd_p, const float* __restrict__ gamma, const float* __restrict__ loc,
+    const float* __restrict__ w_loc, const float* __restrict__ w_areas, float* __restrict__ d_loc,
+    float* __restrict__ d_areas, float* __restrict__ d_sum_out, int M, int H, uint32_t thr, float scale, uint32_t site,
+    uint64_t seed) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Row<NCH> adg, adb;
+  row_zero(adg); row_zero(adb);
+  for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += (long)gridDim.x * ROWS_PER_BLOCK) {
+    Row<NCH> dy, x;
+    row_load_bf16(dy, dy_p + row * H, H, lane);
+    row_load_bf16(x, sum_p + row * H, H, lane);
+    row_apply_dropmask(dy, H, lane, row, thr, scale, site, seed);
+    row_ln_bwd(dy, x, gamma, H, lane, mean_p[row], rstd_p[row], adg, adb);
+    if (d_sum_out) row_store_f32(dy, d_sum_out + row * H, H, lane);
+    if (d_loc) {
+      bool box = true;
+      if (loc) {
+        const float4 lv = *reinterpret_cast<const float4*>(loc + row * 4);
+        box = fabsf(lv.x) + fabsf(lv.y) + fabsf(lv.z) + fabsf(lv.w) != 0.f;
+      }
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+      if (box) {      // wave-uniform: the row's box
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+          const int c = (lane + 64 * i) * 8;
+          if (c < H) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const float4 wv = *reinterpret_cast<const float4*>(w_loc + (long)(c + j) * 4);
+              a0 = fmaf(dy.v[i][j], wv.x, a0); a1 = fmaf(dy.v[i][j], wv.y, a1);
+              a2 = fmaf(dy.v[i][j], wv.z, a2); a3 = fmaf(dy.v[i][j], wv.w, a3);
+            }
+          }
+        }
+        a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); a3 = wave_sum(a3);
+      }
+      if (lane == 0) *reinterpret_cast<float4*>(d_loc + row * 4) = make_float4(a0, a1, a2, a3);
+    }
+    if (d_areas) {
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        const int c = (lane + 64 * i) * 8;
+        if (c < H) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) a = fmaf(dy.v[i][j], w_areas[c + j], a);      // (the flat offset of areas_emp.weight is not 16-byte aligned)
+        }
+      }
+      a = wave_sum(a);
+      if (lane == 0) d_areas[row] = a;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------ row softmax backward
+// d_x[r][j] = s[r][j] (g[r][j] - sum_k s[r][k] g[r][k]) with s = softmax(x[r]) recomputed in fp32 from the raw features (the bf16 copy
+// the forward keeps would be rounded in front of the cancelling difference).  One wave per row.  NC > 0: the row lives in registers,
+// NC chunks of 4 columns per lane (F <= 256 NC) -- x and g are read once, d_x is written once.  NC == 0: any F, the row is re-read.
+template <bool IN_BF16, int NC>
+__global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const void* __restrict__ x, const float* __restrict__ g,
+                                                               float* __restrict__ dx, int M, int F) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += (long)gridDim.x * ROWS_PER_BLOCK) {
+    const void* xr = IN_BF16 ? (const void*)(reinterpret_cast<const bf16_t*>(x) + row * F) : (const void*)(reinterpret_cast<const float*>(x) + row * F);
+    const float* gr = g + row * F;
+    float* dr = dx + row * F;
+    if constexpr (NC > 0) {
+      float4 xv[NC], gv[NC];
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {      // a chunk past the end re-reads the last one and is masked below
+        const int c = min((lane + 64 * i) * 4, F - 4);
+        xv[i] = softmax_load4<IN_BF16>(xr, c);
+        gv[i] = *reinterpret_cast<const float4*>(gr + c);
+      }
+      float mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        if ((lane + 64 * i) * 4 >= F) { xv[i] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY); gv[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
+        mx = fmaxf(fmaxf(mx, fmaxf(xv[i].x, xv[i].y)), fmaxf(xv[i].z, xv[i].w));
+      }
+      mx = wave_max(mx);
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        xv[i].x = expf(xv[i].x - mx); xv[i].y = expf(xv[i].y - mx); xv[i].z = expf(xv[i].z - mx); xv[i].w = expf(xv[i].w - mx);
+        s += (xv[i].x + xv[i].y) + (xv[i].z + xv[i].w);
+      }
+      const float inv = 1.0f / wave_sum(s);
+      float d = 0.f;
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        xv[i].x *= inv; xv[i].y *= inv; xv[i].z *= inv; xv[i].w *= inv;
+        d = fmaf(xv[i].x, gv[i].x, d); d = fmaf(xv[i].y, gv[i].y, d); d = fmaf(xv[i].z, gv[i].z, d); d = fmaf(xv[i].w, gv[i].w, d);
+      }
+      d = wave_sum(d);
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        const int c = (lane + 64 * i) * 4;
+        if (c < F)
+          *reinterpret_cast<float4*>(dr + c) = make_float4(xv[i].x * (gv[i].x - d), xv[i].y * (gv[i].y - d), xv[i].z * (gv[i].z - d), xv[i].w * (gv[i].w - d));
+      }
+    } else {
+      float mx = -INFINITY;
+      for (int c = lane * 4; c < F; c += 256) {
+        const float4 v = softmax_load4<IN_BF16>(xr, c);
+        mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+      }
+      mx = wave_max(mx);
+      float s = 0.f;
+      for (int c = lane * 4; c < F; c += 256) {
+        const float4 v = softmax_load4<IN_BF16>(xr, c);
+        s += (expf(v.x - mx) + expf(v.y - mx)) + (expf(v.z - mx) + expf(v.w - mx));
+      }
+      const float inv = 1.0f / wave_sum(s);
+      float d = 0.f;
+      for (int c = lane * 4; c < F; c += 256) {
+        const float4 v = softmax_load4<IN_BF16>(xr, c);
+        const float4 gg = *reinterpret_cast<const float4*>(gr + c);
+        d = fmaf(expf(v.x - mx) * inv, gg.x, d); d = fmaf(expf(v.y - mx) * inv, gg.y, d);
+        d = fmaf(expf(v.z - mx) * inv, gg.z, d); d = fmaf(expf(v.w - mx) * inv, gg.w, d);
+      }
+      d = wave_sum(d);
+      for (int c = lane * 4; c < F; c += 256) {
+        const float4 v = softmax_load4<IN_BF16>(xr, c);
+        const float4 gg = *reinterpret_cast<const float4*>(gr + c);
+        *reinterpret_cast<float4*>(dr + c) = make_float4(expf(v.x - mx) * inv * (gg.x - d), expf(v.y - mx) * inv * (gg.y - d),
+                                                         expf(v.z - mx) * inv * (gg.z - d), expf(v.w - mx) * inv * (gg.w - d));
+      }
+    }
+  }
+}
+
 inline int nch_for(int H) { return (H / 8 + 63) / 64; }
 // workgroups of a LayerNorm-forward launch at most (4 rows each per pass; a build-time value for A/B builds).  Re-checked in the step after the
 // kernel stopped writing the fp32 copy of its output (EXPERIMENTS.md, LayerNorm addend): 256 and 512 measured no better than 2048.
@@ -1750,4 +1892,39 @@ extern "C" int crct_embed_image_var_bwd(const void* dy, const void* sum_saved, c
                : embed_image_bwd_run<IMG_NONE>(dy, sum_saved, mean, rstd, loc, target, nullptr, gamma, nullptr, d_color, d_wloc, d_bloc,
                                                nullptr, nullptr, d_gamma, d_beta, partials, M, H, drop_thr, drop_scale, drop_site, seed,
                                                rows_scratch, idx_scratch, n_color, stream);
+}
+
+extern "C" int crct_embed_input_grad(const void* dy, const void* sum_saved, const float* mean, const float* rstd, const float* gamma,
+                                     const float* loc, const float* w_loc, const float* w_areas, float* d_loc, float* d_areas,
+                                     float* d_sum_out, int M, int H, uint32_t drop_thr, float drop_scale, uint32_t drop_site,
+                                     uint64_t seed, crct_stream_t stream) {
+  CRCT_REQUIRE(H % 8 == 0 && H > 0, "embed_input_grad: H=%d must be a positive multiple of 8", H);
+  CRCT_REQUIRE(dy && sum_saved && mean && rstd && gamma, "embed_input_grad: null argument");
+  CRCT_REQUIRE(!d_loc || w_loc, "embed_input_grad: d_loc needs w_loc (the location Linear's weight, fp32 [H][4])");
+  CRCT_REQUIRE(!d_areas || w_areas, "embed_input_grad: d_areas needs w_areas (areas_emp.weight, fp32 [H])");
+  if (M <= 0 || (!d_loc && !d_areas && !d_sum_out)) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  DISPATCH_NCH(H, crct_launch((embed_input_grad_kernel<NCH>), dim3(row_grid(M, 2048)), dim3(256), 0, s, (const bf16_t*)dy,
+                              (const bf16_t*)sum_saved, mean, rstd, gamma, loc, w_loc, w_areas, d_loc, d_areas, d_sum_out, M, H,
+                              drop_thr, drop_scale, drop_site, seed));
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+template <bool IN_BF16>
+static int softmax_bwd_rows_run(const void* x, const float* g, float* dx, int M, int F, hipStream_t s) {
+  CRCT_REQUIRE(F % 4 == 0 && F > 0, "softmax_bwd_rows: F=%d must be a positive multiple of 4", F);
+  CRCT_REQUIRE(x && g && dx, "softmax_bwd_rows: null argument");
+  if (M <= 0) return 0;
+  const dim3 grid(row_grid(M, 4096)), block(256);
+  if (F <= 256) crct_launch((softmax_bwd_rows_kernel<IN_BF16, 1>), grid, block, 0, s, x, g, dx, M, F);
+  else if (F <= 512) crct_launch((softmax_bwd_rows_kernel<IN_BF16, 2>), grid, block, 0, s, x, g, dx, M, F);
+  else if (F <= 1024) crct_launch((softmax_bwd_rows_kernel<IN_BF16, 4>), grid, block, 0, s, x, g, dx, M, F);
+  else if (F <= 2048) crct_launch((softmax_bwd_rows_kernel<IN_BF16, 8>), grid, block, 0, s, x, g, dx, M, F);
+  else crct_launch((softmax_bwd_rows_kernel<IN_BF16, 0>), grid, block, 0, s, x, g, dx, M, F);
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int crct_softmax_bwd_rows(const void* x, int x_bf16, const float* g, float* dx, int M, int F, crct_stream_t stream) {
+  return x_bf16 ? softmax_bwd_rows_run<true>(x, g, dx, M, F, (hipStream_t)stream) : softmax_bwd_rows_run<false>(x, g, dx, M, F, (hipStream_t)stream);
 }

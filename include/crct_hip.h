@@ -304,6 +304,10 @@ int crct_build_keymasks(const int64_t* sep_indices, const int64_t* hist_len, int
 int crct_softmax_rows_f32_bf16(const float* x, void* y, int M, int F, crct_stream_t stream);
 /* The same from bf16 features (a data loader / input pipeline that ships bf16 halves the step's host -> device bytes). */
 int crct_softmax_rows_bf16_bf16(const void* x, void* y, int M, int F, crct_stream_t stream);
+/* Backward of that softmax with respect to the features: dx[r][j] = s[r][j] (g[r][j] - sum_k s[r][k] g[r][k]), g and dx fp32 [M][F].
+ * s is recomputed in fp32 from the raw features x (fp32, or bf16 when x_bf16), never read from the forward's bf16 copy: the
+ * difference cancels.  F a positive multiple of 4; up to F = 2048 a row is read once and held in registers.  dx may not alias g. */
+int crct_softmax_bwd_rows(const void* x, int x_bf16, const float* g, float* dx, int M, int F, crct_stream_t stream);
 
 /* Stand-in for a gradient all-reduce on a box with ONE GPU (bench.py --ghost-ranks N; CRCT/train.py:138-143 is what it stands in for):
  * `channels` workgroups on `stream` (RCCL runs one per channel) stream `bytes` at ptr (16-byte aligned, left unchanged) through HBM
@@ -446,6 +450,21 @@ int crct_embed_image_var_bwd(const void* dy, const void* sum_saved, const float*
                              float* d_gamma, float* d_beta, float* partials, int M, int H,
                              uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
                              float* rows_scratch, int32_t* idx_scratch, int n_color, crct_stream_t stream);
+
+/* Gradients of an embedding's FLOAT inputs, for the text rows and the image rows of every variant.  From what the embedding backward
+ * reads (dy bf16 [M][H], the saved pre-LayerNorm sum, mean, rstd, gamma, the dropout site) the kernel rebuilds the LayerNorm-backward
+ * row d_sum in fp32 -- the arithmetic and mask bits of crct_embed_text_bwd_indexed / crct_embed_image_bwd -- and writes, each only
+ * when its pointer is not NULL:
+ *   d_loc     fp32 [M][4]  = d_sum . W_loc (w_loc fp32 [H][4]).  With loc (fp32 [M][4], the text rows' boxes) a row whose |loc|_1 == 0
+ *                            gets an exact zero: the text embedding adds no location term there (vilbert.py:346-347)
+ *   d_areas   fp32 [M]     = d_sum . w_areas (areas_emp.weight, fp32 [H])
+ *   d_sum_out fp32 [M][H]  = d_sum; rounded to bf16 it is the d_sum crct_embed_image_bwd stores, bit for bit
+ * One wave per row, a fixed summation order, no atomics: an output's bits do not depend on which other outputs are asked for.
+ * H a positive multiple of 8, at most 2048. */
+int crct_embed_input_grad(const void* dy, const void* sum_saved, const float* mean, const float* rstd, const float* gamma,
+                          const float* loc, const float* w_loc, const float* w_areas,
+                          float* d_loc, float* d_areas, float* d_sum_out, int M, int H,
+                          uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed, crct_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Heads + losses: BertPreTrainingHeads.forward (vilbert.py:1048-1062), the tail of
@@ -677,6 +696,28 @@ crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, const char*
 /* areas (fp32 [B][V], device) of the batch the next forward / backward calls run on; NULL = no areas term.  Forward and backward
  * of one batch must see the same value.  Variants DVQA / FIGUREQA only. */
 int crct_engine_set_areas(crct_engine_t*, const float* areas);
+/* Gradients of the loss with respect to the step's FLOAT inputs, written by the crct_engine_backward calls that follow (by the last
+ * segment: the embeddings).  Device buffers, fp32, each NULL = not wanted:
+ *   d_image_feat [B][V][Fv]  through the softmax of the features (variant PLOTQA only: the others never read the features)
+ *   d_image_loc  [B][V][4]
+ *   d_areas      [B][V]      (variants DVQA / FIGUREQA, on a batch with areas: crct_engine_set_areas)
+ *   d_txt_loc    [B][T][4]   (exact zeros on the rows without a box)
+ *   d_text_emb   [B][T][H]   the gradient of the summed text embeddings in front of their LayerNorm (token saliency)
+ * They are written, not accumulated, on the engine's streams; the call's closing join orders them before later work on the caller's
+ * stream.  NULL, or all members NULL, switches the feature off: not one launch, workspace byte or result bit differs from an engine
+ * that never saw this call.  While a request stands, its stream counts as having a gradient below the embeddings
+ * (crct_engine_backward_plan): with every parameter frozen the pass still runs down to them, without any weight-gradient GEMM.
+ * While d_image_feat is requested crct_engine_workspace_bytes grows by max_B * max_V * Fv fp32 (the softmax's upstream gradient); the
+ * bytes below keep their meaning, so a caller may grow its buffer between the forward and the backward of a batch if it keeps them.
+ * A request the variant cannot serve is refused here, d_areas on a batch without areas by crct_engine_backward before any launch. */
+typedef struct {
+  float* d_image_feat;
+  float* d_image_loc;
+  float* d_areas;
+  float* d_txt_loc;
+  float* d_text_emb;
+} CrctInputGrads;
+int crct_engine_set_input_grads(crct_engine_t*, const CrctInputGrads* req);
 /* Which parameters have a gradient in the backward passes that follow: one flag per parameter, in the order given to
  * crct_engine_create* (n = n_params); 0 = the tensor is WITHOUT gradient.  NULL, or all flags set, is the behaviour without this
  * call: not one launch or event differs.  Backward then runs less of itself (crct_engine_backward_plan); the forward is untouched.

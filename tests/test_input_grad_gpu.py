@@ -1,0 +1,502 @@
+"""Gradients of the loss with respect to the step's float inputs (-m gpu): ``image_feat.requires_grad_(True)`` before the call,
+``.grad`` after ``loss.backward()`` -- also ``image_loc``, ``loc`` (the text boxes), ``areas`` and, for token saliency,
+``core.keep_text_embedding_grad`` -> ``core.text_embedding_grad``.
+
+* The embeddings segment per element against fp64 FROM ITS OWN INPUTS (teacher forcing, as tests/test_layers_gpu.py): the hidden gradients
+  the engine hands to its last segment, the yardstick of tests/input_grad_ref.py.
+* The whole step against the oracle under autograd with the same inputs requiring grad, held to the oracle's own bf16-autocast twin.
+* Off means off; all parameters frozen; the autograd surface (dtypes, devices, accumulation, GradScaler, FlatGradDDP, refusals).
+
+Measured figures are in the docstrings of the tests that print them.
+"""
+import os
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import input_grad_ref as IG                         # noqa: E402
+import layer_ref as LR                              # noqa: E402
+from crct import config as C                       # noqa: E402
+from crct import lib as L                          # noqa: E402
+from crct import synthetic as S                    # noqa: E402
+from crct.step_adapter import forward as step_forward   # noqa: E402
+from helpers import ATOMIC_GRADS, _EngineDropout, load_case    # noqa: E402
+from oracle import crct_oracle as O                # noqa: E402
+from test_layers_gpu import _SegmentTaps           # noqa: E402
+from test_step_gpu import _oracle_step_with, _step_seed, build_model, cosine    # noqa: E402
+
+DEV = torch.device("cuda:0")
+
+
+def leaves(batch, names):
+    """The batch with fresh leaf copies of `names` that require grad."""
+    b = dict(batch)
+    for n in names:
+        b[n] = batch[n].detach().clone().requires_grad_(True)
+    return b
+
+
+def bits(t):
+    return t.detach().contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+# ------------------------------------------------------------------------------------------------ the embeddings segment
+SEGMENT_CASES = {"B3_V37_T31": (3, 37, 31, 0.0), "B3_V37_T31_p0.1": (3, 37, 31, 0.1), "B1_V2_T4": (1, 2, 4, 0.0)}
+_MODELS = {}
+
+
+def full_model(p):
+    """One full-width model (config/vilbert.json widths, F_v = 2048) per dropout probability, shared by the cases."""
+    if p not in _MODELS:
+        cfg = C.vilbert_config(v_feature_size=2048, hidden_dropout_prob=p, attention_probs_dropout_prob=p, v_hidden_dropout_prob=p,
+                               v_attention_probs_dropout_prob=p)
+        model, params = build_model(cfg, C.default_params(), weights=None, seed=11)
+        model.bert_pretrained.cls_dropout = p
+        model.train()
+        _MODELS[p] = (cfg, model, params)
+    return _MODELS[p]
+
+
+def _segment_check(cfg, model, params, batch, names, feat, p, what):
+    """One segmented training step with `names` requiring grad; the embeddings' input gradients against fp64 from the engine's own
+    final hidden gradients.  Returns (worst ratio per tensor, the leaves)."""
+    core = model.bert_pretrained
+    B, T = batch["tokens"].shape
+    V = batch["image_target"].shape[1]
+    b = leaves(batch, names)
+    runner = _SegmentTaps(B, T, V)
+    core._ddp = runner
+    core.keep_text_embedding_grad = True
+    try:
+        core.zero_flat_grads()
+        out = step_forward(model, b, params)
+        out[0].backward()
+        torch.cuda.synchronize()
+    finally:
+        core._ddp = None
+        core.keep_text_embedding_grad = False
+    eng = core._engine
+    nseg = len(eng.segments)
+    esd = LR.embed_weights_of(eng.table, core.flat_params, core.flat_shadow)
+    edrops = None
+    if p > 0:
+        ed = _EngineDropout(cfg, B, T, V, _step_seed(core, params), p)
+        edrops = dict(t=ed.keep_of(1, "rows", (B, T, cfg.hidden_size)), v=ed.keep_of(2, "rows", (B, V, cfg.v_hidden_size)))
+    dy_t, dy_v = runner.gt[nseg - 2], runner.gv[nseg - 2]
+    plain = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in b.items()}
+    ref = IG.reference_inputs(esd, cfg, plain, dy_t, dy_v, edrops, p, feat)
+    bud = IG.budget_inputs(esd, cfg, plain, dy_t, dy_v, edrops, p, feat)
+    got = dict(text_emb=core.text_embedding_grad, txt_loc=b["loc"].grad, image_loc=b["image_loc"].grad)
+    if feat:
+        got["image_feat"] = b["image_feat"].grad
+    if "areas" in names:
+        got["areas"] = b["areas"].grad
+    assert set(got) == set(ref) == set(bud), sorted(set(got) ^ set(ref))
+    worst, failures = {}, []
+    for k in ref:
+        assert got[k] is not None, k
+        assert tuple(got[k].shape) == tuple(ref[k].shape) and got[k].dtype == torch.float32, (k, got[k].shape, got[k].dtype)
+        r = IG.ratio(got[k].float(), ref[k], bud[k])
+        worst[k] = float(r.max())
+        if worst[k] > 1.0 or not bool(torch.isfinite(got[k]).all()):
+            i = tuple(int(j) for j in (r > 1).nonzero()[0]) if worst[k] > 1.0 else ()
+            failures.append("%s %s: %d of %d elements beyond the budget, first at %s, worst ratio %.2f" % (what, k, int((r > 1).sum()), r.numel(), i, worst[k]))
+    print("input gradients of the embeddings segment, worst ratios", what, {k: round(v, 3) for k, v in sorted(worst.items())})
+    assert not failures, "\n".join(failures)
+    return worst, b
+
+
+@pytest.mark.parametrize("case", list(SEGMENT_CASES))
+def test_embeddings_segment_input_gradients_match_fp64(case):
+    """Every element of image_feat.grad, image_loc.grad, loc.grad and text_embedding_grad within the budget (ratio <= 1), full widths.
+    Worst ratios measured on MI355X (printed by this test):
+      case             image_feat  image_loc  txt_loc  text_emb
+      B3_V37_T31       0.563       0.351      0.256    0.400
+      B3_V37_T31 p0.1  0.598       0.291      0.260    0.348
+      B1_V2_T4         0.441       0.066      0 (no box in the batch)  0.214
+    (the clean CPU emulator sits at 0.37 - 0.67 on the same tensors: tests/test_input_grad_ref_cpu.py).  Text rows without a box carry an
+    exact zero."""
+    B, V, T, p = SEGMENT_CASES[case]
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    cfg, model, params = full_model(p)
+    batch = S.make_batch(B, T, V, 2048, seed=100 + B, lengths=[max(4, T - 3 * b) for b in range(B)],
+                         n_vis=[max(1, V - 1 - 5 * b) for b in range(B)])
+    worst, b = _segment_check(cfg, model, params, batch, ("image_feat", "image_loc", "loc"), True, p, case)
+    empty = batch["loc"].abs().sum(-1) == 0
+    assert bool(empty.any()) and float(b["loc"].grad[empty].abs().max()) == 0.0
+    assert bool(empty.all()) or float(b["loc"].grad[~empty].abs().max()) > 0.0          # (B1_V2_T4: no token of its four has a box)
+    assert float(b["image_feat"].grad.abs().max()) > 0.0 and float(b["image_loc"].grad.abs().max()) > 0.0
+
+
+def test_variant_with_areas_input_gradients_match_fp64():
+    """DVQA with the CE regressor (tiny fixture, loaded as tests/test_variants_gpu.py does): areas.grad [B, V, 1] and image_loc.grad within
+    the budget, image_feat.grad None -- the variant never reads the features, and the reference drops the term it computes from them.
+    Worst ratios measured on MI355X: areas 0.235, image_loc 0.300, text_emb 0.304, txt_loc exact (no box in the fixture's batch)."""
+    from test_variants_gpu import load_variant, variant_model
+    z, meta, cfg, params, batch = load_variant("variant_tiny_dvqa_ce")
+    model, params = variant_model(meta, cfg, params)
+    model.train()
+    p = float(cfg.hidden_dropout_prob)
+    assert "areas" in batch
+    worst, b = _segment_check(cfg, model, params, batch, ("image_feat", "image_loc", "loc", "areas"), False, p, "variant_tiny_dvqa_ce")
+    assert b["image_feat"].grad is None
+    assert tuple(b["areas"].grad.shape) == tuple(batch["areas"].shape) and float(b["areas"].grad.abs().max()) > 0.0
+
+
+# ------------------------------------------------------------------------------------------------ the whole step against the oracle
+def _oracle_input_grads(sd, cfg, cpu_params, batch, autocast, drop=None, p_cls=0.0):
+    """oracle_step under autograd with the float inputs requiring grad; the text LayerNorm's input is caught for text_emb."""
+    w = {k: v.detach() for k, v in sd.items()}                       # only the inputs' gradients are wanted
+    b = leaves(batch, ("image_feat", "image_loc", "loc"))
+    seen, saved = [], O.layer_norm
+
+    def ln(x, g, bb):
+        if not seen:
+            x.retain_grad()
+            seen.append(x)
+        return saved(x, g, bb)
+    O.layer_norm = ln
+    try:
+        if autocast:
+            with torch.autocast("cpu", dtype=torch.bfloat16):
+                out = _oracle_step_with(drop, w, cfg, cpu_params, b, cls_dropout=p_cls)
+        else:
+            out = _oracle_step_with(drop, w, cfg, cpu_params, b, cls_dropout=p_cls)
+        out[0].float().backward()
+    finally:
+        O.layer_norm = saved
+    return dict(image_feat=b["image_feat"].grad, image_loc=b["image_loc"].grad, loc=b["loc"].grad, text_emb=seen[0].grad.float())
+
+
+# 1 - cos <= factor (1 - cos_yardstick) + 0.004 with the project's factor 1.6 (tests/test_step_gpu.py:953-963) for every tensor but
+# image_feat: over the four full-width draws (seeds 103 - 106) the factor a tensor needs, (deficit - 0.004) / yardstick's deficit, was at
+# most 0.61 for image_loc, loc and text_emb and 0.46, -0.35, 0.29 for image_feat on draws 104 - 106, but 3.884 for image_feat on draw 103 --
+# where this path's deficit is what it is on every draw (0.0053; 0.0008 - 0.0073 over the four) and the bf16-autocast oracle's happens to
+# be 0.00034 against 0.0053 - 0.0090 on the other three.  Its factor is 1.25 x that worst ratio.
+FACTOR = {"image_feat": 1.25 * 3.884}
+
+
+def _whole_step(model, cfg, params, sd, batch, what, norm_tol=0.05):
+    core = model.bert_pretrained
+    cpu_params = dict(params, device=torch.device("cpu"))
+    b = leaves(batch, ("image_feat", "image_loc", "loc"))
+    core.keep_text_embedding_grad = True
+    try:
+        core.zero_flat_grads()
+        step_forward(model, b, params)[0].backward()
+        torch.cuda.synchronize()
+    finally:
+        core.keep_text_embedding_grad = False
+    got = dict(image_feat=b["image_feat"].grad, image_loc=b["image_loc"].grad, loc=b["loc"].grad, text_emb=core.text_embedding_grad.cpu())
+    ref = _oracle_input_grads(sd, cfg, cpu_params, batch, False)
+    yard = _oracle_input_grads(sd, cfg, cpu_params, batch, True)
+    rows, bad = {}, []
+    for k in ref:
+        assert got[k] is not None and tuple(got[k].shape) == tuple(ref[k].shape), k
+        if float(ref[k].abs().max()) == 0.0:          # no token of the batch has a box: an exact zero on both sides
+            assert float(got[k].abs().max()) == 0.0 and float(yard[k].abs().max()) == 0.0, k
+            continue
+        d, dy = 1.0 - cosine(got[k].float().cpu(), ref[k]), 1.0 - cosine(yard[k].float(), ref[k])
+        q = float(got[k].double().norm() / ref[k].double().norm())
+        qy = float(yard[k].double().norm() / ref[k].double().norm())
+        rows[k] = dict(deficit=d, yardstick=dy, norm_ratio=q, yard_norm_ratio=qy)
+        if d > FACTOR.get(k, 1.6) * dy + 0.004 or abs(q - 1.0) > norm_tol:
+            bad.append((k, rows[k]))
+    print("input gradients of the whole step vs the oracle", what, {k: {n: round(v, 5) for n, v in r.items()} for k, r in rows.items()})
+    assert not bad, bad
+    return rows
+
+
+def test_tiny_step_input_gradients_match_the_oracle():
+    """tiny_L1 (the golden weights and batch): cosine deficit of every input gradient against the fp32 oracle under autograd within
+    1.6 x the deficit of the oracle's own CPU bf16-autocast twin + 0.004, norms within 5 % (the tiny step's bound on parameter gradients).
+    Measured on MI355X (deficit / yardstick's deficit): image_feat 2e-5 / 1e-5, image_loc 2e-5 / 1e-5, text_emb 3e-5 / 1e-5, norms within 0.4 %;
+    loc.grad is an exact zero on both sides (no token of the fixture's batch has a box)."""
+    import numpy as np
+    from helpers import GOLDEN
+    z, meta, cfg, params, batch = load_case("tiny_L1")
+    zw = np.load(os.path.join(GOLDEN, "tiny_L1.npz"))
+    model, params = build_model(cfg, params, weights=zw)
+    sd = {k[2:]: torch.from_numpy(zw[k]).clone() for k in zw.files if k.startswith("w.")}
+    _whole_step(model, cfg, params, sd, batch, "tiny_L1")
+
+
+def test_full_width_step_input_gradients_match_the_oracle():
+    """One full-width draw at B 3 (V 37, T 31, dropout 0, the seeded weights; seed 103, the hardest of four): the same bound, image_feat
+    with the factor stated above FACTOR; norms within 8 %, the cap of the full-size step test on parameter gradients (measured: 5.0 % low
+    for image_loc on this draw, within 3.7 % elsewhere; the yardstick itself is off by up to 3.0 %).
+    Measured on MI355X, deficit / yardstick's deficit per draw 103, 104, 105, 106:
+      image_feat  0.00534 / 0.00034   0.00726 / 0.00712   0.00080 / 0.00904   0.00557 / 0.00535
+      image_loc   0.00362 / 0.00013   0.00825 / 0.00839   0.00164 / 0.02913   0.00475 / 0.00470
+      loc         0.00290 / 0.00053   0.00289 / 0.00493   0.00063 / 0.01502   0.01009 / 0.01000
+      text_emb    0.00074 / 0.00087   0.00251 / 0.00414   0.00016 / 0.00867   0.00142 / 0.00160"""
+    from helpers import seeded_weights
+    torch.set_num_threads(max(1, min(32, os.cpu_count() or 1)))
+    cfg, model, params = full_model(0.0)
+    sd = seeded_weights(cfg, dict(params, device=torch.device("cpu")), base_seed=11, requires_grad=False)
+    batch = S.make_batch(3, 31, 37, 2048, seed=103)
+    _whole_step(model, cfg, params, sd, batch, "full width B3 seed 103", norm_tol=0.08)
+
+
+# ------------------------------------------------------------------------------------------------ off means off
+def _tiny(dropout=True, **over):
+    p = 0.1 if dropout else 0.0
+    cfg = C.tiny_config(hidden_dropout_prob=p, attention_probs_dropout_prob=p, v_hidden_dropout_prob=p, v_attention_probs_dropout_prob=p, **over)
+    model, params = build_model(cfg, C.default_params(categories=9, L1=True), weights=None, seed=7)
+    core = model.bert_pretrained
+    core.cls_dropout = p
+    model.train()
+    batch = S.make_batch(3, 9, 5, cfg.v_feature_size, categories=9, vocab_size=cfg.vocab_size, seed=11)
+    return cfg, model, params, core, batch
+
+
+def _counted_step(model, params, core, batch, it=1, scaler=None):
+    """One forward + backward at call number `it` on cleared gradients with every launch of the BACKWARD counted."""
+    lib = L.load()
+    core.zero_flat_grads()
+    core._calls = it - 1
+    out = step_forward(model, batch, params)
+    torch.cuda.synchronize()
+    lib.crct_prof_reset()
+    lib.crct_prof_enable(2)
+    try:
+        (out[0] if scaler is None else scaler.scale(out[0])).backward()
+        torch.cuda.synchronize()
+        n = lib.crct_prof_stamp_count()
+    finally:
+        lib.crct_prof_enable(0)
+        lib.crct_prof_reset()
+    outs = [out[0].detach().clone(), out[4].detach().clone()] + [r.detach().clone().float() for r in (out[5][0], out[5][1], out[5][2], out[5][4])]
+    return n, outs, core.flat_grads.clone()
+
+
+def test_without_a_request_nothing_changes():
+    """One model, one batch, dropout on.  A pass without any request, a requested pass (image_feat, image_loc, loc), then a pass with the
+    request gone again: the two unrequested passes launch the same number of kernels in backward, and give the same outputs, the same
+    flat gradients and the same reported workspace size, bit for bit.  The requested pass leaves every parameter gradient bit-identical
+    to the unrequested one (the tensors in helpers.ATOMIC_GRADS to rounding) and launches exactly 4 kernels more: the text row kernel, the
+    image row kernel, the data-gradient GEMM of new_image_embeddings and the softmax backward.  image_feat alone: 2 more."""
+    cfg, model, params, core, batch = _tiny()
+    n0, out0, g0 = _counted_step(model, params, core, batch)
+    eng = core._engine
+    ws0 = eng.lib.crct_engine_workspace_bytes(eng.handle)
+    b = leaves(batch, ("image_feat", "image_loc", "loc"))
+    n1, out1, g1 = _counted_step(model, params, core, b)
+    assert all(b[k].grad is not None for k in ("image_feat", "image_loc", "loc"))
+    assert eng.lib.crct_engine_workspace_bytes(eng.handle) == ws0                      # the request is gone with the pass
+    n2, out2, g2 = _counted_step(model, params, core, batch)
+    assert core._engine is eng
+    assert n2 == n0 and all(torch.equal(bits(a), bits(c)) for a, c in zip(out0, out2)) and torch.equal(bits(g0), bits(g2))
+    assert all(torch.equal(bits(a), bits(c)) for a, c in zip(out0, out1))
+    for e in core.table:
+        a, c = g0[e.offset:e.offset + e.numel], g1[e.offset:e.offset + e.numel]
+        if e.name in ATOMIC_GRADS:
+            assert torch.allclose(a, c, rtol=1e-3, atol=1e-6), e.name
+        else:
+            assert torch.equal(bits(a), bits(c)), e.name
+    assert n1 == n0 + 4, (n0, n1)
+    n3, _, _ = _counted_step(model, params, core, leaves(batch, ("image_feat",)))
+    assert n3 == n0 + 2, (n0, n3)
+    # while a feature gradient is requested the engine reports the larger workspace; clearing the request gives the size back
+    buf = torch.empty(3, 5, cfg.v_feature_size, device=DEV)
+    eng.set_input_grads(image_feat=buf)
+    assert eng.lib.crct_engine_workspace_bytes(eng.handle) >= ws0 + buf.numel() * 4 and eng.workspace.numel() >= eng.ws_bytes
+    eng.set_input_grads()
+    assert eng.lib.crct_engine_workspace_bytes(eng.handle) == ws0
+
+
+# ------------------------------------------------------------------------------------------------ every parameter frozen
+@pytest.mark.parametrize("fixed_t", [0, 1])
+def test_all_frozen_runs_data_gradients_only(fixed_t):
+    """Every parameter requires_grad_(False), image_feat (and, second half, loc) requiring grad; tiny config, also with fixed_t_layer = 1.
+    With a visual request alone every segment runs except the text-only layers under the first connection layer, which no visual
+    gradient passes through, and the embeddings run their image half only; with a text request too, EVERY segment runs.  A running
+    segment drops all of its weight-gradient GEMMs (4 per self layer, 8 per connection layer, 1 in the embeddings, 13 in the heads),
+    every p.grad is None, and image_feat.grad has the bits of the all-trainable pass."""
+    cfg, model, params, core, batch = _tiny(fixed_t_layer=fixed_t)
+    b = leaves(batch, ("image_feat", "loc"))
+    _counted_step(model, params, core, b)
+    free_feat, free_loc = b["image_feat"].grad.clone(), b["loc"].grad.clone()
+    for p in core.parameters():
+        p.requires_grad_(False)
+    b = leaves(batch, ("image_feat", "loc"))
+    _counted_step(model, params, core, b)
+    assert all(p.grad is None for p in core.parameters())
+    assert torch.equal(bits(b["image_feat"].grad), bits(free_feat)) and torch.equal(bits(b["loc"].grad), bits(free_loc))
+    b = leaves(batch, ("image_feat",))
+    _counted_step(model, params, core, b)
+    assert torch.equal(bits(b["image_feat"].grad), bits(free_feat)) and all(p.grad is None for p in core.parameters())
+    # the plan while a request stands (the forward above has told the engine that nothing is trainable)
+    eng = core._engine
+    sched = O.encoder_schedule(cfg)
+    first_conn = min(i for i, (k, _) in enumerate(sched) if k == "c")
+    want_drop = {"t": 4, "v": 4, "c": 8}
+    feat_buf, loc_buf = torch.empty(3, 5, cfg.v_feature_size, device=DEV), torch.empty(3, 9, 4, device=DEV)
+    try:
+        eng.set_input_grads(image_feat=feat_buf, txt_loc=loc_buf)
+        plan = eng.backward_plan()
+        assert all(pl[0] for pl in plan), plan
+        assert plan[0][3] == 13 and plan[-1] == (True, True, True, 1), (plan[0], plan[-1])
+        for i, (kind, _) in enumerate(sched):
+            assert plan[len(sched) - i] == (True, True, True, want_drop[kind]), (i, kind, plan[len(sched) - i])
+        eng.set_input_grads(image_feat=feat_buf)
+        plan = eng.backward_plan()
+        assert plan[-1] == (True, False, True, 1) and plan[0][:3] == (True, True, True)
+        for i, (kind, _) in enumerate(sched):
+            runs = not (kind == "t" and i < first_conn)
+            assert plan[len(sched) - i][0] == runs, (i, kind, plan[len(sched) - i])
+            if runs:
+                assert plan[len(sched) - i][3] == want_drop[kind]
+    finally:
+        eng.set_input_grads()
+    assert not any(pl[0] for pl in eng.backward_plan())          # nothing requested, nothing trainable: no segment runs
+
+
+# ------------------------------------------------------------------------------------------------ the autograd surface
+def _grads_of(model, params, core, batch, names, it=1, scaler=None, zero=True):
+    b = leaves(batch, names)
+    if zero:
+        core.zero_flat_grads()
+    core._calls = it - 1
+    out = step_forward(model, b, params)
+    (out[0] if scaler is None else scaler.scale(out[0])).backward()
+    torch.cuda.synchronize()
+    return b
+
+
+def test_surface_dtypes_devices_accumulation_and_scaling():
+    cfg, model, params, core, batch = _tiny()
+    base = _grads_of(model, params, core, batch, ("image_feat", "image_loc", "loc"))
+    for k, shape in (("image_feat", (3, 5, cfg.v_feature_size)), ("image_loc", (3, 5, 4)), ("loc", (3, 9, 4))):
+        g = base[k].grad
+        assert g is not None and g.device.type == "cpu" and g.dtype == torch.float32 and tuple(g.shape) == shape, k      # a CPU leaf: its gradient on the CPU
+    assert core.text_embedding_grad is None                                               # off by default
+    # bf16 features give a bf16 gradient: the fp32 one rounded once
+    b16 = dict(batch, image_feat=batch["image_feat"].to(torch.bfloat16))
+    ref16 = _grads_of(model, params, core, dict(batch, image_feat=b16["image_feat"].float()), ("image_feat",))
+    got16 = _grads_of(model, params, core, b16, ("image_feat",))
+    assert got16["image_feat"].grad.dtype == torch.bfloat16
+    assert torch.equal(bits(got16["image_feat"].grad), bits(ref16["image_feat"].grad.to(torch.bfloat16)))
+    # a tensor resident on the device: its gradient on the device, the CPU leaf's bits
+    res = dict(batch)
+    res["image_feat"] = batch["image_feat"].to(DEV).requires_grad_(True)
+    core.zero_flat_grads()
+    core._calls = 0
+    step_forward(model, res, params)[0].backward()
+    torch.cuda.synchronize()
+    assert res["image_feat"].grad.is_cuda and torch.equal(bits(res["image_feat"].grad.cpu()), bits(base["image_feat"].grad))
+    # two backward passes accumulate in .grad, as torch does
+    b = leaves(batch, ("image_loc",))
+    for _ in range(2):
+        core._calls = 0
+        step_forward(model, b, params)[0].backward()
+    torch.cuda.synchronize()
+    assert torch.equal(bits(b["image_loc"].grad), bits(base["image_loc"].grad * 2))
+    # a GradScaler with a fixed scale of 1024: the gradient carries the loss scale, and the factor is exact
+    scaler = torch.cuda.amp.GradScaler(init_scale=1024.0, growth_interval=10 ** 9)
+    sc = _grads_of(model, params, core, batch, ("image_feat", "image_loc", "loc"), scaler=scaler)
+    for k in ("image_feat", "image_loc", "loc"):
+        assert torch.equal(bits(sc[k].grad), bits(base[k].grad * 1024.0)), k
+    # token saliency: fp32 [B, T, H], replaced by every such pass, never left behind by a pass that did not ask
+    core.keep_text_embedding_grad = True
+    _grads_of(model, params, core, batch, ())
+    first = core.text_embedding_grad
+    assert first.dtype == torch.float32 and tuple(first.shape) == (3, 9, cfg.hidden_size) and float(first.abs().max()) > 0
+    _grads_of(model, params, core, batch, ())
+    assert core.text_embedding_grad is not first and torch.equal(bits(core.text_embedding_grad), bits(first))
+    core.keep_text_embedding_grad = False
+
+
+def test_flat_grad_ddp_at_world_one_gives_the_plain_bits():
+    import torch.distributed as dist
+    from crct.ddp import FlatGradDDP
+    cfg, model, params, core, batch = _tiny()
+    base = _grads_of(model, params, core, batch, ("image_feat", "image_loc", "loc"))
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", "29561")
+    torch.cuda.set_device(0)
+    dist.init_process_group(backend="nccl", rank=0, world_size=1, device_id=DEV)
+    try:
+        ddp = FlatGradDDP(model, device_ids=[0], find_unused_parameters=True)
+        got = _grads_of(ddp, params, core, batch, ("image_feat", "image_loc", "loc"))
+        for k in ("image_feat", "image_loc", "loc"):
+            assert torch.equal(bits(got[k].grad), bits(base[k].grad)), k
+    finally:
+        core._ddp = None
+        dist.destroy_process_group()
+
+
+def test_evaluation_and_no_grad_launch_nothing_new():
+    """The evaluation branch and a training forward under no_grad with inputs that require grad: the launches of the same call with plain
+    inputs, no graph, no gradient."""
+    cfg, model, params, core, batch = _tiny(dropout=False)
+    lib = L.load()
+
+    def launches(b, evaluation, no_grad):
+        torch.cuda.synchronize()
+        lib.crct_prof_reset()
+        lib.crct_prof_enable(2)
+        try:
+            if no_grad:
+                with torch.no_grad():
+                    out = step_forward(model, b, params, evaluation=evaluation)
+            else:
+                out = step_forward(model, b, params, evaluation=evaluation)
+            torch.cuda.synchronize()
+            return lib.crct_prof_stamp_count(), out
+        finally:
+            lib.crct_prof_enable(0)
+            lib.crct_prof_reset()
+    step_forward(model, batch, params)                                   # builds the engine
+    model.eval()
+    n_plain, _ = launches(batch, True, False)
+    b = leaves(batch, ("image_feat", "image_loc", "loc"))
+    n_req, out = launches(b, True, False)
+    assert n_req == n_plain and not out[4].requires_grad and b["image_feat"].grad is None
+    model.train()
+    n_plain, _ = launches(batch, False, True)
+    n_req, out = launches(b, False, True)
+    assert n_req == n_plain and not out[0].requires_grad
+
+
+def test_requests_a_variant_cannot_serve_are_refused_before_any_launch():
+    lib = L.load()
+    # PlotQA: no areas term
+    cfg, model, params, core, batch = _tiny(dropout=False)
+    _grads_of(model, params, core, batch, ())
+    eng = core._engine
+    lib.crct_prof_reset()
+    lib.crct_prof_enable(2)
+    try:
+        with pytest.raises(RuntimeError, match="d_areas"):
+            eng.set_input_grads(areas=torch.empty(3, 5, device=DEV))
+        with pytest.raises(ValueError, match="d_image_feat"):
+            eng.set_input_grads(image_feat=torch.empty(3, 5, cfg.v_feature_size))          # not on the device
+        # DVQA: the features are never read; d_areas on a batch without areas
+        from test_variants_gpu import load_variant, variant_model
+        z, meta, vcfg, vparams, vbatch = load_variant("variant_tiny_dvqa_ce")
+        vmodel, vparams = variant_model(meta, vcfg, vparams)
+        vcore = vmodel.bert_pretrained
+        B, V = vbatch["image_target"].shape
+        step_forward(vmodel, vbatch, vparams)                               # builds the engine
+        veng = vcore._engine
+        with pytest.raises(RuntimeError, match="d_image_feat"):
+            veng.set_input_grads(image_feat=torch.empty(B, V, vcfg.v_feature_size, device=DEV))
+        no_areas = {k: v for k, v in vbatch.items() if k != "areas"}
+        out = step_forward(vmodel, no_areas, vparams)
+        torch.cuda.synchronize()
+        before = lib.crct_prof_stamp_count()
+        veng.set_input_grads(areas=torch.empty(B, V, device=DEV))
+        try:
+            with pytest.raises(RuntimeError, match="d_areas"):
+                out[0].backward()
+            torch.cuda.synchronize()
+            assert lib.crct_prof_stamp_count() == before
+        finally:
+            veng.set_input_grads()
+    finally:
+        lib.crct_prof_enable(0)
+        lib.crct_prof_reset()
+        eng.set_input_grads()
