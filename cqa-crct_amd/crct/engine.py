@@ -181,6 +181,33 @@ class StepEngine(object):
             grown[:self.workspace.numel()].copy_(self.workspace)
             self.workspace = grown
 
+    def sequence_outputs(self, text=True, visual=True):
+        """The final hidden states of the LAST forward of this engine (crct_engine_sequence_outputs): (sequence_output_t fp32 [B, T, H],
+        sequence_output_v fp32 [B, V, Hv]), fresh tensors that own their memory; None where not asked for.  One launch each, rebuilt from
+        what the closing LayerNorm left in the workspace; ``.bfloat16()`` of either is the engine's own bf16 state (taps seq_t / seq_v)."""
+        if self._keep is None:
+            raise RuntimeError("sequence_outputs: run a forward pass on this engine first")
+        tensors, _ = self._keep
+        B, T = tensors["tokens"].shape
+        V = tensors["image_feat"].shape[1]
+        seq_t = torch.empty(B, T, self.cfg.hidden_size, dtype=torch.float32, device=self.device) if text else None
+        seq_v = torch.empty(B, V, self.cfg.v_hidden_size, dtype=torch.float32, device=self.device) if visual else None
+        L.check(self.lib.crct_engine_sequence_outputs(self.handle, self._keep_p32.data_ptr(), self.workspace.data_ptr(), B, T, V,
+                                                      L.ptr(seq_t), L.ptr(seq_v), L.current_stream()), "engine_sequence_outputs")
+        return seq_t, seq_v
+
+    def set_output_grads(self, seq_t=None, seq_v=None):
+        """Upstream gradients of the final hidden states for the backward passes that follow (crct_engine_set_output_grads): contiguous
+        fp32 device tensors [B, T, H] / [B, V, Hv], 16-byte aligned; segment 0 adds grad_scale times each onto that stream's running
+        hidden gradient.  None = none, no argument = off.  The backward plan does not depend on it."""
+        req = L.OutputGrads()
+        for name, t in (("d_seq_t", seq_t), ("d_seq_v", seq_v)):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16):
+                raise ValueError("set_output_grads: %s must be a contiguous, 16-byte aligned fp32 tensor on the device" % name)
+            setattr(req, name, L.ptr(t))
+        L.check(self.lib.crct_engine_set_output_grads(self.handle, C.byref(req)), "engine_set_output_grads")
+        self._output_grads = (seq_t, seq_v)      # the engine holds raw pointers
+
     def set_site_policy(self, site, kind, cfg=-1, split_k=0, phase=-1):
         """Launch policy of one GEMM site (crct_engine_set_site_policy): ``site`` / ``kind`` by name (crct.lib.SITE_NAMES /
         KIND_NAMES) or number, ``phase`` 0 = text-only part of the schedule, 1 = beside the visual stream, -1 = both."""
@@ -270,7 +297,7 @@ class StepEngine(object):
         B = tensors["tokens"].shape[0]
         self._set_areas(tensors)
         b, c = self._batch(tensors), self._cfg(step)
-        self._keep = (tensors, step)
+        self._keep, self._keep_p32 = (tensors, step), p32
         L.check(self.lib.crct_engine_forward(self.handle, p32.data_ptr(), p16.data_ptr(), C.byref(b), C.byref(c),
                                              self.workspace.data_ptr(), self.logits.data_ptr(), self.reg.data_ptr(),
                                              self.stats.data_ptr(), L.current_stream()), "engine_forward")

@@ -129,6 +129,10 @@ class InputGrads(C.Structure):      # CrctInputGrads: fp32 device buffers for th
     _fields_ = [("d_image_feat", vp), ("d_image_loc", vp), ("d_areas", vp), ("d_txt_loc", vp), ("d_text_emb", vp)]
 
 
+class OutputGrads(C.Structure):     # CrctOutputGrads: fp32 device buffers holding the upstream gradients of the final hidden states, NULL = none
+    _fields_ = [("d_seq_t", vp), ("d_seq_v", vp)]
+
+
 SEG_ENQUEUED_FN =C.CFUNCTYPE(None, C.c_int, vp)      # void (*seg_enqueued)(int seg, void* user)
 
 
@@ -220,6 +224,10 @@ PROTOTYPES = {
     "crct_engine_set_input_grads": (C.c_int, [vp, C.POINTER(InputGrads)]),
     "crct_embed_input_grad": (C.c_int, [vp] * 11 + [C.c_int] * 2 + _u8 + [vp]),
     "crct_softmax_bwd_rows": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp]),
+    "crct_layernorm_rows_f32": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "crct_hidden_grad_add": (C.c_int, [vp, vp, c_f32, c_i64, vp]),
+    "crct_engine_sequence_outputs": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "crct_engine_set_output_grads": (C.c_int, [vp, C.POINTER(OutputGrads)]),
     "crct_engine_set_trainable": (C.c_int, [vp, vp, C.c_int]),
     "crct_engine_backward_plan": (C.c_int, [vp, vp, C.c_int]),
     "crct_engine_destroy": (None, [vp]),

@@ -42,7 +42,11 @@ class _StepFn(torch.autograd.Function):
     The float inputs of the step -- the device tensors of ``image_feat``, ``image_loc``, ``loc`` (the text boxes) and ``areas``, the same
     objects ``tensors`` holds -- are autograd inputs too: for those that need a gradient, backward hands the engine a buffer
     (``StepEngine.set_input_grads``) for the duration of the pass and returns it with the dtype and shape of the input.  The values
-    carry whatever the upstream gradient carries (a GradScaler's loss scale), and are local: a data-parallel pass never exchanges them."""
+    carry whatever the upstream gradient carries (a GradScaler's loss scale), and are local: a data-parallel pass never exchanges them.
+
+    With ``model.return_sequence_outputs`` the node has two more differentiable outputs behind the six: the encoder's final hidden states
+    (fp32 [B, T, H] and [B, V, Hv]).  Their upstream gradients (None when unused) go to the engine for the duration of the pass
+    (``StepEngine.set_output_grads``), which adds them onto the hidden gradients the heads seed; unused, the pass is the plain one."""
 
     @staticmethod
     def forward(ctx, anchor, model, tensors, step, image_feat=None, image_loc=None, loc=None, areas=None):
@@ -55,15 +59,22 @@ class _StepFn(torch.autograd.Function):
         ctx.mark_non_differentiable(logits, reg_all, stats)
         # the differentiable scalar is a tensor of its own (4 bytes): the reference loop modifies it in place
         # (train.py:204-205 ``loss /= params['batch_multiply']``), which autograd forbids on a view output of a multi-output node
-        return stats[0].clone(), stats[1:2], reg_all[1], logits, reg_all, stats     # the rest: views of the snapshot, no copies
+        out = (stats[0].clone(), stats[1:2], reg_all[1], logits, reg_all, stats)     # the rest: views of the snapshot, no copies
+        if model.return_sequence_outputs:
+            # two more differentiable outputs: the encoder's final hidden states, fresh fp32 tensors (StepEngine.sequence_outputs)
+            out = out + model._engine.sequence_outputs()
+        return out
 
     @staticmethod
-    def backward(ctx, g_loss, g_nsp, g_reg, _gl, _gr, _gs):
+    def backward(ctx, g_loss, g_nsp, g_reg, _gl, _gr, _gs, g_seq_t=None, g_seq_v=None):
         model = ctx.model
         step = dict(ctx.step)
+        g_seq_t, g_seq_v = _upstream_f32(g_seq_t), _upstream_f32(g_seq_v)
         if g_nsp is None and g_reg is None:
             if g_loss is None:
-                return (None,) * 8
+                if g_seq_t is None and g_seq_v is None:
+                    return (None,) * 8
+                g_loss = torch.zeros(1, device=model._flat_p.device)   # only the sequence outputs are differentiated: the heads get zero seeds
             step["g_loss"] = g_loss.reshape(1).float()                 # views / no-ops for the fp32 scalar autograd hands over
         else:                                                          # a caller combining nsp_loss / reg_loss itself
             B = ctx.tensors["tokens"].shape[0]
@@ -73,8 +84,26 @@ class _StepFn(torch.autograd.Function):
             gr = g_reg.reshape(B).float() if g_reg is not None else torch.zeros(B, device=dev)
             step["g_nsp"] = (gn + gl * step["nsp_coeff"]).contiguous()
             step["g_reg"] = (gr + gl * (step["reg_coeff"] / B)).contiguous()
-        grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
+        if g_seq_t is None and g_seq_v is None:
+            grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
+        else:
+            # upstream gradients of the sequence outputs: segment 0 adds them onto the hidden gradients the heads seed (the request stands
+            # for this pass only, like the input-gradient request inside the call; the two compose)
+            eng = model._engine
+            eng.set_output_grads(seq_t=g_seq_t, seq_v=g_seq_v)
+            try:
+                grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
+            finally:
+                eng.set_output_grads()
         return (None, None, None, None) + grads
+
+
+def _upstream_f32(g):
+    """An upstream gradient as the engine reads it: fp32, contiguous, 16-byte aligned (a no-op for what autograd usually hands over)."""
+    if g is None:
+        return None
+    g = g.float().contiguous()
+    return g.clone() if g.data_ptr() % 16 else g
 
 
 class SequenceMask(object):
@@ -160,6 +189,12 @@ class CrctModel(nn.Module):
         # [B, T, H], the gradient with respect to the summed text embeddings in front of their LayerNorm (replaced by every such pass)
         self.keep_text_embedding_grad = False
         self.text_embedding_grad = None
+        # True: every forward also returns ``sequence_output_t`` (fp32 [B, T, H], slot 3 of both tuples: vilbert.py:1659, :1661) and leaves
+        # it and ``sequence_output_v`` (fp32 [B, V, Hv]) here -- under grad in the training branch as differentiable outputs of the step
+        # (an auxiliary loss on the token states trains the encoder through them), otherwise as plain tensors.  Two launches per forward.
+        self.return_sequence_outputs = False
+        self.sequence_output_t = None
+        self.sequence_output_v = None
         self.init_weights(int(params.get("seed", 0)))
         self.register_load_state_dict_post_hook(lambda m, k: m._invalidate_shadow())
 
@@ -726,11 +761,12 @@ class CrctModel(nn.Module):
                 tensors = dict(tensors, image_feat=live[0].detach(), image_loc=live[1].detach(), loc=live[2].detach())
                 if live[3] is not None:
                     tensors["areas"] = live[3].detach()
-            loss, nsp, reg_loss, logits, reg, stats = _StepFn.apply(self._anchor, self, tensors, step, *live)
+            loss, nsp, reg_loss, logits, reg, stats, *seq = _StepFn.apply(self._anchor, self, tensors, step, *live)
         else:
             eng.forward(self._flat_p, self._flat_b16, tensors, step)
             logits, reg, stats = eng.snapshot(B)
             loss, nsp, reg_loss = stats[0], stats[1:2], reg[1]
+            seq = eng.sequence_outputs() if self.return_sequence_outputs else ()
             if output_all_attention_masks and not train_branch:
                 attention_maps = self._attention_maps(eng)
         # the combined training loss as the head kernel computed it (differentiable); the step adapter returns it instead
@@ -748,9 +784,11 @@ class CrctModel(nn.Module):
             # fill kernels per step
             self._const_zeros = (torch.zeros(1, 1, device=dev), torch.zeros(1, 1, device=dev), torch.zeros(1, device=dev))
         lm_zero, img_zero, legend_loss = self._const_zeros
+        # sequence_output_t in slot 3 of both tuples, on request (return_sequence_outputs); both final states stay on the model
+        self.sequence_output_t, self.sequence_output_v = seq if seq else (None, None)
         if train_branch:
-            return lm_zero, img_zero, nsp, None, None, logits, reg_out, legend_loss        # vilbert.py:1659
-        return None, None, logits, None, attention_maps, reg_out, legend_loss               # vilbert.py:1661
+            return lm_zero, img_zero, nsp, self.sequence_output_t, None, logits, reg_out, legend_loss        # vilbert.py:1659
+        return None, None, logits, self.sequence_output_t, attention_maps, reg_out, legend_loss               # vilbert.py:1661
 
     def _attention_maps(self, eng):
         """``output_all_attention_masks=True`` (vilbert.py:842-946, :1562): (text maps, visual maps, co-attention maps) of the forward

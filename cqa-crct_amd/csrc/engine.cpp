@@ -171,6 +171,11 @@ struct crct_engine {
   CrctInputGrads ig = {nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t ws_ig = 0;
   bool emb_own_t = true, emb_own_v = true;
+  // crct_engine_set_output_grads: fp32 upstream gradients of the encoder's final hidden states that segment 0 of the following backward
+  // passes adds onto the running hidden gradients (both NULL: off); fwd_r32: the residual_fp32 of the last forward (-1: none yet), which
+  // says whether the rows crct_engine_sequence_outputs normalises again are fp32 or bf16
+  CrctOutputGrads og = {nullptr, nullptr};
+  int fwd_r32 = -1;
   bool ig_text() const { return ig.d_txt_loc || ig.d_text_emb; }
   bool ig_vis() const { return ig.d_image_feat || ig.d_image_loc || ig.d_areas; }
   size_t ws_base() const { return ln_addend ? ws_core : ws_two_output; }
@@ -1062,6 +1067,7 @@ struct Run {
     V.lin_wgrad(V.A(e->ha.d_pv), D.Hb, V.A(seq_v), ldv, e->v_pool, B);
     V.lin_dgrad(V.A(e->ha.d_pv), D.Hb, e->v_pool, B, V.A(gv), ldv, Opt());
     if (!has_regressor()) {                    // binary answers: the poolers are the whole head
+      output_grads(V, gt, gv);
       flush_wgrads();
       V.flush_wgrads();
       return;
@@ -1082,8 +1088,23 @@ struct Run {
     // pipes; their input gradients accumulate onto the pooler's rows
     V.pipe_bwd(e->vp, V.A(seq_v), ldv, e->ha.v, V.A(g[3]), 512, V.A(gv), ldv, true, B, g + 4);
     pipe_bwd(e->tp, A(seq_t), ldt, e->ha.t, A(g[3]) + 256, 512, A(gt), ldt, true, B, g + 7);
+    output_grads(V, gt, gv);
     flush_wgrads();
     V.flush_wgrads();
+  }
+  // Requested upstream gradients of the final hidden states (crct_engine_set_output_grads) onto the hidden gradients the heads have just
+  // finished -- each on the stream that owns the buffer, behind the last head data gradient into it, and only where segment 0's plan
+  // produces that gradient.  Called at both exits of heads_bwd; without a request it launches nothing.
+  void output_grads(Run& V, size_t gt, size_t gv) {
+    const SegPlan& pl = e->plan[0];
+    if (e->og.d_seq_t && pl.dx_t && !rc) {
+      fail(crct_hidden_grad_add(A(gt), e->og.d_seq_t, c->grad_scale, (int64_t)b->B * b->T * e->d.H, s));
+      ++tick;
+    }
+    if (e->og.d_seq_v && pl.dx_v && !V.rc) {
+      V.fail(crct_hidden_grad_add(V.A(gv), e->og.d_seq_v, c->grad_scale, (int64_t)b->B * b->V * e->d.Hv, V.s));
+      ++V.tick;
+    }
   }
 };
 
@@ -1437,6 +1458,33 @@ extern "C" int crct_engine_set_input_grads(crct_engine_t* e, const CrctInputGrad
   return 0;
 }
 
+extern "C" int crct_engine_set_output_grads(crct_engine_t* e, const CrctOutputGrads* req) {
+  CRCT_REQUIRE(e, "engine_set_output_grads: null engine");
+  const CrctOutputGrads none = {nullptr, nullptr};
+  const CrctOutputGrads r = req ? *req : none;
+  CRCT_REQUIRE((((uintptr_t)r.d_seq_t | (uintptr_t)r.d_seq_v) & 15) == 0, "engine_set_output_grads: d_seq_t / d_seq_v must be 16-byte aligned");
+  e->og = r;      // read by segment 0 of crct_engine_backward only; the plan does not depend on it
+  return 0;
+}
+
+extern "C" int crct_engine_sequence_outputs(crct_engine_t* e, const float* params_f32, const void* workspace, int B, int T, int V,
+                                            float* seq_t, float* seq_v, crct_stream_t stream) {
+  CRCT_REQUIRE(e && params_f32 && workspace, "engine_sequence_outputs: null argument");
+  CRCT_REQUIRE(e->fwd_r32 >= 0, "engine_sequence_outputs: no crct_engine_forward has run on this engine");
+  CRCT_REQUIRE(B >= 1 && T >= 1 && V >= 1 && B <= e->maxB && T <= e->maxT && V <= e->maxV,
+               "engine_sequence_outputs: batch (B=%d,T=%d,V=%d) outside the engine maximum (%d,%d,%d)", B, T, V, e->maxB, e->maxT, e->maxV);
+  const char* ws = (const char*)workspace;
+  // the closing LayerNorm of a stream's last schedule step: the rows it normalised, their statistics, its parameters
+  auto rebuild = [&](const Act& x, float* out, int64_t M, int H) -> int {
+    if (!out) return 0;
+    CRCT_REQUIRE(x.s != NONE, "engine_sequence_outputs: the stream has no encoder layer (its final state is the embeddings' bf16 output)");
+    return crct_layernorm_rows_f32(ws + x.s, e->fwd_r32 ? 0 : 1, (const float*)(ws + x.mean), (const float*)(ws + x.rstd),
+                                   params_f32 + x.ln.g, params_f32 + x.ln.b, out, (int)M, H, stream);
+  };
+  if (int r = rebuild(e->in.back().t, seq_t, (int64_t)B * T, e->d.H)) return r;
+  return rebuild(e->in.back().v, seq_v, (int64_t)B * V, e->d.Hv);
+}
+
 extern "C" int crct_engine_set_trainable(crct_engine_t* e, const uint8_t* flags, int n) {
   CRCT_REQUIRE(e, "engine_set_trainable: null engine");
   CRCT_REQUIRE(!flags || n == (int)e->param_off.size(), "engine_set_trainable: %d flags for %d parameters", n, (int)e->param_off.size());
@@ -1541,6 +1589,7 @@ extern "C" int crct_engine_forward(crct_engine_t* e, const float* params_f32, co
                "engine_forward: the fp8 step is built for the PlotQA model only, not for the dvqa / figure_qa variants");
   if (int r = ensure_streams(e, (hipStream_t)stream)) return r;
   e->evnext = 0;
+  e->fwd_r32 = cfg->residual_fp32 != 0;                   // (host state only: what crct_engine_sequence_outputs reads the rows as)
   CrctDeviceScope on_device;                              // every launch below runs on this thread and the device stays
   // key masks the caller did not supply are built here (one launch) and kept in the workspace for the backward pass
   CrctBatch bl = *batch;

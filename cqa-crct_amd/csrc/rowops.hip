@@ -1301,6 +1301,57 @@ __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const void* __res
   }
 }
 
+// ------------------------------------------------------------------------------ fp32 value of a LayerNorm output, rebuilt
+// y[row][:] = ln_value(s[row][:], mean[row], rstd[row], gamma, beta) from what the LayerNorm's forward left for its backward: the rows it
+// normalised (fp32, or bf16 without the fp32 residual stream) and their statistics.  The same loads and the same ln_value as ln_fwd_body,
+// so the result is bit-identical to the fp32 copy that kernel writes on the two-output route (CrctLnFwdArgs.y_f32), and its bf16 rounding
+// to the stored LayerNorm output.  One wave per row, gamma / beta once per wave; the output is read next by the caller: plain stores.
+template <int NCH, bool S_BF16>
+__global__ __launch_bounds__(256) void ln_rows_f32_kernel(const void* __restrict__ s_p, const float* __restrict__ mean_p,
+                                                          const float* __restrict__ rstd_p, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, float* __restrict__ y, int M, int H) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Row<NCH> g, b;
+  row_load_f32(g, gamma, H, lane);
+  row_load_f32(b, beta, H, lane);
+  for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < M; row += (long)gridDim.x * ROWS_PER_BLOCK) {
+    Row<NCH> r;
+    if constexpr (S_BF16) row_load_bf16(r, reinterpret_cast<const bf16_t*>(s_p) + row * H, H, lane);
+    else row_load_f32(r, reinterpret_cast<const float*>(s_p) + row * H, H, lane);
+    row_normalize(r, g, b, H, lane, mean_p[row], rstd_p[row], row, 0u, 1.f, 0u, 0ull);
+    row_store_f32(r, y + row * H, H, lane);
+  }
+}
+
+// ------------------------------------------------------------------------------ external upstream gradient onto a hidden gradient
+// x[i] = bf16(float(x[i]) + c * g[i]), in place: one fp32 product and one fp32 sum, each rounded on its own, then the round-to-nearest-even
+// bf16 convert -- what two fp32 torch ops and a cast give: __fadd_rn(x, __fmul_rn(c, g)) in meaning.  Those two intrinsics do not
+// guarantee it here: the HIP headers define them as plain * and +, which the device compiler's default contraction turns into ONE
+// v_fmac_f32 (seen in the ISA; 2 of 71424 results then differed from torch by a bf16 step).  So the two operations are written out under
+// a contraction pragma of their own, which holds after inlining too (v_mul_f32, v_add_f32).  Inf / NaN of g pass through both.
+// 8 elements per thread and pass, the tail by the one thread that owns it.
+__device__ __forceinline__ float grad_add1(float x, float c, float g) {
+#pragma clang fp contract(off)
+  const float p = c * g;
+  return x + p;
+}
+__global__ __launch_bounds__(256) void hidden_grad_add_kernel(bf16_t* __restrict__ x, const float* __restrict__ g, float c, long n) {
+  long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
+  const long stride = (long)gridDim.x * blockDim.x * 8;
+  for (; i + 8 <= n; i += stride) {
+    const uint4 u = *reinterpret_cast<const uint4*>(x + i);
+    const float4 a = *reinterpret_cast<const float4*>(g + i), b = *reinterpret_cast<const float4*>(g + i + 4);
+    uint4 o;
+    o.x = pack2bf(grad_add1(bf2f((bf16_t)(u.x & 0xffff)), c, a.x), grad_add1(bf2f((bf16_t)(u.x >> 16)), c, a.y));
+    o.y = pack2bf(grad_add1(bf2f((bf16_t)(u.y & 0xffff)), c, a.z), grad_add1(bf2f((bf16_t)(u.y >> 16)), c, a.w));
+    o.z = pack2bf(grad_add1(bf2f((bf16_t)(u.z & 0xffff)), c, b.x), grad_add1(bf2f((bf16_t)(u.z >> 16)), c, b.y));
+    o.w = pack2bf(grad_add1(bf2f((bf16_t)(u.w & 0xffff)), c, b.z), grad_add1(bf2f((bf16_t)(u.w >> 16)), c, b.w));
+    *reinterpret_cast<uint4*>(x + i) = o;
+  }
+  if (i < n && i + 8 > n)
+    for (long j = i; j < n; ++j) x[j] = f2bf(grad_add1(bf2f(x[j]), c, g[j]));
+}
+
 inline int nch_for(int H) { return (H / 8 + 63) / 64; }
 // workgroups of a LayerNorm-forward launch at most (4 rows each per pass; a build-time value for A/B builds).  Re-checked in the step after the
 // kernel stopped writing the fp32 copy of its output (EXPERIMENTS.md, LayerNorm addend): 256 and 512 measured no better than 2048.
@@ -1365,6 +1416,32 @@ int crct_layernorm_fwd_q(const void* x, const float* gamma, const float* beta, v
   CRCT_REQUIRE(q_out && q_scale, "layernorm_fwd_q: q_out and q_scale are required");
   const CrctLnFwdArgs a = {x, gamma, beta, y, mean, rstd, M, H, eps, drop_thr, drop_scale, drop_site, seed, q_out, q_scale, q_amax, 0, nullptr};
   return ln_fwd_launch(a, (hipStream_t)stream);
+}
+
+int crct_layernorm_rows_f32(const void* s, int s_is_bf16, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                            float* y_f32, int M, int N, crct_stream_t stream) {
+  CRCT_REQUIRE(s && mean && rstd && gamma && beta && y_f32, "layernorm_rows_f32: null argument");
+  CRCT_REQUIRE(N % 8 == 0 && N > 0, "layernorm_rows_f32: N=%d must be a positive multiple of 8", N);
+  CRCT_REQUIRE((((uintptr_t)s | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y_f32) & 15) == 0, "layernorm_rows_f32: 16-byte aligned buffers");
+  if (M <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(row_grid(M, CRCT_LN_FWD_GRID_CAP));
+  if (s_is_bf16) { DISPATCH_NCH(N, crct_launch((ln_rows_f32_kernel<NCH, true>), grid, dim3(256), 0, st, s, mean, rstd, gamma, beta, y_f32, M, N)); }
+  else { DISPATCH_NCH(N, crct_launch((ln_rows_f32_kernel<NCH, false>), grid, dim3(256), 0, st, s, mean, rstd, gamma, beta, y_f32, M, N)); }
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int crct_hidden_grad_add(void* x_bf16, const float* g_f32, float c, int64_t n, crct_stream_t stream) {
+  CRCT_REQUIRE(x_bf16 && g_f32, "hidden_grad_add: null argument");
+  CRCT_REQUIRE((((uintptr_t)x_bf16 | (uintptr_t)g_f32) & 15) == 0, "hidden_grad_add: 16-byte aligned buffers");
+  if (n <= 0) return 0;
+  long blocks = (n / 8 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  crct_launch(hidden_grad_add_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x_bf16, g_f32, c, (long)n);
+  CRCT_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 // the embedding backward kernels write 7 partial rows per wave: fewer, longer-running waves than the LayerNorm backward

@@ -219,6 +219,16 @@ typedef struct CrctLnFwdArgs {
   int32_t x_f32; float* y_f32;
 } CrctLnFwdArgs;
 int crct_layernorm_fwd_args(const CrctLnFwdArgs* a, crct_stream_t stream);
+/* The fp32 value of a LayerNorm output from what its forward left for its backward: y_f32[m][n] = gamma[n] * ((s[m][n] - mean[m]) * rstd[m])
+ * + beta[n] (ln_value, common.hip.h), s = the [M][N] rows the LayerNorm normalised (fp32, or bf16 when s_is_bf16), mean / rstd the
+ * statistics it returned.  To the bit the y_f32 crct_layernorm_fwd_args writes from the same s, gamma and beta, so its bf16 rounding is
+ * that call's bf16 y.  N a positive multiple of 8 up to 2048; s, gamma, beta, y_f32 16-byte aligned.  One wave per row, no LDS, no atomics. */
+int crct_layernorm_rows_f32(const void* s, int s_is_bf16, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                            float* y_f32, int M, int N, crct_stream_t stream);
+/* x[i] = bf16_rn(fp32(x[i]) + c * g[i]) for i < n, in place: an external fp32 upstream gradient g added onto a bf16 hidden-gradient
+ * buffer.  The product and the sum are two fp32 operations, each rounded to nearest and never fused, so (x.float() + c * g).bfloat16()
+ * in torch gives the same bits; Inf / NaN of g arrive in x.  x, g 16-byte aligned; elements at and past n are not touched. */
+int crct_hidden_grad_add(void* x_bf16, const float* g_f32, float c, int64_t n, crct_stream_t stream);
 
 /* Every amax "value" below and in CrctGemmArgs / CrctStepCfg / CrctFp8Shadow is CRCT_FP8_AMAX_LANES consecutive fp32 words
  * (the kernels spread their atomic maxima over them; crct_fp8_update_scales takes the maximum of the words): an amax array
@@ -718,6 +728,30 @@ typedef struct {
   float* d_text_emb;
 } CrctInputGrads;
 int crct_engine_set_input_grads(crct_engine_t*, const CrctInputGrads* req);
+/* The encoder's final hidden states as outputs of the step: sequence_output_t / sequence_output_v of vilbert.py:1561-1575, the tensors
+ * the poolers and the regressor pipes read.
+ * crct_engine_sequence_outputs, after a crct_engine_forward on `workspace` (training or evaluation, any precision mode, any variant; B, T, V
+ * of that batch): writes seq_t fp32 [B][T][H] and / or seq_v fp32 [B][V][Hv] (device; either may be NULL) on `stream`, one launch of
+ * crct_layernorm_rows_f32's kernel per requested state, from the closing LayerNorm of that stream's last schedule step: its input rows
+ * and statistics, which the forward keeps for the backward pass anyway, and its parameters in params_f32.  The engine stores the state
+ * once, as bf16 (the taps "seq_t" / "seq_v"); the fp32 value is rebuilt, not stored, and rounds to exactly those bits.  The forward itself
+ * is untouched: no launch of it changes and no workspace byte moves.
+ * crct_engine_set_output_grads: upstream gradients of those two states for the crct_engine_backward calls that follow, fp32 device
+ * buffers of the same shapes, contiguous and 16-byte aligned, each NULL = none.  While a request stands, segment 0 adds
+ * CrctStepCfg.grad_scale * d_seq_* onto the running hidden gradient of that stream (crct_hidden_grad_add: the factor the head kernel applies
+ * to its own seeds, the same rounding rule) -- one launch per requested stream, on the stream that owns the buffer (text: the caller's,
+ * visual: the engine's visual stream), after the last data gradient of the heads into it, at both exits of the heads' backward (the
+ * binary-answer variants leave right after the poolers).  The buffers are read by segment 0 only, and only for a stream whose hidden
+ * gradient that segment's plan produces (crct_engine_backward_plan: dx_t / dx_v); where nothing below has a gradient the request is
+ * moot.  A request never changes the plan, the heads' launches or any later segment.  NULL, or both members NULL, switches it off:
+ * not one launch, workspace byte, event or result bit differs from an engine that never saw this call. */
+typedef struct {
+  const float* d_seq_t;
+  const float* d_seq_v;
+} CrctOutputGrads;
+int crct_engine_sequence_outputs(crct_engine_t*, const float* params_f32, const void* workspace, int B, int T, int V,
+                                 float* seq_t, float* seq_v, crct_stream_t stream);
+int crct_engine_set_output_grads(crct_engine_t*, const CrctOutputGrads* req);
 /* Which parameters have a gradient in the backward passes that follow: one flag per parameter, in the order given to
  * crct_engine_create* (n = n_params); 0 = the tensor is WITHOUT gradient.  NULL, or all flags set, is the behaviour without this
  * call: not one launch or event differs.  Backward then runs less of itself (crct_engine_backward_plan); the forward is untouched.
