@@ -208,6 +208,19 @@ class StepEngine(object):
         L.check(self.lib.crct_engine_set_output_grads(self.handle, C.byref(req)), "engine_set_output_grads")
         self._output_grads = (seq_t, seq_v)      # the engine holds raw pointers
 
+    def set_score_grads(self, logits=None, value=None):
+        """Upstream gradients of the answer logits [B, 2] and of the regressed value ``reg[0]`` [B] for the backward passes that follow
+        (crct_engine_set_score_grads): contiguous fp32 device tensors; the loss kernel of segment 0 adds grad_scale times each onto its
+        per-row seeds, inside its one launch.  None = none, no argument = off.  ``value`` needs the PlotQA regressor: any other variant
+        refuses it.  The backward plan does not depend on it."""
+        req = L.ScoreGrads()
+        for name, t in (("d_logits", logits), ("d_value", value)):
+            if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError("set_score_grads: %s must be a contiguous fp32 tensor on the device" % name)
+            setattr(req, name, L.ptr(t))
+        L.check(self.lib.crct_engine_set_score_grads(self.handle, C.byref(req)), "engine_set_score_grads")
+        self._score_grads = (logits, value)      # the engine holds raw pointers
+
     def set_site_policy(self, site, kind, cfg=-1, split_k=0, phase=-1):
         """Launch policy of one GEMM site (crct_engine_set_site_policy): ``site`` / ``kind`` by name (crct.lib.SITE_NAMES /
         KIND_NAMES) or number, ``phase`` 0 = text-only part of the schedule, 1 = beside the visual stream, -1 = both."""

@@ -133,6 +133,10 @@ class OutputGrads(C.Structure):     # CrctOutputGrads: fp32 device buffers holdi
     _fields_ = [("d_seq_t", vp), ("d_seq_v", vp)]
 
 
+class ScoreGrads(C.Structure):      # CrctScoreGrads: fp32 device buffers holding the upstream gradients of the logits [B][2] and of reg[0] [B], NULL = none
+    _fields_ = [("d_logits", vp), ("d_value", vp)]
+
+
 SEG_ENQUEUED_FN =C.CFUNCTYPE(None, C.c_int, vp)      # void (*seg_enqueued)(int seg, void* user)
 
 
@@ -210,6 +214,8 @@ PROTOTYPES = {
     "crct_embed_image_var_bwd": (C.c_int, [vp] * 16 + [C.c_int] * 2 + _u8 + [vp, vp, C.c_int, vp]),
     "crct_head_loss": (C.c_int, [C.POINTER(HeadArgs), vp]),
     "crct_head_loss_variant": (C.c_int, [C.POINTER(HeadVariantArgs), vp]),
+    "crct_head_loss_scores": (C.c_int, [C.POINTER(HeadArgs), C.POINTER(ScoreGrads), vp]),
+    "crct_head_loss_variant_scores": (C.c_int, [C.POINTER(HeadVariantArgs), C.POINTER(ScoreGrads), vp]),
     "crct_eval_select": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, c_i64, vp, vp, vp, vp, vp, vp]),
     "crct_eval_score": (C.c_int, [C.POINTER(EvalScoreArgs), vp]),
     "crct_adamw_plan": (c_i64, [vp, C.c_int, vp, vp, c_i64]),
@@ -228,6 +234,7 @@ PROTOTYPES = {
     "crct_hidden_grad_add": (C.c_int, [vp, vp, c_f32, c_i64, vp]),
     "crct_engine_sequence_outputs": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "crct_engine_set_output_grads": (C.c_int, [vp, C.POINTER(OutputGrads)]),
+    "crct_engine_set_score_grads": (C.c_int, [vp, C.POINTER(ScoreGrads)]),
     "crct_engine_set_trainable": (C.c_int, [vp, vp, C.c_int]),
     "crct_engine_backward_plan": (C.c_int, [vp, vp, C.c_int]),
     "crct_engine_destroy": (None, [vp]),

@@ -46,7 +46,12 @@ class _StepFn(torch.autograd.Function):
 
     With ``model.return_sequence_outputs`` the node has two more differentiable outputs behind the six: the encoder's final hidden states
     (fp32 [B, T, H] and [B, V, Hv]).  Their upstream gradients (None when unused) go to the engine for the duration of the pass
-    (``StepEngine.set_output_grads``), which adds them onto the hidden gradients the heads seed; unused, the pass is the plain one."""
+    (``StepEngine.set_output_grads``), which adds them onto the hidden gradients the heads seed; unused, the pass is the plain one.
+
+    With ``model.differentiable_scores`` the node has, behind those, the answer logits [B, 2] and -- where the variant's regressor is the
+    PlotQA one -- the regressed value [B] as differentiable outputs: copies of the snapshot's that own their memory.  Their upstream
+    gradients (None when unused) go to the engine for the duration of the pass (``StepEngine.set_score_grads``) and enter the loss
+    kernel's own launch; unused, the pass is the plain one."""
 
     @staticmethod
     def forward(ctx, anchor, model, tensors, step, image_feat=None, image_loc=None, loc=None, areas=None):
@@ -63,38 +68,56 @@ class _StepFn(torch.autograd.Function):
         if model.return_sequence_outputs:
             # two more differentiable outputs: the encoder's final hidden states, fresh fp32 tensors (StepEngine.sequence_outputs)
             out = out + model._engine.sequence_outputs()
+        ctx.n_seq = len(out) - 6
+        ctx.scores = bool(model.differentiable_scores)
+        if ctx.scores:
+            # the logits, and the PlotQA regressor's value, as differentiable outputs: tensors of their own (two B-sized copies)
+            out = out + (logits.clone(),)
+            if model.variant[1] == "plotqa":
+                out = out + (reg_all[0].clone(),)
         return out
 
     @staticmethod
-    def backward(ctx, g_loss, g_nsp, g_reg, _gl, _gr, _gs, g_seq_t=None, g_seq_v=None):
+    def backward(ctx, g_loss, g_nsp, g_reg, _gl, _gr, _gs, *g_more):
         model = ctx.model
         step = dict(ctx.step)
-        g_seq_t, g_seq_v = _upstream_f32(g_seq_t), _upstream_f32(g_seq_v)
+        B = ctx.tensors["tokens"].shape[0]
+        g_seq_t, g_seq_v = (_upstream_f32(g) for g in g_more[:2]) if ctx.n_seq else (None, None)
+        g_scores = tuple(_upstream_f32(g) for g in g_more[ctx.n_seq:]) if ctx.scores else ()
+        g_logits = g_scores[0].reshape(B, 2) if g_scores and g_scores[0] is not None else None
+        g_value = g_scores[1].reshape(B) if len(g_scores) > 1 and g_scores[1] is not None else None
+        upstream_out, upstream_scores = g_seq_t is not None or g_seq_v is not None, g_logits is not None or g_value is not None
         if g_nsp is None and g_reg is None:
             if g_loss is None:
-                if g_seq_t is None and g_seq_v is None:
+                if not upstream_out and not upstream_scores:
                     return (None,) * 8
-                g_loss = torch.zeros(1, device=model._flat_p.device)   # only the sequence outputs are differentiated: the heads get zero seeds
+                g_loss = torch.zeros(1, device=model._flat_p.device)   # only the sequence outputs / scores are differentiated: the heads get zero loss seeds
             step["g_loss"] = g_loss.reshape(1).float()                 # views / no-ops for the fp32 scalar autograd hands over
         else:                                                          # a caller combining nsp_loss / reg_loss itself
-            B = ctx.tensors["tokens"].shape[0]
             dev = model._flat_p.device
             gl = g_loss.reshape(1).float() if g_loss is not None else torch.zeros(1, device=dev)
             gn = g_nsp.reshape(1).float() if g_nsp is not None else torch.zeros(1, device=dev)
             gr = g_reg.reshape(B).float() if g_reg is not None else torch.zeros(B, device=dev)
             step["g_nsp"] = (gn + gl * step["nsp_coeff"]).contiguous()
             step["g_reg"] = (gr + gl * (step["reg_coeff"] / B)).contiguous()
-        if g_seq_t is None and g_seq_v is None:
+        if not upstream_out and not upstream_scores:
             grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
         else:
-            # upstream gradients of the sequence outputs: segment 0 adds them onto the hidden gradients the heads seed (the request stands
-            # for this pass only, like the input-gradient request inside the call; the two compose)
+            # upstream gradients of the sequence outputs: segment 0 adds them onto the hidden gradients the heads seed; of the scores: the
+            # loss kernel adds them onto its per-row seeds (each request stands for this pass only, like the input-gradient request inside
+            # the call; the three compose)
             eng = model._engine
-            eng.set_output_grads(seq_t=g_seq_t, seq_v=g_seq_v)
             try:
+                if upstream_out:
+                    eng.set_output_grads(seq_t=g_seq_t, seq_v=g_seq_v)
+                if upstream_scores:
+                    eng.set_score_grads(logits=g_logits, value=g_value)
                 grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
             finally:
-                eng.set_output_grads()
+                if upstream_scores:
+                    eng.set_score_grads()
+                if upstream_out:
+                    eng.set_output_grads()
         return (None, None, None, None) + grads
 
 
@@ -195,6 +218,15 @@ class CrctModel(nn.Module):
         self.return_sequence_outputs = False
         self.sequence_output_t = None
         self.sequence_output_v = None
+        # True: in the training branch under grad the answer logits (slot 5 of the training tuple, the step adapter's ``nsp_scores``) and,
+        # where the regressor is the PlotQA one, the regressed value (``reg_out[0]``, the adapter's ``regression[0]``) carry a graph, as the
+        # reference's do (vilbert.py:1060, :1644, :1659): a loss the caller writes on them -- label smoothing, distillation, a margin
+        # between candidate rows -- trains the model, and ``scores[:, 0].sum().backward()`` with ``image_feat.requires_grad_(True)`` is the
+        # saliency of the answer.  The CE regressor's value is a table lookup and the binary-answer models have none: no gradient, as
+        # in the reference.  The inference tuple (no labels) stays plain: score saliency without real labels is the training branch with
+        # every next_sentence_label -1 (the NSP term is then 0), in eval() or train() as the caller likes.  Two B-sized copies per forward;
+        # the backward pass launches what it launched.
+        self.differentiable_scores = False
         self.init_weights(int(params.get("seed", 0)))
         self.register_load_state_dict_post_hook(lambda m, k: m._invalidate_shadow())
 
@@ -761,8 +793,13 @@ class CrctModel(nn.Module):
                 tensors = dict(tensors, image_feat=live[0].detach(), image_loc=live[1].detach(), loc=live[2].detach())
                 if live[3] is not None:
                     tensors["areas"] = live[3].detach()
-            loss, nsp, reg_loss, logits, reg, stats, *seq = _StepFn.apply(self._anchor, self, tensors, step, *live)
+            loss, nsp, reg_loss, logits, reg, stats, *more = _StepFn.apply(self._anchor, self, tensors, step, *live)
+            seq, scores = (more[:2], more[2:]) if self.return_sequence_outputs else ((), more)
+            value = scores[1] if len(scores) > 1 else None
+            if scores:
+                logits = scores[0]                     # differentiable_scores: the copies that are part of the graph
         else:
+            value = None
             eng.forward(self._flat_p, self._flat_b16, tensors, step)
             logits, reg, stats = eng.snapshot(B)
             loss, nsp, reg_loss = stats[0], stats[1:2], reg[1]
@@ -778,7 +815,7 @@ class CrctModel(nn.Module):
             right = (int(stats[4].item()), int(stats[5].item()))          # vilbert.py:1647 (.item() host syncs)
         else:
             right = (stats[4], stats[5])
-        reg_out = [reg[0], reg_loss, reg[2], right, reg[4]]
+        reg_out = [reg[0] if value is None else value, reg_loss, reg[2], right, reg[4]]
         if self._const_zeros is None or self._const_zeros[0].device != dev:
             # the placeholder losses of vilbert.py:1583,1652-1653 (lm, image, legend): constant tensors made once, not three
             # fill kernels per step

@@ -176,6 +176,9 @@ struct crct_engine {
   // says whether the rows crct_engine_sequence_outputs normalises again are fp32 or bf16
   CrctOutputGrads og = {nullptr, nullptr};
   int fwd_r32 = -1;
+  // crct_engine_set_score_grads: fp32 upstream gradients of the logits and of the regressed value, handed to the loss kernel of the
+  // following backward passes (both NULL: off)
+  CrctScoreGrads sg = {nullptr, nullptr};
   bool ig_text() const { return ig.d_txt_loc || ig.d_text_emb; }
   bool ig_vis() const { return ig.d_image_feat || ig.d_image_loc || ig.d_areas; }
   size_t ws_base() const { return ln_addend ? ws_core : ws_two_output; }
@@ -997,15 +1000,16 @@ struct Run {
   }
   bool has_regressor() const { return e->var.regressor != CRCT_REGRESSOR_NONE; }
   bool plain_head() const { return e->var.dataset == CRCT_DATASET_PLOTQA && e->var.regressor == CRCT_REGRESSOR_PLOTQA; }
-  // the loss kernel: crct_head_loss for the PlotQA model, crct_head_loss_variant otherwise
-  int head_loss(const CrctHeadArgs& h) {
-    if (plain_head()) return crct_head_loss(&h, s);
+  // the loss kernel: crct_head_loss for the PlotQA model, crct_head_loss_variant otherwise; `scores`: the standing request of
+  // crct_engine_set_score_grads (backward only), NULL = the plain launch
+  int head_loss(const CrctHeadArgs& h, const CrctScoreGrads* scores = nullptr) {
+    if (plain_head()) return crct_head_loss_scores(&h, scores, s);
     CrctHeadVariantArgs va;
     memset(&va, 0, sizeof(va));
     va.h = h; va.variant = e->var;
     va.snap = e->var.dataset == CRCT_DATASET_DVQA && e->var.regressor == CRCT_REGRESSOR_PLOTQA && !c->training;   // vilbert.py:1619-1625
     va.ce_scratch = e->var.regressor == CRCT_REGRESSOR_CE ? F(e->ha.ce) : nullptr;
-    return crct_head_loss_variant(&va, s);
+    return crct_head_loss_variant_scores(&va, scores, s);
   }
   void fill_head_args(CrctHeadArgs& h, float* logits, float* reg, float* stats, bool with_grad) {
     const CrctModelDims& D = e->d;
@@ -1052,7 +1056,7 @@ struct Run {
     {
       CrctHeadArgs h;
       fill_head_args(h, logits, reg, stats, true);
-      if (!rc) fail(head_loss(h));
+      if (!rc) fail(head_loss(h, e->sg.d_logits || e->sg.d_value ? &e->sg : nullptr));
     }
     if (rc) return;
     if (!V.rc) V.fail(order_streams(e, s, V.s));                              // d_pooled_v is ready
@@ -1455,6 +1459,16 @@ extern "C" int crct_engine_set_input_grads(crct_engine_t* e, const CrctInputGrad
   e->ig = r;
   e->ws_update();
   if (changed) replan(e);
+  return 0;
+}
+
+extern "C" int crct_engine_set_score_grads(crct_engine_t* e, const CrctScoreGrads* req) {
+  CRCT_REQUIRE(e, "engine_set_score_grads: null engine");
+  const CrctScoreGrads none = {nullptr, nullptr};
+  const CrctScoreGrads r = req ? *req : none;
+  CRCT_REQUIRE(!r.d_value || e->var.regressor == CRCT_REGRESSOR_PLOTQA, "engine_set_score_grads: d_value: only the PlotQA regressor's value has a gradient (this engine's regressor is %s)",
+               e->var.regressor == CRCT_REGRESSOR_CE ? "the CE table lookup" : "absent");
+  e->sg = r;                        // read by heads_bwd alone: the plan does not depend on it
   return 0;
 }
 

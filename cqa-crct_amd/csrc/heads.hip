@@ -31,8 +31,10 @@ struct HeadValues { float v[CRCT_CE_CLASSES]; int n; };
 enum { HEAD_PLOTQA = 0, HEAD_SNAP = 1, HEAD_NONE = 2 };
 
 // scratch row layout (fp32 x 8): dlogit0, dlogit1, dz, nsp_loss_b, valid, ok5, okt, needs
+// sg: upstream gradients of the logits and of the regressed value reg[0] (CrctScoreGrads, members NULL = none): added to dlogit0 / dlogit1
+// and dz before anything is formed from them, so every gradient below carries them with the one rounding it always had
 template <int MODE>
-__global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, float* scratch, const HeadValues hv) {
+__global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, float* scratch, const HeadValues hv, const CrctScoreGrads sg) {
   __shared__ float red[4];
   const int b = blockIdx.x, tid = threadIdx.x;
   const bf16_t* pt = reinterpret_cast<const bf16_t*>(a.pooled_t) + (long)b * a.Hb;
@@ -81,6 +83,9 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, fl
     dl0 = (expf(l0 - lse) - (label == 0 ? 1.f : 0.f)) * w;
     dl1 = (expf(l1 - lse) - (label == 1 ? 1.f : 0.f)) * w;
   }
+  if (sg.d_logits) {                       // every row, label -1 included: the logits are outputs whatever the label says
+    dl0 += a.grad_scale * sg.d_logits[b * 2]; dl1 += a.grad_scale * sg.d_logits[b * 2 + 1];
+  }
   const float* Rb = a.R + (long)b * 4;
   const bool needs = Rb[1] == 1.0f;
   const float target = Rb[0] / Rb[3];
@@ -113,7 +118,9 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, fl
   if (!a.kind_l1 && fabsf(target) > 1.f) { rl = 0.f; drl = 0.f; }
   if (!needs) { rl = 0.f; drl = 0.f; }
   if (MODE == HEAD_SNAP) drl = 0.f;       // the snapped value is a constant
-  const float dz = drl * g_reg * (1.f - r * r);
+  float dz = drl * g_reg * (1.f - r * r);
+  // reg[0] = r * R[:,3] on the needs rows: its upstream passes the tanh whatever the loss rules above zeroed; the snapped value is a constant
+  if (MODE == HEAD_PLOTQA && sg.d_value && needs) dz += a.grad_scale * sg.d_value[b] * Rb[3] * (1.f - r * r);
   if (MODE == HEAD_NONE) {                // no regressor module: reg rows stay zero (vilbert.py:1592-1598)
     if (tid == 0) {
       a.logits[b * 2] = l0; a.logits[b * 2 + 1] = l1;
@@ -226,7 +233,8 @@ __global__ __launch_bounds__(256) void head_reduce_kernel(const CrctHeadArgs a, 
 // (65 outputs, the four waves take them in turn), p = softmax(z), CrossEntropyLoss(p, target) -- the reference feeds the Softmax
 // output to CrossEntropyLoss, so the softmax is taken twice -- argmax (first maximum), value lookup and flags.  Writes the gradient
 // seed w.r.t. ce_fusion.4's pre-activation and the per-row dL/dz (ce [B][65]) for the weight gradients of ce_fusion.6.
-__global__ __launch_bounds__(256) void head_ce_rows_kernel(const CrctHeadArgs a, float* scratch, float* ce, const HeadValues hv) {
+__global__ __launch_bounds__(256) void head_ce_rows_kernel(const CrctHeadArgs a, float* scratch, float* ce, const HeadValues hv,
+                                                           const CrctScoreGrads sg) {
   __shared__ float red[4];
   __shared__ float zs[CRCT_CE_CLASSES], ps[CRCT_CE_CLASSES], dzs[CRCT_CE_CLASSES];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -269,6 +277,9 @@ __global__ __launch_bounds__(256) void head_ce_rows_kernel(const CrctHeadArgs a,
     const float w = g_nsp / (float)max(n_valid, 1);
     dl0 = (expf(l0 - lse) - (label == 0 ? 1.f : 0.f)) * w;
     dl1 = (expf(l1 - lse) - (label == 1 ? 1.f : 0.f)) * w;
+  }
+  if (sg.d_logits) {                       // every row, label -1 included: the logits are outputs whatever the label says
+    dl0 += a.grad_scale * sg.d_logits[b * 2]; dl1 += a.grad_scale * sg.d_logits[b * 2 + 1];
   }
   // p = softmax(z)
   float zm = zs[0];
@@ -524,11 +535,22 @@ extern "C" int crct_eval_score(const CrctEvalScoreArgs* args, crct_stream_t stre
   return 0;
 }
 
-extern "C" int crct_head_loss(const CrctHeadArgs* args, crct_stream_t stream) {
+// what a score request may ask of a launch: gradient outputs to seed, and a value only where the regressor has a differentiable one
+static int score_request(const CrctHeadArgs& a, const CrctScoreGrads* req, bool plotqa, CrctScoreGrads* sg) {
+  sg->d_logits = req ? req->d_logits : nullptr;
+  sg->d_value = req ? req->d_value : nullptr;
+  CRCT_REQUIRE(!sg->d_value || plotqa, "head_loss_scores: d_value: only the PlotQA regressor's value has a gradient (the CE regressor's is a table lookup, without a regressor it is zero)");
+  CRCT_REQUIRE(!(sg->d_logits || sg->d_value) || a.d_pooled_t, "head_loss_scores: d_logits / d_value need the gradient outputs (d_pooled_t is NULL: an evaluation launch)");
+  return 0;
+}
+
+extern "C" int crct_head_loss_scores(const CrctHeadArgs* args, const CrctScoreGrads* scores, crct_stream_t stream) {
   CRCT_REQUIRE(args && args->B > 0 && args->Hb > 0, "head_loss: bad sizes");
   CRCT_REQUIRE(args->scratch, "head_loss: scratch (fp32 [B][8]) is required");
+  CrctScoreGrads sg;
+  if (const int rc = score_request(*args, scores, true, &sg)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  crct_launch(head_rows_kernel<HEAD_PLOTQA>, dim3(args->B), dim3(256), 0, s, *args, args->scratch, HeadValues{});
+  crct_launch(head_rows_kernel<HEAD_PLOTQA>, dim3(args->B), dim3(256), 0, s, *args, args->scratch, HeadValues{}, sg);
   CRCT_CHECK_HIP(hipGetLastError());
   const int nb = ((args->Hb > 256 ? args->Hb : 256) + 31) / 32;
   crct_launch(head_reduce_kernel, dim3(nb), dim3(256), 0, s, *args, (const float*)args->scratch);
@@ -536,11 +558,15 @@ extern "C" int crct_head_loss(const CrctHeadArgs* args, crct_stream_t stream) {
   return 0;
 }
 
-extern "C" int crct_head_loss_variant(const CrctHeadVariantArgs* args, crct_stream_t stream) {
+extern "C" int crct_head_loss(const CrctHeadArgs* args, crct_stream_t stream) { return crct_head_loss_scores(args, nullptr, stream); }
+
+extern "C" int crct_head_loss_variant_scores(const CrctHeadVariantArgs* args, const CrctScoreGrads* scores, crct_stream_t stream) {
   CRCT_REQUIRE(args && args->h.B > 0 && args->h.Hb > 0, "head_loss_variant: bad sizes");
   CRCT_REQUIRE(args->h.scratch, "head_loss_variant: scratch (fp32 [B][8]) is required");
   const CrctVariant& v = args->variant;
   CRCT_REQUIRE(v.n_values >= 0 && v.n_values <= CRCT_CE_CLASSES, "head_loss_variant: %d table values (at most %d)", v.n_values, CRCT_CE_CLASSES);
+  CrctScoreGrads sg;
+  if (const int rc = score_request(args->h, scores, v.regressor == CRCT_REGRESSOR_PLOTQA, &sg)) return rc;
   HeadValues hv = {};
   for (int k = 0; k < v.n_values; ++k) hv.v[k] = v.values[k];
   hv.n = v.n_values;
@@ -551,17 +577,17 @@ extern "C" int crct_head_loss_variant(const CrctHeadVariantArgs* args, crct_stre
     CRCT_REQUIRE(a.fus_h && a.w_f6 && a.b_f6, "head_loss_variant: the PlotQA regressor needs fus_h, w_f6, b_f6");
     if (args->snap) {
       CRCT_REQUIRE(v.n_values > 0, "head_loss_variant: the DVQA snap needs the value table");
-      crct_launch(head_rows_kernel<HEAD_SNAP>, dim3(a.B), dim3(256), 0, s, a, a.scratch, hv);
+      crct_launch(head_rows_kernel<HEAD_SNAP>, dim3(a.B), dim3(256), 0, s, a, a.scratch, hv, sg);
     } else {
-      crct_launch(head_rows_kernel<HEAD_PLOTQA>, dim3(a.B), dim3(256), 0, s, a, a.scratch, hv);
+      crct_launch(head_rows_kernel<HEAD_PLOTQA>, dim3(a.B), dim3(256), 0, s, a, a.scratch, hv, sg);
     }
   } else if (v.regressor == CRCT_REGRESSOR_NONE) {
-    crct_launch(head_rows_kernel<HEAD_NONE>, dim3(a.B), dim3(256), 0, s, a, a.scratch, hv);
+    crct_launch(head_rows_kernel<HEAD_NONE>, dim3(a.B), dim3(256), 0, s, a, a.scratch, hv, sg);
     r.d_w_f6 = nullptr; r.d_b_f6 = nullptr;
   } else if (v.regressor == CRCT_REGRESSOR_CE) {
     CRCT_REQUIRE(v.n_values == CRCT_CE_CLASSES, "head_loss_variant: the CE regressor needs %d table values, got %d", CRCT_CE_CLASSES, v.n_values);
     CRCT_REQUIRE(a.fus_h && a.w_f6 && a.b_f6 && args->ce_scratch, "head_loss_variant: the CE regressor needs fus_h, w_f6, b_f6, ce_scratch");
-    crct_launch(head_ce_rows_kernel, dim3(a.B), dim3(256), 0, s, a, a.scratch, args->ce_scratch, hv);
+    crct_launch(head_ce_rows_kernel, dim3(a.B), dim3(256), 0, s, a, a.scratch, args->ce_scratch, hv, sg);
     CRCT_CHECK_HIP(hipGetLastError());
     if (a.d_w_f6) {
       crct_launch(head_ce_wgrad_kernel, dim3(CRCT_CE_CLASSES), dim3(256), 0, s, a, (const float*)args->ce_scratch);
@@ -575,4 +601,8 @@ extern "C" int crct_head_loss_variant(const CrctHeadVariantArgs* args, crct_stre
   crct_launch(head_reduce_kernel, dim3(nb), dim3(256), 0, s, r, (const float*)a.scratch);
   CRCT_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+extern "C" int crct_head_loss_variant(const CrctHeadVariantArgs* args, crct_stream_t stream) {
+  return crct_head_loss_variant_scores(args, nullptr, stream);
 }

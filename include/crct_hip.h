@@ -540,6 +540,21 @@ typedef struct CrctHeadVariantArgs {
   float* ce_scratch;
 } CrctHeadVariantArgs;
 int crct_head_loss_variant(const CrctHeadVariantArgs* args, crct_stream_t stream);
+/* The answer logits and the regressed value reg[0] as differentiable outputs: upstream gradients of the two, fp32 device buffers, each NULL =
+ * none.  With c = grad_scale they enter the head launch itself, in front of everything formed from the per-row seeds:
+ *   dlogit_k[b] += c * d_logits[b][k]                      every row -- label -1 and a batch of such labels included, where the NSP term is 0
+ *   dz[b]       += c * d_value[b] * R[b][3] * (1 - r^2)    on the rows with needs (R[b][1] == 1), where reg[0] = r * R[b][3]; 0 elsewhere
+ * so d_pooled_*, d_fus_h, d_w_cls, d_b_cls, d_w_f6, d_b_f6 and scratch[b][0..2] carry them with the one rounding they always had: no
+ * further launch.  The |target| > 1 rule and the loss kind zero the LOSS term of dz only.  Under snap the value is a table constant and
+ * d_value contributes exactly 0; the CE regressor's value (a table lookup) and the absent regressor's (zero) have no gradient: d_value is
+ * refused there.  A request needs the gradient outputs (d_pooled_t != NULL).  scores == NULL, or both members NULL: the launches and bits
+ * of crct_head_loss / crct_head_loss_variant, which are these calls with NULL. */
+typedef struct {
+  const float* d_logits;          /* fp32 [B][2] */
+  const float* d_value;           /* fp32 [B] */
+} CrctScoreGrads;
+int crct_head_loss_scores(const CrctHeadArgs* args, const CrctScoreGrads* scores, crct_stream_t stream);
+int crct_head_loss_variant_scores(const CrctHeadVariantArgs* args, const CrctScoreGrads* scores, crct_stream_t stream);
 
 /* Evaluation scoring, answer selection per question (replaces the per-question Python loop with .item() syncs of
  * evaluation.py:281-292): question q owns num_ans[q] consecutive candidate rows of the N scored rows;
@@ -752,6 +767,15 @@ typedef struct {
 int crct_engine_sequence_outputs(crct_engine_t*, const float* params_f32, const void* workspace, int B, int T, int V,
                                  float* seq_t, float* seq_v, crct_stream_t stream);
 int crct_engine_set_output_grads(crct_engine_t*, const CrctOutputGrads* req);
+/* The answer logits and the regressed value as outputs of the step: upstream gradients of logits [B][2] and of reg[0] [B] (CrctScoreGrads,
+ * fp32 device buffers of the batch's B, each NULL = none) for the crct_engine_backward calls that follow.  While a request stands, the
+ * loss kernel that segment 0 re-runs with gradient outputs is crct_head_loss_scores / crct_head_loss_variant_scores with it: the upstream,
+ * times CrctStepCfg.grad_scale, rides in that launch, and the 13 small GEMMs below it see it through the seeds.  The forward's launch of
+ * the loss kernel never sees it.  A request never changes the plan, the number of launches or any later segment.  d_value on an engine
+ * whose variant has no PlotQA regressor is refused here; in an evaluation-mode pass of the DVQA model (snap) it contributes exactly 0.
+ * NULL, or both members NULL, switches it off: not one launch, workspace byte, event or result bit differs from an engine that never saw
+ * this call. */
+int crct_engine_set_score_grads(crct_engine_t*, const CrctScoreGrads* req);
 /* Which parameters have a gradient in the backward passes that follow: one flag per parameter, in the order given to
  * crct_engine_create* (n = n_params); 0 = the tensor is WITHOUT gradient.  NULL, or all flags set, is the behaviour without this
  * call: not one launch or event differs.  Backward then runs less of itself (crct_engine_backward_plan); the forward is untouched.
