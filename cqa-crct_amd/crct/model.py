@@ -22,6 +22,7 @@ from . import lib as L
 from . import ops
 from .config import BertConfig
 from .engine import StepEngine
+from .fp8 import AMAX_WINDOW, Fp8State
 from .layout import frozen_tensors, is_frozen, model_variant, optional_grad, parameter_table
 
 
@@ -290,99 +291,17 @@ class CrctModel(nn.Module):
             ops.cast_bf16(self._flat_p, out=self._flat_b16)
             self._shadow_ver = v
             if self._fp8 is not None:
-                self._fp8_requantize()
+                self._fp8.requantize(self._flat_p, L.current_stream())
 
-    # ------------------------------------------------------------------ fp8 forward state
+    # ------------------------------------------------------------------ fp8 state (crct/fp8.py)
+    FP8_AMAX_WINDOW = AMAX_WINDOW
+
     def _fp8_state(self, eng):
-        """Device state of the fp8 forward, created with the first engine: e4m3 weight shadow (same element offsets as the
-        flat fp32 buffer), weight scales / amax per shadowed weight, activation scales / amax per producer site."""
+        """The model's Fp8State, created with the first engine and quantised from the current fp32 weights."""
         if self._fp8 is None:
-            n_sites, weights = eng.fp8_layout()
-            dev = self._flat_p.device
-            st = dict(n_sites=n_sites, weights=weights,
-                      q=torch.zeros(self.total, dtype=torch.uint8, device=dev),
-                      w_scale=torch.ones(max(len(weights), 1), device=dev), w_amax=torch.zeros(max(len(weights), 1) * L.FP8_AMAX_LANES, device=dev),
-                      a_scale=torch.ones(max(n_sites, 1), device=dev), a_amax=torch.zeros(max(n_sites, 1) * L.FP8_AMAX_LANES, device=dev),
-                      calibrated=False)
-            # chunk table over the shadowed weights themselves (one segment per weight, slot = its index)
-            lens = [n for _, n in weights]
-            blk_seg, blk_off = ops.adamw_plan(lens) if lens else (torch.zeros(0, dtype=torch.int32), torch.zeros(0, dtype=torch.int64))
-            st["seg_off"] = torch.tensor([o for o, _ in weights], dtype=torch.int64, device=dev)
-            st["seg_len"] = torch.tensor(lens, dtype=torch.int64, device=dev)
-            st["seg_slot"] = torch.arange(len(weights), dtype=torch.int32, device=dev)
-            st["blk_seg"], st["blk_off"] = blk_seg.to(dev), blk_off.to(dev)
-            # fp8 backward: transposed shadow (same byte offsets, every weight stored [in][out]), gradient scale sites
-            by_off = {e.offset: e for e in self.table}
-            outs, ins, begins, nt, transposed = [], [], [], 0, []
-            for off, num in weights:
-                n_in = by_off[off].shape[1]
-                outs.append(num // n_in)
-                ins.append(n_in)
-                begins.append(nt)
-                # every shadowed weight has a transposed copy (the fp8 data gradients; a fused QKV weight [3H][H] is one of them)
-                transposed.append(True)
-                if transposed[-1]:
-                    nt += ((num // n_in + 63) // 64) * ((n_in + 63) // 64)
-            st["transposed"] = transposed
-            st["qt"] = torch.zeros(self.total, dtype=torch.uint8, device=dev) if self.fp8_backward else None
-            st["w_out"] = torch.tensor(outs, dtype=torch.int32, device=dev)
-            st["w_in"] = torch.tensor(ins, dtype=torch.int32, device=dev)
-            st["tile_begin"] = torch.tensor(begins, dtype=torch.int64, device=dev)
-            st["n_tiles"] = nt
-            n_g = eng.lib.crct_engine_fp8_grad_sites(eng.handle)
-            st["n_gsites"] = n_g
-            st["g_scale"] = torch.ones(max(n_g, 1), device=dev)
-            st["g_amax"] = torch.zeros(max(n_g, 1) * L.FP8_AMAX_LANES, device=dev)
-            st["bwd_calibrated"] = False
-            self._fp8 = st
-            self._fp8_requantize()
+            self._fp8 = Fp8State(self.table, self.total, self._flat_p.device, eng, self.fp8_backward, self.fp8_wgrad, self.fp8_forward)
+            self._fp8.requantize(self._flat_p, L.current_stream())
         return self._fp8
-
-    def _fp8_requantize(self):
-        """Exact per-tensor quantisation of the current fp32 weights (start-up, load_state_dict, foreign optimizers); the
-        fused AdamW keeps the shadow current by itself afterwards."""
-        st = self._fp8
-        if not st["weights"]:
-            return
-        L.check(L.load().crct_fp8_quantize_weights(self._flat_p.data_ptr(), st["q"].data_ptr(), st["seg_off"].data_ptr(),
-                                                   st["seg_len"].data_ptr(), st["seg_slot"].data_ptr(), st["blk_seg"].data_ptr(),
-                                                   st["blk_off"].data_ptr(), st["blk_seg"].numel(), st["w_scale"].data_ptr(),
-                                                   st["w_amax"].data_ptr(), len(st["weights"]), L.current_stream()), "fp8_quantize_weights")
-        self._fp8_transpose(L.current_stream())
-
-    def _fp8_update_grad_scales(self, stream):
-        """Gradient scales of the fp8 backward from the maxima the last backward pass collected (delayed scaling).  The fused
-        AdamW calls it on its own stream, off the critical path; without it the next backward pass does it first thing."""
-        st = self._fp8
-        if st is None or not self.fp8_backward or not st.get("bwd_calibrated") or st["n_gsites"] <= 0:
-            return
-        st["g_updates"] = st.get("g_updates", 0) + 1
-        L.check(L.load().crct_fp8_update_scales(st["g_scale"].data_ptr(), st["g_amax"].data_ptr(), st["n_gsites"],
-                                                int(st["g_updates"] % self.FP8_AMAX_WINDOW == 0), None, 57344.0, stream),
-                "fp8_update_scales (gradients)")
-        st["g_scales_fresh"] = True
-
-    def _fp8_transpose(self, stream, max_workgroups=0):
-        """The transposed e4m3 weight shadow the fp8 data-gradient GEMMs read, rebuilt from the shadow (one launch, 2 bytes per
-        shadowed weight element); called whenever the shadow has been rewritten -- here and by the fused AdamW, on its stream."""
-        st = self._fp8
-        if st is None or st.get("qt") is None or not st["weights"]:
-            return
-        L.check(L.load().crct_fp8_transpose_weights(st["q"].data_ptr(), st["qt"].data_ptr(), st["seg_off"].data_ptr(), st["w_out"].data_ptr(),
-                                                    st["w_in"].data_ptr(), st["tile_begin"].data_ptr(), len(st["weights"]), st["n_tiles"],
-                                                    int(max_workgroups), stream), "fp8_transpose_weights")
-
-    def _fp8_step_args(self, eng):
-        st = self._fp8_state(eng)
-        return (st["q"], st["w_scale"], st["a_scale"], st["a_amax"])
-
-    FP8_AMAX_WINDOW = 256      # steps between resets of the running activation / weight maxima (see crct_fp8_update_scales)
-
-    def _fp8_update_act_scales(self):
-        st = self._fp8
-        st["updates"] = st.get("updates", 0) + 1
-        L.check(L.load().crct_fp8_update_scales(st["a_scale"].data_ptr(), st["a_amax"].data_ptr(), st["n_sites"],
-                                                int(st["updates"] % self.FP8_AMAX_WINDOW == 0), None, 448.0, L.current_stream()), "fp8_update_scales")
 
     def _apply(self, fn, recurse=True):
         probe = fn(torch.zeros(1, device=self._flat_p.device))
@@ -643,16 +562,8 @@ class CrctModel(nn.Module):
         self._backward_passes = getattr(self, "_backward_passes", 0) + 1
         if tensors.get("areas") is not None and not self._optional_live:
             self._set_optional_grads(True)
-        if self.fp8_backward and self._fp8 is not None and step.get("fp8") is not None and self._fp8["n_gsites"] > 0:
-            # fp8 data gradients: the first pass only collects the gradient maxima (its GEMMs run in bf16), from then on the e5m2
-            # copies are quantised with the scales of the previous passes (delayed scaling, running maxima over a window)
-            st = self._fp8
-            mode = 1 if st["bwd_calibrated"] else 2
-            if mode == 1 and not st.get("g_scales_fresh"):      # normally done by the optimizer on its stream (_fp8_update_grad_scales)
-                self._fp8_update_grad_scales(L.current_stream())
-            st["g_scales_fresh"] = False
-            st["bwd_calibrated"] = True
-            step = dict(step, fp8_bwd=(mode, st["qt"], st["g_scale"], st["g_amax"], self.fp8_wgrad))
+        if self._fp8 is not None:
+            step = self._fp8.begin_backward(step, L.current_stream())      # fp8 data gradients: step['fp8_bwd']
         if self._ddp is None and self.record_segment_events:
             evs = self.segment_done_events()
             step = dict(step, seg_done_events=evs)
@@ -768,23 +679,9 @@ class CrctModel(nn.Module):
                     seg_events=self._param_events, residual_fp32=self.residual_fp32)
         self._param_events = None
         dev = self._flat_p.device
-        if self.fp8 and not self.fp8_forward and not self.fp8_wgrad:
-            # fp8 DATA GRADIENTS only: nothing of the forward pass is quantised (no e4m3 copies, no activation maxima); the backward
-            # pass multiplies e5m2 gradients (copies written by the backward kernels themselves) with the transposed e4m3 weight shadow
-            step["fp8"] = self._fp8_step_args(eng)
-            step["fp8_backward_only"] = True
-            if not (train_branch and torch.is_grad_enabled()):
-                del step["fp8"]
-        elif self.fp8:
-            step["fp8"] = self._fp8_step_args(eng)
-            if not self._fp8["calibrated"]:            # first fp8 forward: one dry pass collects every activation amax
-                eng.forward(self._flat_p, self._flat_b16, tensors, dict(step, seg_events=None, fp8_mode=2))      # bf16 GEMMs, maxima only
-                self._fp8["calibrated"] = True
-            if self.training or not self._fp8.get("scaled"):
-                self._fp8_update_act_scales()          # delayed scaling: this pass quantises with the previous pass's amax
-                self._fp8["scaled"] = True
-            if not self.fp8_forward:
-                step["fp8_mode"] = 2                   # bf16 forward GEMMs; the e4m3 copies / maxima for the fp8 backward are still written
+        if self.fp8:                                   # step['fp8'] / ['fp8_mode'] / ['fp8_backward_only'], dry pass, activation scales
+            self._fp8_state(eng).begin_forward(step, train_branch and torch.is_grad_enabled(), self.training,
+                                               lambda dry: eng.forward(self._flat_p, self._flat_b16, tensors, dry))
         attention_maps = None
         if train_branch and torch.is_grad_enabled():
             # the float inputs as autograd inputs; the engine's dict keeps detached aliases of the ones that are part of a graph

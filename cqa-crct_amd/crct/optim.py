@@ -96,7 +96,6 @@ class FusedAdamW(torch.optim.Optimizer):
         self._wd_dev = torch.empty(len(self._segs), dtype=torch.float32, device=dev)
         self._last = None
         self._step_dev, self._amp_arg, self._amp_keep = None, None, None
-        self._fp8_keep = None
         self._g16 = None                     # bf16 gradient source of the running update (data-parallel bf16 exchange), else None
         # clip_grad_norm_: the pending clip coefficient (device scalar, folded into exactly the next step()) and what it came from
         self._clip = None
@@ -126,7 +125,6 @@ class FusedAdamW(torch.optim.Optimizer):
         self.early = False
         self._upload_done = None
         self._opt_stream = None
-        self._fp8_transposes = False
         self._seg_blocks = None
         self._events = None
         # expose the moments the way torch.optim.AdamW does (views of the flat buffers)
@@ -240,67 +238,27 @@ class FusedAdamW(torch.optim.Optimizer):
         self._amp_arg = C.byref(st)
         return True
 
+    def _fp8_state(self):
+        """The model's Fp8State (crct/fp8.py) where there is an e4m3 weight shadow to maintain, else None."""
+        st = getattr(self.core, "_fp8", None) if getattr(self.core, "fp8", False) else None
+        return st if st is not None and st.weights else None
+
     def _fp8_arg(self):
         """CrctFp8Shadow of the model's e4m3 weight shadow (None unless the model runs the fp8 forward)."""
-        core = self.core
-        st = getattr(core, "_fp8", None)
-        if not getattr(core, "fp8", False) or st is None or not st["weights"]:
-            return None
-        if self._fp8_keep is None or self._fp8_keep[0] is not st:
-            import bisect
-            import ctypes as C
-            by_start = sorted(range(len(st["weights"])), key=lambda i: st["weights"][i][0])      # the engine lists them in model order, not by offset
-            starts = [st["weights"][i][0] for i in by_start]
-            slots, t_in, t_base, t_ld = [], [], [], []
-            w_in = st["w_in"].tolist()
-            for e in self._segs:                         # AdamW segments are parameter tensors: a fused QKV weight spans three
-                k = bisect.bisect_right(starts, e.offset) - 1
-                k = by_start[k] if k >= 0 else -1
-                inside = k >= 0 and e.offset + e.numel <= st["weights"][k][0] + st["weights"][k][1]
-                slots.append(k if inside else -1)
-                # transposed shadow (fp8 backward): kept by the update itself, in whole 64 x 64 tiles, where the segment is a band
-                # of whole rows of the weight (the weight itself, or the Q / K / V part of a fused QKV weight)
-                ok = inside and st.get("qt") is not None and st["transposed"][k]
-                if ok:
-                    w_off, w_num = st["weights"][k]
-                    n_in = w_in[k]
-                    ok = n_in % 64 == 0 and (e.offset - w_off) % n_in == 0 and e.numel % (64 * n_in) == 0 and ((e.offset - w_off) // n_in) % 16 == 0
-                t_in.append(w_in[k] if ok else 0)
-                t_base.append(st["weights"][k][0] + (e.offset - st["weights"][k][0]) // w_in[k] if ok else 0)
-                t_ld.append(st["weights"][k][1] // w_in[k] if ok else 0)
-            dev = core.flat_params.device
-            seg_slot = torch.tensor(slots, dtype=torch.int32, device=dev)
-            seg_in = torch.tensor(t_in, dtype=torch.int32, device=dev)
-            seg_t_base = torch.tensor(t_base, dtype=torch.int64, device=dev)
-            seg_t_ld = torch.tensor(t_ld, dtype=torch.int32, device=dev)
-            sh = L.Fp8Shadow()
-            sh.q, sh.seg_slot, sh.scale, sh.amax = st["q"].data_ptr(), seg_slot.data_ptr(), st["w_scale"].data_ptr(), st["w_amax"].data_ptr()
-            # every weight that has a transposed copy must be covered, or the separate launch stays (crct_fp8_transpose_weights)
-            if set(s for s in slots if s >= 0) != set(range(len(st["weights"]))):
-                raise RuntimeError("fused AdamW: %d of the model's %d fp8-shadowed weights are not covered by optimizer segments; their "
-                                   "shadow would go stale" % (len(st["weights"]) - len(set(s for s in slots if s >= 0)), len(st["weights"])))
-            covered = [0] * len(st["weights"])
-            for s, t, e in zip(slots, t_in, self._segs):
-                if s >= 0 and t > 0:
-                    covered[s] += e.numel
-            fused = st.get("qt") is not None and all(covered[k] == st["weights"][k][1] for k in range(len(covered)) if st["transposed"][k])
-            if fused:
-                sh.qt, sh.seg_in, sh.seg_t_base, sh.seg_t_ld = st["qt"].data_ptr(), seg_in.data_ptr(), seg_t_base.data_ptr(), seg_t_ld.data_ptr()
-            self._fp8_transposes = fused
-            self._fp8_keep = (st, seg_slot, sh, C.byref(sh), seg_in, seg_t_base, seg_t_ld)
-        return self._fp8_keep[3]
+        st = self._fp8_state()
+        return st.shadow_for(self._segs)[0] if st is not None else None
+
+    @property
+    def _fp8_transposes(self):
+        """Does the update kernel itself keep the transposed shadow current?"""
+        st = self._fp8_state()
+        return st is not None and st.shadow_for(self._segs)[1]
 
     def _fp8_before_update(self, stream):
-        """Delayed scaling of the weight shadow: the scales this update quantises with come from the amax the previous update saw."""
-        if self._fp8_arg() is not None:
-            st = self.core._fp8
-            # the window is counted on the host per CALL (under GradScaler the host step counter is frozen: the device counter
-            # takes over), and a step the scaler skips leaves shadow AND scales alone
-            st["w_updates"] = st.get("w_updates", 0) + 1
-            found = self._amp_keep[1] if (self._amp_arg is not None and self._amp_keep is not None) else None
-            L.check(L.load().crct_fp8_update_scales(st["w_scale"].data_ptr(), st["w_amax"].data_ptr(), len(st["weights"]),
-                                                    int(st["w_updates"] % self.core.FP8_AMAX_WINDOW == 0), L.ptr(found), 448.0, stream),
-                    "fp8_update_scales")
+        """Delayed scaling of the weight shadow: the scales this update quantises with come from the amax the previous update saw
+        (a step the GradScaler skips leaves shadow AND scales alone)."""
+        if self._fp8_arg() is not None:     # (builds the descriptor: an optimizer that misses a shadowed weight is refused before any launch)
+            self.core._fp8.weight.update(stream, skip_if=self._amp_keep[1] if (self._amp_arg is not None and self._amp_keep is not None) else None)
 
     def _launch_groups(self, order):
         """``order`` (segments in first-use order) cut into ``launch_groups`` runs of similar block counts, the first segment alone."""
@@ -350,7 +308,8 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _follow_device(self):
         """The model was moved (``model.to('cuda:1')`` after the optimizer was built): the moments and tables follow, and
-        everything bound to the old device -- update stream, segment events, fp8 shadow descriptor -- is made again."""
+        everything bound to the old device -- update stream, segment events -- is made again (the fp8 shadow descriptor lives
+        in the model's Fp8State, which the move has dropped)."""
         dev = self.core.flat_params.device
         if self._m.device == dev:
             return
@@ -364,7 +323,7 @@ class FusedAdamW(torch.optim.Optimizer):
             setattr(self, k, getattr(self, k).to(dev))
         self._last = None
         self._upload_done = None
-        self._fp8_keep = self._events = self._opt_stream = self._seg_blocks = None
+        self._events = self._opt_stream = self._seg_blocks = None
         self._clip = self._clip_partials = self._clip_seg_norms = self._clip_keep = None
         self._step_dev = self._step_dev.to(dev) if self._step_dev is not None else None
 
@@ -442,13 +401,11 @@ class FusedAdamW(torch.optim.Optimizer):
             self._upload_hyper()
             self._fp8_before_update(L.current_stream())
             self._launch(0, self._blk_seg.numel(), inv_scale, L.current_stream())
-        if getattr(core, "fp8_backward", False) and self._fp8_arg() is not None:
-            # the update rewrote the e4m3 weight shadow: its transposed copy (fp8 data gradients) follows on the same stream
+        st = self._fp8_state()
+        if st is not None:                              # transposed shadow and gradient scales follow the update on the same stream
             beside = self.overlap and not amp and self._opt_stream is not None
-            side = self._opt_stream.cuda_stream if beside else L.current_stream()
-            if not self._fp8_transposes:                # normally the update kernel has written the transposed copy itself
-                core._fp8_transpose(side, self.fp8_transpose_workgroups if beside else 0)
-            core._fp8_update_grad_scales(side)          # the scales the NEXT backward pass quantises its gradients with
+            st.after_update(self._opt_stream.cuda_stream if beside else L.current_stream(), self._fp8_transposes,
+                            self.fp8_transpose_workgroups if beside else 0)
         core.note_params_updated_natively()
         # under GradScaler the kernel returns at once on a skipped step and zeroes nothing: only without it the clear is certain
         self._grads_cleared = bool(self.fuse_zero_grad) and not amp
