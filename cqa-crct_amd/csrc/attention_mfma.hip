@@ -100,7 +100,7 @@ __device__ __forceinline__ void store_rows_q(bf16_t* dst, uint8_t* qdst, long ld
     for (int j = 0; j < 4; ++j) { f[2 * j] = bf2f((bf16_t)(w[j] & 0xffff)); f[2 * j + 1] = bf2f((bf16_t)(w[j] >> 16)); }
     uint32_t o[2] = {0u, 0u};
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { am = fmaxf(am, fabsf(f[j])); f[j] = fminf(fmaxf(f[j] * qs, -LIM), LIM); }
+    for (int j = 0; j < 8; ++j) { am = amax_join(am, f[j]); f[j] = fp8_sat(f[j] * qs, LIM); }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if constexpr (BF8) {
@@ -383,11 +383,11 @@ __global__ __launch_bounds__(64 * W * SP) void attn_bwd_mfma(ATTN_HOT_PARAMS) {
               *reinterpret_cast<uint2*>(a.dq + ((long)b * a.Tq + i) * a.lddq + h * d + 16 * ct + 4 * (lane >> 4)) = pk;
               if (a.dq_q) {                 // e5m2 copy of the bf16-rounded values
                 const float f0 = bf2f((bf16_t)(pk.x & 0xffff)), f1 = bf2f((bf16_t)(pk.x >> 16)), f2 = bf2f((bf16_t)(pk.y & 0xffff)), f3 = bf2f((bf16_t)(pk.y >> 16));
-                dq_am = fmaxf(fmaxf(dq_am, fmaxf(fabsf(f0), fabsf(f1))), fmaxf(fabsf(f2), fabsf(f3)));
+                dq_am = amax_join(amax_join(dq_am, amax_pair(f0, f1)), amax_pair(f2, f3));
                 const float qs = a.dq_qscale[0];
                 uint32_t o = 0u;
-                o = __builtin_amdgcn_cvt_pk_bf8_f32(fminf(fmaxf(f0 * qs, -57344.f), 57344.f), fminf(fmaxf(f1 * qs, -57344.f), 57344.f), o, false);
-                o = __builtin_amdgcn_cvt_pk_bf8_f32(fminf(fmaxf(f2 * qs, -57344.f), 57344.f), fminf(fmaxf(f3 * qs, -57344.f), 57344.f), o, true);
+                o = __builtin_amdgcn_cvt_pk_bf8_f32(bf8_clamp(f0 * qs), bf8_clamp(f1 * qs), o, false);
+                o = __builtin_amdgcn_cvt_pk_bf8_f32(bf8_clamp(f2 * qs), bf8_clamp(f3 * qs), o, true);
                 *reinterpret_cast<uint32_t*>(a.dq_q + ((long)b * a.Tq + i) * a.lddq + h * d + 16 * ct + 4 * (lane >> 4)) = o;
               }
             }
@@ -398,9 +398,7 @@ __global__ __launch_bounds__(64 * W * SP) void attn_bwd_mfma(ATTN_HOT_PARAMS) {
   }
   if constexpr (DQ_DIRECT) {
     if (a.dq_q) {
-      dq_am = fmaxf(dq_am, __shfl_xor(dq_am, 32, 64)); dq_am = fmaxf(dq_am, __shfl_xor(dq_am, 16, 64)); dq_am = fmaxf(dq_am, __shfl_xor(dq_am, 8, 64));
-      dq_am = fmaxf(dq_am, __shfl_xor(dq_am, 4, 64)); dq_am = fmaxf(dq_am, __shfl_xor(dq_am, 2, 64)); dq_am = fmaxf(dq_am, __shfl_xor(dq_am, 1, 64));
-      if (lane == 0) amax_update(a.dq_qamax, dq_am);
+      wave_amax(a.dq_qamax, dq_am, lane);
     }
   }
   group_sync<SP>();                     // K is consumed (its image becomes the staging tile); the P image is complete

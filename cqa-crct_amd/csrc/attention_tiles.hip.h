@@ -48,10 +48,11 @@ __device__ __forceinline__ float xsum2(float v) {
   return v + __shfl_xor(v, 32, 64);
 }
 
-// wave maximum of `am` into the amax slot of the workgroup (fp8 copies: CrctAttnQuant)
+// wave maximum of `am` into the amax slot of the workgroup (fp8 copies: CrctAttnQuant).  amax_wave is the DPP / v_readlane tree of
+// common.hip.h: ALL 64 LANES MUST BE ACTIVE at the call (an inactive lane's value is undefined in a DPP read), so call it only
+// under wave-uniform conditions and behind reconverged loops, as every caller does
 __device__ __forceinline__ void wave_amax(float* dst, float am, int lane) {
-  am = fmaxf(am, __shfl_xor(am, 32, 64)); am = fmaxf(am, __shfl_xor(am, 16, 64)); am = fmaxf(am, __shfl_xor(am, 8, 64));
-  am = fmaxf(am, __shfl_xor(am, 4, 64)); am = fmaxf(am, __shfl_xor(am, 2, 64)); am = fmaxf(am, __shfl_xor(am, 1, 64));
+  am = amax_wave(am);           // on bit patterns: a NaN reaches the words (common.hip.h)
   if (lane == 0) amax_update(dst, am);
 }
 // four values -> four fp8 bytes of f * qs (E4M3: OCP e4m3, else e5m2), saturated to the format's largest finite value; am <- max(am, |f|)
@@ -60,7 +61,7 @@ __device__ __forceinline__ uint32_t sat_cvt4(const float (&v)[4], float qs, floa
   constexpr float LIM = E4M3 ? 448.f : 57344.f;
   float f[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) { am = fmaxf(am, fabsf(v[r])); f[r] = fminf(fmaxf(v[r] * qs, -LIM), LIM); }
+  for (int r = 0; r < 4; ++r) { am = amax_join(am, v[r]); f[r] = fp8_sat(v[r] * qs, LIM); }
   uint32_t o = 0u;
   if constexpr (E4M3) {
     o = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], o, false);

@@ -156,7 +156,7 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 __device__ __forceinline__ float act_apply(int act, float x) {
   switch (act) {
     case ACT_GELU: return gelu_erf(x);
-    case ACT_RELU: return x > 0.f ? x : 0.f;
+    case ACT_RELU: return x <= 0.f ? 0.f : x;       // NaN stays NaN, as torch.relu keeps it (x > 0 ? x : 0 would print 0); -0 -> +0 as before
     case ACT_LEAKY: return x > 0.f ? x : 0.01f * x;
     case ACT_TANH: return tanhf(x);
     default: return x;
@@ -182,10 +182,33 @@ __device__ __forceinline__ float act_grad(int act, float s) {
 #ifndef CRCT_FP8_AMAX_LANES
 #define CRCT_FP8_AMAX_LANES 64      // = include/crct_hip.h
 #endif
-__device__ __forceinline__ void amax_update(float* dst, float v) {
-  float* w = dst + (blockIdx.x & (CRCT_FP8_AMAX_LANES - 1));
-  if (v > __builtin_nontemporal_load(w)) atomicMax(reinterpret_cast<int*>(w), __float_as_int(v));
+// A NaN must reach the words (crct_fp8_update_scales then keeps the scale and clears them, and the step is skipped as a whole), and
+// fmaxf / a float compare drop it: the maximum is taken on the BIT PATTERNS of |x|, where every NaN sorts above +inf.  Accumulators
+// stay floats that start at 0.f: amax_join(acc, x) per element, amax_wave once per wave, amax_update from one lane.
+__device__ __forceinline__ float amax_join(float acc, float x) {
+  const uint32_t ua = __float_as_uint(acc), ux = __float_as_uint(fabsf(x));
+  return __uint_as_float(ua > ux ? ua : ux);
 }
+__device__ __forceinline__ float amax_pair(float x, float y) { return amax_join(fabsf(x), y); }      // max(|x|, |y|): neither is an accumulator
+__device__ __forceinline__ float amax_wave(float v) {      // the DPP tree of wave_max with amax_join
+  v = amax_join(v, dpp_f32<0xB1>(v));
+  v = amax_join(v, dpp_f32<0x4E>(v));
+  v = amax_join(v, dpp_f32<0x141>(v));
+  v = amax_join(v, dpp_f32<0x140>(v));
+  return amax_join(amax_join(lane_f32(v, 0), lane_f32(v, 16)), amax_join(lane_f32(v, 32), lane_f32(v, 48)));
+}
+__device__ __forceinline__ void amax_update(float* dst, float v) {
+  int* w = reinterpret_cast<int*>(dst + (blockIdx.x & (CRCT_FP8_AMAX_LANES - 1)));
+  if (__float_as_int(v) > __builtin_nontemporal_load(w)) atomicMax(w, __float_as_int(v));
+}
+
+// ------------------------------------------------------------------ fp8 saturation
+// The hardware conversions do not saturate, so every fp8 copy clamps first: to the largest finite value of OCP e4m3 (448) or e5m2
+// (57344).  +-inf saturates; a NaN passes through both selects and converts to the format's NaN byte (fminf(fmaxf(x, -LIM), LIM) would
+// turn it into -LIM, a finite number that hides it from everything downstream).
+__device__ __forceinline__ float fp8_sat(float x, float lim) { return x < -lim ? -lim : (x > lim ? lim : x); }
+__device__ __forceinline__ float f8_clamp(float x) { return fp8_sat(x, 448.0f); }
+__device__ __forceinline__ float bf8_clamp(float x) { return fp8_sat(x, 57344.0f); }
 
 // Kernels of the two data streams' dependent chains raise their waves' issue priority (s_setprio 3): on a SIMD they share with waves of the
 // work that is off the path by dependency -- the grouped weight gradients, AdamW, the column-sum passes, all at the default 0 -- they issue

@@ -150,8 +150,8 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const CrctHeadArgs a, fl
       float df = dl0 * a.w_cls[c] + dl1 * a.w_cls[a.Hb + c];
       df = head_keep(a, b, c) ? df * dsc : 0.f;
       const float gt = a.fusion_sum ? df : df * v, gv = a.fusion_sum ? df : df * t;
-      dpt[c] = f2bf(t > 0.f ? gt : 0.f);        // relu'(pre) == (post > 0)
-      dpv[c] = f2bf(v > 0.f ? gv : 0.f);
+      dpt[c] = f2bf(t <= 0.f ? 0.f : gt);       // relu'(pre) == (post > 0); a NaN post lets the gradient through, as torch's threshold_backward does
+      dpv[c] = f2bf(v <= 0.f ? 0.f : gv);
     }
     if (MODE != HEAD_NONE) {
       bf16_t* dfh = reinterpret_cast<bf16_t*>(a.d_fus_h) + (long)b * 256;
@@ -332,8 +332,8 @@ __global__ __launch_bounds__(256) void head_ce_rows_kernel(const CrctHeadArgs a,
       float df = dl0 * a.w_cls[c] + dl1 * a.w_cls[a.Hb + c];
       df = head_keep(a, b, c) ? df * dsc : 0.f;
       const float gt = a.fusion_sum ? df : df * v, gv = a.fusion_sum ? df : df * tv;
-      dpt[c] = f2bf(tv > 0.f ? gt : 0.f);
-      dpv[c] = f2bf(v > 0.f ? gv : 0.f);
+      dpt[c] = f2bf(tv <= 0.f ? 0.f : gt);
+      dpv[c] = f2bf(v <= 0.f ? 0.f : gv);
     }
     bf16_t* dfh = reinterpret_cast<bf16_t*>(a.d_fus_h) + (long)b * 256;
     for (int c = tid; c < 256; c += 256) {

@@ -111,10 +111,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
 #endif
       if (pb) *reinterpret_cast<uint2*>(pb + e) = make_uint2(pack2bf(pa[0], pa[1]), pack2bf(pa[2], pa[3]));
       if (qslot >= 0) {
-        qmax = fmaxf(fmaxf(qmax, fmaxf(fabsf(pa[0]), fabsf(pa[1]))), fmaxf(fabsf(pa[2]), fabsf(pa[3])));
+        qmax = amax_join(amax_join(qmax, amax_pair(pa[0], pa[1])), amax_pair(pa[2], pa[3]));
         uint32_t w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(pa[0] * qs, -448.f), 448.f), fminf(fmaxf(pa[1] * qs, -448.f), 448.f), w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(pa[2] * qs, -448.f), 448.f), fminf(fmaxf(pa[3] * qs, -448.f), 448.f), w, true);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(pa[0] * qs), f8_clamp(pa[1] * qs), w, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(pa[2] * qs), f8_clamp(pa[3] * qs), w, true);
         *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(f8.q) + e) = w;
         if (tin > 0) tile[i >> 6][(i & 63) >> 2] = w;
       }
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     }
   }
   if (qslot >= 0) {          // fp8-shadowed tensors are multiples of 4 elements (Linear weights): the scalar tail never holds them
-    qmax = wave_max(qmax);
+    qmax = amax_wave(qmax);
     if ((threadIdx.x & 63) == 0) amax_update(f8.amax + (long)qslot * CRCT_FP8_AMAX_LANES, qmax);
   }
   if (tin > 0) {             // uniform over the workgroup (one tensor per chunk)

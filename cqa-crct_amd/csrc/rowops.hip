@@ -98,8 +98,7 @@ __device__ __forceinline__ void row_store_bf16(const Row<NCH>& r, bf16_t* p, int
     }
   }
 }
-// OCP e4m3 copy of a row, q = clamp(x * qs, +-448); returns max |x| over this lane's elements (the NEXT step's scale)
-__device__ __forceinline__ float f8_clamp(float x) { return fminf(fmaxf(x, -448.0f), 448.0f); }
+// OCP e4m3 copy of a row, q = f8_clamp(x * qs) (common.hip.h: +-448, NaN stays); returns max |x| over this lane's elements (the NEXT step's scale)
 __device__ __forceinline__ uint2 pack8_fp8(const float (&v)[8], float qs) {
   uint32_t w0 = 0, w1 = 0;
   w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(v[0] * qs), f8_clamp(v[1] * qs), w0, false);
@@ -118,14 +117,13 @@ __device__ __forceinline__ float row_store_fp8(const Row<NCH>& r, uint8_t* p, in
       // the bf16 copy is what backward and the bf16 GEMMs see: quantise the bf16-rounded value, so both copies agree
       float v[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { v[j] = bf2f(f2bf(r.v[i][j])); amax = fmaxf(amax, fabsf(v[j])); }
+      for (int j = 0; j < 8; ++j) { v[j] = bf2f(f2bf(r.v[i][j])); amax = amax_join(amax, v[j]); }
       *reinterpret_cast<uint2*>(p + c) = pack8_fp8(v, qs);
     }
   }
   return amax;
 }
 // OCP e5m2 copy of a row (a GRADIENT that the next data-gradient GEMM reads as its fp8 A operand): q = clamp(x * qs, +-57344)
-__device__ __forceinline__ float bf8_clamp(float x) { return fminf(fmaxf(x, -57344.0f), 57344.0f); }
 __device__ __forceinline__ uint2 pack8_bf8(const float (&v)[8], float qs) {
   uint32_t w0 = 0, w1 = 0;
   w0 = __builtin_amdgcn_cvt_pk_bf8_f32(bf8_clamp(v[0] * qs), bf8_clamp(v[1] * qs), w0, false);
@@ -143,7 +141,7 @@ __device__ __forceinline__ float row_store_bf8(const Row<NCH>& r, uint8_t* p, in
     if (c < H) {
       float v[8];      // the bf16-rounded value, as in row_store_fp8: the bf16 copy (weight gradients) and this one agree
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { v[j] = bf2f(f2bf(r.v[i][j])); amax = fmaxf(amax, fabsf(v[j])); }
+      for (int j = 0; j < 8; ++j) { v[j] = bf2f(f2bf(r.v[i][j])); amax = amax_join(amax, v[j]); }
       *reinterpret_cast<uint2*>(p + c) = pack8_bf8(v, qs);
     }
   }
@@ -625,11 +623,11 @@ __device__ __forceinline__ void ln_fwd_body(const LnFwdP& a, const int blk, cons
     row_normalize(r, g, b, H, lane, mean, rstd, row, a.thr, a.scale, a.site, a.seed);
     row_store_bf16(r, a.y + row * H, H, lane);
     if (a.y_f32) row_store_f32_nt(r, a.y_f32 + row * H, H, lane);
-    if (a.q_out) amax = fmaxf(amax, row_store_fp8(r, a.q_out + row * H, H, lane, qs));     // the fp8 GEMMs' operand (BASELINE configs[4])
+    if (a.q_out) amax = amax_join(amax, row_store_fp8(r, a.q_out + row * H, H, lane, qs));     // the fp8 GEMMs' operand (BASELINE configs[4])
     if (lane == 0) { a.mean_o[row] = mean; a.rstd_o[row] = rstd; }
   }
   if (a.q_out && a.q_amax) {
-    amax = wave_max(amax);
+    amax = amax_wave(amax);
     if (lane == 0) amax_update(a.q_amax, amax);
   }
 }
@@ -703,11 +701,11 @@ __device__ __forceinline__ void ln_bwd_body(const LnBwdP& a, const int blk, cons
       row_apply_dropmask(dy, H, lane, row, lin_thr, lin_scale, lin_site, seed);
       row_store_bf16(dy, dxl_p + row * H, H, lane);
     }
-    if (a.q_out) q_amax = fmaxf(q_amax, row_store_bf8(dy, a.q_out + row * H, H, lane, qs));
+    if (a.q_out) q_amax = amax_join(q_amax, row_store_bf8(dy, a.q_out + row * H, H, lane, qs));
     row_acc(adl, dy);
   }
   if (a.q_out && a.q_amax) {
-    q_amax = wave_max(q_amax);
+    q_amax = amax_wave(q_amax);
     if (lane == 0) amax_update(a.q_amax, q_amax);
   }
   if constexpr (COMBINE) {
@@ -1049,10 +1047,11 @@ __global__ __launch_bounds__(256) void embed_text_bwd_kernel(
       if (tyid >= 0) row_atomic_add(dy, d_type + (long)tyid * H, H, lane);
     }
     const float4 lv = *reinterpret_cast<const float4*>(loc + row * 4);
-    if (fabsf(lv.x) + fabsf(lv.y) + fabsf(lv.z) + fabsf(lv.w) != 0.f) {
-      row_acc(abl, dy);
-      row_acc(aw0, dy, lv.x); row_acc(aw1, dy, lv.y); row_acc(aw2, dy, lv.z); row_acc(aw3, dy, lv.w);
-    }
+    // The location gate (|loc|_1 != 0) as a FACTOR, as the reference multiplies by it: a gated-out row adds dy * 0 -- the same bits for
+    // finite dy (its loc is all zero, so the weight terms are dy * 0 anyway), and a NaN row gradient reaches d W_loc / d b_loc.
+    const float gate = fabsf(lv.x) + fabsf(lv.y) + fabsf(lv.z) + fabsf(lv.w) != 0.f ? 1.f : 0.f;
+    row_acc(abl, dy, gate);
+    row_acc(aw0, dy, lv.x); row_acc(aw1, dy, lv.y); row_acc(aw2, dy, lv.z); row_acc(aw3, dy, lv.w);
   }
   // every WAVE stores its own partial rows ([7 or 9][4 * gridDim.x][H]; the finalize pass sums them): no LDS tree and no
   // workgroup barrier in this kernel.  (The wrong lanes 48..63 once seen here beside the dgrad / wgrad GEMMs came from
@@ -1591,11 +1590,11 @@ __global__ __launch_bounds__(256) void fp8_quantize_bf16_kernel(const bf16_t* __
 #pragma unroll
     for (int j = 0; j < 4; ++j) { v[2 * j] = bf2f((bf16_t)(w[j] & 0xffff)); v[2 * j + 1] = bf2f((bf16_t)(w[j] >> 16)); }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+    for (int j = 0; j < 8; ++j) amax = amax_join(amax, v[j]);
     *reinterpret_cast<uint2*>(q + i) = pack8_fp8(v, qs);
   }
   if (amax_out) {
-    amax = wave_max(amax);
+    amax = amax_wave(amax);
     if ((threadIdx.x & 63) == 0) amax_update(amax_out, amax);
   }
 }
@@ -1617,7 +1616,7 @@ __global__ __launch_bounds__(256) void fp8_weights_kernel(const float* __restric
     float am = 0.f;
     for (int64_t i = (int64_t)threadIdx.x * 4; i + 4 <= n; i += 1024) {
       const float4 v = *reinterpret_cast<const float4*>(p + base + i);
-      if (MODE == 0) am = fmaxf(fmaxf(am, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+      if (MODE == 0) am = amax_join(amax_join(am, amax_pair(v.x, v.y)), amax_pair(v.z, v.w));
       else {
         uint32_t w = 0;
         w = __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(v.x * qs), f8_clamp(v.y * qs), w, false);
@@ -1626,7 +1625,7 @@ __global__ __launch_bounds__(256) void fp8_weights_kernel(const float* __restric
       }
     }
     if (MODE == 0) {
-      am = wave_max(am);
+      am = amax_wave(am);
       if ((threadIdx.x & 63) == 0) amax_update(amax + (long)slot * CRCT_FP8_AMAX_LANES, am);
     }
   }
