@@ -17,6 +17,10 @@ A file written here loads in the reference and vice versa: identical keys, shape
 tensor with ``step`` / ``exp_avg`` / ``exp_avg_sq`` per trained tensor (tests/golden/ckpt_schema.json, generated from
 a real reference checkpoint, is what the tests compare against).  Tensors are written as independent CPU copies,
 never as views of the flat HBM buffers.
+
+One entry the reference does not have, and only while ``FusedAdamW.enable_ema()`` is on: ``'ema_state_dict'``, the averaged
+weights under the model's own keys.  ``resume`` restores it into an optimizer that has the average enabled,
+``load_model_weights(..., use_ema=True)`` loads it in place of the weights; the reference ignores the key.
 """
 import os
 
@@ -53,6 +57,8 @@ def checkpoint_dict(model, optimizer, scheduler, iter_id, loss_avg=None):
            "iter_id": int(iter_id)}
     if loss_avg is not None:
         out["loss_avg"] = loss_avg
+    if getattr(optimizer, "ema_enabled", False):      # the averaged weights (FusedAdamW.enable_ema), under the model's own keys; absent
+        out["ema_state_dict"] = _cpu_copy(optimizer.ema_state_dict(_unwrap(model)))      # otherwise: exactly the reference's keys
     return out
 
 
@@ -66,11 +72,16 @@ def save_checkpoint(save_path, model, optimizer, scheduler, epoch, step_iter_id,
     return path
 
 
-def load_model_weights(model, ckpt, strict_nonempty=True):
+def load_model_weights(model, ckpt, strict_nonempty=True, use_ema=False):
     """Key-intersection load (train.py:94-104, evaluation.py:31-41).  ``ckpt`` is a path or an already loaded dict.
-    Returns the number of tensors transferred."""
+    Returns the number of tensors transferred.  ``use_ema``: load the averaged weights (``'ema_state_dict'``, written while
+    ``FusedAdamW.enable_ema`` is on) instead -- the deployment path; KeyError if the file has none."""
     pretrained = _read(ckpt, _device_of(model))
-    if "model_state_dict" in pretrained:
+    if use_ema:
+        if "ema_state_dict" not in pretrained:
+            raise KeyError("ema_state_dict: the checkpoint holds no averaged weights (it was written without FusedAdamW.enable_ema())")
+        pretrained = pretrained["ema_state_dict"]
+    elif "model_state_dict" in pretrained:
         pretrained = pretrained["model_state_dict"]
     target = _unwrap(model)
     model_dict = target.state_dict()
@@ -100,6 +111,8 @@ def resume(model, optimizer, ckpt_path, params, iters_per_epoch, scheduler_cls=W
     optimizer_dict.update({k: v for k, v in pretrained["optimizer_state_dict"].items() if k in optimizer_dict})
     target.load_state_dict(model_dict)
     optimizer.load_state_dict(optimizer_dict)
+    if "ema_state_dict" in pretrained and getattr(optimizer, "ema_enabled", False):
+        optimizer.load_ema_state_dict(pretrained["ema_state_dict"], target)
     scheduler = scheduler_cls(optimizer, warmup_steps=params["warmup"], min_lr=params["min_lr"],
                               t_total=iters_per_epoch * 20, last_epoch=pretrained["iter_id"])   # train.py:121-122
     scheduler.load_state_dict(pretrained["scheduler_state_dict"])

@@ -220,6 +220,7 @@ PROTOTYPES = {
     "crct_eval_score": (C.c_int, [C.POINTER(EvalScoreArgs), vp]),
     "crct_adamw_plan": (c_i64, [vp, C.c_int, vp, vp, c_i64]),
     "crct_adamw_step": (C.c_int, [vp] * 11 + [c_i64, c_f32, c_f32, c_f32, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
+    "crct_adamw_step_ema": (C.c_int, [vp] * 11 + [c_i64, c_f32, c_f32, c_f32, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, c_f32, vp]),
     "crct_adamw_advance": (C.c_int, [vp, vp, vp]),
     "crct_grad_sumsq": (C.c_int, [vp] * 6 + [c_i64, vp, C.c_int, C.c_int, vp]),
     "crct_grad_norm_finalize": (C.c_int, [vp, vp, c_i64, C.c_int, C.c_int, c_f32, vp, vp, vp, vp, vp]),

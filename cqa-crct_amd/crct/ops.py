@@ -487,18 +487,22 @@ def _fp8_shadow(fp8):
 
 
 def adamw_step(p, g, m, v, seg_off, seg_len, seg_lr, seg_wd, blk_seg, blk_off, step=1, betas=(0.9, 0.999), eps=1e-8, p_bf16=None,
-               inv_scale=None, amp=None, fp8=None, max_workgroups=0, zero_grads=False, g_bf16=None):
+               inv_scale=None, amp=None, fp8=None, max_workgroups=0, zero_grads=False, g_bf16=None, ema=None, ema_weight=0.0):
     """crct_adamw_step in place on the flat fp32 buffers p, g, m, v over the device tables (seg_*, blk_* from ``adamw_plan``).
-    inv_scale: device fp32 scalar; amp / fp8: dicts of device tensors named after the fields of CrctAmpState / CrctFp8Shadow."""
+    inv_scale: device fp32 scalar; amp / fp8: dicts of device tensors named after the fields of CrctAmpState / CrctFp8Shadow.
+    ema (flat fp32, the element offsets of p): crct_adamw_step_ema instead -- ema += ema_weight * (p' - ema) in the same launch."""
     amp_keep, amp_arg = _amp_state(amp)
     f8_keep, f8_arg = _fp8_shadow(fp8)
-    L.check(L.load().crct_adamw_step(L.ptr(_chk(p, torch.float32)), L.ptr(_chk(g, torch.float32)), L.ptr(_chk(m, torch.float32)),
-                                     L.ptr(_chk(v, torch.float32)), L.ptr(_chk(p_bf16, torch.bfloat16)), L.ptr(_chk(seg_off, torch.int64)),
-                                     L.ptr(_chk(seg_len, torch.int64)), L.ptr(_chk(seg_lr, torch.float32)), L.ptr(_chk(seg_wd, torch.float32)),
-                                     L.ptr(_chk(blk_seg, torch.int32)), L.ptr(_chk(blk_off, torch.int64)), blk_seg.numel(),
-                                     float(betas[0]), float(betas[1]), float(eps), int(step), L.ptr(_chk(inv_scale, torch.float32)),
-                                     amp_arg, f8_arg, int(max_workgroups), int(bool(zero_grads)), L.ptr(_chk(g_bf16, torch.bfloat16)),
-                                     L.current_stream()), "adamw_step")
+    args = (L.ptr(_chk(p, torch.float32)), L.ptr(_chk(g, torch.float32)), L.ptr(_chk(m, torch.float32)),
+            L.ptr(_chk(v, torch.float32)), L.ptr(_chk(p_bf16, torch.bfloat16)), L.ptr(_chk(seg_off, torch.int64)),
+            L.ptr(_chk(seg_len, torch.int64)), L.ptr(_chk(seg_lr, torch.float32)), L.ptr(_chk(seg_wd, torch.float32)),
+            L.ptr(_chk(blk_seg, torch.int32)), L.ptr(_chk(blk_off, torch.int64)), blk_seg.numel(),
+            float(betas[0]), float(betas[1]), float(eps), int(step), L.ptr(_chk(inv_scale, torch.float32)),
+            amp_arg, f8_arg, int(max_workgroups), int(bool(zero_grads)), L.ptr(_chk(g_bf16, torch.bfloat16)))
+    if ema is None:
+        L.check(L.load().crct_adamw_step(*args, L.current_stream()), "adamw_step")
+    else:
+        L.check(L.load().crct_adamw_step_ema(*args, L.ptr(_chk(ema, torch.float32)), float(ema_weight), L.current_stream()), "adamw_step_ema")
 
 
 def adamw_advance(step_dev, found_inf=None):

@@ -13,6 +13,7 @@ import contextlib
 import json
 import os
 
+import numpy as np
 import torch
 from torch.optim.lr_scheduler import _LRScheduler
 
@@ -104,6 +105,7 @@ class FusedAdamW(torch.optim.Optimizer):
         # back to fp32 (a weak reference: an optimizer that was built and discarded must not change what .grad holds)
         import weakref
         core._fused_optimizer = weakref.ref(self)
+        self._model_ref = weakref.ref(model)         # ema_state_dict() speaks the keys of the model the optimizer was built for
         # overlap mode: the update runs as one launch per engine backward-segment on its own stream, in first-use
         # order, each followed by an event; the next forward waits for segment s right before it needs it, so
         # AdamW (HBM-bound, ~1.2 ms) and the gradient memset overlap the next step's forward
@@ -127,6 +129,14 @@ class FusedAdamW(torch.optim.Optimizer):
         self._opt_stream = None
         self._seg_blocks = None
         self._events = None
+        # exponential moving average of the weights (enable_ema): a flat fp32 buffer with the offsets of the weights that every update
+        # launch moves along (crct_adamw_step_ema).  ``ema_decay`` is a plain attribute read at every step(): a decay schedule is the
+        # caller's one line.  Under a GradScaler a skipped step leaves the average alone (decided on the device), but a host-side
+        # schedule that counts step() calls counts the skipped ones too.
+        self._ema = None
+        self.ema_decay = 0.999
+        self._ema_weight = 0.0
+        self._ema_swapped = False
         # expose the moments the way torch.optim.AdamW does (views of the flat buffers)
         for e in self._segs:
             p = byname[e.name]
@@ -196,15 +206,19 @@ class FusedAdamW(torch.optim.Optimizer):
         frozen = [] if getattr(core, "optional_grads_live", True) else [e for lo, hi, e in self._opt_blocks if lo < b1 and hi > b0]
         if frozen:               # areas_emp without a gradient: its weights, moments and shadow are put back behind the update
             side = torch.cuda.ExternalStream(stream, device=core.flat_params.device)
-            bufs = (core.flat_params, self._m, self._v, core.flat_shadow)
+            bufs = (core.flat_params, self._m, self._v, core.flat_shadow) + ((self._ema,) if self._ema is not None else ())
             with torch.cuda.stream(side):
                 kept = [(e, [b[e.offset:e.offset + e.numel].clone() for b in bufs]) for e in frozen]
-        L.check(L.load().crct_adamw_step(core.flat_params.data_ptr(), core.flat_grads.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
-                                         core.flat_shadow.data_ptr(), self._seg_off.data_ptr(), self._seg_len.data_ptr(),
-                                         self._lr_dev.data_ptr(), self._wd_dev.data_ptr(), self._blk_seg.data_ptr() + 4 * b0,
-                                         self._blk_off.data_ptr() + 8 * b0, b1 - b0, g0["betas"][0], g0["betas"][1], g0["eps"],
-                                         max(self._step, 1), L.ptr(inv_scale), self._amp_arg, self._fp8_arg(), int(max_workgroups),
-                                         int(self.fuse_zero_grad), L.ptr(self._g16), stream), "adamw_step")
+        args = (core.flat_params.data_ptr(), core.flat_grads.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
+                core.flat_shadow.data_ptr(), self._seg_off.data_ptr(), self._seg_len.data_ptr(),
+                self._lr_dev.data_ptr(), self._wd_dev.data_ptr(), self._blk_seg.data_ptr() + 4 * b0,
+                self._blk_off.data_ptr() + 8 * b0, b1 - b0, g0["betas"][0], g0["betas"][1], g0["eps"],
+                max(self._step, 1), L.ptr(inv_scale), self._amp_arg, self._fp8_arg(), int(max_workgroups),
+                int(self.fuse_zero_grad), L.ptr(self._g16))
+        if self._ema is None:
+            L.check(L.load().crct_adamw_step(*args, stream), "adamw_step")
+        else:            # the average of the weights moves in the same launch (enable_ema)
+            L.check(L.load().crct_adamw_step_ema(*args, self._ema.data_ptr(), self._ema_weight, stream), "adamw_step_ema")
         if frozen:
             with torch.cuda.stream(side):
                 for e, saved in kept:
@@ -315,6 +329,8 @@ class FusedAdamW(torch.optim.Optimizer):
             return
         old_m, old_v = self._m, self._v
         self._m, self._v = old_m.to(dev), old_v.to(dev)
+        if self._ema is not None:
+            self._ema = self._ema.to(dev)
         for e in self._segs:
             st = self.state[self._byname[e.name]]
             st["exp_avg"] = self._m[e.offset:e.offset + e.numel].view(e.shape)
@@ -329,9 +345,13 @@ class FusedAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, inv_scale=None):
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.step() inside swap_ema(): the weights are the averaged ones; leave the context first")
         loss = closure() if closure is not None else None
         core = self.core
         self._follow_device()
+        if self._ema is not None:
+            self._ema_weight = float(np.float32(1.0 - float(self.ema_decay)))
         self._sync_active()
         amp = self._amp_begin()
         if not amp:
@@ -506,6 +526,139 @@ class FusedAdamW(torch.optim.Optimizer):
         """Order the current stream after an in-flight overlapped update (before reading weights outside forward)."""
         if self._opt_stream is not None:
             order_streams(self._opt_stream, torch.cuda.current_stream())
+
+    # ---- exponential moving average of the weights, kept by the update launches themselves
+    @property
+    def ema_enabled(self):
+        return self._ema is not None
+
+    @torch.no_grad()
+    def enable_ema(self, decay=0.999):
+        """Keep an exponential moving average of the weights: ``ema += (1 - ema_decay) * (w_new - ema)`` for every element an update
+        launch writes, inside that launch -- it follows the overlap / early streams, a GradScaler's skipped steps and the frozen
+        tensors without a host sync or a launch of its own (4 B read + 4 B written per parameter).  The buffer (the size of the fp32
+        weights) starts as a copy of the current weights, so tensors no update ever touches read as their weights for ever."""
+        if self._ema_swapped:
+            raise RuntimeError("enable_ema() inside swap_ema()")
+        self._follow_device()
+        self.ema_decay = decay
+        self._ema = torch.zeros_like(self.core.flat_params)
+        self.ema_reset()
+
+    def disable_ema(self):
+        """Stop averaging and free the buffer."""
+        if self._ema_swapped:
+            raise RuntimeError("disable_ema() inside swap_ema()")
+        self.synchronize()
+        self._ema = None
+
+    @torch.no_grad()
+    def ema_reset(self):
+        """The average := the current weights (after ``load_state_dict`` on the model, or to restart the average)."""
+        self._need_ema()
+        self._follow_device()
+        self.synchronize()
+        self._ema.copy_(self.core.flat_params)
+
+    def _need_ema(self):
+        if self._ema is None:
+            raise RuntimeError("the weight average is off: call enable_ema() first")
+
+    def _ema_keys(self, model=None):
+        """(state-dict key, table entry) in the order of ``model.state_dict()``: every table entry under the key that model gives it
+        (``bert_pretrained.`` in front for the VisualDialogEncoder wrapper), and the tied decoder weight under its second key.
+        ``model``: the model the optimizer was built for, unless given."""
+        model = model if model is not None else self._model_ref()
+        prefix = ""
+        if model is not None and model is not self.core and hasattr(model, "named_modules"):
+            for name, mod in model.named_modules():
+                if mod is self.core:
+                    prefix = name + "."
+        by = {e.name: e for e in self.core.table}
+        tied = {"cls.predictions.decoder.weight": "bert.embeddings.word_embeddings.weight"}
+        return [(prefix + k, by[tied.get(k, k)]) for k in self.core.state_dict().keys()]
+
+    @torch.no_grad()
+    def ema_state_dict(self, model=None):
+        """``{name: tensor}`` of the averaged weights with the keys, shapes and order of ``model.state_dict()`` (the model the optimizer
+        was built for, or the wrapper / core model given): independent copies, the tied ``cls.predictions.decoder.weight`` included as
+        the model's own state dict includes it; loads into any such model with ``load_state_dict``."""
+        self._need_ema()
+        self.synchronize()
+        src = self.core.flat_params if self._ema_swapped else self._ema
+        return {k: src[e.offset:e.offset + e.numel].view(e.shape).clone() for k, e in self._ema_keys(model)}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd, model=None):
+        """The reverse of ``ema_state_dict`` by key intersection; returns the number of tensors taken."""
+        self._need_ema()
+        if self._ema_swapped:
+            raise RuntimeError("load_ema_state_dict() inside swap_ema()")
+        self._follow_device()
+        self.synchronize()
+        n = 0
+        for k, e in self._ema_keys(model):
+            if k in sd:
+                self._ema[e.offset:e.offset + e.numel].view(e.shape).copy_(sd[k])
+                n += 1
+        return n
+
+    @torch.no_grad()
+    def _exchange_with_ema(self):
+        """flat weights <-> average, through a bounded staging buffer"""
+        p, a = self.core.flat_params, self._ema
+        piece = 1 << 26
+        for o in range(0, p.numel(), piece):
+            t = p[o:o + piece].clone()
+            p[o:o + piece].copy_(a[o:o + piece])
+            a[o:o + piece].copy_(t)
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """``with optimizer.swap_ema(): evaluate(model)`` -- inside, the model's weights ARE the averaged ones (the flat weights and the
+        average exchange contents; the bf16 shadow, and with fp8 the e4m3 shadows and their scales, are rebuilt from them by the next
+        forward).  On exit the training weights come back together with the shadows and fp8 scale state exactly as the last update left
+        them: the next training step is bit-identical to one of a run that never swapped.  ``step()`` inside, and nesting, raise."""
+        self._need_ema()
+        if self._ema_swapped:
+            raise RuntimeError("swap_ema() is already active (it does not nest)")
+        core = self.core
+        self._follow_device()
+        self.synchronize()
+        # what the updates have written beside the weights: restored bit for bit, not recomputed (the fp8 weight scales are DELAYED
+        # ones, which a requantisation from the weights would replace by exact ones)
+        saved_b16 = core.flat_shadow.clone() if core._shadow_ver == core._param_version() else None
+        st = getattr(core, "_fp8", None)
+        saved_f8 = None
+        if st is not None:
+            sets = (st.weight, st.act, st.grad)
+            saved_f8 = (st.q.clone(), st.qt.clone() if st.qt is not None else None,
+                        [(x.scale.clone(), x.amax.clone(), x.updates) for x in sets],
+                        (st.calibrated, st.scaled, st.bwd_calibrated, st.g_scales_fresh))
+        self._exchange_with_ema()
+        core._invalidate_shadow()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange_with_ema()
+            self._ema_swapped = False
+            if saved_b16 is not None:
+                core.flat_shadow.copy_(saved_b16)
+                core.note_params_updated_natively()
+            else:
+                core._invalidate_shadow()
+            if saved_f8 is not None and getattr(core, "_fp8", None) is st:
+                st.q.copy_(saved_f8[0])
+                if st.qt is not None:
+                    st.qt.copy_(saved_f8[1])
+                for x, (sc, am, n) in zip((st.weight, st.act, st.grad), saved_f8[2]):
+                    x.scale.copy_(sc)
+                    x.amax.copy_(am)
+                    x.updates = n
+                st.calibrated, st.scaled, st.bwd_calibrated, st.g_scales_fresh = saved_f8[3]
+            elif getattr(core, "_fp8", None) is not None:     # the fp8 state was made inside the context, from the averaged weights:
+                core._fp8.requantize(core.flat_params, L.current_stream())      # start-up quantisation again, from the training weights
 
     def zero_grad(self, set_to_none=True):
         # one memset; .grad views stay attached (set_to_none would only force a re-attach next step)

@@ -4,7 +4,8 @@
 // eps 1e-8) -- decoupled decay p *= 1 - lr*wd, then the bias-corrected Adam update -- plus the
 // refresh of the bf16 weight shadow the GEMMs read.  HBM-bound: 16 B read + 12 B (+2 B) written per
 // parameter; each workgroup owns up to 4096 contiguous elements of ONE tensor (no divergence on
-// lr / wd), float4 accesses.
+// lr / wd), float4 accesses.  With an exponential moving average of the weights (crct_adamw_step_ema, adamw_kernel<true>) 4 B more
+// are read and 4 B more written per parameter, in the same loop.
 #include <stdlib.h>
 
 #include "common.hip.h"
@@ -24,6 +25,22 @@ __global__ __launch_bounds__(1024) void lab_spin_kernel(long long ticks) {      
 }
 #endif
 
+// Exponential moving average of the weights, folded into the update's own launch (EMA = true): behind the store of the new weight p'
+// the average e of that element moves towards it by the fraction w = 1 - decay,
+//     d = p' - e            one fp32 subtraction, rounded
+//     e' = fmaf(w, d, e)    one fused multiply-add, rounded once
+// spelled with the explicit fmaf so that no contraction is left to the compiler: the vector path and the scalar tail round alike, and
+// tests/ema_ref.py derives its budget from exactly these two roundings.  w = 0 returns e bit for bit for every finite d; a NaN / inf in
+// p' or e arrives in e' of that element alone.
+__device__ __forceinline__ float ema_update(float e, float p_new, float w) {
+  const float d = p_new - e;
+  return fmaf(w, d, e);
+}
+
+// EMA = false is the update as it always was (`ema`, `ema_w` are not read); EMA = true adds one stream to the same loop: `ema`, a flat
+// fp32 buffer with the element offsets of p, is loaded with p / g / m / v and stored with them (4 B read + 4 B written per parameter on top
+// of 30, no LDS, no atomics).  The element index is the loop's own, so the plain chunk and the 64 x 64 tile walk are covered alike.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16_t* __restrict__ pb,
                                                     const int64_t* __restrict__ seg_off, const int64_t* __restrict__ seg_len,
@@ -31,7 +48,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
                                                     const int32_t* __restrict__ blk_seg, const int64_t* __restrict__ blk_off,
                                                     float beta1, float beta2, float eps, float inv_bc1, float inv_sqrt_bc2,
                                                     const float* __restrict__ inv_scale_dev, const CrctAmpState amp, const CrctFp8Shadow f8,
-                                                    int n_blk, int zero_g, const bf16_t* __restrict__ g16) {
+                                                    int n_blk, int zero_g, const bf16_t* __restrict__ g16,
+                                                    float* __restrict__ ema, float ema_w) {
  // loss scaling (torch.amp.GradScaler): a step whose gradients held an inf / nan is skipped as a whole, the scale divides
  // the gradients, and the step count behind the bias corrections is the device counter that only advances on real steps
  if (amp.found_inf && amp.found_inf[0] != 0.f) return;
@@ -86,10 +104,14 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
       }
       const f4_t mv = __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(m + e));
       const f4_t vv = __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(v + e));
+      f4_t ev;
+      if constexpr (EMA) ev = __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(ema + e));
 #else
       const f4_t pv = *reinterpret_cast<const f4_t*>(p + e);
       f4_t gv = g16 ? f4_t{bf2f(g16[e]), bf2f(g16[e + 1]), bf2f(g16[e + 2]), bf2f(g16[e + 3])} : *reinterpret_cast<const f4_t*>(g + e);
       const f4_t mv = *reinterpret_cast<const f4_t*>(m + e), vv = *reinterpret_cast<const f4_t*>(v + e);
+      f4_t ev;
+      if constexpr (EMA) ev = *reinterpret_cast<const f4_t*>(ema + e);
 #endif
       float pa[4] = {pv[0], pv[1], pv[2], pv[3]}, ga[4] = {gv[0] * gsc, gv[1] * gsc, gv[2] * gsc, gv[3] * gsc};
       float ma[4] = {mv[0], mv[1], mv[2], mv[3]}, va[4] = {vv[0], vv[1], vv[2], vv[3]};
@@ -104,10 +126,16 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
       __builtin_nontemporal_store(f4_t{pa[0], pa[1], pa[2], pa[3]}, reinterpret_cast<f4_t*>(p + e));
       __builtin_nontemporal_store(f4_t{ma[0], ma[1], ma[2], ma[3]}, reinterpret_cast<f4_t*>(m + e));
       __builtin_nontemporal_store(f4_t{va[0], va[1], va[2], va[3]}, reinterpret_cast<f4_t*>(v + e));
+      if constexpr (EMA)
+        __builtin_nontemporal_store(f4_t{ema_update(ev[0], pa[0], ema_w), ema_update(ev[1], pa[1], ema_w), ema_update(ev[2], pa[2], ema_w),
+                                         ema_update(ev[3], pa[3], ema_w)}, reinterpret_cast<f4_t*>(ema + e));
 #else
       *reinterpret_cast<float4*>(p + e) = make_float4(pa[0], pa[1], pa[2], pa[3]);
       *reinterpret_cast<float4*>(m + e) = make_float4(ma[0], ma[1], ma[2], ma[3]);
       *reinterpret_cast<float4*>(v + e) = make_float4(va[0], va[1], va[2], va[3]);
+      if constexpr (EMA)
+        *reinterpret_cast<float4*>(ema + e) = make_float4(ema_update(ev[0], pa[0], ema_w), ema_update(ev[1], pa[1], ema_w),
+                                                          ema_update(ev[2], pa[2], ema_w), ema_update(ev[3], pa[3], ema_w));
 #endif
       if (pb) *reinterpret_cast<uint2*>(pb + e) = make_uint2(pack2bf(pa[0], pa[1]), pack2bf(pa[2], pa[3]));
       if (qslot >= 0) {
@@ -128,6 +156,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
         const float va = beta2 * v[q] + (1.0f - beta2) * ga * ga;
         pa -= step_size * ma / (sqrtf(va) * inv_sqrt_bc2 + eps);
         p[q] = pa; m[q] = ma; v[q] = va;
+        if constexpr (EMA) ema[q] = ema_update(ema[q], pa, ema_w);
         if (pb) pb[q] = f2bf(pa);
         if (zero_g) g[q] = 0.f;
       }
@@ -401,12 +430,15 @@ extern "C" int64_t crct_adamw_plan(const int64_t* seg_len, int n_seg, int32_t* b
   return nb;
 }
 
-extern "C" int crct_adamw_step(float* p, float* g, float* m, float* v, void* p_bf16, const int64_t* seg_off,
-                               const int64_t* seg_len, const float* seg_lr, const float* seg_wd, const int32_t* blk_seg,
-                               const int64_t* blk_off, int64_t n_blk, float beta1, float beta2, float eps, int step,
-                               const float* inv_scale_dev, const CrctAmpState* amp_state, const CrctFp8Shadow* fp8_shadow,
-                               int max_workgroups, int zero_grads, const void* g_bf16, crct_stream_t stream) {
+// the one host path of crct_adamw_step (ema == NULL: adamw_kernel<false>) and crct_adamw_step_ema
+static int adamw_step_host(float* p, float* g, float* m, float* v, void* p_bf16, const int64_t* seg_off,
+                           const int64_t* seg_len, const float* seg_lr, const float* seg_wd, const int32_t* blk_seg,
+                           const int64_t* blk_off, int64_t n_blk, float beta1, float beta2, float eps, int step,
+                           const float* inv_scale_dev, const CrctAmpState* amp_state, const CrctFp8Shadow* fp8_shadow,
+                           int max_workgroups, int zero_grads, const void* g_bf16, float* ema, float ema_weight, crct_stream_t stream) {
   CRCT_REQUIRE(step >= 1, "adamw: step must be >= 1 (got %d)", step);
+  CRCT_REQUIRE(ema_weight >= 0.f && ema_weight <= 1.f, "adamw: ema_weight must lie in [0, 1] (got %g)", (double)ema_weight);
+  CRCT_REQUIRE(((uintptr_t)ema & 15) == 0, "adamw: ema must be 16-byte aligned (got %p)", (void*)ema);
   CrctAmpState amp = {nullptr, nullptr, nullptr};
   if (amp_state) amp = *amp_state;
   CrctFp8Shadow f8 = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -428,11 +460,33 @@ extern "C" int crct_adamw_step(float* p, float* g, float* m, float* v, void* p_b
     return 0;
   }
 #endif
-  crct_launch(adamw_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
-                     seg_off, seg_len, seg_lr, seg_wd, blk_seg, blk_off, beta1, beta2, eps, (float)(1.0 / bc1),
-                     (float)(1.0 / sqrt(bc2)), inv_scale_dev, amp, f8, (int)n_blk, zero_grads, (const bf16_t*)g_bf16);
+#define CRCT_ADAMW_LAUNCH(EMA)                                                                                                  \
+  crct_launch(adamw_kernel<EMA>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,          \
+              seg_off, seg_len, seg_lr, seg_wd, blk_seg, blk_off, beta1, beta2, eps, (float)(1.0 / bc1),                        \
+              (float)(1.0 / sqrt(bc2)), inv_scale_dev, amp, f8, (int)n_blk, zero_grads, (const bf16_t*)g_bf16, ema, ema_weight)
+  if (ema) CRCT_ADAMW_LAUNCH(true); else CRCT_ADAMW_LAUNCH(false);
+#undef CRCT_ADAMW_LAUNCH
   CRCT_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+extern "C" int crct_adamw_step(float* p, float* g, float* m, float* v, void* p_bf16, const int64_t* seg_off,
+                               const int64_t* seg_len, const float* seg_lr, const float* seg_wd, const int32_t* blk_seg,
+                               const int64_t* blk_off, int64_t n_blk, float beta1, float beta2, float eps, int step,
+                               const float* inv_scale_dev, const CrctAmpState* amp_state, const CrctFp8Shadow* fp8_shadow,
+                               int max_workgroups, int zero_grads, const void* g_bf16, crct_stream_t stream) {
+  return adamw_step_host(p, g, m, v, p_bf16, seg_off, seg_len, seg_lr, seg_wd, blk_seg, blk_off, n_blk, beta1, beta2, eps, step,
+                         inv_scale_dev, amp_state, fp8_shadow, max_workgroups, zero_grads, g_bf16, nullptr, 0.f, stream);
+}
+
+extern "C" int crct_adamw_step_ema(float* p, float* g, float* m, float* v, void* p_bf16, const int64_t* seg_off,
+                                   const int64_t* seg_len, const float* seg_lr, const float* seg_wd, const int32_t* blk_seg,
+                                   const int64_t* blk_off, int64_t n_blk, float beta1, float beta2, float eps, int step,
+                                   const float* inv_scale_dev, const CrctAmpState* amp_state, const CrctFp8Shadow* fp8_shadow,
+                                   int max_workgroups, int zero_grads, const void* g_bf16, float* ema, float ema_weight,
+                                   crct_stream_t stream) {
+  return adamw_step_host(p, g, m, v, p_bf16, seg_off, seg_len, seg_lr, seg_wd, blk_seg, blk_off, n_blk, beta1, beta2, eps, step,
+                         inv_scale_dev, amp_state, fp8_shadow, max_workgroups, zero_grads, g_bf16, ema, ema_weight, stream);
 }
 
 extern "C" int crct_adamw_advance(int32_t* step_dev, const float* found_inf_dev, crct_stream_t stream) {

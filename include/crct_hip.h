@@ -642,6 +642,24 @@ int crct_adamw_step(float* p, float* g, float* m, float* v, void* p_bf16,
 /* g_bf16 (may be NULL): bf16 gradient buffer with the element offsets of g -- the data-parallel exchange's payload
  * (crct/ddp.py: each bucket is packed to bf16, all-reduced, and consumed here as it lies: 2 B instead of 4 B per parameter on
  * the wire and in this kernel's reads).  When set, every gradient element is read from it; g is only written (zero_grads). */
+/* crct_adamw_step with an exponential moving average of the weights kept in the same launch.  ema: flat fp32 device buffer with the
+ * element offsets of p, 16-byte aligned like p; ema_weight = 1 - decay, in [0, 1] (anything else, NaN included, is refused before
+ * any launch and crct_last_error() names ema_weight).  For every element the update writes, behind the store of the new weight p'
+ * (the fp32 value it stores to p):
+ *     d  = p' - e               one fp32 subtraction, rounded to nearest
+ *     e' = fmaf(ema_weight, d, e)   one fused multiply-add, rounded once
+ * -- two rounding points, no contraction left to the compiler, the same in the 16-byte path and in the scalar tail, in the plain
+ * chunk and in the tile walk of a weight with a transposed e4m3 shadow.  ema_weight = 0 leaves e bit-identical (finite p', e); a
+ * NaN / inf in p' or e arrives in e' of that element alone.  Elements the launch does not update (outside the chunk table, or every
+ * element when amp->found_inf != 0) keep their e.  4 B read + 4 B written per parameter on top of the update's 30; no LDS, no
+ * atomics.  Everything else -- p, g, m, v, the bf16 / e4m3 shadows, amax -- is to the bit what crct_adamw_step writes.
+ * ema == NULL is crct_adamw_step itself: the same kernel instantiation, the same bits (ema_weight is still checked). */
+int crct_adamw_step_ema(float* p, float* g, float* m, float* v, void* p_bf16,
+                        const int64_t* seg_off, const int64_t* seg_len, const float* seg_lr, const float* seg_wd,
+                        const int32_t* blk_seg, const int64_t* blk_off, int64_t n_blk,
+                        float beta1, float beta2, float eps, int step, const float* inv_scale_dev, const CrctAmpState* amp,
+                        const CrctFp8Shadow* fp8_shadow, int max_workgroups, int zero_grads, const void* g_bf16,
+                        float* ema, float ema_weight, crct_stream_t stream);
 
 /* Global-norm gradient clipping on the flat gradient buffer, over the chunk table (seg_off, seg_len, blk_seg, blk_off, n_blk) of
  * crct_adamw_plan and with the source rule of crct_adamw_step: g_bf16 != NULL -> EVERY element is read from it and g_f32 is never
