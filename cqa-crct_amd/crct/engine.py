@@ -221,6 +221,29 @@ class StepEngine(object):
         L.check(self.lib.crct_engine_set_score_grads(self.handle, C.byref(req)), "engine_set_score_grads")
         self._score_grads = (logits, value)      # the engine holds raw pointers
 
+    def set_attention_map_grads(self, requests=()):
+        """Upstream gradients of attention maps for the backward passes that follow (crct_engine_set_attention_map_grads): a list of
+        ``(kind, index, direction, tensor)`` -- kind / index / direction as ``attention_probs``, the tensor a contiguous fp32 device tensor
+        of that map's shape.  Each layer's backward adds grad_scale times the map's contribution onto its own dq / dk, two launches per
+        map behind its attention backward.  No argument = off.  The statistics scratch grows the workspace here and KEEPS its bytes
+        (the request usually arrives between the forward and the backward of a batch).  The backward plan does not depend on it."""
+        reqs = []
+        for kind, index, direction, t in requests:
+            kind = {"text": 0, "visual": 1, "conn": 2}.get(kind, kind)
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("set_attention_map_grads: (%r, %r, %r) must come with a contiguous fp32 tensor on the device" % (kind, index, direction))
+            reqs.append((int(kind), int(index), int(direction), t))
+        arr = (L.AttnMapGrad * max(len(reqs), 1))()
+        for r, (kind, index, direction, t) in zip(arr, reqs):
+            r.kind, r.index, r.direction, r.d_probs = kind, index, direction, L.ptr(t)
+        L.check(self.lib.crct_engine_set_attention_map_grads(self.handle, arr if reqs else None, len(reqs)), "engine_set_attention_map_grads")
+        self._map_grads = [t for _, _, _, t in reqs]      # the engine holds raw pointers
+        self.ws_bytes = self.lib.crct_engine_workspace_bytes(self.handle)
+        if self.workspace.numel() < self.ws_bytes:
+            grown = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+            grown[:self.workspace.numel()].copy_(self.workspace)
+            self.workspace = grown
+
     def set_site_policy(self, site, kind, cfg=-1, split_k=0, phase=-1):
         """Launch policy of one GEMM site (crct_engine_set_site_policy): ``site`` / ``kind`` by name (crct.lib.SITE_NAMES /
         KIND_NAMES) or number, ``phase`` 0 = text-only part of the schedule, 1 = beside the visual stream, -1 = both."""

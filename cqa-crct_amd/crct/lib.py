@@ -137,6 +137,10 @@ class ScoreGrads(C.Structure):      # CrctScoreGrads: fp32 device buffers holdin
     _fields_ = [("d_logits", vp), ("d_value", vp)]
 
 
+class AttnMapGrad(C.Structure):     # CrctAttnMapGrad: fp32 device buffer holding the upstream gradient of one attention map (24 bytes)
+    _fields_ = [("kind", c_i32), ("index", c_i32), ("direction", c_i32), ("pad", c_i32), ("d_probs", vp)]
+
+
 SEG_ENQUEUED_FN =C.CFUNCTYPE(None, C.c_int, vp)      # void (*seg_enqueued)(int seg, void* user)
 
 
@@ -199,6 +203,7 @@ PROTOTYPES = {
     "crct_cast_runs_bf16_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, c_i64, vp]),
     "crct_attention_fwd": (C.c_int, [vp] * 5 + [C.c_int] * 5 + [c_i64] * 4 + _u8 + [vp]),
     "crct_attention_probs": (C.c_int, [vp] * 4 + [C.c_int] * 5 + [c_i64] * 2 + _u8 + [vp]),
+    "crct_attention_probs_bwd": (C.c_int, [vp] * 4 + [c_f32, vp, vp, vp] + [C.c_int] * 6 + [c_i64] * 4 + _u8 + [vp]),
     "crct_attention_bwd": (C.c_int, [vp] * 8 + [C.c_int] * 5 + [c_i64] * 7 + _u8 + [vp]),
     "crct_attention_fwd_q": (C.c_int, [vp] * 5 + [C.c_int] * 5 + [c_i64] * 4 + _u8 + [vp, vp]),
     "crct_attention_bwd_q": (C.c_int, [vp] * 8 + [C.c_int] * 5 + [c_i64] * 7 + _u8 + [vp, vp]),
@@ -236,6 +241,7 @@ PROTOTYPES = {
     "crct_engine_sequence_outputs": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "crct_engine_set_output_grads": (C.c_int, [vp, C.POINTER(OutputGrads)]),
     "crct_engine_set_score_grads": (C.c_int, [vp, C.POINTER(ScoreGrads)]),
+    "crct_engine_set_attention_map_grads": (C.c_int, [vp, C.POINTER(AttnMapGrad), C.c_int]),
     "crct_engine_set_trainable": (C.c_int, [vp, vp, C.c_int]),
     "crct_engine_backward_plan": (C.c_int, [vp, vp, C.c_int]),
     "crct_engine_destroy": (None, [vp]),

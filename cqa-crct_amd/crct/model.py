@@ -52,7 +52,11 @@ class _StepFn(torch.autograd.Function):
     With ``model.differentiable_scores`` the node has, behind those, the answer logits [B, 2] and -- where the variant's regressor is the
     PlotQA one -- the regressed value [B] as differentiable outputs: copies of the snapshot's that own their memory.  Their upstream
     gradients (None when unused) go to the engine for the duration of the pass (``StepEngine.set_score_grads``) and enter the loss
-    kernel's own launch; unused, the pass is the plain one."""
+    kernel's own launch; unused, the pass is the plain one.
+
+    With ``model.attention_map_outputs`` the node has, behind those, one differentiable output per requested attention map (fp32, one
+    launch each).  The upstream gradients of the maps that have one go to the engine for the duration of the pass
+    (``StepEngine.set_attention_map_grads``); each layer adds its map's contribution behind its own attention backward."""
 
     @staticmethod
     def forward(ctx, anchor, model, tensors, step, image_feat=None, image_loc=None, loc=None, areas=None):
@@ -76,7 +80,10 @@ class _StepFn(torch.autograd.Function):
             out = out + (logits.clone(),)
             if model.variant[1] == "plotqa":
                 out = out + (reg_all[0].clone(),)
-        return out
+        ctx.n_scores = len(out) - 6 - ctx.n_seq
+        # the requested attention maps as differentiable outputs: fresh fp32 tensors, one launch each (StepEngine.attention_probs)
+        ctx.map_keys = model._attention_map_keys()
+        return out + tuple(model._engine.attention_probs(*key) for key in ctx.map_keys)
 
     @staticmethod
     def backward(ctx, g_loss, g_nsp, g_reg, _gl, _gr, _gs, *g_more):
@@ -84,15 +91,17 @@ class _StepFn(torch.autograd.Function):
         step = dict(ctx.step)
         B = ctx.tensors["tokens"].shape[0]
         g_seq_t, g_seq_v = (_upstream_f32(g) for g in g_more[:2]) if ctx.n_seq else (None, None)
-        g_scores = tuple(_upstream_f32(g) for g in g_more[ctx.n_seq:]) if ctx.scores else ()
+        g_scores = tuple(_upstream_f32(g) for g in g_more[ctx.n_seq:ctx.n_seq + ctx.n_scores]) if ctx.scores else ()
         g_logits = g_scores[0].reshape(B, 2) if g_scores and g_scores[0] is not None else None
         g_value = g_scores[1].reshape(B) if len(g_scores) > 1 and g_scores[1] is not None else None
+        # the maps with an upstream gradient: (kind, index, direction, fp32 tensor) as the engine takes them
+        g_maps = [key + (_upstream_f32(g),) for key, g in zip(ctx.map_keys, g_more[ctx.n_seq + ctx.n_scores:]) if g is not None]
         upstream_out, upstream_scores = g_seq_t is not None or g_seq_v is not None, g_logits is not None or g_value is not None
         if g_nsp is None and g_reg is None:
             if g_loss is None:
-                if not upstream_out and not upstream_scores:
+                if not upstream_out and not upstream_scores and not g_maps:
                     return (None,) * 8
-                g_loss = torch.zeros(1, device=model._flat_p.device)   # only the sequence outputs / scores are differentiated: the heads get zero loss seeds
+                g_loss = torch.zeros(1, device=model._flat_p.device)   # only the sequence outputs / scores / maps are differentiated: the heads get zero loss seeds
             step["g_loss"] = g_loss.reshape(1).float()                 # views / no-ops for the fp32 scalar autograd hands over
         else:                                                          # a caller combining nsp_loss / reg_loss itself
             dev = model._flat_p.device
@@ -101,20 +110,24 @@ class _StepFn(torch.autograd.Function):
             gr = g_reg.reshape(B).float() if g_reg is not None else torch.zeros(B, device=dev)
             step["g_nsp"] = (gn + gl * step["nsp_coeff"]).contiguous()
             step["g_reg"] = (gr + gl * (step["reg_coeff"] / B)).contiguous()
-        if not upstream_out and not upstream_scores:
+        if not upstream_out and not upstream_scores and not g_maps:
             grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
         else:
             # upstream gradients of the sequence outputs: segment 0 adds them onto the hidden gradients the heads seed; of the scores: the
-            # loss kernel adds them onto its per-row seeds (each request stands for this pass only, like the input-gradient request inside
-            # the call; the three compose)
+            # loss kernel adds them onto its per-row seeds; of the attention maps: each layer adds its map's contribution behind its own
+            # attention backward (each request stands for this pass only, like the input-gradient request inside the call; the four compose)
             eng = model._engine
             try:
                 if upstream_out:
                     eng.set_output_grads(seq_t=g_seq_t, seq_v=g_seq_v)
                 if upstream_scores:
                     eng.set_score_grads(logits=g_logits, value=g_value)
+                if g_maps:
+                    eng.set_attention_map_grads(g_maps)
                 grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
             finally:
+                if g_maps:
+                    eng.set_attention_map_grads()
                 if upstream_scores:
                     eng.set_score_grads()
                 if upstream_out:
@@ -228,6 +241,14 @@ class CrctModel(nn.Module):
         # every next_sentence_label -1 (the NSP term is then 0), in eval() or train() as the caller likes.  Two B-sized copies per forward;
         # the backward pass launches what it launched.
         self.differentiable_scores = False
+        # [("conn", 0, 0), ("text", 11), ...]: (kind, index[, direction]) as ``StepEngine.attention_probs``.  After every forward
+        # ``attention_maps`` holds these maps, keyed (kind, index, direction), as fp32 tensors of their own (one launch each); in the
+        # training branch under grad they carry a graph, as the reference's all_attention_mask does (vilbert.py:842-946): a loss on a map
+        # -- legend supervision on the co-attention, distillation, an entropy penalty -- trains the query / key projections and everything
+        # below them.  The backward pass adds two launches per map that has an upstream gradient.  Not with fp8 data gradients
+        # (params['fp8_backward']).  The return tuples are unchanged.
+        self.attention_map_outputs = ()
+        self.attention_maps = {}
         self.init_weights(int(params.get("seed", 0)))
         self.register_load_state_dict_post_hook(lambda m, k: m._invalidate_shadow())
 
@@ -661,6 +682,11 @@ class CrctModel(nn.Module):
                                "supported; set it to 0" % float(self.params["mask_prob_img"]))
         if image_target is None:
             raise ValueError("image_target is required by the image embeddings (vilbert.py:1479)")
+        map_keys = self._attention_map_keys()
+        if map_keys and self.fp8 and self.fp8_backward:
+            raise NotImplementedError("attention_map_outputs with params['fp8_backward']: the e5m2 copies of the fused dq | dk | dv gradients are "
+                                      "written by the attention backward itself, so a map's contribution would miss them; set "
+                                      "params['fp8_backward'] = False or leave attention_map_outputs empty")
         R, kind = gt_reg[0], gt_reg[1]
         train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
         tensors = self._device_inputs(input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
@@ -692,6 +718,7 @@ class CrctModel(nn.Module):
                     tensors["areas"] = live[3].detach()
             loss, nsp, reg_loss, logits, reg, stats, *more = _StepFn.apply(self._anchor, self, tensors, step, *live)
             seq, scores = (more[:2], more[2:]) if self.return_sequence_outputs else ((), more)
+            scores, maps = scores[:len(scores) - len(map_keys)], scores[len(scores) - len(map_keys):]
             value = scores[1] if len(scores) > 1 else None
             if scores:
                 logits = scores[0]                     # differentiable_scores: the copies that are part of the graph
@@ -701,8 +728,10 @@ class CrctModel(nn.Module):
             logits, reg, stats = eng.snapshot(B)
             loss, nsp, reg_loss = stats[0], stats[1:2], reg[1]
             seq = eng.sequence_outputs() if self.return_sequence_outputs else ()
+            maps = [eng.attention_probs(*key) for key in map_keys]
             if output_all_attention_masks and not train_branch:
                 attention_maps = self._attention_maps(eng)
+        self.attention_maps = dict(zip(map_keys, maps))
         # the combined training loss as the head kernel computed it (differentiable); the step adapter returns it instead
         # of re-deriving it from nsp_loss / reg_loss with five more torch kernels and their autograd nodes
         self.last_loss = loss if train_branch else None
@@ -723,6 +752,18 @@ class CrctModel(nn.Module):
         if train_branch:
             return lm_zero, img_zero, nsp, self.sequence_output_t, None, logits, reg_out, legend_loss        # vilbert.py:1659
         return None, None, logits, self.sequence_output_t, attention_maps, reg_out, legend_loss               # vilbert.py:1661
+
+    def _attention_map_keys(self):
+        """``attention_map_outputs`` as the keys of ``attention_maps``: (kind, index, direction), kind by name, direction 0 by default."""
+        names = {0: "text", 1: "visual", 2: "conn"}
+        keys = []
+        for item in self.attention_map_outputs or ():
+            kind, index, direction = (tuple(item) + (0,))[:3]
+            kind = names.get(kind, kind)
+            if kind not in ("text", "visual", "conn"):
+                raise ValueError("attention_map_outputs: kind must be 'text', 'visual' or 'conn'; got %r" % (kind,))
+            keys.append((kind, int(index), int(direction)))
+        return tuple(keys)
 
     def _attention_maps(self, eng):
         """``output_all_attention_masks=True`` (vilbert.py:842-946, :1562): (text maps, visual maps, co-attention maps) of the forward

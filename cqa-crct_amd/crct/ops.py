@@ -357,6 +357,39 @@ def attention_probs(q, k, keymask, heads, d, p_drop=0.0, site=0, seed=0, out=Non
     return out
 
 
+def attention_probs_bwd(q, k, keymask, d_probs, heads, d, outs, accumulate=True, scale=1.0, p_drop=0.0, site=0, seed=0):
+    """Backward of the map ``attention_probs`` returns for the same q / k / keymask / (p_drop, site, seed) (crct_attention_probs_bwd):
+    with the upstream gradient ``d_probs`` (contiguous fp32 [B, heads, Tq, Tk]) times ``scale`` it adds the map's contribution onto
+    ``outs = (dq, dk)`` -- bf16 [B, Tq, lddq] / [B, Tk, lddk] with the column layout of q / k, column slices of wider buffers included --
+    or, ``accumulate=False``, writes the contribution alone.  Two launches, bit-reproducible; returns ``outs``."""
+    lib = L.load()
+    _chk(q, torch.bfloat16), _chk(k, torch.bfloat16)
+    if q.dim() != 3 or k.dim() != 3 or q.shape[0] != k.shape[0] or q.shape[2] != heads * d or k.shape[2] != heads * d:
+        raise RuntimeError("attention_probs_bwd: q [B, Tq, heads * d] and k [B, Tk, heads * d] expected with heads * d = %d; got %s and %s"
+                           % (heads * d, tuple(q.shape), tuple(k.shape)))
+    B, Tq, Tk = q.shape[0], q.shape[1], k.shape[1]
+    dq, dk = outs
+    _chk(dq, torch.bfloat16), _chk(dk, torch.bfloat16)
+    if tuple(dq.shape) != tuple(q.shape) or tuple(dk.shape) != tuple(k.shape):
+        raise RuntimeError("attention_probs_bwd: outs = (dq, dk) must have the shapes of q and k; got %s and %s" % (tuple(dq.shape), tuple(dk.shape)))
+    for t, T, what in ((q, Tq, "q"), (k, Tk, "k"), (dq, Tq, "dq"), (dk, Tk, "dk")):
+        if t.stride(2) != 1 or (B > 1 and t.stride(0) != T * t.stride(1)):
+            raise RuntimeError("attention_probs_bwd: %s needs unit column stride and batch stride T * stride(1); got strides %s" % (what, tuple(t.stride())))
+    _chk(keymask, torch.uint8)
+    if tuple(keymask.shape) != (B, Tk) or not keymask.is_contiguous():
+        raise RuntimeError("attention_probs_bwd: keymask must be a contiguous uint8 [%d, %d]; got %s" % (B, Tk, tuple(keymask.shape)))
+    _chk(d_probs, torch.float32)
+    if tuple(d_probs.shape) != (B, heads, Tq, Tk) or not d_probs.is_contiguous():
+        raise RuntimeError("attention_probs_bwd: d_probs must be a contiguous fp32 [%d, %d, %d, %d]; got shape %s strides %s"
+                           % (B, heads, Tq, Tk, tuple(d_probs.shape), tuple(d_probs.stride())))
+    scratch = torch.empty(max(B * heads * Tq * 3, 1), device=q.device, dtype=torch.float32)      # row statistics: m, 1 / l, delta
+    thr, sc, st = _drop(p_drop, site)
+    L.check(lib.crct_attention_probs_bwd(L.ptr(q), L.ptr(k), L.ptr(keymask), L.ptr(d_probs), float(scale), L.ptr(dq), L.ptr(dk), L.ptr(scratch),
+                                         int(bool(accumulate)), B, heads, Tq, Tk, d, q.stride(1), k.stride(1), dq.stride(1), dk.stride(1),
+                                         thr, sc, st, seed, L.current_stream()), "attention_probs_bwd")
+    return outs
+
+
 def attention_fwd_q(q, k, v, keymask, heads, d, q_scale, q_amax, p_drop=0.0, site=0, seed=0, out=None):
     """attention_fwd that also returns the e4m3 copy of ctx (uint8, same shape and strides), quantised with the device scalar q_scale."""
     lib = L.load()

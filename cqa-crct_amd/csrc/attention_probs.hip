@@ -42,15 +42,6 @@ struct ProbArgs {
   int vec;          // rows are 16-byte aligned: float4 stores
 };
 
-// fragment X[r0 + (lane & 15)][c0 + 4 (lane >> 4) + e] from global memory; rows >= T and columns >= d read as zero (never touched)
-__device__ __forceinline__ s4_t frag_rows_global_tail(const bf16_t* src, long ld, int T, int d, int r0, int c0, int lane) {
-  const int r = r0 + (lane & 15), c = c0 + 4 * (lane >> 4);
-  const bool ok = r < T && c < d;
-  const uint2 u = *reinterpret_cast<const uint2*>(src + (long)min(r, T - 1) * ld + (c < d ? c : 0));
-  const uint32_t m = ok ? 0xffffffffu : 0u;
-  return __builtin_bit_cast(s4_t, make_uint2(u.x & m, u.y & m));
-}
-
 template <int ND>
 __global__ __launch_bounds__(64 * NW) void attn_probs_kernel(const bf16_t* q, const bf16_t* k, const uint8_t* keymask, int B, int heads, int Tq,
                                                              int Tk, int ldq, int ldk, const ProbArgs a) {

@@ -88,6 +88,15 @@ __device__ __forceinline__ s4_t frag_rows_global(const bf16_t* src, long ld, int
   return __builtin_bit_cast(s4_t, make_uint2(u.x & m, u.y & m));
 }
 
+// fragment X[r0 + (lane & 15)][c0 + 4 (lane >> 4) + e] from global memory, for head sizes that are no multiple of 16; rows >= T and columns >= d read as zero (never touched)
+__device__ __forceinline__ s4_t frag_rows_global_tail(const bf16_t* src, long ld, int T, int d, int r0, int c0, int lane) {
+  const int r = r0 + (lane & 15), c = c0 + 4 * (lane >> 4);
+  const bool ok = r < T && c < d;
+  const uint2 u = *reinterpret_cast<const uint2*>(src + (long)min(r, T - 1) * ld + (c < d ? c : 0));
+  const uint32_t m = ok ? 0xffffffffu : 0u;
+  return __builtin_bit_cast(s4_t, make_uint2(u.x & m, u.y & m));
+}
+
 // Kernel-argument preload (gemm.hip, GEMM_HOT_PARAMS): what the first instructions need (operand pointers, sizes, leading dimensions) as 15
 // leading scalar arguments -- gfx950 hands the first argument dwords to the wave in SGPRs; a struct passed by value is fetched by scalar loads.
 #define ATTN_HOT_PARAMS const bf16_t* hq, const bf16_t* hk, const bf16_t* hv, const uint8_t* hkm, int hB, int hheads, int hTq, int hTk, int hldq, int hldk, int hldv, const AttnArgs a_in

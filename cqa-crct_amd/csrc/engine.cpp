@@ -179,10 +179,16 @@ struct crct_engine {
   // crct_engine_set_score_grads: fp32 upstream gradients of the logits and of the regressed value, handed to the loss kernel of the
   // following backward passes (both NULL: off)
   CrctScoreGrads sg = {nullptr, nullptr};
+  // crct_engine_set_attention_map_grads: the maps whose fp32 upstream gradients the following backward passes add behind each layer's own
+  // attention backward (empty: off), and the row-statistics scratch of crct_attention_probs_bwd, one of ws_amg bytes per data stream
+  // (text, visual: the two run side by side), behind the input-gradient space and counted only while a request stands
+  std::vector<CrctAttnMapGrad> amg;
+  size_t ws_amg = 0;
+  size_t amg_scratch(int which) const { return ws_base() + ws_ig + (size_t)which * ws_amg; }
   bool ig_text() const { return ig.d_txt_loc || ig.d_text_emb; }
   bool ig_vis() const { return ig.d_image_feat || ig.d_image_loc || ig.d_areas; }
   size_t ws_base() const { return ln_addend ? ws_core : ws_two_output; }
-  void ws_update() { ws_bytes = ws_base() + (ig.d_image_feat ? ws_ig : 0); }
+  void ws_update() { ws_bytes = amg.empty() ? ws_base() + (ig.d_image_feat ? ws_ig : 0) : amg_scratch(2); }
   struct { size_t sum, y, mean, rstd, yq; int site; } eta;
   struct { size_t soft, lin, sum, y, mean, rstd, yq; int site; } eva;
   LinearP t_pool, v_pool, cls, tp[4], vp[4], fu[4];
@@ -711,6 +717,19 @@ struct Run {
     fail(crct_attention_bwd_q(q, k, v, km, dctx, dq, dk, dv, B, heads, Tq, Tk, d, ldq, ldk, ldk, ldo, lddq, lddk, lddk, dr.thr, dr.scale,
                               dr.site, seed, &qz, s));
   }
+  // The requested maps of one attention (crct_engine_set_attention_map_grads), right behind its attn_bwd on this stream: each adds its
+  // contribution onto the dq / dk columns that launch wrote (same q, k, key mask and dropout stream; c = the step's gradient scale).
+  // No request: nothing is launched and `tick` stays as it is
+  void attn_map_grads(int kind, int index, int direction, const bf16_t* q, const bf16_t* k, int64_t ld, const uint8_t* km, bf16_t* dq, bf16_t* dk,
+                      int64_t ldd, int B, int heads, int Tq, int Tk, int d, const Drop& dr) {
+    for (const CrctAttnMapGrad& r : e->amg) {
+      if (rc) return;
+      if (r.kind != kind || r.index != index || r.direction != direction) continue;
+      ++tick;
+      fail(crct_attention_probs_bwd(q, k, km, r.d_probs, c->grad_scale, dq, dk, F(e->amg_scratch(which)), 1, B, heads, Tq, Tk, d, ld, ld, ldd, ldd,
+                                    dr.thr, dr.scale, dr.site, c->seed, s));
+    }
+  }
   // the attention kernels that write fp8 copies cover this shape (MFMA kernels: include/crct_hip.h, CrctAttnQuant)
   static bool attn_q_ok(int Tq, int Tk, int d) { return crct_attention_quant_ok(Tq, Tk, d) != 0; }
   // The attention context as both passes see it: its e4m3 copy exists where the attention kernel covers the shape (aq) and the
@@ -784,6 +803,10 @@ struct Run {
     attn_bwd(A(a.qkv), 3 * H, A(a.qkv) + H, A(a.qkv) + 2 * H, 3 * H, km, A(sc.dctx), H, A(sc.dqkv), 3 * H, A(sc.dqkv) + H,
              A(sc.dqkv) + 2 * H, 3 * H, B, p.heads, T, T, d, drop(p.p_attn, p.site), dq8, a.g_dqkv, gq ? dq8 + H : nullptr,
              gq ? dq8 + 2 * H : nullptr, a.g_dqkv, a.lse, A(a.ctx), H);
+    // (text layers run on the text stream's Run, visual layers on the visual one: `which` is the map's kind)
+    if (!e->amg.empty())
+      attn_map_grads(which, (int)(&p - (which ? e->vl : e->tl).data()), 0, A(a.qkv), A(a.qkv) + H, 3 * H, km, A(sc.dqkv), A(sc.dqkv) + H, 3 * H, B,
+                     p.heads, T, T, d, drop(p.p_attn, p.site));
     lin_wgrad(A(sc.dqkv), 3 * H, A(x.x), H, p.qkv, M, true, WgQ8{dqkvq, x});
     Opt o; o.addend = A(sc.dres_b); o.ld_add = H;
     if (dx) lin_dgrad(A(sc.dqkv), 3 * H, p.qkv, M, A(gx), H, o, dqkvq);
@@ -848,6 +871,14 @@ struct Run {
     V.attn_bwd(A(a.qkv1), 3 * Hb, A(a.qkv2) + Hb, A(a.qkv2) + 2 * Hb, 3 * Hb, b->text_keymask, A(sv.dctx), Hb, A(sv.dqkv),
                3 * Hb, A(st.dqkv) + Hb, A(st.dqkv) + 2 * Hb, 3 * Hb, B, D.b_heads, b->V, b->T, d, drop(D.p_attn, p.site + 1),
                vq8, a.g_dqkv1, gq ? tq8 + Hb : nullptr, gq ? tq8 + 2 * Hb : nullptr, a.g_dqkv2, a.lse2, A(a.ctx2), Hb);
+    // the requested maps of the two attentions, each behind its own backward on that stream and onto the very columns it wrote
+    if (!e->amg.empty()) {
+      const int ci = (int)(&p - e->cl.data());
+      attn_map_grads(2, ci, 0, A(a.qkv2), A(a.qkv1) + Hb, 3 * Hb, b->image_keymask, A(st.dqkv), A(sv.dqkv) + Hb, 3 * Hb, B, D.b_heads, b->T, b->V, d,
+                     drop(D.p_v_attn, p.site));
+      V.attn_map_grads(2, ci, 1, A(a.qkv1), A(a.qkv2) + Hb, 3 * Hb, b->text_keymask, A(sv.dqkv), A(st.dqkv) + Hb, 3 * Hb, B, D.b_heads, b->V, b->T, d,
+                       drop(D.p_attn, p.site + 1));
+    }
     // each stream's dqkv buffer has been written by BOTH attention backward kernels
     cross_sync(V);
     V.lin_wgrad(A(sv.dqkv), 3 * Hb, A(x.v.x), D.Hv, p.qkv1, Mv, true, WgQ8{dqkvq_v, x.v});
@@ -1388,6 +1419,7 @@ extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, 
   }
   e->ws_two_output = ar.top;
   e->ws_ig = e->feat ? align_up(Mv * D.Fv * 4, 256) : 0;
+  e->ws_amg = align_up((size_t)max_B * std::max(D.heads, std::max(D.v_heads, D.b_heads)) * std::max(max_T, max_V) * 3 * 4, 256);
   e->ws_update();
 
   // ---- the hidden states every schedule step starts from (the last entry: the encoder's outputs), and the taps on them
@@ -1469,6 +1501,30 @@ extern "C" int crct_engine_set_score_grads(crct_engine_t* e, const CrctScoreGrad
   CRCT_REQUIRE(!r.d_value || e->var.regressor == CRCT_REGRESSOR_PLOTQA, "engine_set_score_grads: d_value: only the PlotQA regressor's value has a gradient (this engine's regressor is %s)",
                e->var.regressor == CRCT_REGRESSOR_CE ? "the CE table lookup" : "absent");
   e->sg = r;                        // read by heads_bwd alone: the plan does not depend on it
+  return 0;
+}
+
+extern "C" int crct_engine_set_attention_map_grads(crct_engine_t* e, const CrctAttnMapGrad* req, int n) {
+  CRCT_REQUIRE(e, "engine_set_attention_map_grads: null engine");
+  CRCT_REQUIRE(n >= 0 && (req || n == 0), "engine_set_attention_map_grads: %d requests without an array", n);
+  for (int i = 0; req && i < n; ++i) {
+    const CrctAttnMapGrad& r = req[i];
+    if (r.kind == 0 || r.kind == 1) {
+      const int layers = (int)(r.kind == 0 ? e->tl : e->vl).size();
+      CRCT_REQUIRE(r.index >= 0 && r.index < layers, "engine_set_attention_map_grads: %s layer %d out of range [0,%d)", r.kind == 0 ? "text" : "visual",
+                   r.index, layers);
+      CRCT_REQUIRE(r.direction == 0, "engine_set_attention_map_grads: direction %d belongs to connection layers (kind 2)", r.direction);
+    } else {
+      CRCT_REQUIRE(r.kind == 2, "engine_set_attention_map_grads: unknown kind %d (0 text, 1 visual, 2 connection layer)", r.kind);
+      const int layers = e->d.with_coattention ? (int)e->cl.size() : 0;
+      CRCT_REQUIRE(r.index >= 0 && r.index < layers, "engine_set_attention_map_grads: connection layer %d out of range [0,%d)", r.index, layers);
+      CRCT_REQUIRE(r.direction == 0 || r.direction == 1, "engine_set_attention_map_grads: direction %d must be 0 (text over visual) or 1 (visual over text)",
+                   r.direction);
+    }
+    CRCT_REQUIRE(r.d_probs && (uintptr_t)r.d_probs % 4 == 0, "engine_set_attention_map_grads: request %d: d_probs must be a 4-byte aligned device buffer", i);
+  }
+  e->amg.assign(req, req + (req ? n : 0));      // read by self_bwd / conn_bwd alone: the plan does not depend on it
+  e->ws_update();
   return 0;
 }
 
@@ -1663,6 +1719,8 @@ extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, c
   CRCT_REQUIRE(batch && batch->labels, "engine_backward: labels are required (training step)");
   if (int r = check_batch(e, batch)) return r;
   CRCT_REQUIRE(!e->ig.d_areas || e->areas, "engine_backward: d_areas is requested (crct_engine_set_input_grads) but the batch has no areas (crct_engine_set_areas)");
+  CRCT_REQUIRE(e->amg.empty() || !cfg->fp8_bwd, "engine_backward: attention-map gradients are requested (crct_engine_set_attention_map_grads) with fp8_bwd=%d: "
+               "the e5m2 copies of dqkv are written by the attention backward itself and would go stale", cfg->fp8_bwd);
   if (int r = ensure_streams(e, (hipStream_t)stream)) return r;
   e->evnext = 0;
   CrctDeviceScope on_device;                              // every launch below runs on this thread and the device stays

@@ -389,6 +389,21 @@ int crct_attention_probs(const void* q, const void* k, const uint8_t* keymask, f
                          uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
                          crct_stream_t stream);
 
+/* Backward of such a map (csrc/attention_probs_bwd.hip): with the upstream gradient d_probs (fp32 [B][heads][Tq][Tk], contiguous) of the
+ * map M = keep / (1 - p) o P that crct_attention_probs returns for the same operands, and a scalar c,
+ *   dP = c d_probs o keep / (1 - p) ;  delta_i = sum_j P_ij dP_ij ;  dS = P o (dP - delta)
+ *   dq[b][i][h d + x] = bf16(float(dq) + 1/sqrt(d) sum_j dS_ij k_jx)      dk[b][j][h d + x] = bf16(float(dk) + 1/sqrt(d) sum_i dS_ij q_ix)
+ * added onto the bf16 dq / dk (accumulate != 0; accumulate = 0 writes bf16 of the sum alone), which are column slices of fused buffers like
+ * q / k (lddq, lddk multiples of 4, dq / dk 8-byte aligned).  P is recomputed (MFMA, dS rounded to bf16 in front of the two products);
+ * scratch: B * heads * Tq * 3 floats (row statistics m, 1 / l, delta, handed from the query-owning launch to the key-owning one).  Every
+ * output element is summed by one wave in a fixed order: bit-reproducible.  Operand and shape domain, dropout arguments and refusals as
+ * crct_attention_probs. */
+int crct_attention_probs_bwd(const void* q, const void* k, const uint8_t* keymask, const float* d_probs, float c,
+                             void* dq, void* dk, float* scratch, int accumulate,
+                             int B, int heads, int Tq, int Tk, int d, int64_t ldq, int64_t ldk, int64_t lddq, int64_t lddk,
+                             uint32_t drop_thr, float drop_scale, uint32_t drop_site, uint64_t seed,
+                             crct_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Text embeddings: BertEmbeddingLocation.forward, vilbert.py:320-358.
  *  sum = word[ids] + pos[posid]*(qa) + type[seg']*(seg != 0) + (W_loc loc + b_loc)*(|loc|_1 != 0)
@@ -794,6 +809,21 @@ int crct_engine_set_output_grads(crct_engine_t*, const CrctOutputGrads* req);
  * NULL, or both members NULL, switches it off: not one launch, workspace byte, event or result bit differs from an engine that never saw
  * this call. */
 int crct_engine_set_score_grads(crct_engine_t*, const CrctScoreGrads* req);
+/* The attention maps as outputs of the step: upstream gradients of the maps crct_engine_attention_probs returns (kind / index / direction
+ * as there; d_probs fp32 device, contiguous, the map's shape for the batch of the pass) for the crct_engine_backward calls that follow.
+ * While a request stands, each requested map's crct_attention_probs_bwd (c = CrctStepCfg.grad_scale, accumulate) is launched right behind
+ * that layer's own attention backward launch, on the same stream, and adds onto the columns of the dqkv scratch that launch wrote -- self
+ * layers: dq -> dqkv[:, 0:H], dk -> dqkv[:, H:2H]; connection layers: direction 0 (text stream) dq -> the text buffer's [:, 0:Hb], dk -> the
+ * visual buffer's [:, Hb:2Hb], direction 1 (visual stream) the other way round -- in front of the stream ordering that precedes the QKV
+ * gradients.  It is launched exactly where, and only if, that attention backward is launched: a request never changes the plan
+ * (crct_engine_backward_plan), and a layer whose segment does not run contributes nothing.  While a request stands
+ * crct_engine_workspace_bytes grows by the statistics scratch of the two data streams (behind everything else, the input-gradient space
+ * included; the bytes below keep their meaning).  Maps out of range are refused here (wording of crct_engine_attention_probs); a
+ * crct_engine_backward with CrctStepCfg.fp8_bwd != 0 while a request stands is refused before any launch: the e5m2 copies of dqkv are
+ * written by the attention backward itself and would go stale.  NULL or n = 0 switches it off: not one launch, workspace byte, event or
+ * result bit differs from an engine that never saw this call.  The request array is copied; the buffers must outlive the passes. */
+typedef struct { int32_t kind, index, direction, pad; const float* d_probs; } CrctAttnMapGrad;
+int crct_engine_set_attention_map_grads(crct_engine_t*, const CrctAttnMapGrad* req, int n);
 /* Which parameters have a gradient in the backward passes that follow: one flag per parameter, in the order given to
  * crct_engine_create* (n = n_params); 0 = the tensor is WITHOUT gradient.  NULL, or all flags set, is the behaviour without this
  * call: not one launch or event differs.  Backward then runs less of itself (crct_engine_backward_plan); the forward is untouched.
