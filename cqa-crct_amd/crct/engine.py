@@ -4,6 +4,7 @@ One ``forward`` call = embeddings + 24 encoder steps + heads + loss on the curre
 ``backward`` = the gradients of all 524 used tensors accumulated into the flat fp32 gradient buffer,
 optionally segment by segment so the caller can launch gradient all-reduces in between.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -153,14 +154,28 @@ class StepEngine(object):
             c.seg_enqueued = C.cast(fn, C.c_void_p)
         return c
 
+    # -- per-pass requests: four families of buffers, each standing in the engine until replaced; `requests` pairs set and clear
+    def _f32(self, who, name, t, align=0):
+        """The pointer of an optional contiguous fp32 device tensor, optionally `align`-byte aligned, as the C ABI takes it."""
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or (align and t.data_ptr() % align)):
+            raise ValueError("%s: %s must be a contiguous%s fp32 tensor on the device" % (who, name, ", %d-byte aligned" % align if align else ""))
+        return L.ptr(t)
+
+    def _fit_workspace(self, keep):
+        """Grow ``workspace`` to the size the library reports now, with its bytes where ``keep``; it never shrinks."""
+        self.ws_bytes = self.lib.crct_engine_workspace_bytes(self.handle)
+        if self.workspace.numel() < self.ws_bytes:
+            grown = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+            if keep:
+                grown[:self.workspace.numel()].copy_(self.workspace)
+            self.workspace = grown
+
     def set_ln_addend(self, on):
         """How the block-closing GEMMs of the fp32 residual stream get their fp32 addend (crct_engine_set_ln_addend): True (default)
         = rebuilt in the epilogue from the producing LayerNorm's inputs, False = from an fp32 copy the LayerNorm writes.  The copies'
         buffers are part of the workspace only on the second route: it grows here when needed.  Same bits either way."""
         L.check(self.lib.crct_engine_set_ln_addend(self.handle, int(bool(on))), "set_ln_addend")
-        self.ws_bytes = self.lib.crct_engine_workspace_bytes(self.handle)
-        if self.workspace.numel() < self.ws_bytes:
-            self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        self._fit_workspace(keep=False)
 
     def set_input_grads(self, image_feat=None, image_loc=None, areas=None, txt_loc=None, text_emb=None):
         """Where the backward passes that follow leave the gradients of the step's float inputs (crct_engine_set_input_grads): contiguous
@@ -168,18 +183,11 @@ class StepEngine(object):
         text embeddings in front of their LayerNorm) -- each written, not accumulated; None = not wanted, no argument = off.  A feature
         gradient needs B * V * Fv fp32 more workspace: it grows here and KEEPS its bytes, since the request usually arrives between
         the forward and the backward of a batch."""
-        req = L.InputGrads()
-        for name, t in (("d_image_feat", image_feat), ("d_image_loc", image_loc), ("d_areas", areas), ("d_txt_loc", txt_loc), ("d_text_emb", text_emb)):
-            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise ValueError("set_input_grads: %s must be a contiguous fp32 tensor on the device" % name)
-            setattr(req, name, L.ptr(t))
+        named = (("d_image_feat", image_feat), ("d_image_loc", image_loc), ("d_areas", areas), ("d_txt_loc", txt_loc), ("d_text_emb", text_emb))
+        req = L.InputGrads(**{name: self._f32("set_input_grads", name, t) for name, t in named})
         L.check(self.lib.crct_engine_set_input_grads(self.handle, C.byref(req)), "engine_set_input_grads")
         self._input_grads = (image_feat, image_loc, areas, txt_loc, text_emb)      # the engine holds raw pointers
-        self.ws_bytes = self.lib.crct_engine_workspace_bytes(self.handle)
-        if self.workspace.numel() < self.ws_bytes:
-            grown = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
-            grown[:self.workspace.numel()].copy_(self.workspace)
-            self.workspace = grown
+        self._fit_workspace(keep=True)
 
     def sequence_outputs(self, text=True, visual=True):
         """The final hidden states of the LAST forward of this engine (crct_engine_sequence_outputs): (sequence_output_t fp32 [B, T, H],
@@ -200,11 +208,7 @@ class StepEngine(object):
         """Upstream gradients of the final hidden states for the backward passes that follow (crct_engine_set_output_grads): contiguous
         fp32 device tensors [B, T, H] / [B, V, Hv], 16-byte aligned; segment 0 adds grad_scale times each onto that stream's running
         hidden gradient.  None = none, no argument = off.  The backward plan does not depend on it."""
-        req = L.OutputGrads()
-        for name, t in (("d_seq_t", seq_t), ("d_seq_v", seq_v)):
-            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16):
-                raise ValueError("set_output_grads: %s must be a contiguous, 16-byte aligned fp32 tensor on the device" % name)
-            setattr(req, name, L.ptr(t))
+        req = L.OutputGrads(d_seq_t=self._f32("set_output_grads", "d_seq_t", seq_t, 16), d_seq_v=self._f32("set_output_grads", "d_seq_v", seq_v, 16))
         L.check(self.lib.crct_engine_set_output_grads(self.handle, C.byref(req)), "engine_set_output_grads")
         self._output_grads = (seq_t, seq_v)      # the engine holds raw pointers
 
@@ -213,11 +217,7 @@ class StepEngine(object):
         (crct_engine_set_score_grads): contiguous fp32 device tensors; the loss kernel of segment 0 adds grad_scale times each onto its
         per-row seeds, inside its one launch.  None = none, no argument = off.  ``value`` needs the PlotQA regressor: any other variant
         refuses it.  The backward plan does not depend on it."""
-        req = L.ScoreGrads()
-        for name, t in (("d_logits", logits), ("d_value", value)):
-            if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise ValueError("set_score_grads: %s must be a contiguous fp32 tensor on the device" % name)
-            setattr(req, name, L.ptr(t))
+        req = L.ScoreGrads(d_logits=self._f32("set_score_grads", "d_logits", logits), d_value=self._f32("set_score_grads", "d_value", value))
         L.check(self.lib.crct_engine_set_score_grads(self.handle, C.byref(req)), "engine_set_score_grads")
         self._score_grads = (logits, value)      # the engine holds raw pointers
 
@@ -227,22 +227,47 @@ class StepEngine(object):
         of that map's shape.  Each layer's backward adds grad_scale times the map's contribution onto its own dq / dk, two launches per
         map behind its attention backward.  No argument = off.  The statistics scratch grows the workspace here and KEEPS its bytes
         (the request usually arrives between the forward and the backward of a batch).  The backward plan does not depend on it."""
-        reqs = []
-        for kind, index, direction, t in requests:
-            kind = {"text": 0, "visual": 1, "conn": 2}.get(kind, kind)
-            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("set_attention_map_grads: (%r, %r, %r) must come with a contiguous fp32 tensor on the device" % (kind, index, direction))
-            reqs.append((int(kind), int(index), int(direction), t))
+        reqs = [self.map_key(r[:3]) + (r[3],) for r in requests]
         arr = (L.AttnMapGrad * max(len(reqs), 1))()
         for r, (kind, index, direction, t) in zip(arr, reqs):
-            r.kind, r.index, r.direction, r.d_probs = kind, index, direction, L.ptr(t)
+            r.kind, r.index, r.direction, r.d_probs = kind, index, direction, self._f32("set_attention_map_grads", (kind, index, direction), t)
         L.check(self.lib.crct_engine_set_attention_map_grads(self.handle, arr if reqs else None, len(reqs)), "engine_set_attention_map_grads")
         self._map_grads = [t for _, _, _, t in reqs]      # the engine holds raw pointers
-        self.ws_bytes = self.lib.crct_engine_workspace_bytes(self.handle)
-        if self.workspace.numel() < self.ws_bytes:
-            grown = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
-            grown[:self.workspace.numel()].copy_(self.workspace)
-            self.workspace = grown
+        self._fit_workspace(keep=True)
+
+    @contextlib.contextmanager
+    def requests(self, input_grads=None, output_grads=None, score_grads=None, attention_map_grads=None):
+        """The requests of ONE backward pass: sets the families it is given -- a dict of that setter's keyword arguments, for
+        ``attention_map_grads`` its list -- and on the way out clears exactly those, in reverse order, also when the body raises.  A family
+        left None is not touched: a request standing from before stays.  The plan and the workspace size the library reports follow the
+        requests both ways; the workspace tensor keeps what it grew to."""
+        given = ((self.set_input_grads, input_grads), (self.set_output_grads, output_grads), (self.set_score_grads, score_grads),
+                 (self.set_attention_map_grads, attention_map_grads))
+        done = []
+        try:
+            for setter, arg in given:
+                if arg is not None:
+                    setter(**arg) if isinstance(arg, dict) else setter(arg)
+                    done.append(setter)
+            yield self
+        finally:
+            for setter in reversed(done):
+                setter()
+
+    MAP_KINDS = ("text", "visual", "conn")      # an attention's kind by number (AttnSite.kind in csrc/engine.cpp)
+
+    @classmethod
+    def map_key(cls, item):
+        """``(kind, index[, direction])``, kind by name or number, as three ints (what names no kind passes through: the library refuses it)."""
+        kind, index, direction = (tuple(item) + (0,))[:3]
+        kind = cls.MAP_KINDS.index(kind) if kind in cls.MAP_KINDS else kind
+        return kind if isinstance(kind, str) else int(kind), int(index), int(direction)
+
+    def map_shape(self, kind, direction, B, T, V):
+        """Shape of the attention map of a kind (by number) and direction at batch sizes B, T, V; None for what names no kind."""
+        cfg = self.cfg
+        return {0: (B, cfg.num_attention_heads, T, T), 1: (B, cfg.v_num_attention_heads, V, V),
+                2: (B, cfg.bi_num_attention_heads, V, T) if direction else (B, cfg.bi_num_attention_heads, T, V)}.get(kind)
 
     def set_site_policy(self, site, kind, cfg=-1, split_k=0, phase=-1):
         """Launch policy of one GEMM site (crct_engine_set_site_policy): ``site`` / ``kind`` by name (crct.lib.SITE_NAMES /
@@ -347,18 +372,14 @@ class StepEngine(object):
         if self._keep is None:
             raise RuntimeError("attention_probs: run a forward pass on this engine first")
         tensors, step = self._keep
-        kind = {"text": 0, "visual": 1, "conn": 2}.get(kind, kind)
-        B, T = tensors["tokens"].shape
-        V = tensors["image_feat"].shape[1]
-        cfg = self.cfg
-        shape = {0: (B, cfg.num_attention_heads, T, T), 1: (B, cfg.v_num_attention_heads, V, V),
-                 2: (B, cfg.bi_num_attention_heads, V, T) if direction else (B, cfg.bi_num_attention_heads, T, V)}.get(kind)
+        kind, index, direction = self.map_key((kind, index, direction))
+        shape = self.map_shape(kind, direction, tensors["tokens"].shape[0], tensors["tokens"].shape[1], tensors["image_feat"].shape[1])
         if shape is None:
             raise ValueError("attention_probs: kind must be 0 / 'text', 1 / 'visual' or 2 / 'conn'; got %r" % (kind,))
         out = torch.empty(shape, dtype=torch.float32, device=self.device)
         b, c = self._batch(tensors), self._cfg(dict(step, seg_events=None))
-        n = self.lib.crct_engine_attention_probs(self.handle, C.byref(b), C.byref(c), self.workspace.data_ptr(), int(kind), int(index),
-                                                 int(direction), out.data_ptr(), out.numel(), L.current_stream())
+        n = self.lib.crct_engine_attention_probs(self.handle, C.byref(b), C.byref(c), self.workspace.data_ptr(), kind, index,
+                                                 direction, out.data_ptr(), out.numel(), L.current_stream())
         if n != out.numel():
             raise RuntimeError("attention_probs(%r, %d, %d): %s" % (kind, index, direction, self.lib.crct_last_error().decode()))
         return out

@@ -11,6 +11,7 @@ parameters are views into ONE flat fp32 HBM buffer (+ a bf16 shadow, + a flat fp
 and ``forward`` / ``backward`` are single calls into the native step engine (hand-written gfx950
 kernels, ``include/crct_hip.h``).  The module refuses to run without the HIP library or off-GPU.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -33,6 +34,10 @@ class _Node(nn.Module):
         raise RuntimeError("structural node of the CRCT parameter tree; call the model instead")
 
 
+# Where each family of extra outputs sits behind the six fixed ones of a _StepFn result: three slices of result[6:]
+_StepLayout = collections.namedtuple("_StepLayout", "seq scores maps")
+
+
 class _StepFn(torch.autograd.Function):
     """Autograd bridge.  Differentiable outputs: the COMBINED loss (0-dim, = nsp_coeff * nsp + reg_coeff * mean_B reg_loss,
     computed by the head kernel, encoder_decorator.py:144-153), nsp_loss [1] and the per-row regression loss [B]; backward
@@ -40,66 +45,66 @@ class _StepFn(torch.autograd.Function):
     into the flat buffer (``param.grad`` are views of it).  The usual case -- only ``loss`` is differentiated -- costs no
     torch kernel besides autograd's own seed: the head kernel scales its built-in seeds by the upstream scalar.
 
-    The float inputs of the step -- the device tensors of ``image_feat``, ``image_loc``, ``loc`` (the text boxes) and ``areas``, the same
-    objects ``tensors`` holds -- are autograd inputs too: for those that need a gradient, backward hands the engine a buffer
-    (``StepEngine.set_input_grads``) for the duration of the pass and returns it with the dtype and shape of the input.  The values
-    carry whatever the upstream gradient carries (a GradScaler's loss scale), and are local: a data-parallel pass never exchanges them.
-
-    With ``model.return_sequence_outputs`` the node has two more differentiable outputs behind the six: the encoder's final hidden states
-    (fp32 [B, T, H] and [B, V, Hv]).  Their upstream gradients (None when unused) go to the engine for the duration of the pass
-    (``StepEngine.set_output_grads``), which adds them onto the hidden gradients the heads seed; unused, the pass is the plain one.
-
-    With ``model.differentiable_scores`` the node has, behind those, the answer logits [B, 2] and -- where the variant's regressor is the
-    PlotQA one -- the regressed value [B] as differentiable outputs: copies of the snapshot's that own their memory.  Their upstream
-    gradients (None when unused) go to the engine for the duration of the pass (``StepEngine.set_score_grads``) and enter the loss
-    kernel's own launch; unused, the pass is the plain one.
-
-    With ``model.attention_map_outputs`` the node has, behind those, one differentiable output per requested attention map (fp32, one
-    launch each).  The upstream gradients of the maps that have one go to the engine for the duration of the pass
-    (``StepEngine.set_attention_map_grads``); each layer adds its map's contribution behind its own attention backward."""
+    Everything else that can carry a gradient goes through ONE mechanism, the engine's per-pass requests (``StepEngine.requests``):
+    backward collects the buffers autograd asks for and the engine holds them for the duration of the pass; a pass that asks for nothing
+    is the plain one, launch for launch.  Inputs: the device tensors of ``image_feat``, ``image_loc``, ``loc`` (the text boxes) and
+    ``areas``, the same objects ``tensors`` holds; those that need a gradient get a buffer the pass writes, returned with the dtype and
+    shape of the input (``CrctModel._run_backward_with_inputs``) -- it carries whatever the upstream gradient carries (a GradScaler's loss
+    scale) and is local: a data-parallel pass never exchanges it.  Extra outputs behind the six, in three families whose places
+    ``ctx.layout`` records and ``split`` reads back: the encoder's final hidden states (``model.return_sequence_outputs``), the logits and
+    the PlotQA regressor's value (``model.differentiable_scores``) and the requested attention maps (``model.attention_map_outputs``) --
+    see those attributes.  An output without an upstream gradient asks for nothing."""
 
     @staticmethod
     def forward(ctx, anchor, model, tensors, step, image_feat=None, image_loc=None, loc=None, areas=None):
         # (fp8 data gradients only: the forward pass is the plain bf16 one -- no fp8 state, no copies -- the backward pass gets it)
         fwd_step = {k: v for k, v in step.items() if k != "fp8"} if step.get("fp8_backward_only") else step
-        model._engine.forward(model._flat_p, model._flat_b16, tensors, fwd_step)
+        eng = model._engine
+        eng.forward(model._flat_p, model._flat_b16, tensors, fwd_step)
         ctx.model, ctx.tensors, ctx.step = model, tensors, step
         ctx.set_materialize_grads(False)
-        logits, reg_all, stats = model._engine.snapshot(tensors["tokens"].shape[0])    # one copy; the engine reuses its buffer
+        logits, reg_all, stats = eng.snapshot(tensors["tokens"].shape[0])    # one copy; the engine reuses its buffer
         ctx.mark_non_differentiable(logits, reg_all, stats)
         # the differentiable scalar is a tensor of its own (4 bytes): the reference loop modifies it in place
         # (train.py:204-205 ``loss /= params['batch_multiply']``), which autograd forbids on a view output of a multi-output node
-        out = (stats[0].clone(), stats[1:2], reg_all[1], logits, reg_all, stats)     # the rest: views of the snapshot, no copies
-        if model.return_sequence_outputs:
-            # two more differentiable outputs: the encoder's final hidden states, fresh fp32 tensors (StepEngine.sequence_outputs)
-            out = out + model._engine.sequence_outputs()
-        ctx.n_seq = len(out) - 6
-        ctx.scores = bool(model.differentiable_scores)
-        if ctx.scores:
-            # the logits, and the PlotQA regressor's value, as differentiable outputs: tensors of their own (two B-sized copies)
-            out = out + (logits.clone(),)
-            if model.variant[1] == "plotqa":
-                out = out + (reg_all[0].clone(),)
-        ctx.n_scores = len(out) - 6 - ctx.n_seq
-        # the requested attention maps as differentiable outputs: fresh fp32 tensors, one launch each (StepEngine.attention_probs)
+        out = [stats[0].clone(), stats[1:2], reg_all[1], logits, reg_all, stats]     # the rest: views of the snapshot, no copies
+
+        def family(ts):
+            out.extend(ts)
+            return slice(len(out) - 6 - len(ts), len(out) - 6)
+        # the encoder's final hidden states, fresh fp32 tensors (StepEngine.sequence_outputs)
+        seq = family(eng.sequence_outputs() if model.return_sequence_outputs else ())
+        # the logits, and the PlotQA regressor's value: tensors of their own (two B-sized copies)
+        with_value = model.variant[1] == "plotqa"
+        scores = family([t.clone() for t in ((logits, reg_all[0]) if with_value else (logits,))] if model.differentiable_scores else ())
+        # the requested attention maps, fresh fp32 tensors, one launch each (StepEngine.attention_probs)
         ctx.map_keys = model._attention_map_keys()
-        return out + tuple(model._engine.attention_probs(*key) for key in ctx.map_keys)
+        maps = family([eng.attention_probs(*key) for key in ctx.map_keys])
+        ctx.layout = model._step_layout = _StepLayout(seq, scores, maps)
+        return tuple(out)
+
+    @staticmethod
+    def split(model, result):
+        """A result of ``apply`` as (the six fixed outputs, sequence outputs, scores, maps)."""
+        return (result[:6],) + tuple(result[6:][sl] for sl in model._step_layout)
 
     @staticmethod
     def backward(ctx, g_loss, g_nsp, g_reg, _gl, _gr, _gs, *g_more):
         model = ctx.model
         step = dict(ctx.step)
         B = ctx.tensors["tokens"].shape[0]
-        g_seq_t, g_seq_v = (_upstream_f32(g) for g in g_more[:2]) if ctx.n_seq else (None, None)
-        g_scores = tuple(_upstream_f32(g) for g in g_more[ctx.n_seq:ctx.n_seq + ctx.n_scores]) if ctx.scores else ()
-        g_logits = g_scores[0].reshape(B, 2) if g_scores and g_scores[0] is not None else None
-        g_value = g_scores[1].reshape(B) if len(g_scores) > 1 and g_scores[1] is not None else None
-        # the maps with an upstream gradient: (kind, index, direction, fp32 tensor) as the engine takes them
-        g_maps = [key + (_upstream_f32(g),) for key, g in zip(ctx.map_keys, g_more[ctx.n_seq + ctx.n_scores:]) if g is not None]
-        upstream_out, upstream_scores = g_seq_t is not None or g_seq_v is not None, g_logits is not None or g_value is not None
+        g_seq, g_scores, g_maps = ([_upstream_f32(g) for g in g_more[sl]] for sl in ctx.layout)
+        # what the pass asks of the engine besides the loss: the families with an upstream gradient, as StepEngine.requests takes them
+        requests = {}
+        if any(g is not None for g in g_seq):
+            requests["output_grads"] = dict(zip(("seq_t", "seq_v"), g_seq))
+        if any(g is not None for g in g_scores):
+            requests["score_grads"] = dict(zip(("logits", "value"), g_scores))      # (autograd hands them over as [B, 2] and [B])
+        if any(g is not None for g in g_maps):
+            requests["attention_map_grads"] = [key + (g,) for key, g in zip(ctx.map_keys, g_maps) if g is not None]
         if g_nsp is None and g_reg is None:
             if g_loss is None:
-                if not upstream_out and not upstream_scores and not g_maps:
+                if not requests:
                     return (None,) * 8
                 g_loss = torch.zeros(1, device=model._flat_p.device)   # only the sequence outputs / scores / maps are differentiated: the heads get zero loss seeds
             step["g_loss"] = g_loss.reshape(1).float()                 # views / no-ops for the fp32 scalar autograd hands over
@@ -110,29 +115,7 @@ class _StepFn(torch.autograd.Function):
             gr = g_reg.reshape(B).float() if g_reg is not None else torch.zeros(B, device=dev)
             step["g_nsp"] = (gn + gl * step["nsp_coeff"]).contiguous()
             step["g_reg"] = (gr + gl * (step["reg_coeff"] / B)).contiguous()
-        if not upstream_out and not upstream_scores and not g_maps:
-            grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
-        else:
-            # upstream gradients of the sequence outputs: segment 0 adds them onto the hidden gradients the heads seed; of the scores: the
-            # loss kernel adds them onto its per-row seeds; of the attention maps: each layer adds its map's contribution behind its own
-            # attention backward (each request stands for this pass only, like the input-gradient request inside the call; the four compose)
-            eng = model._engine
-            try:
-                if upstream_out:
-                    eng.set_output_grads(seq_t=g_seq_t, seq_v=g_seq_v)
-                if upstream_scores:
-                    eng.set_score_grads(logits=g_logits, value=g_value)
-                if g_maps:
-                    eng.set_attention_map_grads(g_maps)
-                grads = model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8])
-            finally:
-                if g_maps:
-                    eng.set_attention_map_grads()
-                if upstream_scores:
-                    eng.set_score_grads()
-                if upstream_out:
-                    eng.set_output_grads()
-        return (None, None, None, None) + grads
+        return (None, None, None, None) + model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8], requests)
 
 
 def _upstream_f32(g):
@@ -600,18 +583,16 @@ class CrctModel(nn.Module):
         else:
             self._ddp.backward(self, eng, tensors, step)
 
-    def _run_backward_with_inputs(self, tensors, step, need):
-        """``_run_backward`` with the gradients of the float inputs: ``need`` = which of (image_feat, image_loc, loc, areas) autograd wants.
-        Returns the four gradients (None where not wanted, and for the features of the dvqa / figure_qa variants, which never read them --
-        the reference computes that term and drops it), each with the dtype and shape of its tensor in ``tensors``.  With
-        ``keep_text_embedding_grad`` the pass also leaves ``text_embedding_grad``.  The request stands for this pass only."""
+    def _run_backward_with_inputs(self, tensors, step, need, requests=None):
+        """``_run_backward`` under ONE ``StepEngine.requests``: what ``_StepFn.backward`` collected (``requests``, its keyword arguments) and
+        the gradients of the float inputs -- ``need`` = which of (image_feat, image_loc, loc, areas) autograd wants.  Returns those four
+        (None where not wanted, and for the features of the dvqa / figure_qa variants, which never read them -- the reference computes
+        that term and drops it), each with the dtype and shape of its tensor in ``tensors``; with ``keep_text_embedding_grad`` the pass
+        also leaves ``text_embedding_grad``.  A pass that asks for nothing makes no request call into the library at all."""
         want_feat, want_iloc, want_tloc, want_areas = (bool(n) for n in need)
         want_feat = want_feat and self.variant[0] == "plotqa"
         want_areas = want_areas and tensors.get("areas") is not None
         keep_emb = bool(self.keep_text_embedding_grad)
-        if not (want_feat or want_iloc or want_tloc or want_areas or keep_emb):
-            self._run_backward(tensors, step)
-            return None, None, None, None
         dev = self._flat_p.device
         B, T = tensors["tokens"].shape
 
@@ -620,12 +601,10 @@ class CrctModel(nn.Module):
         d_feat, d_iloc = buf(tensors["image_feat"], want_feat), buf(tensors["image_loc"], want_iloc)
         d_tloc, d_areas = buf(tensors["loc"], want_tloc), buf(tensors.get("areas"), want_areas)
         d_emb = torch.empty(B, T, self.config.hidden_size, dtype=torch.float32, device=dev) if keep_emb else None
-        eng = self._engine
-        eng.set_input_grads(image_feat=d_feat, image_loc=d_iloc, areas=d_areas, txt_loc=d_tloc, text_emb=d_emb)
-        try:
+        if want_feat or want_iloc or want_tloc or want_areas or keep_emb:
+            requests = dict(requests or {}, input_grads=dict(image_feat=d_feat, image_loc=d_iloc, areas=d_areas, txt_loc=d_tloc, text_emb=d_emb))
+        with self._engine.requests(**(requests or {})):
             self._run_backward(tensors, step)
-        finally:
-            eng.set_input_grads()
         if keep_emb:
             self.text_embedding_grad = d_emb
         if d_feat is not None and tensors["image_feat"].dtype != torch.float32:
@@ -716,9 +695,7 @@ class CrctModel(nn.Module):
                 tensors = dict(tensors, image_feat=live[0].detach(), image_loc=live[1].detach(), loc=live[2].detach())
                 if live[3] is not None:
                     tensors["areas"] = live[3].detach()
-            loss, nsp, reg_loss, logits, reg, stats, *more = _StepFn.apply(self._anchor, self, tensors, step, *live)
-            seq, scores = (more[:2], more[2:]) if self.return_sequence_outputs else ((), more)
-            scores, maps = scores[:len(scores) - len(map_keys)], scores[len(scores) - len(map_keys):]
+            (loss, nsp, reg_loss, logits, reg, stats), seq, scores, maps = _StepFn.split(self, _StepFn.apply(self._anchor, self, tensors, step, *live))
             value = scores[1] if len(scores) > 1 else None
             if scores:
                 logits = scores[0]                     # differentiable_scores: the copies that are part of the graph
@@ -755,14 +732,12 @@ class CrctModel(nn.Module):
 
     def _attention_map_keys(self):
         """``attention_map_outputs`` as the keys of ``attention_maps``: (kind, index, direction), kind by name, direction 0 by default."""
-        names = {0: "text", 1: "visual", 2: "conn"}
         keys = []
         for item in self.attention_map_outputs or ():
-            kind, index, direction = (tuple(item) + (0,))[:3]
-            kind = names.get(kind, kind)
-            if kind not in ("text", "visual", "conn"):
+            kind, index, direction = StepEngine.map_key(item)
+            if kind not in (0, 1, 2):
                 raise ValueError("attention_map_outputs: kind must be 'text', 'visual' or 'conn'; got %r" % (kind,))
-            keys.append((kind, int(index), int(direction)))
+            keys.append((StepEngine.MAP_KINDS[kind], index, direction))
         return tuple(keys)
 
     def _attention_maps(self, eng):

@@ -104,6 +104,11 @@ struct Arena {
 };
 
 struct Drop { uint32_t thr = 0; float scale = 1.f; uint32_t site = 0; };
+inline Drop drop_of(const CrctStepCfg* c, float p, uint32_t site) {      // dropout p at `site` under step configuration c: off outside training
+  Drop d; d.site = site;
+  if (c->training && p > 0.f) { d.thr = thr_of(p); d.scale = 1.0f / (1.0f - p); }
+  return d;
+}
 
 // ---- parameter offsets (elements into the flat buffers)
 struct LinearP { int64_t w = -1, b = -1; int in = 0, out = 0; int site = 0; int parts = 1; };      // parts: 3 for a fused QKV (three tensors back to back)
@@ -147,6 +152,38 @@ struct Tap { std::string name; size_t off; char stream; int width = 0; };      /
 // input are produced (the embedding segment: whether that stream's half runs), how many weight-gradient GEMMs it leaves out
 struct SegPlan { bool runs = true, dx_t = true, dx_v = true; int dropped = 0; };
 
+// One attention of the schedule as every launch that touches it sees it (crct_engine::attn_site).  kind 0 / 1: self-attention of text /
+// visual layer `index`; 2: connection layer, direction 0 = text queries over visual keys, 1 = visual queries over text keys.  q, k, v:
+// workspace offsets of its columns in the fused q | k | v buffers (ld elements a row); image_keys: the IMAGE key mask, else the text one;
+// p / site: attention dropout; lse: row statistics of the long kernels; ctx / ctxq / site_ctx: the context, its e4m3 copy and scale site
+struct AttnSite {
+  int kind = 0, index = 0, direction = 0;
+  size_t q = 0, k = 0, v = 0; int64_t ld = 0;
+  int heads = 0, d = 0, Tq = 0, Tk = 0;
+  bool image_keys = false;
+  float p = 0.f; uint32_t site = 0;
+  size_t lse = NONE, ctx = 0, ctxq = NONE; int site_ctx = -1;
+  int H() const { return heads * d; }
+};
+
+// The per-pass gradient requests, each standing until its setter (crct_engine_set_*_grads) replaces it; all NULL / empty: off.  ig: where
+// backward leaves the gradients of the float inputs -- the one family replan reads; og / sg: upstream gradients of the final hidden states
+// (segment 0 adds them onto the running hidden gradients) and of the logits and the regressed value (heads_bwd's loss kernel); amg: the maps
+// whose upstream gradients are added behind their attention backward.  Workspace behind the plan's own `base` bytes: ws_ig, the fp32
+// [maxB * maxV][Fv] upstream gradient of the feature softmax, counted while d_image_feat is requested; behind it the scratch of
+// crct_attention_probs_bwd, ws_amg bytes per data stream (the two run side by side), counted while a map request stands
+struct Requests {
+  CrctInputGrads ig = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  CrctOutputGrads og = {nullptr, nullptr};
+  CrctScoreGrads sg = {nullptr, nullptr};
+  std::vector<CrctAttnMapGrad> amg;
+  size_t ws_ig = 0, ws_amg = 0;
+  bool ig_text() const { return ig.d_txt_loc || ig.d_text_emb; }
+  bool ig_vis() const { return ig.d_image_feat || ig.d_image_loc || ig.d_areas; }
+  size_t amg_scratch(size_t base, int which) const { return base + ws_ig + (size_t)which * ws_amg; }
+  size_t ws_bytes(size_t base) const { return amg.empty() ? base + (ig.d_image_feat ? ws_ig : 0) : amg_scratch(base, 2); }
+};
+
 }  // namespace
 
 struct crct_engine {
@@ -164,31 +201,15 @@ struct crct_engine {
   CrctVariant var = {CRCT_DATASET_PLOTQA, CRCT_REGRESSOR_PLOTQA, 0, {}};
   bool feat = true;
   const float* areas = nullptr;        // crct_engine_set_areas: fp32 [B][V] of the running batch, or NULL
-  // crct_engine_set_input_grads: where the following backward passes leave the gradients of the float inputs (all NULL: off), the fp32
-  // [maxB * maxV][Fv] upstream gradient of the feature softmax behind everything else in the workspace (counted only while
-  // d_image_feat is requested), and whether a tensor WITH gradient sits in the text / image embedding (replan): an embedding half
-  // that runs for a requested input gradient alone leaves the parameter-gradient kernels out
-  CrctInputGrads ig = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t ws_ig = 0;
-  bool emb_own_t = true, emb_own_v = true;
-  // crct_engine_set_output_grads: fp32 upstream gradients of the encoder's final hidden states that segment 0 of the following backward
-  // passes adds onto the running hidden gradients (both NULL: off); fwd_r32: the residual_fp32 of the last forward (-1: none yet), which
-  // says whether the rows crct_engine_sequence_outputs normalises again are fp32 or bf16
-  CrctOutputGrads og = {nullptr, nullptr};
-  int fwd_r32 = -1;
-  // crct_engine_set_score_grads: fp32 upstream gradients of the logits and of the regressed value, handed to the loss kernel of the
-  // following backward passes (both NULL: off)
-  CrctScoreGrads sg = {nullptr, nullptr};
-  // crct_engine_set_attention_map_grads: the maps whose fp32 upstream gradients the following backward passes add behind each layer's own
-  // attention backward (empty: off), and the row-statistics scratch of crct_attention_probs_bwd, one of ws_amg bytes per data stream
-  // (text, visual: the two run side by side), behind the input-gradient space and counted only while a request stands
-  std::vector<CrctAttnMapGrad> amg;
-  size_t ws_amg = 0;
-  size_t amg_scratch(int which) const { return ws_base() + ws_ig + (size_t)which * ws_amg; }
-  bool ig_text() const { return ig.d_txt_loc || ig.d_text_emb; }
-  bool ig_vis() const { return ig.d_image_feat || ig.d_image_loc || ig.d_areas; }
+  // the standing per-pass requests; the workspace is the plan's own bytes (ws_base) and what they add: the one place its size is set
+  Requests req;
   size_t ws_base() const { return ln_addend ? ws_core : ws_two_output; }
-  void ws_update() { ws_bytes = amg.empty() ? ws_base() + (ig.d_image_feat ? ws_ig : 0) : amg_scratch(2); }
+  void ws_update() { ws_bytes = req.ws_bytes(ws_base()); }
+  // whether a tensor WITH gradient sits in the text / image embedding (replan): an embedding half that runs for a requested input
+  // gradient alone leaves the parameter-gradient kernels out
+  bool emb_own_t = true, emb_own_v = true;
+  int fwd_r32 = -1;      // residual_fp32 of the last forward (-1: none yet): whether crct_engine_sequence_outputs reads fp32 or bf16 rows
+  int attn_site(const char* who, int kind, int index, int direction, int T, int V, AttnSite* out) const;
   struct { size_t sum, y, mean, rstd, yq; int site; } eta;
   struct { size_t soft, lin, sum, y, mean, rstd, yq; int site; } eva;
   LinearP t_pool, v_pool, cls, tp[4], vp[4], fu[4];
@@ -267,6 +288,39 @@ struct crct_engine {
     return it->second;
   }
 };
+
+// The attention (kind, index, direction) at token / visual lengths T / V; a triple that names none is refused with `who` in front of the
+// message.  The only place that knows the co-attention's cross wiring (vilbert.py:684-723): text queries read the VISUAL keys and values
+// (qkv1) under the image mask with p_v_attn at the layer's first dropout site, visual queries the TEXT ones (qkv2) under the text mask
+// with p_attn at the site behind it.
+int crct_engine::attn_site(const char* who, int kind, int index, int direction, int T, int V, AttnSite* out) const {
+  AttnSite s;
+  s.kind = kind; s.index = index; s.direction = direction;
+  if (kind == 0 || kind == 1) {
+    const std::vector<SelfLayerP>& lp = kind == 0 ? tl : vl;
+    CRCT_REQUIRE(index >= 0 && index < (int)lp.size(), "%s: %s layer %d out of range [0,%d)", who, kind == 0 ? "text" : "visual", index, (int)lp.size());
+    CRCT_REQUIRE(direction == 0, "%s: direction %d belongs to connection layers (kind 2)", who, direction);
+    const SelfLayerP& p = lp[index];
+    const SelfLayerA& a = (kind == 0 ? tla : vla)[index];
+    s.heads = p.heads; s.d = p.H / p.heads; s.Tq = s.Tk = kind == 0 ? T : V; s.image_keys = kind == 1;
+    s.q = s.k = a.qkv; s.p = p.p_attn; s.site = p.site;
+    s.lse = a.lse; s.ctx = a.ctx; s.ctxq = a.ctxq; s.site_ctx = a.site_ctx;
+  } else {
+    CRCT_REQUIRE(kind == 2, "%s: unknown kind %d (0 text, 1 visual, 2 connection layer)", who, kind);
+    const int layers = d.with_coattention ? (int)cl.size() : 0;
+    CRCT_REQUIRE(index >= 0 && index < layers, "%s: connection layer %d out of range [0,%d)", who, index, layers);
+    CRCT_REQUIRE(direction == 0 || direction == 1, "%s: direction %d must be 0 (text over visual) or 1 (visual over text)", who, direction);
+    const ConnLayerA& a = cla[index];
+    const bool tq = direction == 0;      // text queries
+    s.heads = d.b_heads; s.d = d.Hb / d.b_heads; s.Tq = tq ? T : V; s.Tk = tq ? V : T; s.image_keys = tq;
+    s.q = tq ? a.qkv2 : a.qkv1; s.k = tq ? a.qkv1 : a.qkv2; s.p = tq ? d.p_v_attn : d.p_attn; s.site = cl[index].site + (tq ? 0 : 1);
+    s.lse = tq ? a.lse1 : a.lse2; s.ctx = tq ? a.ctx1 : a.ctx2; s.ctxq = tq ? a.ctx1q : a.ctx2q; s.site_ctx = tq ? a.site_ctx1 : a.site_ctx2;
+  }
+  s.k += (size_t)s.H() * sizeof(bf16_t);      // q | k | v side by side in a row of the key side's buffer
+  s.v = s.k + (size_t)s.H() * sizeof(bf16_t); s.ld = 3 * (int64_t)s.H();
+  *out = s;
+  return 0;
+}
 
 namespace {
 
@@ -437,12 +491,14 @@ struct Run {
   const float* P(int64_t o) const { return p32 + o; }
   const bf16_t* PB(int64_t o) const { return p16 + o; }
   float* G(int64_t o) const { return g32 + o; }
-  Drop drop(float p, uint32_t site) const {
-    Drop d; d.site = site;
-    if (c->training && p > 0.f) { d.thr = thr_of(p); d.scale = 1.0f / (1.0f - p); }
-    return d;
-  }
+  Drop drop(float p, uint32_t site) const { return drop_of(c, p, site); }
   void fail(int r) { if (!rc && r) rc = r; }
+  AttnSite site(int kind, int index, int direction) {      // an attention of the running batch (schedule indices: never refused)
+    AttnSite a;
+    fail(e->attn_site("engine", kind, index, direction, b->T, b->V, &a));
+    return a;
+  }
+  const uint8_t* keymask(const AttnSite& a) const { return a.image_keys ? b->image_keymask : b->text_keymask; }
 
   struct Opt {
     void* preact = nullptr; const void* dact_src = nullptr; int dact = 0; int act = 0;
@@ -690,51 +746,51 @@ struct Run {
     return dr.thr ? dlin : dres;
   }
   // ctx.site >= 0: also the e4m3 copy of ctx (the fp8 forward GEMM and weight gradient of the attention-output projection read it)
-  void attn_fwd(const bf16_t* q, int64_t ldq, const bf16_t* k, const bf16_t* v, int64_t ldk, const uint8_t* km, const Act& ctx,
-                int64_t ldo, int B, int heads, int Tq, int Tk, int d, const Drop& dr, size_t lse = NONE) {
+  void attn_fwd(const AttnSite& a, const Act& ctx) {
     if (rc) return;
     ++tick;
-    const uint64_t seed = c->seed;
+    const Drop dr = drop(a.p, a.site);
     CrctAttnQuant qz;
     memset(&qz, 0, sizeof(qz));
-    if (lse != NONE) qz.row_lse = F(lse);
+    qz.row_lse = F(a.lse);
     if (ctx.site >= 0) { const Q8 c8 = q8(ctx); qz.ctx_q = c8.q; qz.ctx_scale = c8.scale; qz.ctx_amax = c8.amax; }
-    fail(crct_attention_fwd_q(q, k, v, km, A(ctx.x), B, heads, Tq, Tk, d, ldq, ldk, ldk, ldo, dr.thr, dr.scale, dr.site, seed, &qz, s));
+    fail(crct_attention_fwd_q(A(a.q), A(a.k), A(a.v), keymask(a), A(ctx.x), b->B, a.heads, a.Tq, a.Tk, a.d, a.ld, a.ld, a.ld, a.H(), dr.thr,
+                              dr.scale, dr.site, c->seed, &qz, s));
   }
-  // dqq / g_dq, dkq / dvq / g_dkv: also e5m2 copies of dq and of dk / dv (columns of fused dqkv buffers: one scale site per buffer)
-  void attn_bwd(const bf16_t* q, int64_t ldq, const bf16_t* k, const bf16_t* v, int64_t ldk, const uint8_t* km,
-                const bf16_t* dctx, int64_t ldo, bf16_t* dq, int64_t lddq, bf16_t* dk, bf16_t* dv, int64_t lddk, int B,
-                int heads, int Tq, int Tk, int d, const Drop& dr, uint8_t* dqq = nullptr, int g_dq = -1, uint8_t* dkq = nullptr,
-                uint8_t* dvq = nullptr, int g_dkv = -1, size_t lse = NONE, const bf16_t* ctx = nullptr, int64_t ldc = 0) {
+  // dq goes to the query columns of the fused dqkv buffer at dqkv_q, dk / dv to the key and value columns of the one at dqkv_kv (the other
+  // stream's in a co-attention); qq / kvq: the e5m2 copies of those buffers (one gradient scale site each), written where site >= 0
+  void attn_bwd(const AttnSite& a, size_t dctx, size_t dqkv_q, size_t dqkv_kv, const GradQ& qq, const GradQ& kvq) {
     if (rc) return;
     ++tick;
-    const uint64_t seed = c->seed;
+    const Drop dr = drop(a.p, a.site);
+    const int H = a.H();
     CrctAttnQuant qz;
     memset(&qz, 0, sizeof(qz));
-    if (lse != NONE && ctx) { qz.row_lse = F(lse); qz.ctx = ctx; qz.ld_ctx = ldc; }
-    if (dqq && g_dq >= 0) { qz.dq_q = dqq; qz.dq_scale = gscale(g_dq); qz.dq_amax = gamax(g_dq); }
-    if (dkq && dvq && g_dkv >= 0) { qz.dk_q = dkq; qz.dv_q = dvq; qz.dkv_scale = gscale(g_dkv); qz.dkv_amax = gamax(g_dkv); }
-    fail(crct_attention_bwd_q(q, k, v, km, dctx, dq, dk, dv, B, heads, Tq, Tk, d, ldq, ldk, ldk, ldo, lddq, lddk, lddk, dr.thr, dr.scale,
-                              dr.site, seed, &qz, s));
+    qz.row_lse = F(a.lse); qz.ctx = A(a.ctx); qz.ld_ctx = H;
+    if (qq.site >= 0) { const Q8 d8 = q8(qq); qz.dq_q = d8.q; qz.dq_scale = d8.scale; qz.dq_amax = d8.amax; }
+    if (kvq.site >= 0) { const Q8 d8 = q8(kvq); qz.dk_q = d8.q + H; qz.dv_q = d8.q + 2 * H; qz.dkv_scale = d8.scale; qz.dkv_amax = d8.amax; }
+    fail(crct_attention_bwd_q(A(a.q), A(a.k), A(a.v), keymask(a), A(dctx), A(dqkv_q), A(dqkv_kv) + H, A(dqkv_kv) + 2 * H, b->B, a.heads, a.Tq, a.Tk,
+                              a.d, a.ld, a.ld, a.ld, H, a.ld, a.ld, a.ld, dr.thr, dr.scale, dr.site, c->seed, &qz, s));
   }
   // The requested maps of one attention (crct_engine_set_attention_map_grads), right behind its attn_bwd on this stream: each adds its
   // contribution onto the dq / dk columns that launch wrote (same q, k, key mask and dropout stream; c = the step's gradient scale).
   // No request: nothing is launched and `tick` stays as it is
-  void attn_map_grads(int kind, int index, int direction, const bf16_t* q, const bf16_t* k, int64_t ld, const uint8_t* km, bf16_t* dq, bf16_t* dk,
-                      int64_t ldd, int B, int heads, int Tq, int Tk, int d, const Drop& dr) {
-    for (const CrctAttnMapGrad& r : e->amg) {
+  void attn_map_grads(const AttnSite& a, size_t dqkv_q, size_t dqkv_kv) {
+    for (const CrctAttnMapGrad& r : e->req.amg) {
       if (rc) return;
-      if (r.kind != kind || r.index != index || r.direction != direction) continue;
+      if (r.kind != a.kind || r.index != a.index || r.direction != a.direction) continue;
       ++tick;
-      fail(crct_attention_probs_bwd(q, k, km, r.d_probs, c->grad_scale, dq, dk, F(e->amg_scratch(which)), 1, B, heads, Tq, Tk, d, ld, ld, ldd, ldd,
-                                    dr.thr, dr.scale, dr.site, c->seed, s));
+      const Drop dr = drop(a.p, a.site);
+      fail(crct_attention_probs_bwd(A(a.q), A(a.k), keymask(a), r.d_probs, c->grad_scale, A(dqkv_q), A(dqkv_kv) + a.H(),
+                                    F(e->req.amg_scratch(e->ws_base(), which)), 1, b->B, a.heads, a.Tq, a.Tk, a.d, a.ld, a.ld, a.ld, a.ld, dr.thr,
+                                    dr.scale, dr.site, c->seed, s));
     }
   }
   // the attention kernels that write fp8 copies cover this shape (MFMA kernels: include/crct_hip.h, CrctAttnQuant)
-  static bool attn_q_ok(int Tq, int Tk, int d) { return crct_attention_quant_ok(Tq, Tk, d) != 0; }
+  static bool attn_q_ok(const AttnSite& a) { return crct_attention_quant_ok(a.Tq, a.Tk, a.d) != 0; }
   // The attention context as both passes see it: its e4m3 copy exists where the attention kernel covers the shape (aq) and the
   // output projection `dense` runs its forward in fp8
-  Act ctx_act(size_t ctx, size_t ctxq, int site, const LinearP& dense, bool aq) const { return {ctx, ctxq, aq && f8_lin(dense) ? site : -1}; }
+  Act ctx_act(const AttnSite& a, const LinearP& dense, bool aq) const { return {a.ctx, a.ctxq, aq && f8_lin(dense) ? a.site_ctx : -1}; }
   // The FFN's hidden activation as both passes see it: hq exists when both forward GEMMs run in fp8
   Act ffn_h(const FfnP& p, const FfnA& a) const { return {a.h, a.hq, f8_lin(p.up) && f8_lin(p.down) ? a.site_h : -1}; }
 
@@ -781,32 +837,32 @@ struct Run {
   }
 
   // ---------------------------------------------------------------- self-attention layer
-  void self_fwd(const SelfLayerP& p, const SelfLayerA& a, const Act& x, const uint8_t* km, int B, int T) {
-    const int M = B * T, H = p.H, d = H / p.heads;
+  // layer `idx` of this Run's stack: the text layers run on the text stream's Run, the visual layers on the visual one (`which` is the
+  // attention's kind)
+  void self_fwd(int idx, const Act& x) {
+    const SelfLayerP& p = (which ? e->vl : e->tl)[idx]; const SelfLayerA& a = (which ? e->vla : e->tla)[idx];
+    const AttnSite at = site(which, idx, 0);
+    const int M = b->B * at.Tq, H = p.H;
     lin_fwd(x, p.qkv.in, p.qkv, M, Act{a.qkv}, 3 * H, Opt());
-    const Act ctx = ctx_act(a.ctx, a.ctxq, a.site_ctx, p.proj.dense, attn_q_ok(T, T, d));
-    attn_fwd(A(a.qkv), 3 * H, A(a.qkv) + H, A(a.qkv) + 2 * H, 3 * H, km, ctx, H, B, p.heads, T, T, d, drop(p.p_attn, p.site), a.lse);
+    const Act ctx = ctx_act(at, p.proj.dense, attn_q_ok(at));
+    attn_fwd(at, ctx);
     proj_fwd(p.proj, a.proj, ctx, x, M, drop(p.p_hid, p.site + 1));
     ffn_fwd(p.ffn, a.ffn, a.proj.out(p.proj.ln), M, drop(p.p_hid, p.site + 2));
   }
   // x: the layer input (its e4m3 copy serves the fp8 weight gradient of the QKV projection); g: grad of the output, gx: of x
   // dx = false (the lowest running step of its stream, SegPlan): gx has no reader and the launch that only produces it is not issued
-  void self_bwd(const SelfLayerP& p, const SelfLayerA& a, const Act& x, size_t g, size_t gx, const uint8_t* km, int B, int T, bool dx = true) {
-    const int M = B * T, H = p.H, d = H / p.heads;
+  void self_bwd(int idx, const Act& x, size_t g, size_t gx, bool dx = true) {
+    const SelfLayerP& p = (which ? e->vl : e->tl)[idx]; const SelfLayerA& a = (which ? e->vla : e->tla)[idx];
+    const AttnSite at = site(which, idx, 0);
+    const int M = b->B * at.Tq, H = p.H;
     const StreamScratch& sc = layer_begin();
     ffn_bwd(p.ffn, a.ffn, a.proj.out(p.proj.ln), g, sc.gc, sc, M, drop(p.p_hid, p.site + 2));
-    const bool aq = attn_q_ok(T, T, d);
+    const bool aq = attn_q_ok(at);
     const bool gq = aq && f8b_lin(p.qkv) && f8_lin(p.qkv);      // e5m2 copy of dqkv: fp8 data and weight gradient of the QKV projection
     const GradQ dqkvq{sc.dqkvq, gq ? a.g_dqkv : -1};
-    proj_bwd(p.proj, a.proj, ctx_act(a.ctx, a.ctxq, a.site_ctx, p.proj.dense, aq), sc.gc, sc, M, drop(p.p_hid, p.site + 1));
-    uint8_t* dq8 = gq ? W<uint8_t>(sc.dqkvq) : nullptr;
-    attn_bwd(A(a.qkv), 3 * H, A(a.qkv) + H, A(a.qkv) + 2 * H, 3 * H, km, A(sc.dctx), H, A(sc.dqkv), 3 * H, A(sc.dqkv) + H,
-             A(sc.dqkv) + 2 * H, 3 * H, B, p.heads, T, T, d, drop(p.p_attn, p.site), dq8, a.g_dqkv, gq ? dq8 + H : nullptr,
-             gq ? dq8 + 2 * H : nullptr, a.g_dqkv, a.lse, A(a.ctx), H);
-    // (text layers run on the text stream's Run, visual layers on the visual one: `which` is the map's kind)
-    if (!e->amg.empty())
-      attn_map_grads(which, (int)(&p - (which ? e->vl : e->tl).data()), 0, A(a.qkv), A(a.qkv) + H, 3 * H, km, A(sc.dqkv), A(sc.dqkv) + H, 3 * H, B,
-                     p.heads, T, T, d, drop(p.p_attn, p.site));
+    proj_bwd(p.proj, a.proj, ctx_act(at, p.proj.dense, aq), sc.gc, sc, M, drop(p.p_hid, p.site + 1));
+    attn_bwd(at, sc.dctx, sc.dqkv, sc.dqkv, dqkvq, dqkvq);
+    attn_map_grads(at, sc.dqkv, sc.dqkv);
     lin_wgrad(A(sc.dqkv), 3 * H, A(x.x), H, p.qkv, M, true, WgQ8{dqkvq, x});
     Opt o; o.addend = A(sc.dres_b); o.ld_add = H;
     if (dx) lin_dgrad(A(sc.dqkv), 3 * H, p.qkv, M, A(gx), H, o, dqkvq);
@@ -815,20 +871,19 @@ struct Run {
 
   // ---------------------------------------------------------------- connection layer (vilbert.py:774-788)
   // `this` drives the TEXT stream, `V` the VISUAL stream (they may share one HIP stream).
-  void conn_fwd(Run& V, const ConnLayerP& p, const ConnLayerA& a, const StepIn& x) {
+  void conn_fwd(Run& V, int idx, const StepIn& x) {
+    const ConnLayerP& p = e->cl[idx]; const ConnLayerA& a = e->cla[idx];
     const CrctModelDims& D = e->d;
-    const int B = b->B, Mv = B * b->V, Mt = B * b->T, Hb = D.Hb, d = Hb / D.b_heads;
+    const int B = b->B, Mv = B * b->V, Mt = B * b->T, Hb = D.Hb;
     V.lin_fwd(x.v, p.qkv1.in, p.qkv1, Mv, Act{a.qkv1}, 3 * Hb, Opt());      // query1/key1/value1  :662-664
     lin_fwd(x.t, p.qkv2.in, p.qkv2, Mt, Act{a.qkv2}, 3 * Hb, Opt());        // query2/key2/value2  :673-675
     cross_sync(V);                                    // text needs k1, v1; visual needs k2, v2
-    const bool aq = attn_q_ok(b->T, b->V, d) && attn_q_ok(b->V, b->T, d);
-    const Act ctx1 = ctx_act(a.ctx1, a.ctx1q, a.site_ctx1, p.proj_t.dense, aq), ctx2 = V.ctx_act(a.ctx2, a.ctx2q, a.site_ctx2, p.proj_v.dense, aq);
-    // text queries over visual keys/values -> ctx1 [B,T,Hb]  :684-701 (dropout1 = v_attention prob)
-    attn_fwd(A(a.qkv2), 3 * Hb, A(a.qkv1) + Hb, A(a.qkv1) + 2 * Hb, 3 * Hb, b->image_keymask, ctx1, Hb, B, D.b_heads,
-             b->T, b->V, d, drop(D.p_v_attn, p.site), a.lse1);
-    // visual queries over text keys/values -> ctx2 [B,V,Hb]  :704-723
-    V.attn_fwd(A(a.qkv1), 3 * Hb, A(a.qkv2) + Hb, A(a.qkv2) + 2 * Hb, 3 * Hb, b->text_keymask, ctx2, Hb, B, D.b_heads,
-               b->V, b->T, d, drop(D.p_attn, p.site + 1), a.lse2);
+    // text queries over visual keys/values -> ctx1 [B,T,Hb]  :684-701; visual queries over text keys/values -> ctx2 [B,V,Hb]  :704-723
+    const AttnSite at = site(2, idx, 0), av = V.site(2, idx, 1);
+    const bool aq = attn_q_ok(at) && attn_q_ok(av);
+    const Act ctx1 = ctx_act(at, p.proj_t.dense, aq), ctx2 = V.ctx_act(av, p.proj_v.dense, aq);
+    attn_fwd(at, ctx1);
+    V.attn_fwd(av, ctx2);
     // cross wiring :780 -- visual stream takes ctx2, text stream takes ctx1
     V.proj_fwd(p.proj_v, a.proj_v, ctx2, x.v, Mv, drop(D.p_v_hidden, p.site + 2));
     proj_fwd(p.proj_t, a.proj_t, ctx1, x.t, Mt, drop(D.p_hidden, p.site + 3));
@@ -837,21 +892,22 @@ struct Run {
   }
   // x: the two layer inputs (their e4m3 copies serve the fp8 weight gradients of the QKV projections); gv / gt: grads of the two
   // outputs, gxv / gxt: of the inputs (dxv / dxt = false: not produced, as in self_bwd)
-  void conn_bwd(Run& V, const ConnLayerP& p, const ConnLayerA& a, const StepIn& x, size_t gv, size_t gt, size_t gxv, size_t gxt,
-                bool dxv = true, bool dxt = true) {
+  void conn_bwd(Run& V, int idx, const StepIn& x, size_t gv, size_t gt, size_t gxv, size_t gxt, bool dxv = true, bool dxt = true) {
+    const ConnLayerP& p = e->cl[idx]; const ConnLayerA& a = e->cla[idx];
     const CrctModelDims& D = e->d;
     hipEvent_t free_v = V.set_free[V.parity], free_t = set_free[parity];      // "the last readers of this scratch set are done"
     const StreamScratch& sv = V.layer_begin(); const StreamScratch& st = layer_begin();
-    const int B = b->B, Mv = B * b->V, Mt = B * b->T, Hb = D.Hb, d = Hb / D.b_heads;
+    const int B = b->B, Mv = B * b->V, Mt = B * b->T, Hb = D.Hb;
+    const AttnSite at = site(2, idx, 0), av = V.site(2, idx, 1);      // ctx1 = attn(q2, k1, v1) on the text stream, ctx2 = attn(q1, k2, v2) on the visual one
     V.ffn_bwd(p.ffn_v, a.ffn_v, a.proj_v.out(p.proj_v.ln), gv, sv.gc, sv, Mv, drop(D.p_v_hidden, p.site + 4));
     ffn_bwd(p.ffn_t, a.ffn_t, a.proj_t.out(p.proj_t.ln), gt, st.gc, st, Mt, drop(D.p_hidden, p.site + 5));
-    const bool aq = attn_q_ok(b->T, b->V, d) && attn_q_ok(b->V, b->T, d);
+    const bool aq = attn_q_ok(at) && attn_q_ok(av);
     // e5m2 copies of the two fused dqkv buffers: only when BOTH QKV projections run their gradients in fp8 (each buffer is written by
     // both attention kernels)
     const bool gq = aq && f8b_lin(p.qkv1) && f8b_lin(p.qkv2) && f8_lin(p.qkv1) && f8_lin(p.qkv2);
     const GradQ dqkvq_v{sv.dqkvq, gq ? a.g_dqkv1 : -1}, dqkvq_t{st.dqkvq, gq ? a.g_dqkv2 : -1};
-    V.proj_bwd(p.proj_v, a.proj_v, V.ctx_act(a.ctx2, a.ctx2q, a.site_ctx2, p.proj_v.dense, aq), sv.gc, sv, Mv, drop(D.p_v_hidden, p.site + 2));   // dctx2 [Mv,Hb]
-    proj_bwd(p.proj_t, a.proj_t, ctx_act(a.ctx1, a.ctx1q, a.site_ctx1, p.proj_t.dense, aq), st.gc, st, Mt, drop(D.p_hidden, p.site + 3));         // dctx1 [Mt,Hb]
+    V.proj_bwd(p.proj_v, a.proj_v, V.ctx_act(av, p.proj_v.dense, aq), sv.gc, sv, Mv, drop(D.p_v_hidden, p.site + 2));   // dctx2 [Mv,Hb]
+    proj_bwd(p.proj_t, a.proj_t, ctx_act(at, p.proj_t.dense, aq), st.gc, st, Mt, drop(D.p_hidden, p.site + 3));         // dctx1 [Mt,Hb]
     // each attention backward also writes into the OTHER stream's dqkv scratch, which the layer that used this scratch set
     // last (its dgrad, and its weight-gradient GEMMs on the side stream) may still be reading.  With side streams that
     // layer's end is marked by the set's free event (recorded on the side stream behind everything the layer enqueued):
@@ -862,23 +918,12 @@ struct Run {
       if (free_t && !V.rc && hipStreamWaitEvent(V.s, free_t, 0) != hipSuccess) { crct_set_error("engine: stream wait failed"); V.rc = 1; }
     } else cross_sync(V);
     // ctx1 = attn(q2, k1, v1): dq2 -> dqkv2[:, 0:Hb], dk1/dv1 -> dqkv1[:, Hb:3Hb]            (text stream)
-    uint8_t* tq8 = gq ? W<uint8_t>(st.dqkvq) : nullptr;      // text buffer (site g_dqkv2), visual buffer (site g_dqkv1)
-    uint8_t* vq8 = gq ? W<uint8_t>(sv.dqkvq) : nullptr;
-    attn_bwd(A(a.qkv2), 3 * Hb, A(a.qkv1) + Hb, A(a.qkv1) + 2 * Hb, 3 * Hb, b->image_keymask, A(st.dctx), Hb, A(st.dqkv),
-             3 * Hb, A(sv.dqkv) + Hb, A(sv.dqkv) + 2 * Hb, 3 * Hb, B, D.b_heads, b->T, b->V, d, drop(D.p_v_attn, p.site),
-             tq8, a.g_dqkv2, gq ? vq8 + Hb : nullptr, gq ? vq8 + 2 * Hb : nullptr, a.g_dqkv1, a.lse1, A(a.ctx1), Hb);
+    attn_bwd(at, st.dctx, st.dqkv, sv.dqkv, dqkvq_t, dqkvq_v);
     // ctx2 = attn(q1, k2, v2): dq1 -> dqkv1[:, 0:Hb], dk2/dv2 -> dqkv2[:, Hb:3Hb]            (visual stream)
-    V.attn_bwd(A(a.qkv1), 3 * Hb, A(a.qkv2) + Hb, A(a.qkv2) + 2 * Hb, 3 * Hb, b->text_keymask, A(sv.dctx), Hb, A(sv.dqkv),
-               3 * Hb, A(st.dqkv) + Hb, A(st.dqkv) + 2 * Hb, 3 * Hb, B, D.b_heads, b->V, b->T, d, drop(D.p_attn, p.site + 1),
-               vq8, a.g_dqkv1, gq ? tq8 + Hb : nullptr, gq ? tq8 + 2 * Hb : nullptr, a.g_dqkv2, a.lse2, A(a.ctx2), Hb);
+    V.attn_bwd(av, sv.dctx, sv.dqkv, st.dqkv, dqkvq_v, dqkvq_t);
     // the requested maps of the two attentions, each behind its own backward on that stream and onto the very columns it wrote
-    if (!e->amg.empty()) {
-      const int ci = (int)(&p - e->cl.data());
-      attn_map_grads(2, ci, 0, A(a.qkv2), A(a.qkv1) + Hb, 3 * Hb, b->image_keymask, A(st.dqkv), A(sv.dqkv) + Hb, 3 * Hb, B, D.b_heads, b->T, b->V, d,
-                     drop(D.p_v_attn, p.site));
-      V.attn_map_grads(2, ci, 1, A(a.qkv1), A(a.qkv2) + Hb, 3 * Hb, b->text_keymask, A(sv.dqkv), A(st.dqkv) + Hb, 3 * Hb, B, D.b_heads, b->V, b->T, d,
-                       drop(D.p_attn, p.site + 1));
-    }
+    attn_map_grads(at, st.dqkv, sv.dqkv);
+    V.attn_map_grads(av, sv.dqkv, st.dqkv);
     // each stream's dqkv buffer has been written by BOTH attention backward kernels
     cross_sync(V);
     V.lin_wgrad(A(sv.dqkv), 3 * Hb, A(x.v.x), D.Hv, p.qkv1, Mv, true, WgQ8{dqkvq_v, x.v});
@@ -959,7 +1004,7 @@ struct Run {
     const Drop dt = drop(D.p_hidden, 1);
     ++tick;
     if (!rc) fail(crct_embed_input_grad(A(gt), A(e->eta.sum), F(e->eta.mean), F(e->eta.rstd), P(e->et.ln.g), b->loc, P(e->et.wloc), nullptr,
-                                        e->ig.d_txt_loc, nullptr, e->ig.d_text_emb, b->B * b->T, D.H, dt.thr, dt.scale, dt.site, c->seed, s));
+                                        e->req.ig.d_txt_loc, nullptr, e->req.ig.d_text_emb, b->B * b->T, D.H, dt.thr, dt.scale, dt.site, c->seed, s));
   }
   // ... image rows: d_loc and d_areas from the row kernel; the features' gradient through new_image_embeddings and the softmax:
   // g[Mv][Fv] = d_sum W as fp32 (its bf16 rounding would sit in front of the softmax backward's cancelling difference) from the bf16
@@ -968,19 +1013,19 @@ struct Run {
     const CrctModelDims& D = e->d;
     const int Mv = b->B * b->V;
     const Drop dv = drop(D.p_hidden, 2);
-    if (e->ig.d_image_loc || e->ig.d_areas) {
+    if (e->req.ig.d_image_loc || e->req.ig.d_areas) {
       ++tick;
       if (!rc) fail(crct_embed_input_grad(A(gv), A(e->eva.sum), F(e->eva.mean), F(e->eva.rstd), P(e->ev.ln.g), nullptr, P(e->ev.wloc),
-                                          e->ig.d_areas ? P(e->ev.areas.w) : nullptr, e->ig.d_image_loc, e->ig.d_areas, nullptr, Mv, D.Hv,
+                                          e->req.ig.d_areas ? P(e->ev.areas.w) : nullptr, e->req.ig.d_image_loc, e->req.ig.d_areas, nullptr, Mv, D.Hv,
                                           dv.thr, dv.scale, dv.site, c->seed, s));
     }
-    if (!e->ig.d_image_feat) return;
+    if (!e->req.ig.d_image_feat) return;
     const StreamScratch& sc = *sets[parity];               // the set embed_image_bwd has just written (layer_begin does not advance it)
     float* g = F(e->ws_base());
     Opt o; o.f32 = true;
     lin_dgrad(A(sc.gc), D.Hv, e->ev.img, Mv, g, D.Fv, o);
     ++tick;
-    if (!rc) fail(crct_softmax_bwd_rows(b->image_feat, b->image_feat_bf16, g, e->ig.d_image_feat, Mv, D.Fv, s));
+    if (!rc) fail(crct_softmax_bwd_rows(b->image_feat, b->image_feat_bf16, g, e->req.ig.d_image_feat, Mv, D.Fv, s));
   }
 
   // ---------------------------------------------------------------- heads
@@ -1087,7 +1132,7 @@ struct Run {
     {
       CrctHeadArgs h;
       fill_head_args(h, logits, reg, stats, true);
-      if (!rc) fail(head_loss(h, e->sg.d_logits || e->sg.d_value ? &e->sg : nullptr));
+      if (!rc) fail(head_loss(h, e->req.sg.d_logits || e->req.sg.d_value ? &e->req.sg : nullptr));
     }
     if (rc) return;
     if (!V.rc) V.fail(order_streams(e, s, V.s));                              // d_pooled_v is ready
@@ -1132,12 +1177,12 @@ struct Run {
   // produces that gradient.  Called at both exits of heads_bwd; without a request it launches nothing.
   void output_grads(Run& V, size_t gt, size_t gv) {
     const SegPlan& pl = e->plan[0];
-    if (e->og.d_seq_t && pl.dx_t && !rc) {
-      fail(crct_hidden_grad_add(A(gt), e->og.d_seq_t, c->grad_scale, (int64_t)b->B * b->T * e->d.H, s));
+    if (e->req.og.d_seq_t && pl.dx_t && !rc) {
+      fail(crct_hidden_grad_add(A(gt), e->req.og.d_seq_t, c->grad_scale, (int64_t)b->B * b->T * e->d.H, s));
       ++tick;
     }
-    if (e->og.d_seq_v && pl.dx_v && !V.rc) {
-      V.fail(crct_hidden_grad_add(V.A(gv), e->og.d_seq_v, c->grad_scale, (int64_t)b->B * b->V * e->d.Hv, V.s));
+    if (e->req.og.d_seq_v && pl.dx_v && !V.rc) {
+      V.fail(crct_hidden_grad_add(V.A(gv), e->req.og.d_seq_v, c->grad_scale, (int64_t)b->B * b->V * e->d.Hv, V.s));
       ++V.tick;
     }
   }
@@ -1177,8 +1222,8 @@ void replan(crct_engine* e) {
                  e->grad_at(e->ev.bloc) || ln(e->ev.ln);
   e->emb_own_t = below_t; e->emb_own_v = below_v;
   // a requested input gradient counts as something with gradient below the embeddings of its stream (crct_engine_set_input_grads)
-  below_t = below_t || e->ig_text();
-  below_v = below_v || e->ig_vis();
+  below_t = below_t || e->req.ig_text();
+  below_v = below_v || e->req.ig_vis();
   SegPlan& emb = e->plan[nseg - 1];
   emb.runs = below_t || below_v; emb.dx_t = below_t; emb.dx_v = below_v;
   emb.dropped = (e->feat && below_v) ? drops(e->ev.img, false) : 0;      // (also when the half runs for an input gradient alone)
@@ -1418,8 +1463,8 @@ extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, 
     a.proj_t.a32 = ar.take(Mt * D.H * 4); a.ffn_t.y32 = ar.take(Mt * D.H * 4);
   }
   e->ws_two_output = ar.top;
-  e->ws_ig = e->feat ? align_up(Mv * D.Fv * 4, 256) : 0;
-  e->ws_amg = align_up((size_t)max_B * std::max(D.heads, std::max(D.v_heads, D.b_heads)) * std::max(max_T, max_V) * 3 * 4, 256);
+  e->req.ws_ig = e->feat ? align_up(Mv * D.Fv * 4, 256) : 0;
+  e->req.ws_amg = align_up((size_t)max_B * std::max(D.heads, std::max(D.v_heads, D.b_heads)) * std::max(max_T, max_V) * 3 * 4, 256);
   e->ws_update();
 
   // ---- the hidden states every schedule step starts from (the last entry: the encoder's outputs), and the taps on them
@@ -1483,24 +1528,22 @@ extern "C" int crct_engine_set_areas(crct_engine_t* e, const float* areas) {
 
 extern "C" int crct_engine_set_input_grads(crct_engine_t* e, const CrctInputGrads* req) {
   CRCT_REQUIRE(e, "engine_set_input_grads: null engine");
-  const CrctInputGrads none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  const CrctInputGrads r = req ? *req : none;
+  const CrctInputGrads r = req ? *req : Requests().ig;
   CRCT_REQUIRE(!r.d_image_feat || e->feat, "engine_set_input_grads: d_image_feat: the 'dvqa' / 'figure_qa' image embeddings never read the features (vilbert.py:1481-1483)");
   CRCT_REQUIRE(!r.d_areas || !e->feat, "engine_set_input_grads: d_areas: the 'plotqa' image embeddings have no areas term (vilbert.py:1463-1465)");
-  const bool changed = (r.d_txt_loc || r.d_text_emb) != e->ig_text() || (r.d_image_feat || r.d_image_loc || r.d_areas) != e->ig_vis();
-  e->ig = r;
+  const bool text = e->req.ig_text(), vis = e->req.ig_vis();
+  e->req.ig = r;
   e->ws_update();
-  if (changed) replan(e);
+  if (text != e->req.ig_text() || vis != e->req.ig_vis()) replan(e);      // a requested input gradient keeps its stream's segments running
   return 0;
 }
 
 extern "C" int crct_engine_set_score_grads(crct_engine_t* e, const CrctScoreGrads* req) {
   CRCT_REQUIRE(e, "engine_set_score_grads: null engine");
-  const CrctScoreGrads none = {nullptr, nullptr};
-  const CrctScoreGrads r = req ? *req : none;
+  const CrctScoreGrads r = req ? *req : Requests().sg;
   CRCT_REQUIRE(!r.d_value || e->var.regressor == CRCT_REGRESSOR_PLOTQA, "engine_set_score_grads: d_value: only the PlotQA regressor's value has a gradient (this engine's regressor is %s)",
                e->var.regressor == CRCT_REGRESSOR_CE ? "the CE table lookup" : "absent");
-  e->sg = r;                        // read by heads_bwd alone: the plan does not depend on it
+  e->req.sg = r;
   return 0;
 }
 
@@ -1508,32 +1551,20 @@ extern "C" int crct_engine_set_attention_map_grads(crct_engine_t* e, const CrctA
   CRCT_REQUIRE(e, "engine_set_attention_map_grads: null engine");
   CRCT_REQUIRE(n >= 0 && (req || n == 0), "engine_set_attention_map_grads: %d requests without an array", n);
   for (int i = 0; req && i < n; ++i) {
-    const CrctAttnMapGrad& r = req[i];
-    if (r.kind == 0 || r.kind == 1) {
-      const int layers = (int)(r.kind == 0 ? e->tl : e->vl).size();
-      CRCT_REQUIRE(r.index >= 0 && r.index < layers, "engine_set_attention_map_grads: %s layer %d out of range [0,%d)", r.kind == 0 ? "text" : "visual",
-                   r.index, layers);
-      CRCT_REQUIRE(r.direction == 0, "engine_set_attention_map_grads: direction %d belongs to connection layers (kind 2)", r.direction);
-    } else {
-      CRCT_REQUIRE(r.kind == 2, "engine_set_attention_map_grads: unknown kind %d (0 text, 1 visual, 2 connection layer)", r.kind);
-      const int layers = e->d.with_coattention ? (int)e->cl.size() : 0;
-      CRCT_REQUIRE(r.index >= 0 && r.index < layers, "engine_set_attention_map_grads: connection layer %d out of range [0,%d)", r.index, layers);
-      CRCT_REQUIRE(r.direction == 0 || r.direction == 1, "engine_set_attention_map_grads: direction %d must be 0 (text over visual) or 1 (visual over text)",
-                   r.direction);
-    }
-    CRCT_REQUIRE(r.d_probs && (uintptr_t)r.d_probs % 4 == 0, "engine_set_attention_map_grads: request %d: d_probs must be a 4-byte aligned device buffer", i);
+    AttnSite at;
+    if (int r = e->attn_site("engine_set_attention_map_grads", req[i].kind, req[i].index, req[i].direction, 1, 1, &at)) return r;
+    CRCT_REQUIRE(req[i].d_probs && (uintptr_t)req[i].d_probs % 4 == 0, "engine_set_attention_map_grads: request %d: d_probs must be a 4-byte aligned device buffer", i);
   }
-  e->amg.assign(req, req + (req ? n : 0));      // read by self_bwd / conn_bwd alone: the plan does not depend on it
+  e->req.amg.assign(req, req + (req ? n : 0));
   e->ws_update();
   return 0;
 }
 
 extern "C" int crct_engine_set_output_grads(crct_engine_t* e, const CrctOutputGrads* req) {
   CRCT_REQUIRE(e, "engine_set_output_grads: null engine");
-  const CrctOutputGrads none = {nullptr, nullptr};
-  const CrctOutputGrads r = req ? *req : none;
+  const CrctOutputGrads r = req ? *req : Requests().og;
   CRCT_REQUIRE((((uintptr_t)r.d_seq_t | (uintptr_t)r.d_seq_v) & 15) == 0, "engine_set_output_grads: d_seq_t / d_seq_v must be 16-byte aligned");
-  e->og = r;      // read by segment 0 of crct_engine_backward only; the plan does not depend on it
+  e->req.og = r;
   return 0;
 }
 
@@ -1698,9 +1729,9 @@ extern "C" int crct_engine_forward(crct_engine_t* e, const float* params_f32, co
     Rt.phase = (e->first_conn < 0 || (int)i < e->first_conn) ? 0 : 1;      // text-only prefix: nothing else on the data path
     if (st.kind != 'v') wait_params(Rt, seg);
     if (st.kind != 't') wait_params(Rv, seg);
-    if (st.kind == 't') Rt.self_fwd(e->tl[st.idx], e->tla[st.idx], x.t, batch->text_keymask, batch->B, batch->T);
-    else if (st.kind == 'v') Rv.self_fwd(e->vl[st.idx], e->vla[st.idx], x.v, batch->image_keymask, batch->B, batch->V);
-    else Rt.conn_fwd(Rv, e->cl[st.idx], e->cla[st.idx], x);
+    if (st.kind == 't') Rt.self_fwd(st.idx, x.t);
+    else if (st.kind == 'v') Rv.self_fwd(st.idx, x.v);
+    else Rt.conn_fwd(Rv, st.idx, x);
   }
   Rt.phase = 1;
   wait_params(Rt, 0);
@@ -1718,8 +1749,8 @@ extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, c
   CRCT_REQUIRE(e && params_f32 && params_bf16 && cfg && workspace && grads_f32 && logits && reg && stats, "engine_backward: null argument");
   CRCT_REQUIRE(batch && batch->labels, "engine_backward: labels are required (training step)");
   if (int r = check_batch(e, batch)) return r;
-  CRCT_REQUIRE(!e->ig.d_areas || e->areas, "engine_backward: d_areas is requested (crct_engine_set_input_grads) but the batch has no areas (crct_engine_set_areas)");
-  CRCT_REQUIRE(e->amg.empty() || !cfg->fp8_bwd, "engine_backward: attention-map gradients are requested (crct_engine_set_attention_map_grads) with fp8_bwd=%d: "
+  CRCT_REQUIRE(!e->req.ig.d_areas || e->areas, "engine_backward: d_areas is requested (crct_engine_set_input_grads) but the batch has no areas (crct_engine_set_areas)");
+  CRCT_REQUIRE(e->req.amg.empty() || !cfg->fp8_bwd, "engine_backward: attention-map gradients are requested (crct_engine_set_attention_map_grads) with fp8_bwd=%d: "
                "the e5m2 copies of dqkv are written by the attention backward itself and would go stale", cfg->fp8_bwd);
   if (int r = ensure_streams(e, (hipStream_t)stream)) return r;
   e->evnext = 0;
@@ -1753,16 +1784,16 @@ extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, c
       // each half: the parameter gradients where a tensor of the embedding has one -- the image half of 'plotqa' also for a requested
       // feature gradient, whose GEMM reads the bf16 d_sum that kernel stores -- then the requested input gradients on the same stream
       if (pl.dx_t && e->emb_own_t) Rt.embed_text_bwd(e->st.dy[e->cur_t]);
-      if (pl.dx_t && e->ig_text()) Rt.embed_text_input_grads(e->st.dy[e->cur_t]);
-      if (pl.dx_v && (e->emb_own_v || e->ig.d_image_feat)) Rv.embed_image_bwd(e->sv.dy[e->cur_v]);
-      if (pl.dx_v && e->ig_vis()) Rv.embed_image_input_grads(e->sv.dy[e->cur_v]);
+      if (pl.dx_t && e->req.ig_text()) Rt.embed_text_input_grads(e->st.dy[e->cur_t]);
+      if (pl.dx_v && (e->emb_own_v || e->req.ig.d_image_feat)) Rv.embed_image_bwd(e->sv.dy[e->cur_v]);
+      if (pl.dx_v && e->req.ig_vis()) Rv.embed_image_input_grads(e->sv.dy[e->cur_v]);
     } else {
       const Step& st = e->sched[si];
       const StepIn& x = e->in[si];
       const size_t gt = e->st.dy[e->cur_t], gxt = e->st.dy[e->cur_t ^ 1], gv = e->sv.dy[e->cur_v], gxv = e->sv.dy[e->cur_v ^ 1];
-      if (st.kind == 't') Rt.self_bwd(e->tl[st.idx], e->tla[st.idx], x.t, gt, gxt, batch->text_keymask, batch->B, batch->T, pl.dx_t);
-      else if (st.kind == 'v') Rv.self_bwd(e->vl[st.idx], e->vla[st.idx], x.v, gv, gxv, batch->image_keymask, batch->B, batch->V, pl.dx_v);
-      else Rt.conn_bwd(Rv, e->cl[st.idx], e->cla[st.idx], x, gv, gt, gxv, gxt, pl.dx_v, pl.dx_t);
+      if (st.kind == 't') Rt.self_bwd(st.idx, x.t, gt, gxt, pl.dx_t);
+      else if (st.kind == 'v') Rv.self_bwd(st.idx, x.v, gv, gxv, pl.dx_v);
+      else Rt.conn_bwd(Rv, st.idx, x, gv, gt, gxv, gxt, pl.dx_v, pl.dx_t);
       if (st.kind != 'v') e->cur_t ^= 1;
       if (st.kind != 't') e->cur_v ^= 1;
     }
@@ -1918,44 +1949,16 @@ extern "C" int64_t crct_engine_attention_probs(crct_engine_t* e, const CrctBatch
                                                int index, int direction, float* out, int64_t cap, crct_stream_t stream) {
   if (!e || !cfg || !workspace || !out) { crct_set_error("engine_attention_probs: null argument"); return -1; }
   if (check_batch(e, batch)) return -1;
-  const CrctModelDims& D = e->d;
+  AttnSite a;
+  if (e->attn_site("engine_attention_probs", kind, index, direction, batch->T, batch->V, &a)) return -1;
   const char* ws = (const char*)workspace;
-  // the key masks as crct_engine_backward resolves them: the caller's, else the ones the forward built in the workspace
-  const uint8_t* km_t = batch->text_keymask ? batch->text_keymask : (const uint8_t*)ws + e->km_t;
-  const uint8_t* km_v = batch->image_keymask ? batch->image_keymask : (const uint8_t*)ws + e->km_v;
-  const int B = batch->B, T = batch->T, V = batch->V;
-  const bf16_t* q = nullptr;
-  const bf16_t* k = nullptr;
-  const uint8_t* km = nullptr;
-  int heads = 0, Tq = 0, Tk = 0, H = 0;
-  float p = 0.f;
-  uint32_t site = 0;
-  if (kind == 0 || kind == 1) {
-    const std::vector<SelfLayerP>& lp = kind == 0 ? e->tl : e->vl;
-    const std::vector<SelfLayerA>& la = kind == 0 ? e->tla : e->vla;
-    if (index < 0 || index >= (int)lp.size()) { crct_set_error("engine_attention_probs: %s layer %d out of range [0,%d)", kind == 0 ? "text" : "visual", index, (int)lp.size()); return -1; }
-    if (direction != 0) { crct_set_error("engine_attention_probs: direction %d belongs to connection layers (kind 2)", direction); return -1; }
-    H = lp[index].H; heads = lp[index].heads; Tq = Tk = kind == 0 ? T : V;
-    q = (const bf16_t*)(ws + la[index].qkv); k = q + H;
-    km = kind == 0 ? km_t : km_v;
-    p = lp[index].p_attn; site = lp[index].site;
-  } else if (kind == 2) {
-    if (index < 0 || index >= (int)e->cl.size() || !D.with_coattention) { crct_set_error("engine_attention_probs: connection layer %d out of range [0,%d)", index, D.with_coattention ? (int)e->cl.size() : 0); return -1; }
-    if (direction != 0 && direction != 1) { crct_set_error("engine_attention_probs: direction %d must be 0 (text over visual) or 1 (visual over text)", direction); return -1; }
-    const ConnLayerA& a = e->cla[index];
-    H = D.Hb; heads = D.b_heads;
-    const bf16_t* qkv1 = (const bf16_t*)(ws + a.qkv1);      // visual stream
-    const bf16_t* qkv2 = (const bf16_t*)(ws + a.qkv2);      // text stream
-    if (direction == 0) { q = qkv2; k = qkv1 + H; km = km_v; Tq = T; Tk = V; p = D.p_v_attn; site = e->cl[index].site; }
-    else { q = qkv1; k = qkv2 + H; km = km_t; Tq = V; Tk = T; p = D.p_attn; site = e->cl[index].site + 1; }
-  } else {
-    crct_set_error("engine_attention_probs: unknown kind %d (0 text, 1 visual, 2 connection layer)", kind);
-    return -1;
-  }
-  const int64_t n = (int64_t)B * heads * Tq * Tk;
+  // the key mask as crct_engine_backward resolves it: the caller's, else the one the forward built in the workspace
+  const uint8_t* km = a.image_keys ? (batch->image_keymask ? batch->image_keymask : (const uint8_t*)ws + e->km_v)
+                                   : (batch->text_keymask ? batch->text_keymask : (const uint8_t*)ws + e->km_t);
+  const int64_t n = (int64_t)batch->B * a.heads * a.Tq * a.Tk;
   if (n > cap) { crct_set_error("engine_attention_probs: %lld elements do not fit the buffer of %lld", (long long)n, (long long)cap); return -1; }
-  Drop dr;
-  if (cfg->training && p > 0.f) { dr.thr = thr_of(p); dr.scale = 1.0f / (1.0f - p); }
-  if (crct_attention_probs(q, k, km, out, B, heads, Tq, Tk, H / heads, 3 * H, 3 * H, dr.thr, dr.scale, site, cfg->seed, stream)) return -1;
+  const Drop dr = drop_of(cfg, a.p, a.site);
+  if (crct_attention_probs((const bf16_t*)(ws + a.q), (const bf16_t*)(ws + a.k), km, out, batch->B, a.heads, a.Tq, a.Tk, a.d, a.ld, a.ld, dr.thr, dr.scale,
+                           dr.site, cfg->seed, stream)) return -1;
   return n;
 }

@@ -500,3 +500,82 @@ def test_requests_a_variant_cannot_serve_are_refused_before_any_launch():
         lib.crct_prof_enable(0)
         lib.crct_prof_reset()
         eng.set_input_grads()
+
+
+# ------------------------------------------------------------------------------------------------ the request manager
+def _frozen_text_embeddings_tiny():
+    """_tiny() with the text embeddings frozen: without a request the embeddings segment leaves its text half out, so the backward plan
+    shows whether a text input request stands."""
+    cfg, model, params, core, batch = _tiny()
+    for k, p in core.named_parameters():
+        if k.startswith("bert.embeddings."):
+            p.requires_grad_(False)
+    return cfg, model, params, core, batch
+
+
+def _same_step(core, a, b):
+    (na, outa, ga), (nb, outb, gb) = a, b
+    assert na == nb and all(torch.equal(bits(x), bits(y)) for x, y in zip(outa, outb))
+    for e in core.table:
+        if not e.used or e.name in core.tensors_without_grad:
+            continue
+        x, y = ga[e.offset:e.offset + e.numel], gb[e.offset:e.offset + e.numel]
+        if e.name in ATOMIC_GRADS:
+            assert torch.allclose(x, y, rtol=1e-3, atol=1e-6), e.name
+        else:
+            assert torch.equal(bits(x), bits(y)), e.name
+
+
+def test_requests_clear_exactly_what_they_set_also_when_the_body_raises():
+    """``StepEngine.requests`` holding all four families, left by an exception: the library reports the workspace size it reported before
+    (the tensor itself keeps what it grew to, enough for the same requests again), the backward plan is the one from before, no buffer
+    is held any more, and the next plain step has the launches and the bits of that step on a fresh model.  Entered with the scores
+    alone, it leaves a standing input request alone: the plan keeps the text half of the embeddings, and a plain pass writes the buffer."""
+    cfg, model, params, core, batch = _frozen_text_embeddings_tiny()
+    first = _counted_step(model, params, core, batch)
+    eng = core._engine
+    nbytes = lambda: eng.lib.crct_engine_workspace_bytes(eng.handle)
+    ws0, plan0 = nbytes(), eng.backward_plan()
+    assert plan0[-1][:3] == (True, False, True), plan0[-1]
+    B, T, V = 3, 9, 5
+    new = lambda *shape: torch.zeros(*shape, device=DEV)
+    families = dict(input_grads=dict(image_feat=new(B, V, cfg.v_feature_size), txt_loc=new(B, T, 4)),
+                    output_grads=dict(seq_t=new(B, T, cfg.hidden_size), seq_v=new(B, V, cfg.v_hidden_size)),
+                    score_grads=dict(logits=new(B, 2), value=new(B)),
+                    attention_map_grads=[("conn", 0, 1, new(B, cfg.bi_num_attention_heads, V, T)), ("text", 1, 0, new(B, cfg.num_attention_heads, T, T))])
+
+    class Boom(Exception):
+        pass
+    seen = {}
+    with pytest.raises(Boom):
+        with eng.requests(**families):
+            seen.update(ws=nbytes(), plan=eng.backward_plan(), held=(eng._input_grads[0], eng._output_grads[0], eng._score_grads[0], len(eng._map_grads)))
+            raise Boom()
+    assert seen["ws"] > ws0 and eng.workspace.numel() >= seen["ws"]
+    assert seen["plan"][-1][:3] == (True, True, True) and seen["plan"] != plan0
+    assert seen["held"][0] is families["input_grads"]["image_feat"] and seen["held"][1] is families["output_grads"]["seq_t"]
+    assert seen["held"][2] is families["score_grads"]["logits"] and seen["held"][3] == 2
+    assert nbytes() == ws0 and eng.workspace.numel() >= seen["ws"]                         # reported size back; the tensor did not shrink
+    assert eng.backward_plan() == plan0
+    assert eng._input_grads == (None,) * 5 and eng._output_grads == (None, None) and eng._score_grads == (None, None) and eng._map_grads == []
+    numel = eng.workspace.numel()
+    with eng.requests(**families):                                                       # the same requests again: nothing left to grow
+        assert nbytes() == seen["ws"] and eng.workspace.numel() == numel
+    again = _counted_step(model, params, core, batch)
+    _same_step(core, first, again)
+    _, fmodel, fparams, fcore, _ = _frozen_text_embeddings_tiny()
+    _same_step(core, _counted_step(fmodel, fparams, fcore, batch), again)
+    # the manager clears exactly what it set
+    loc_buf = torch.full((B, T, 4), float("nan"), device=DEV)
+    eng.set_input_grads(txt_loc=loc_buf)
+    try:
+        held, plan_req = eng._input_grads, eng.backward_plan()
+        assert plan_req[-1][:3] == (True, True, True)
+        with eng.requests(score_grads=dict(logits=families["score_grads"]["logits"])):
+            assert eng._score_grads[0] is families["score_grads"]["logits"] and eng._input_grads is held
+        assert eng._score_grads == (None, None) and eng._input_grads is held and eng.backward_plan() == plan_req
+        _counted_step(model, params, core, batch)                                        # a plain pass: the standing request is served
+        assert bool(torch.isfinite(loc_buf).all())                                       # every element written over its NaN
+    finally:
+        eng.set_input_grads()
+    assert eng.backward_plan() == plan0 and nbytes() == ws0
