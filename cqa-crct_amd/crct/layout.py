@@ -14,7 +14,8 @@ Layout rules (MI355X-first):
     them as one [3H, H] operand, while ``state_dict`` still exposes the reference's separate keys;
   * every tensor starts on a 64-element boundary (256 B fp32 / 128 B bf16);
   * parameters that never receive a gradient on this path (biOutput.q_dense1/2,
-    cls.predictions.*, cls.imagePredictions.*, v_embeddings.type_embeddings) sit at the end.
+    cls.predictions.*, cls.imagePredictions.*, v_embeddings.type_embeddings) sit at the end; the masked-LM head
+    (cls.predictions.{bias, transform.*}) stays there when params['lm_loss_coeff'] > 0 makes it live: only its ``used`` flags change.
 """
 import math
 from collections import namedtuple
@@ -188,8 +189,16 @@ def is_unused(name, params=None):
     if params is not None and model_variant(params)[0] != "plotqa":
         if name.startswith("bert.v_embeddings.new_image_embeddings.") or name == "bert.v_embeddings.sep_emb.weight":
             return True
-    return (".biOutput.q_dense" in name or name.startswith("cls.predictions.") or name.startswith("cls.imagePredictions.")
+    if name.startswith("cls.predictions."):
+        # the masked-LM head: live with params['lm_loss_coeff'] > 0 (its offsets are those of the dead tensors: the tail of the buffers)
+        return lm_loss_coeff(params) <= 0.0
+    return (".biOutput.q_dense" in name or name.startswith("cls.imagePredictions.")
             or name == "bert.v_embeddings.type_embeddings.weight")
+
+
+def lm_loss_coeff(params):
+    """params['lm_loss_coeff'] (encoder_decorator.py:148-150); absent, None or 0: the masked-LM loss is off."""
+    return float((params or {}).get("lm_loss_coeff", 0.0) or 0.0)
 
 
 def optional_grad(name):

@@ -238,6 +238,13 @@ PROTOTYPES = {
     "crct_softmax_bwd_rows": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp]),
     "crct_layernorm_rows_f32": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
     "crct_hidden_grad_add": (C.c_int, [vp, vp, c_f32, c_i64, vp]),
+    "crct_lm_gather_rows": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "crct_lm_scatter_rows": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+    "crct_lm_pad_operands": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "crct_lm_ce_fwd": (C.c_int, [vp, c_i64, vp, vp, vp, vp, C.c_int, C.c_int, c_f32, vp]),
+    "crct_lm_ce_bwd": (C.c_int, [vp, c_i64, vp, vp, vp, c_f32, vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "crct_lm_add_f32": (C.c_int, [vp, vp, c_i64, C.c_int, vp]),
+    "crct_lm_gelu_bwd": (C.c_int, [vp, vp, vp, c_i64, vp]),
     "crct_engine_sequence_outputs": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "crct_engine_set_output_grads": (C.c_int, [vp, C.POINTER(OutputGrads)]),
     "crct_engine_set_score_grads": (C.c_int, [vp, C.POINTER(ScoreGrads)]),

@@ -24,7 +24,7 @@ from . import ops
 from .config import BertConfig
 from .engine import StepEngine
 from .fp8 import AMAX_WINDOW, Fp8State
-from .layout import frozen_tensors, is_frozen, model_variant, optional_grad, parameter_table
+from .layout import frozen_tensors, is_frozen, lm_loss_coeff, model_variant, optional_grad, parameter_table
 
 
 class _Node(nn.Module):
@@ -73,7 +73,8 @@ class _StepFn(torch.autograd.Function):
             out.extend(ts)
             return slice(len(out) - 6 - len(ts), len(out) - 6)
         # the encoder's final hidden states, fresh fp32 tensors (StepEngine.sequence_outputs)
-        seq = family(eng.sequence_outputs() if model.return_sequence_outputs else ())
+        # (also what the masked-LM head reads: _LmLossFn hangs on sequence_output_t, so its gradient comes back as that output's upstream)
+        seq = family(eng.sequence_outputs() if model.return_sequence_outputs or model._lm_pending is not None else ())
         # the logits, and the PlotQA regressor's value: tensors of their own (two B-sized copies)
         with_value = model.variant[1] == "plotqa"
         scores = family([t.clone() for t in ((logits, reg_all[0]) if with_value else (logits,))] if model.differentiable_scores else ())
@@ -116,6 +117,31 @@ class _StepFn(torch.autograd.Function):
             step["g_nsp"] = (gn + gl * step["nsp_coeff"]).contiguous()
             step["g_reg"] = (gr + gl * (step["reg_coeff"] / B)).contiguous()
         return (None, None, None, None) + model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8], requests)
+
+
+# One batch's masked rows as the masked-LM head takes them: flat row indices into [B * T] and their labels (int32, on the device, one
+# pinned upload), R of them, 1 / n
+_LmJob = collections.namedtuple("_LmJob", "rows labels R inv_n")
+
+
+class _LmLossFn(torch.autograd.Function):
+    """The masked-LM loss (params['lm_loss_coeff'] > 0) as a node of its own on ``sequence_output_t``, the differentiable output of
+    ``_StepFn``: forward = ``CrctModel._lm_forward`` (gather, transform, vocabulary projection, cross-entropy over the R masked rows),
+    backward = ``CrctModel._lm_backward``, which accumulates the head's parameter gradients and the decoder term of the word table into
+    the flat gradient buffer and RETURNS d lm_loss / d sequence_output_t -- autograd hands it to ``_StepFn.backward`` as the upstream
+    gradient of that output, i.e. through the engine's output-gradient request, so the text stream, the co-attention and any
+    requested input gradient see it.  The upstream gradient of the loss (a GradScaler's scale, a caller's weight) is a device scalar
+    the gradient kernel reads: no ``.item()``."""
+
+    @staticmethod
+    def forward(ctx, seq_t, model, job):
+        lm_loss, ctx.saved = model._lm_forward(seq_t, job)
+        ctx.model, ctx.job, ctx.shape = model, job, seq_t.shape
+        return lm_loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.model._lm_backward(ctx.job, ctx.saved, ctx.shape, g), None, None
 
 
 def _upstream_f32(g):
@@ -232,6 +258,17 @@ class CrctModel(nn.Module):
         # (params['fp8_backward']).  The return tuples are unchanged.
         self.attention_map_outputs = ()
         self.attention_maps = {}
+        # params['lm_loss_coeff'] > 0: the masked-LM objective (encoder_decorator.py:148-150, vilbert.py:1016-1037).  In the training
+        # branch slot 0 of the tuple is then lm_loss = mean over the n tokens with masked_lm_labels >= 0 of logsumexp(logits) - logits[label],
+        # fp32 [1, 1], differentiable under grad; the five cls.predictions.* head tensors and the word table (the tied decoder) get
+        # gradients.  The labels are taken where the loader leaves them, on the HOST (a device tensor costs one .cpu() per step): the row
+        # list is compacted there and uploaded with one pinned copy, every launch is sized by it.  No label (n == 0): the constant zero of
+        # the stub and no launch -- torch's CrossEntropyLoss gives NaN there.  The head runs in bf16, also with params['fp8'].
+        # Its Linear weight gradient is always accumulated (the lazy clear zeroes it like a bias).
+        self.lm_loss_coeff = lm_loss_coeff(params)
+        self._lm_pending = None
+        self._lm_pad, self._lm_pad_gen, self._shadow_gen = None, -1, 0
+        self._lm_host, self._lm_upload_done = None, None
         self.init_weights(int(params.get("seed", 0)))
         self.register_load_state_dict_post_hook(lambda m, k: m._invalidate_shadow())
 
@@ -294,6 +331,7 @@ class CrctModel(nn.Module):
         if self._shadow_ver != v:
             ops.cast_bf16(self._flat_p, out=self._flat_b16)
             self._shadow_ver = v
+            self._shadow_gen += 1
             if self._fp8 is not None:
                 self._fp8.requantize(self._flat_p, L.current_stream())
 
@@ -325,6 +363,7 @@ class CrctModel(nn.Module):
             self._const_zeros = None
             self._param_events = None
             self._opt_stream = None
+            self._lm_pad, self._lm_pad_gen = None, -1
             self._rebind()
         return self
 
@@ -357,6 +396,7 @@ class CrctModel(nn.Module):
     def note_params_updated_natively(self):
         """Called by the fused optimizer, which rewrites the flat buffers and the shadow itself."""
         self._shadow_ver = self._param_version()
+        self._shadow_gen += 1        # (native writes move no torch version counter: what follows the shadow -- the LM head's padded table -- counts these)
 
     def zero_flat_grads(self, lazy=False):
         """Clear the gradients.  ``lazy``: only the gradients that backward ACCUMULATES into (biases, LayerNorm, embeddings,
@@ -611,6 +651,108 @@ class CrctModel(nn.Module):
             d_feat = d_feat.to(tensors["image_feat"].dtype)
         return d_feat, d_iloc, d_tloc, d_areas
 
+    # ------------------------------------------------------------------ masked-LM head (csrc/lm_head.hip; see lm_loss_coeff above)
+    LM_HEAD = ("cls.predictions.bias", "cls.predictions.transform.dense.weight", "cls.predictions.transform.dense.bias",
+               "cls.predictions.transform.LayerNorm.weight", "cls.predictions.transform.LayerNorm.bias")
+    WORD_TABLE = "bert.embeddings.word_embeddings.weight"
+
+    def _lm_job(self, masked_lm_labels):
+        """Host side of one batch's masked-LM loss, before any launch: the labels are checked (-1 = no label, else a token id), the rows
+        with a label are compacted and (rows | labels) go up in one pinned, asynchronous copy.  None when no token has a label."""
+        lab = masked_lm_labels
+        if lab.is_cuda:
+            lab = lab.cpu()                                   # the loader leaves them on the host (encoder_decorator.py:85); this is a sync
+        lab = lab.reshape(-1).to(torch.int64)
+        V = self.config.vocab_size
+        if bool(((lab >= V) | (lab < -1)).any()):
+            bad = lab[(lab >= V) | (lab < -1)]
+            raise ValueError("masked_lm_labels: %d is neither -1 (no label) nor a token id below vocab_size = %d" % (int(bad[0]), V))
+        rows = (lab >= 0).nonzero().flatten()
+        R = int(rows.numel())
+        if R == 0:
+            return None
+        if self._lm_upload_done is not None:
+            self._lm_upload_done.synchronize()                # the staging buffer is free again (long done in practice)
+        if self._lm_host is None or self._lm_host.numel() < 2 * R:
+            self._lm_host = torch.empty(max(2 * R, 4096), dtype=torch.int32).pin_memory()
+        self._lm_host[:R] = rows
+        self._lm_host[R:2 * R] = lab[rows]
+        dev = torch.empty(2 * R, dtype=torch.int32, device=self._flat_p.device)
+        dev.copy_(self._lm_host[:2 * R], non_blocking=True)
+        if self._lm_upload_done is None:
+            self._lm_upload_done = torch.cuda.Event()
+        self._lm_upload_done.record()
+        return _LmJob(dev[:R], dev[R:], R, 1.0 / R)
+
+    def _flat_view(self, flat, name):
+        e = self._entries[name]
+        return flat[e.offset:e.offset + e.numel].view(e.shape)
+
+    def _lm_operands(self):
+        """(bf16 [Vp, H] copy of the word table's bf16 shadow with zero pad rows, fp32 [Vp] padded bias), refreshed whenever the shadow was."""
+        if self._lm_pad is None or self._lm_pad_gen != self._shadow_gen:
+            self._lm_pad = ops.lm_pad_operands(self._flat_view(self._flat_b16, self.WORD_TABLE), self._flat_view(self._flat_p, self.LM_HEAD[0]),
+                                               *(self._lm_pad or ()))
+            self._lm_pad_gen = self._shadow_gen
+        return self._lm_pad
+
+    def _lm_forward(self, seq_t, job):
+        """lm_loss fp32 [1, 1] of the masked rows of ``seq_t`` (fp32 [B, T, H]) and what the backward needs.  z = LayerNorm(gelu(h W^T + b)),
+        logits = z E^T + bias on the padded operands (fp32 [Rp, Vp]), loss over the V real columns."""
+        if self._opt_stream is not None:             # an overlapped optimizer update may still be writing the head's weights and shadow
+            from .events import order_streams
+            order_streams(self._opt_stream, torch.cuda.current_stream())
+        H, V = self.config.hidden_size, self.config.vocab_size
+        _, w, b, gamma, beta = self.LM_HEAD
+        table, bias = self._lm_operands()
+        hb = ops.lm_gather_rows(seq_t.view(-1, H), job.rows, job.R)
+        Rp, Vp = hb.shape[0], table.shape[0]
+        pre = torch.empty(Rp, H, device=hb.device, dtype=torch.bfloat16)
+        a = ops.gemm(hb, self._flat_view(self._flat_b16, w), Rp, H, H, bias=self._flat_view(self._flat_p, b), act="gelu", preact_out=pre)
+        z, mean, rstd = ops.layernorm_fwd(a, self._flat_view(self._flat_p, gamma), self._flat_view(self._flat_p, beta), eps=1e-12)
+        logits = ops.gemm(z, table, Rp, Vp, H, bias=bias, out_f32=True)
+        _, lse, lm_loss = ops.lm_ce_fwd(logits, job.labels, job.R, V, job.inv_n)
+        return lm_loss, (hb, pre, a, mean, rstd, z, logits, lse, table)
+
+    def _lm_backward(self, job, saved, shape, g):
+        """Accumulates the gradients of the five head tensors and the decoder term of the word table (each only where the tensor has a
+        gradient) and returns d lm_loss / d sequence_output_t, fp32 ``shape``, zero outside the masked rows.  Runs before the engine's
+        backward pass of the same batch (autograd orders it so) and does that pass's bookkeeping on the gradient buffer first."""
+        hb, pre, a, mean, rstd, z, logits, lse, table = saved
+        if self._opt_stream is not None:
+            from .events import order_streams
+            order_streams(self._opt_stream, torch.cuda.current_stream())
+        self._ensure_grad_views()
+        self._grads_dirty = True
+        if self._wgrad_overwrite_next and not (self._lazy_plan_key is not None and self._engine.wgrad_owned_key() == self._lazy_plan_key):
+            self._flat_g.zero_()                     # (_run_backward would do this AFTER the head's gradients are in place)
+            self._wgrad_overwrite_next = False
+        H, V = self.config.hidden_size, self.config.vocab_size
+        Rp, Vp = logits.shape
+        bias, w, b, gamma, beta = self.LM_HEAD
+        live = lambda name: name not in self._nograd      # noqa: E731
+        # a data-parallel pass folds 1 / world into the gradient seeds (crct/ddp.py); the engine applies it to the upstream of
+        # sequence_output_t itself, so the row gradients handed back are taken out of it again
+        world = float(self._ddp.world) if self._ddp is not None and getattr(self._ddp, "world", 1) > 1 else 1.0
+        dL = ops.lm_ce_bwd(logits, job.labels, lse, g.reshape(1).float(), job.inv_n / world, job.R, V)
+        if live(bias):
+            ops.lm_add(self._flat_view(self._flat_g, bias), ops.colsum(dL, Rp, Vp), V, True)
+        if live(self.WORD_TABLE):
+            ops.lm_decoder_wgrad(dL, z, self._flat_view(self._flat_g, self.WORD_TABLE), V, True)
+        dz = ops.gemm(dL, table, Rp, H, Vp, tb=True)
+        dx = ops.layernorm_bwd(dz, a, mean, rstd, self._flat_view(self._flat_p, gamma),
+                               dgamma=self._flat_view(self._flat_g, gamma) if live(gamma) else None,
+                               dbeta=self._flat_view(self._flat_g, beta) if live(beta) else None, accumulate=True)[0]
+        dpre = ops.lm_gelu_bwd(dx, pre)
+        if live(w):
+            ops.gemm(dpre, hb, H, H, Rp, ta=True, tb=True, out=self._flat_view(self._flat_g, w), accumulate=True)
+        if live(b):
+            ops.colsum(dpre, Rp, H, out=self._flat_view(self._flat_g, b), accumulate=True)
+        dh = ops.gemm(dpre, self._flat_view(self._flat_b16, w), Rp, H, H, tb=True, out_f32=True, alpha=world)
+        d_seq = torch.zeros(shape, dtype=torch.float32, device=dh.device)
+        ops.lm_scatter_rows(dh, job.rows, d_seq.view(-1, H), job.R)
+        return d_seq
+
     def _device_inputs(self, input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
                        image_attention_mask, image_target, R, labels, areas=None):
         dev = self._flat_p.device
@@ -668,6 +810,8 @@ class CrctModel(nn.Module):
                                       "params['fp8_backward'] = False or leave attention_map_outputs empty")
         R, kind = gt_reg[0], gt_reg[1]
         train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
+        # the masked-LM loss of this batch (host work only; a bad label is refused here, before any launch); None: off, or no token has a label
+        lm_job = self._lm_job(masked_lm_labels) if train_branch and self.lm_loss_coeff > 0.0 else None
         tensors = self._device_inputs(input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
                                       image_attention_mask, image_target, R, next_sentence_label if train_branch else None, areas)
         B, T = tensors["tokens"].shape
@@ -695,7 +839,12 @@ class CrctModel(nn.Module):
                 tensors = dict(tensors, image_feat=live[0].detach(), image_loc=live[1].detach(), loc=live[2].detach())
                 if live[3] is not None:
                     tensors["areas"] = live[3].detach()
-            (loss, nsp, reg_loss, logits, reg, stats), seq, scores, maps = _StepFn.split(self, _StepFn.apply(self._anchor, self, tensors, step, *live))
+            self._lm_pending = lm_job
+            try:
+                (loss, nsp, reg_loss, logits, reg, stats), seq, scores, maps = _StepFn.split(self, _StepFn.apply(self._anchor, self, tensors, step, *live))
+            finally:
+                self._lm_pending = None
+            lm_loss = _LmLossFn.apply(seq[0], self, lm_job) if lm_job is not None else None
             value = scores[1] if len(scores) > 1 else None
             if scores:
                 logits = scores[0]                     # differentiable_scores: the copies that are part of the graph
@@ -704,7 +853,8 @@ class CrctModel(nn.Module):
             eng.forward(self._flat_p, self._flat_b16, tensors, step)
             logits, reg, stats = eng.snapshot(B)
             loss, nsp, reg_loss = stats[0], stats[1:2], reg[1]
-            seq = eng.sequence_outputs() if self.return_sequence_outputs else ()
+            seq = eng.sequence_outputs() if self.return_sequence_outputs or lm_job is not None else ()
+            lm_loss = self._lm_forward(seq[0], lm_job)[0] if lm_job is not None else None      # torch.no_grad() in the training branch: forward only
             maps = [eng.attention_probs(*key) for key in map_keys]
             if output_all_attention_masks and not train_branch:
                 attention_maps = self._attention_maps(eng)
@@ -725,9 +875,9 @@ class CrctModel(nn.Module):
             self._const_zeros = (torch.zeros(1, 1, device=dev), torch.zeros(1, 1, device=dev), torch.zeros(1, device=dev))
         lm_zero, img_zero, legend_loss = self._const_zeros
         # sequence_output_t in slot 3 of both tuples, on request (return_sequence_outputs); both final states stay on the model
-        self.sequence_output_t, self.sequence_output_v = seq if seq else (None, None)
+        self.sequence_output_t, self.sequence_output_v = seq if seq and self.return_sequence_outputs else (None, None)
         if train_branch:
-            return lm_zero, img_zero, nsp, self.sequence_output_t, None, logits, reg_out, legend_loss        # vilbert.py:1659
+            return lm_zero if lm_loss is None else lm_loss, img_zero, nsp, self.sequence_output_t, None, logits, reg_out, legend_loss        # vilbert.py:1659
         return None, None, logits, self.sequence_output_t, attention_maps, reg_out, legend_loss               # vilbert.py:1661
 
     def _attention_map_keys(self):

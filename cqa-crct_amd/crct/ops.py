@@ -609,3 +609,80 @@ def zero_runs(g, run_off, run_len, blk_seg, blk_off):
                                     L.ptr(_chk(blk_seg, torch.int32)), L.ptr(_chk(blk_off, torch.int64)), blk_seg.numel(),
                                     L.current_stream()), "zero_runs")
     return g
+
+
+# ---- masked-LM head (csrc/lm_head.hip): the row kernels around the three vocabulary-sized GEMMs on padded operands
+def pad64(n):
+    return (int(n) + 63) // 64 * 64
+
+
+def lm_gather_rows(src, rows, R, Rp=None):
+    """bf16 [Rp, H]: row r < R = bf16(src[rows[r]]) (src fp32 [N, H], rows int32 on the device), the pad rows +0 (crct_lm_gather_rows)."""
+    H = src.shape[-1]
+    Rp = pad64(max(R, 1)) if Rp is None else int(Rp)
+    out = torch.empty(Rp, H, device=src.device, dtype=torch.bfloat16)
+    L.check(L.load().crct_lm_gather_rows(L.ptr(_chk(src, torch.float32)), L.ptr(_chk(rows, torch.int32)), L.ptr(out), int(R), Rp, H,
+                                         L.current_stream()), "lm_gather_rows")
+    return out
+
+
+def lm_scatter_rows(src, rows, dst, R):
+    """dst[rows[r]] = src[r] for r < R (fp32, distinct rows; the rest of dst is untouched) (crct_lm_scatter_rows)."""
+    H = src.shape[-1]
+    L.check(L.load().crct_lm_scatter_rows(L.ptr(_chk(src, torch.float32)), L.ptr(_chk(rows, torch.int32)), L.ptr(_chk(dst, torch.float32)),
+                                          int(R), H, L.current_stream()), "lm_scatter_rows")
+    return dst
+
+
+def lm_pad_operands(table, bias, table_pad=None, bias_pad=None):
+    """(bf16 [Vp, H] copy of the bf16 table [V, H] with zero pad rows, fp32 [Vp] copy of the fp32 bias [V] with zero pad), Vp = pad64(V)."""
+    V, H = table.shape
+    Vp = pad64(V)
+    table_pad = torch.empty(Vp, H, device=table.device, dtype=torch.bfloat16) if table_pad is None else table_pad
+    bias_pad = torch.empty(Vp, device=table.device, dtype=torch.float32) if bias_pad is None else bias_pad
+    L.check(L.load().crct_lm_pad_operands(L.ptr(_chk(table, torch.bfloat16)), L.ptr(_chk(bias, torch.float32)), L.ptr(table_pad), L.ptr(bias_pad),
+                                          V, Vp, H, L.current_stream()), "lm_pad_operands")
+    return table_pad, bias_pad
+
+
+def lm_ce_fwd(logits, labels, R, V, inv_n):
+    """(loss fp32 [R], lse fp32 [R], lm_loss fp32 [1, 1] = inv_n * sum loss) over the first V columns of the fp32 logits [>= R, ld]."""
+    dev = logits.device
+    loss, lse, total = torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(1, 1, device=dev)
+    L.check(L.load().crct_lm_ce_fwd(L.ptr(_chk(logits, torch.float32)), logits.stride(0), L.ptr(_chk(labels, torch.int32)), L.ptr(loss), L.ptr(lse),
+                                    L.ptr(total), int(R), int(V), float(inv_n), L.current_stream()), "lm_ce_fwd")
+    return loss, lse, total
+
+
+def lm_ce_bwd(logits, labels, lse, g, inv_n, R, V):
+    """dL bf16 [Rp, Vp] = (softmax - onehot) * g * inv_n over the real rows and columns, +0 in every pad row and column; g: device fp32 scalar."""
+    Rp, Vp = logits.shape
+    dL = torch.empty(Rp, Vp, device=logits.device, dtype=torch.bfloat16)
+    L.check(L.load().crct_lm_ce_bwd(L.ptr(_chk(logits, torch.float32)), logits.stride(0), L.ptr(_chk(labels, torch.int32)), L.ptr(_chk(lse, torch.float32)),
+                                    L.ptr(_chk(g, torch.float32)), float(inv_n), L.ptr(dL), Vp, int(R), Rp, int(V), Vp, L.current_stream()), "lm_ce_bwd")
+    return dL
+
+
+def lm_add(dst, src, n, accumulate=True):
+    """dst.flatten()[:n] (+)= src.flatten()[:n] (fp32, contiguous); nothing at or past n is touched (crct_lm_add_f32)."""
+    L.check(L.load().crct_lm_add_f32(L.ptr(_chk(dst, torch.float32)), L.ptr(_chk(src, torch.float32)), int(n), int(bool(accumulate)),
+                                     L.current_stream()), "lm_add")
+    return dst
+
+
+def lm_gelu_bwd(dy, pre):
+    """bf16(dy * gelu'(pre)), bf16 tensors of one shape (crct_lm_gelu_bwd)."""
+    dx = torch.empty_like(dy)
+    L.check(L.load().crct_lm_gelu_bwd(L.ptr(_chk(dy, torch.bfloat16)), L.ptr(_chk(pre, torch.bfloat16)), L.ptr(dx), dy.numel(), L.current_stream()),
+            "lm_gelu_bwd")
+    return dx
+
+
+def lm_decoder_wgrad(dL, z, out, V, accumulate=True):
+    """out fp32 [V, H] (+)= (dL^T z)[:V]: the decoder's weight gradient onto the word-table gradient.  dL bf16 [Rp, Vp], z bf16 [Rp, H].  The
+    transposed operand's extent must be a multiple of 8 and V is not, so the product goes to an own fp32 [Vp, H] scratch and its first V rows
+    are added (or written) by a row kernel: whatever follows ``out`` in memory is never touched."""
+    Rp, Vp = dL.shape
+    H = z.shape[1]
+    scratch = gemm(dL, z, Vp, H, Rp, ta=True, tb=True, out_f32=True)
+    return lm_add(out, scratch, V * H, accumulate)

@@ -179,6 +179,11 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def set_early(self, on=True):
         """Overlap the update with the rest of backward (needs ``overlap``); see ``early`` above."""
+        if on and getattr(self.core, "lm_loss_coeff", 0.0) > 0.0:
+            # the masked-LM head's gradients are written by its own node in front of the engine's pass, whose segment events the early
+            # update waits for: not built
+            raise RuntimeError("FusedAdamW.set_early(True) with params['lm_loss_coeff'] > 0 is not supported: use the overlapped update "
+                               "(overlap = True) without early mode")
         self.early = bool(on)
         self.core.record_segment_events = bool(on)
 

@@ -66,6 +66,11 @@ def forward(dialog_encoder, batch, params, output_nsp_scores=False, output_lm_sc
             reg_loss = regression[1].mean()
             loss = (params["nsp_loss_coeff"] * nsp_loss) + (params["reg_loss_coeff"] * reg_loss)     # :145
             loss = loss.sum()
+        # the masked-LM term (encoder_decorator.py:148-150): lm_loss is the model's own node on sequence_output_t, the other two
+        # terms stay the head kernel's fused loss
+        lm_coeff = float(params.get("lm_loss_coeff", 0.0) or 0.0)
+        if lm_coeff > 0.0 and lm_loss is not None:
+            loss = loss + lm_coeff * lm_loss.sum()
     if evaluation:
         return loss, lm_loss, nsp_loss, img_loss, nsp_scores, regression
     return loss, lm_loss, nsp_loss, img_loss, nsp_scores, regression, legend_loss

@@ -254,6 +254,10 @@ struct crct_engine {
   std::vector<hipEvent_t> evpool;
   size_t evnext = 0;
   std::vector<std::pair<int64_t, int64_t>> seg_range;
+  // 1: segment 0 is the masked-LM head's (cls.predictions.*, params['lm_loss_coeff'] > 0): its gradients are produced by the host side
+  // (csrc/lm_head.hip) before the pass starts, so it launches nothing here and only takes part in the events; the heads' segment and
+  // everything behind it then sit one place further back.  0 (those tensors have size 0): segments and ranges as without it.
+  int lm_seg = 0;
   // weight-gradient ownership (CrctStepCfg.wgrad_overwrite): the Linear weights whose gradient is produced by exactly ONE
   // weight-gradient GEMM per backward pass and by nothing else -- every Linear of the encoder layers, the image embedding,
   // the poolers and the regressor pipes.  Fixed by the schedule at crct_engine_create (offset -> numel); `wgrad_pass` counts
@@ -1176,7 +1180,7 @@ struct Run {
   // finished -- each on the stream that owns the buffer, behind the last head data gradient into it, and only where segment 0's plan
   // produces that gradient.  Called at both exits of heads_bwd; without a request it launches nothing.
   void output_grads(Run& V, size_t gt, size_t gv) {
-    const SegPlan& pl = e->plan[0];
+    const SegPlan& pl = e->plan[e->lm_seg];
     if (e->req.og.d_seq_t && pl.dx_t && !rc) {
       fail(crct_hidden_grad_add(A(gt), e->req.og.d_seq_t, c->grad_scale, (int64_t)b->B * b->T * e->d.H, s));
       ++tick;
@@ -1206,8 +1210,9 @@ int check_batch(const crct_engine* e, const CrctBatch* b) {
 //    float inputs (crct_engine_set_input_grads) -- which therefore keeps every step above it on that stream running;
 //  * `dropped`: the weight-gradient GEMMs a running segment leaves out (crct_engine::drops_wgrad).
 void replan(crct_engine* e) {
-  const size_t nseg = e->sched.size() + 2;
+  const size_t nseg = e->sched.size() + 2 + e->lm_seg;
   e->plan.assign(nseg, SegPlan());
+  if (e->lm_seg) e->plan[0].dx_t = e->plan[0].dx_v = false;      // the masked-LM head's segment: no launch of the engine's
   e->emb_own_t = e->emb_own_v = true;
   if (e->nograd.empty()) return;
   auto lin = [&](const LinearP& l) { return e->w_grad(l) || e->b_grad(l); };
@@ -1229,7 +1234,7 @@ void replan(crct_engine* e) {
   emb.dropped = (e->feat && below_v) ? drops(e->ev.img, false) : 0;      // (also when the half runs for an input gradient alone)
   for (size_t i = 0; i < e->sched.size(); ++i) {
     const Step& st = e->sched[i];
-    SegPlan& pl = e->plan[e->sched.size() - i];
+    SegPlan& pl = e->plan[e->sched.size() - i + e->lm_seg];
     pl.dx_t = below_t; pl.dx_v = below_v;
     if (st.kind == 't' || st.kind == 'v') {
       const SelfLayerP& l = st.kind == 't' ? e->tl[st.idx] : e->vl[st.idx];
@@ -1247,7 +1252,7 @@ void replan(crct_engine* e) {
     if (!pl.runs) pl.dx_t = pl.dx_v = false;
   }
   // heads: both input gradients are the running activation gradients the encoder's backward starts from
-  SegPlan& hd = e->plan[0];
+  SegPlan& hd = e->plan[e->lm_seg];
   const bool reg = e->var.regressor != CRCT_REGRESSOR_NONE;
   bool own = lin(e->t_pool) || lin(e->v_pool) || lin(e->cls);
   int dropped = drops(e->t_pool, false) + drops(e->v_pool, false);
@@ -1504,6 +1509,10 @@ extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, 
     if (hi < 0) { lo = 0; hi = 0; }
     return std::make_pair(lo, hi);
   };
+  {
+    const auto lm = range_of({"cls.predictions."});
+    if (lm.second > lm.first) { e->lm_seg = 1; e->seg_range.push_back(lm); }
+  }
   e->seg_range.push_back(range_of({"bert.t_pooler.", "bert.v_pooler.", "cls.bi_seq_relationship.", "regressor."}));
   for (int i = (int)e->sched.size() - 1; i >= 0; --i) {
     const Step& st = e->sched[i];
@@ -1725,7 +1734,7 @@ extern "C" int crct_engine_forward(crct_engine_t* e, const float* params_f32, co
   for (size_t i = 0; i < e->sched.size(); ++i) {
     const Step& st = e->sched[i];
     const StepIn& x = e->in[i];
-    const int seg = (int)(e->sched.size() - i);          // backward segment of this schedule step
+    const int seg = (int)(e->sched.size() - i) + e->lm_seg;          // backward segment of this schedule step
     Rt.phase = (e->first_conn < 0 || (int)i < e->first_conn) ? 0 : 1;      // text-only prefix: nothing else on the data path
     if (st.kind != 'v') wait_params(Rt, seg);
     if (st.kind != 't') wait_params(Rv, seg);
@@ -1734,8 +1743,8 @@ extern "C" int crct_engine_forward(crct_engine_t* e, const float* params_f32, co
     else Rt.conn_fwd(Rv, st.idx, x);
   }
   Rt.phase = 1;
-  wait_params(Rt, 0);
-  wait_params(Rv, 0);
+  wait_params(Rt, e->lm_seg);
+  wait_params(Rv, e->lm_seg);
   Rt.heads_branch_fwd(false, e->in.back().t.x);
   Rv.heads_branch_fwd(true, e->in.back().v.x);
   Rt.fail(order_streams(e, Rv.s, Rt.s));                 // join
@@ -1771,13 +1780,16 @@ extern "C" int crct_engine_backward(crct_engine_t* e, const float* params_f32, c
   Rv.fail(order_streams(e, Rt.s, Rv.s));
   int ev_from = s0;                                      // segments enqueued completely but not yet marked for the data-parallel caller
   for (int sgi = s0; sgi < s1 && !Rt.rc && !Rv.rc; ++sgi) {
-    const bool in_sched = sgi != 0 && sgi != nseg - 1;
-    const size_t si = in_sched ? e->sched.size() - (size_t)sgi : 0;
+    const int hd = e->lm_seg;                            // the heads' segment (behind the masked-LM head's, which launches nothing here)
+    const bool in_sched = sgi > hd && sgi != nseg - 1;
+    const size_t si = in_sched ? e->sched.size() - (size_t)(sgi - hd) : 0;
     Rt.phase = (in_sched && (e->first_conn < 0 || (int)si < e->first_conn)) ? 0 : 1;      // backward tail through the text-only layers
     const SegPlan& pl = e->plan[sgi];
     if (!pl.runs) {
       // not run; its events below are still recorded, so a caller waiting on them never sees the previous pass's
-    } else if (sgi == 0) {
+    } else if (sgi < hd) {
+      // the masked-LM head's segment: its gradients are in place
+    } else if (sgi == hd) {
       e->cur_t = 0; e->cur_v = 0;
       Rt.heads_bwd(Rv, e->in.back().t.x, e->in.back().v.x, e->st.dy[0], e->sv.dy[0], logits, reg, stats);
     } else if (sgi == nseg - 1) {

@@ -230,6 +230,35 @@ int crct_layernorm_rows_f32(const void* s, int s_is_bf16, const float* mean, con
  * in torch gives the same bits; Inf / NaN of g arrive in x.  x, g 16-byte aligned; elements at and past n are not touched. */
 int crct_hidden_grad_add(void* x_bf16, const float* g_f32, float c, int64_t n, crct_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Masked-LM head (BertPreTrainingHeads.predictions, vilbert.py:1016-1037, with CrossEntropyLoss(ignore_index=-1) over the rows that carry
+ * a label): the row kernels around the three vocabulary-sized products, which run on crct_gemm_bf16 from PADDED operands.  V = vocabulary,
+ * Vp = V rounded up to 64, R = masked rows, Rp = R rounded up to 64.  All launches are bit-reproducible (no atomics, fixed summation order)
+ * and use vector stores only; all buffers 16-byte aligned.
+ *  crct_lm_gather_rows   dst bf16 [Rp][H]: row r < R = bf16(src[rows[r]][:]) (src fp32 [.][H]), rows R .. Rp-1 = +0.  H % 8 == 0.
+ *  crct_lm_scatter_rows  dst[rows[r]][:] = src[r][:] for r < R (fp32, H % 4 == 0; the rows are distinct: plain stores, the rest of dst untouched).
+ *  crct_lm_pad_operands  table_pad bf16 [Vp][H] = table_bf16 [V][H] with zero pad rows; bias_pad fp32 [Vp] = bias [V] with zero pad.  Either pair may be NULL.
+ *  crct_lm_ce_fwd        per row r < R over columns 0 .. V-1 of logits fp32 [R][ld] (pad columns are never read into a result):
+ *                        lse[r] = max + log(sum exp(x - max)), loss[r] = lse[r] - x[labels[r]] (0 <= labels[r] < V: the caller checks);
+ *                        lm_loss (optional) = inv_n * sum_r loss[r], a second one-workgroup launch.
+ *  crct_lm_ce_bwd        dL bf16 [Rp][ldd]: (exp(x[r][j] - lse[r]) - [j == labels[r]]) * (*g * inv_n) for r < R, j < V; +0 for every pad
+ *                        column V .. Vp-1 and pad row R .. Rp-1.  g: device fp32 scalar (the upstream gradient; a GradScaler's scale rides in it).
+ *  crct_lm_add_f32       dst[i] = (accumulate ? dst[i] : 0) + src[i], i < n; nothing at or past n is touched.  The decoder weight gradient
+ *                        dL^T z is produced as an own fp32 [Vp][H] scratch (a transposed GEMM operand needs M % 8 == 0, and V has no such
+ *                        factor) and its first V rows land on the word-table gradient through this; same for the bias column sums.
+ *  crct_lm_gelu_bwd      dx = bf16(dy * gelu'(pre)) over n bf16 elements (n % 8 == 0): the transform's GELU sits in front of a LayerNorm,
+ *                        so no GEMM epilogue can carry its derivative. */
+int crct_lm_gather_rows(const float* src, const int32_t* rows, void* dst_bf16, int R, int Rp, int H, crct_stream_t stream);
+int crct_lm_scatter_rows(const float* src, const int32_t* rows, float* dst, int R, int H, crct_stream_t stream);
+int crct_lm_pad_operands(const void* table_bf16, const float* bias, void* table_pad, float* bias_pad, int V, int Vp, int H,
+                         crct_stream_t stream);
+int crct_lm_ce_fwd(const float* logits, int64_t ld, const int32_t* labels, float* loss, float* lse, float* lm_loss, int R, int V,
+                   float inv_n, crct_stream_t stream);
+int crct_lm_ce_bwd(const float* logits, int64_t ld, const int32_t* labels, const float* lse, const float* g, float inv_n,
+                   void* dL_bf16, int64_t ldd, int R, int Rp, int V, int Vp, crct_stream_t stream);
+int crct_lm_add_f32(float* dst, const float* src, int64_t n, int accumulate, crct_stream_t stream);
+int crct_lm_gelu_bwd(const void* dy, const void* pre, void* dx, int64_t n, crct_stream_t stream);
+
 /* Every amax "value" below and in CrctGemmArgs / CrctStepCfg / CrctFp8Shadow is CRCT_FP8_AMAX_LANES consecutive fp32 words
  * (the kernels spread their atomic maxima over them; crct_fp8_update_scales takes the maximum of the words): an amax array
  * for n tensors has n * CRCT_FP8_AMAX_LANES words and entry i starts at word i * CRCT_FP8_AMAX_LANES. */
@@ -841,7 +870,11 @@ void crct_engine_destroy(crct_engine_t*);
 size_t crct_engine_workspace_bytes(const crct_engine_t*);
 int crct_engine_num_segments(const crct_engine_t*);
 /* Backward segment s (0 = heads ... last = embeddings) has finished writing gradient elements
- * [lo, hi) of the flat gradient buffer once crct_engine_backward(.., s, ..) returns. */
+ * [lo, hi) of the flat gradient buffer once crct_engine_backward(.., s, ..) returns.
+ * An engine created with non-zero sizes for the cls.predictions.* tensors (the masked-LM head, crct_lm_* below) has ONE MORE segment in
+ * front: 0 = the masked-LM head's tensors, 1 = heads, ... last = embeddings.  The caller produces those gradients itself before the pass;
+ * the engine launches nothing for that segment and treats it like any other in its events, callbacks and CrctStepCfg arrays.  With size
+ * 0 for those tensors the segments and every range are what they were. */
 int crct_engine_segment_range(const crct_engine_t*, int seg, int64_t* lo, int64_t* hi);
 
 typedef struct CrctBatch {
