@@ -264,3 +264,56 @@ def plotqa_evaluate(dataloader, dataset, params, eval_batch_size, dialog_encoder
     """The PlotQA evaluation loop under its earlier name: ``evaluate``.
     Returns (total_correct_tensor [6, 2], breakdown_tensor [5, 4, 3, 3], histogram [13]) on the device."""
     return evaluate(dataloader, dataset, params, eval_batch_size, dialog_encoder, group=group, with_histogram=with_histogram)
+
+
+def masked_lm_evaluate(dataloader, params, encoder, topk=(1, 5), eval_batch_size=None, group=None):
+    """Masked-token accuracy, loss and perplexity of the LM head over the tokens that carry a label (``batch['mask']``, -1 = none): per batch,
+    in chunks of ``eval_batch_size`` rows like ``evaluate`` (None: the whole batch), an evaluation forward and then
+    ``lm_predict(labels=mask, k=max(topk))`` on the labelled rows.  The token count, the count of ``label_rank < k`` for every k (int64) and the
+    sum of ``-label_logprob`` (fp64) are accumulated on the device with stock torch reductions over the [R] vectors -- no host sync inside
+    the loop with the labels on the host, where the loader leaves them -- then all-reduced once when a process group is up and read with one
+    transfer.  Returns ``dict(n, loss, perplexity, acc={k: ...})``; without any labelled token n = 0 and the rest is NaN.  max(topk) must be
+    1, 5 or 8; every k <= max(topk)."""
+    import math
+    topk = tuple(int(k) for k in topk)
+    kmax = max(topk)
+    core = getattr(encoder, "module", encoder).bert_pretrained
+    dev = torch.device(params["device"])
+    counts = torch.zeros(1 + len(topk), dtype=torch.int64, device=dev)        # n, hits per k
+    nll = torch.zeros(1, dtype=torch.float64, device=dev)
+    was_training = encoder.training
+    encoder.eval()
+    try:
+        with torch.no_grad():
+            for batch in dataloader:
+                N = batch["tokens"].shape[0]
+                step = N if eval_batch_size is None else int(eval_batch_size)
+                for lo in range(0, N, max(step, 1)):
+                    hi = min(lo + step, N)
+                    step_forward(encoder, batch, params, evaluation=True, sample_ids=None if (lo, hi) == (0, N) else np.arange(lo, hi))
+                    pred = core.lm_predict(labels=batch["mask"][lo:hi], k=kmax)
+                    if pred.rows.numel() == 0:
+                        continue
+                    counts[0] += int(pred.rows.numel())
+                    for i, k in enumerate(topk):
+                        counts[1 + i] += (pred.label_rank < k).sum()
+                    nll += (-pred.label_logprob.double()).sum()
+    finally:
+        if was_training:
+            encoder.train()
+    packed = torch.cat([counts.double(), nll])                                    # counts below 2^53: exact in fp64
+    if dist.is_available() and dist.is_initialized():
+        if dist.get_backend(group) == "gloo":
+            host = packed.cpu()
+            dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+            packed = host
+        else:
+            dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    host = packed.cpu().tolist()
+    n = int(host[0])
+    loss = host[-1] / n if n else float("nan")
+    try:
+        ppl = math.exp(loss)
+    except OverflowError:
+        ppl = float("inf")
+    return dict(n=n, loss=loss, perplexity=ppl, acc={k: (host[1 + i] / n if n else float("nan")) for i, k in enumerate(topk)})

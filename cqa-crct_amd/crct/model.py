@@ -74,7 +74,7 @@ class _StepFn(torch.autograd.Function):
             return slice(len(out) - 6 - len(ts), len(out) - 6)
         # the encoder's final hidden states, fresh fp32 tensors (StepEngine.sequence_outputs)
         # (also what the masked-LM head reads: _LmLossFn hangs on sequence_output_t, so its gradient comes back as that output's upstream)
-        seq = family(eng.sequence_outputs() if model.return_sequence_outputs or model._lm_pending is not None else ())
+        seq = family(eng.sequence_outputs() if model.return_sequence_outputs or model._lm_pending is not None or model.return_lm_scores else ())
         # the logits, and the PlotQA regressor's value: tensors of their own (two B-sized copies)
         with_value = model.variant[1] == "plotqa"
         scores = family([t.clone() for t in ((logits, reg_all[0]) if with_value else (logits,))] if model.differentiable_scores else ())
@@ -142,6 +142,32 @@ class _LmLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return ctx.model._lm_backward(ctx.job, ctx.saved, ctx.shape, g), None, None
+
+
+class _LmScoresFn(torch.autograd.Function):
+    """``prediction_scores_t`` (``CrctModel.return_lm_scores``) as a node on ``sequence_output_t``, beside ``_LmLossFn``: forward =
+    ``CrctModel._lm_logits`` over ALL B * T rows, the output a [B, T, V] view of the padded logits; backward packs the upstream [B, T, V]
+    gradient into the bf16 [Rp, Vp] form the loss's gradient kernel leaves (``ops.lm_scores_grad_pack``) and runs the same chain,
+    ``CrctModel._lm_grads``: head gradients and the decoder term where the tensor has a gradient, d / d sequence_output_t returned."""
+
+    @staticmethod
+    def forward(ctx, seq_t, model):
+        scores, rows, ctx.saved = model._lm_scores(seq_t)
+        ctx.model, ctx.rows, ctx.shape = model, rows, seq_t.shape
+        ctx.set_materialize_grads(False)
+        return scores
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None
+        return ctx.model._lm_scores_backward(ctx.rows, ctx.saved, ctx.shape, g), None
+
+
+# What ``CrctModel.lm_predict`` returns: the flat row indices into [B * T] (int32), the k most probable token ids of each row (int32 [R, k], most
+# probable first, ties to the smaller id) with their log-probabilities (fp32 [R, k]), and -- with labels, else None -- each row's label
+# log-probability (fp32 [R]) and rank (int32 [R]: the number of tokens in front of the label; ``rank < k`` = "label in the top k")
+LmPrediction = collections.namedtuple("LmPrediction", "rows ids logprobs label_logprob label_rank")
 
 
 def _upstream_f32(g):
@@ -266,6 +292,19 @@ class CrctModel(nn.Module):
         # the stub and no launch -- torch's CrossEntropyLoss gives NaN there.  The head runs in bf16, also with params['fp8'].
         # Its Linear weight gradient is always accumulated (the lazy clear zeroes it like a bias).
         self.lm_loss_coeff = lm_loss_coeff(params)
+        # True: every forward leaves ``prediction_scores_t`` here and returns it in slot 4 of the training tuple and slot 0 of the inference
+        # tuple (vilbert.py:1579, :1659, :1661): the LM head's scores of ALL B * T rows, fp32 [B, T, vocab_size] -- a VIEW into the padded
+        # [B * T rounded up to 64, vocab_size rounded up to 64] logits, so NOT contiguous (``.contiguous()`` copies; at B 80, T 124 and the
+        # BERT vocabulary the buffer is 1.2 GB).  With or without params['lm_loss_coeff'], params['fp8'] (the head runs in bf16) and
+        # labels; under grad in the training branch the scores carry a graph (``_LmScoresFn``): a loss on them trains the encoder through
+        # sequence_output_t, the word table through the tied decoder and, with lm_loss_coeff > 0, the five head tensors.  With
+        # lm_loss_coeff == 0 those five are no part of the step -- no ``.grad``, not in the optimizer -- and get none here either: then only
+        # d / d sequence_output_t and the word table's decoder term flow (the word table is a live tensor either way).  With the loss
+        # on too the head runs twice, on the masked rows and on all rows; the loss keeps its launches and bits.
+        self.return_lm_scores = False
+        self.prediction_scores_t = None
+        self._lm_all_rows = {}
+        self._lm_book_pass = -1
         self._lm_pending = None
         self._lm_pad, self._lm_pad_gen, self._shadow_gen = None, -1, 0
         self._lm_host, self._lm_upload_done = None, None
@@ -405,6 +444,7 @@ class CrctModel(nn.Module):
         therefore holds stale values between ``zero_grad()`` and ``backward()``; the values after backward are bit-identical
         to the eager path.  Falls back to the full fill until one backward pass has run."""
         self._set_optional_grads(False)
+        self._lm_book_pass = -1
         plan = self._lazy_zero_plan() if lazy else None
         if plan is None:
             self._flat_g.zero_()
@@ -696,29 +736,43 @@ class CrctModel(nn.Module):
             self._lm_pad_gen = self._shadow_gen
         return self._lm_pad
 
-    def _lm_forward(self, seq_t, job):
-        """lm_loss fp32 [1, 1] of the masked rows of ``seq_t`` (fp32 [B, T, H]) and what the backward needs.  z = LayerNorm(gelu(h W^T + b)),
-        logits = z E^T + bias on the padded operands (fp32 [Rp, Vp]), loss over the V real columns."""
+    def _lm_logits(self, seq_t, rows, R):
+        """The head on rows ``rows`` (int32 [R], device) of ``seq_t`` (fp32 [B, T, H]): z = LayerNorm(gelu(h W^T + b)), logits = z E^T + bias on the
+        padded operands.  Returns (logits fp32 [Rp, Vp] -- rows R .. and columns V .. are padding --, what ``_lm_grads`` needs).  The one
+        forward of the loss, the scores and the predictions."""
         if self._opt_stream is not None:             # an overlapped optimizer update may still be writing the head's weights and shadow
             from .events import order_streams
             order_streams(self._opt_stream, torch.cuda.current_stream())
-        H, V = self.config.hidden_size, self.config.vocab_size
+        H = self.config.hidden_size
         _, w, b, gamma, beta = self.LM_HEAD
         table, bias = self._lm_operands()
-        hb = ops.lm_gather_rows(seq_t.view(-1, H), job.rows, job.R)
+        hb = ops.lm_gather_rows(seq_t.view(-1, H), rows, R)
         Rp, Vp = hb.shape[0], table.shape[0]
         pre = torch.empty(Rp, H, device=hb.device, dtype=torch.bfloat16)
         a = ops.gemm(hb, self._flat_view(self._flat_b16, w), Rp, H, H, bias=self._flat_view(self._flat_p, b), act="gelu", preact_out=pre)
         z, mean, rstd = ops.layernorm_fwd(a, self._flat_view(self._flat_p, gamma), self._flat_view(self._flat_p, beta), eps=1e-12)
         logits = ops.gemm(z, table, Rp, Vp, H, bias=bias, out_f32=True)
-        _, lse, lm_loss = ops.lm_ce_fwd(logits, job.labels, job.R, V, job.inv_n)
-        return lm_loss, (hb, pre, a, mean, rstd, z, logits, lse, table)
+        return logits, (hb, pre, a, mean, rstd, z, table)
 
-    def _lm_backward(self, job, saved, shape, g):
-        """Accumulates the gradients of the five head tensors and the decoder term of the word table (each only where the tensor has a
-        gradient) and returns d lm_loss / d sequence_output_t, fp32 ``shape``, zero outside the masked rows.  Runs before the engine's
-        backward pass of the same batch (autograd orders it so) and does that pass's bookkeeping on the gradient buffer first."""
-        hb, pre, a, mean, rstd, z, logits, lse, table = saved
+    def _lm_forward(self, seq_t, job):
+        """lm_loss fp32 [1, 1] of the masked rows of ``seq_t`` (fp32 [B, T, H]) and what the backward needs: ``_lm_logits``, loss over the V
+        real columns."""
+        logits, saved = self._lm_logits(seq_t, job.rows, job.R)
+        _, lse, lm_loss = ops.lm_ce_fwd(logits, job.labels, job.R, self.config.vocab_size, job.inv_n)
+        return lm_loss, (saved, logits, lse)
+
+    def _lm_world(self):
+        """A data-parallel pass folds 1 / world into the gradient seeds (crct/ddp.py); the engine applies it to the upstream of
+        sequence_output_t itself, so the row gradients handed back are taken out of it again."""
+        return float(self._ddp.world) if self._ddp is not None and getattr(self._ddp, "world", 1) > 1 else 1.0
+
+    def _lm_bookkeeping(self):
+        """The engine pass's bookkeeping on the gradient buffer, which a head node needs done BEFORE it accumulates (autograd runs the head's
+        nodes before the engine's pass of the same batch).  Once per pass, whichever node runs first: the token is the count of engine
+        passes, which moves with ``_run_backward``; a clear in between drops it."""
+        if self._lm_book_pass == self._backward_passes:
+            return
+        self._lm_book_pass = self._backward_passes
         if self._opt_stream is not None:
             from .events import order_streams
             order_streams(self._opt_stream, torch.cuda.current_stream())
@@ -727,14 +781,16 @@ class CrctModel(nn.Module):
         if self._wgrad_overwrite_next and not (self._lazy_plan_key is not None and self._engine.wgrad_owned_key() == self._lazy_plan_key):
             self._flat_g.zero_()                     # (_run_backward would do this AFTER the head's gradients are in place)
             self._wgrad_overwrite_next = False
+
+    def _lm_grads(self, dL, saved, rows, R, shape, world):
+        """dL bf16 [Rp, Vp] (the gradient of the padded logits, pad rows and columns +0, 1 / world folded in) -> accumulates the gradients of
+        the five head tensors and the decoder term of the word table, each only where the tensor is part of the step and has a gradient,
+        and returns d / d sequence_output_t, fp32 ``shape``, zero outside ``rows``.  The one backward of the loss and the scores."""
+        hb, pre, a, mean, rstd, z, table = saved
         H, V = self.config.hidden_size, self.config.vocab_size
-        Rp, Vp = logits.shape
+        Rp, Vp = dL.shape
         bias, w, b, gamma, beta = self.LM_HEAD
-        live = lambda name: name not in self._nograd      # noqa: E731
-        # a data-parallel pass folds 1 / world into the gradient seeds (crct/ddp.py); the engine applies it to the upstream of
-        # sequence_output_t itself, so the row gradients handed back are taken out of it again
-        world = float(self._ddp.world) if self._ddp is not None and getattr(self._ddp, "world", 1) > 1 else 1.0
-        dL = ops.lm_ce_bwd(logits, job.labels, lse, g.reshape(1).float(), job.inv_n / world, job.R, V)
+        live = lambda name: self._entries[name].used and name not in self._nograd      # noqa: E731
         if live(bias):
             ops.lm_add(self._flat_view(self._flat_g, bias), ops.colsum(dL, Rp, Vp), V, True)
         if live(self.WORD_TABLE):
@@ -750,8 +806,81 @@ class CrctModel(nn.Module):
             ops.colsum(dpre, Rp, H, out=self._flat_view(self._flat_g, b), accumulate=True)
         dh = ops.gemm(dpre, self._flat_view(self._flat_b16, w), Rp, H, H, tb=True, out_f32=True, alpha=world)
         d_seq = torch.zeros(shape, dtype=torch.float32, device=dh.device)
-        ops.lm_scatter_rows(dh, job.rows, d_seq.view(-1, H), job.R)
+        ops.lm_scatter_rows(dh, rows, d_seq.view(-1, H), R)
         return d_seq
+
+    def _lm_backward(self, job, saved, shape, g):
+        """Accumulates the gradients of the five head tensors and the decoder term of the word table (each only where the tensor has a
+        gradient) and returns d lm_loss / d sequence_output_t, fp32 ``shape``, zero outside the masked rows.  Runs before the engine's
+        backward pass of the same batch (autograd orders it so) and does that pass's bookkeeping on the gradient buffer first."""
+        saved, logits, lse = saved
+        self._lm_bookkeeping()
+        world = self._lm_world()
+        dL = ops.lm_ce_bwd(logits, job.labels, lse, g.reshape(1).float(), job.inv_n / world, job.R, self.config.vocab_size)
+        return self._lm_grads(dL, saved, job.rows, job.R, shape, world)
+
+    def _lm_scores(self, seq_t):
+        """(prediction_scores_t fp32 [B, T, V], a view of the padded logits; the identity row list; what the backward needs).  All B * T rows go
+        through the head; the row list is cached per row count and needs no host labels."""
+        B, T, _ = seq_t.shape
+        N, V = B * T, self.config.vocab_size
+        rows = self._lm_all_rows.get(N)
+        if rows is None or rows.device != seq_t.device:
+            rows = self._lm_all_rows[N] = torch.arange(N, dtype=torch.int32, device=seq_t.device)
+        logits, saved = self._lm_logits(seq_t, rows, N)
+        return logits[:N].view(B, T, logits.shape[1])[:, :, :V], rows, saved
+
+    def _lm_scores_backward(self, rows, saved, shape, g):
+        """d (upstream g on the scores) / d sequence_output_t; the head's and the word table's gradients are accumulated (``_lm_grads``).  g is
+        taken where autograd left it when its rows are 16-byte aligned fp32 with a stride that is a multiple of 4, else through one copy
+        into such rows (vocab_size itself need not be a multiple of 4)."""
+        self._lm_bookkeeping()
+        world = self._lm_world()
+        V = self.config.vocab_size
+        N = int(rows.numel())
+        table = saved[-1]
+        g = g.reshape(N, V)
+        if g.dtype != torch.float32 or g.stride(1) != 1 or g.stride(0) % 4 or g.data_ptr() % 16:
+            buf = torch.empty(N, ops.pad64(V), dtype=torch.float32, device=g.device)
+            buf[:, :V].copy_(g)
+            g = buf[:, :V]
+        dL = ops.lm_scores_grad_pack(g, N, ops.pad64(max(N, 1)), V, table.shape[0], 1.0 / world)
+        return self._lm_grads(dL, saved, rows, N, shape, world)
+
+    @torch.no_grad()
+    def lm_predict(self, labels=None, rows=None, k=5):
+        """The LM head's top-k predictions for rows of the LAST forward (any branch; no flag needed: it reads the engine's final text states,
+        ``eng.sequence_outputs()``, and the weights as that forward saw them).  Exactly one of ``labels``: [B, T] int64 with -1 = skip, on the host
+        or the device (``batch['mask']``; a device tensor costs one ``.cpu()``), compacted as the loss compacts them -- and ``rows``: flat row
+        indices into [B * T], without labels.  k in {1, 5, 8}.  Returns an ``LmPrediction``; no row selected: empty tensors and no launch.
+        The head runs on the selected rows only (gather, two GEMMs, LayerNorm, one top-k launch per call)."""
+        if (labels is None) == (rows is None):
+            raise ValueError("lm_predict: give exactly one of labels= ([B, T], -1 = skip) and rows= (flat row indices)")
+        if int(k) not in (1, 5, 8):
+            raise ValueError("lm_predict: k = %r must be 1, 5 or 8" % (k,))
+        eng = self._engine
+        if eng is None or eng._keep is None:
+            raise RuntimeError("lm_predict: run a forward pass first")
+        B, T = eng._keep[0]["tokens"].shape
+        dev = self._flat_p.device
+        if labels is not None:
+            if labels.numel() != B * T:
+                raise ValueError("lm_predict: labels has %d elements, the last forward had B * T = %d * %d rows" % (labels.numel(), B, T))
+            job = self._lm_job(labels)
+            row_idx, lab, R = (job.rows, job.labels, job.R) if job is not None else (None, None, 0)
+        else:
+            r64 = torch.as_tensor(rows).reshape(-1).to(torch.int64).cpu()
+            R, lab = int(r64.numel()), None
+            if R and bool(((r64 < 0) | (r64 >= B * T)).any()):
+                raise ValueError("lm_predict: rows must lie in [0, B * T = %d)" % (B * T))
+            row_idx = r64.to(torch.int32).to(dev) if R else None
+        if R == 0:
+            e_i, e_f = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, device=dev)
+            return LmPrediction(e_i, e_i.reshape(0, int(k)), e_f.reshape(0, int(k)), e_f if labels is not None else None, e_i if labels is not None else None)
+        seq_t = eng.sequence_outputs(visual=False)[0]
+        logits, _ = self._lm_logits(seq_t, row_idx, R)
+        ids, logprob, _, lab_lp, lab_rank = ops.lm_topk_rows(logits, R, self.config.vocab_size, int(k), lab)
+        return LmPrediction(row_idx, ids, logprob, lab_lp, lab_rank)
 
     def _device_inputs(self, input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
                        image_attention_mask, image_target, R, labels, areas=None):
@@ -845,6 +974,7 @@ class CrctModel(nn.Module):
             finally:
                 self._lm_pending = None
             lm_loss = _LmLossFn.apply(seq[0], self, lm_job) if lm_job is not None else None
+            lm_scores = _LmScoresFn.apply(seq[0], self) if self.return_lm_scores else None
             value = scores[1] if len(scores) > 1 else None
             if scores:
                 logits = scores[0]                     # differentiable_scores: the copies that are part of the graph
@@ -853,8 +983,9 @@ class CrctModel(nn.Module):
             eng.forward(self._flat_p, self._flat_b16, tensors, step)
             logits, reg, stats = eng.snapshot(B)
             loss, nsp, reg_loss = stats[0], stats[1:2], reg[1]
-            seq = eng.sequence_outputs() if self.return_sequence_outputs or lm_job is not None else ()
+            seq = eng.sequence_outputs() if self.return_sequence_outputs or lm_job is not None or self.return_lm_scores else ()
             lm_loss = self._lm_forward(seq[0], lm_job)[0] if lm_job is not None else None      # torch.no_grad() in the training branch: forward only
+            lm_scores = self._lm_scores(seq[0])[0] if self.return_lm_scores else None
             maps = [eng.attention_probs(*key) for key in map_keys]
             if output_all_attention_masks and not train_branch:
                 attention_maps = self._attention_maps(eng)
@@ -876,9 +1007,10 @@ class CrctModel(nn.Module):
         lm_zero, img_zero, legend_loss = self._const_zeros
         # sequence_output_t in slot 3 of both tuples, on request (return_sequence_outputs); both final states stay on the model
         self.sequence_output_t, self.sequence_output_v = seq if seq and self.return_sequence_outputs else (None, None)
+        self.prediction_scores_t = lm_scores                 # (return_lm_scores; None otherwise)
         if train_branch:
-            return lm_zero if lm_loss is None else lm_loss, img_zero, nsp, self.sequence_output_t, None, logits, reg_out, legend_loss        # vilbert.py:1659
-        return None, None, logits, self.sequence_output_t, attention_maps, reg_out, legend_loss               # vilbert.py:1661
+            return lm_zero if lm_loss is None else lm_loss, img_zero, nsp, self.sequence_output_t, lm_scores, logits, reg_out, legend_loss   # vilbert.py:1659
+        return lm_scores, None, logits, self.sequence_output_t, attention_maps, reg_out, legend_loss               # vilbert.py:1661
 
     def _attention_map_keys(self):
         """``attention_map_outputs`` as the keys of ``attention_maps``: (kind, index, direction), kind by name, direction 0 by default."""
@@ -948,12 +1080,19 @@ class VisualDialogEncoder(nn.Module):
                   masked_lm_labels=masked_lm_labels, next_sentence_label=next_sentence_label,
                   image_attention_mask=image_attention_mask, image_label=image_label, image_target=image_target,
                   gt_reg=gt_reg, areas=areas, legend_pred=legend_pred)
-        if next_sentence_label is not None and masked_lm_labels is not None and image_target is not None:
-            masked_lm_loss, masked_img_loss, nsp_loss, _, prediction_scores_t, seq_relationship_score, reg_loss, legend_loss = \
-                self.bert_pretrained(input_ids, txt_loc, image_feat, image_loc, **kw)
-        else:
-            prediction_scores_t, _, seq_relationship_score, _, _, reg_loss, legend_loss = \
-                self.bert_pretrained(input_ids, txt_loc, image_feat, image_loc, **kw)
+        core = self.bert_pretrained
+        was = core.return_lm_scores
+        if output_lm_scores:                 # the flag for this call: the appended element is the tensor (encoder_decorator.py:52-53)
+            core.return_lm_scores = True
+        try:
+            if next_sentence_label is not None and masked_lm_labels is not None and image_target is not None:
+                masked_lm_loss, masked_img_loss, nsp_loss, _, prediction_scores_t, seq_relationship_score, reg_loss, legend_loss = \
+                    core(input_ids, txt_loc, image_feat, image_loc, **kw)
+            else:
+                prediction_scores_t, _, seq_relationship_score, _, _, reg_loss, legend_loss = \
+                    core(input_ids, txt_loc, image_feat, image_loc, **kw)
+        finally:
+            core.return_lm_scores = was
         out = (masked_lm_loss, masked_img_loss, nsp_loss, seq_relationship_score)
         if output_lm_scores:
             out = out + (prediction_scores_t,)

@@ -686,3 +686,33 @@ def lm_decoder_wgrad(dL, z, out, V, accumulate=True):
     H = z.shape[1]
     scratch = gemm(dL, z, Vp, H, Rp, ta=True, tb=True, out_f32=True)
     return lm_add(out, scratch, V * H, accumulate)
+
+
+def lm_topk_rows(logits, R, V, k, labels=None):
+    """The k first columns of each of the first R rows of the fp32 logits [>= R, ld] over their first V columns, in the order "larger value
+    first, then smaller column" (NaN above +inf, -0 below +0): (ids int32 [R, k], logprob fp32 [R, k] = x - lse, lse fp32 [R], label_logprob
+    fp32 [R], label_rank int32 [R]); the last two are None without ``labels`` (int32 [R] on the device).  ``label_rank`` counts the columns in
+    front of the label, so ``rank < k`` is "label in the top k"; ``lse`` holds the bits of ``lm_ce_fwd``'s.  k in {1, 5, 8}, V >= k and a row
+    stride that is a multiple of 4 -- anything else is refused before a launch; R == 0 launches nothing (crct_lm_topk_rows)."""
+    dev = logits.device
+    R, k = int(R), int(k)
+    ids, logprob = torch.empty(R, k, dtype=torch.int32, device=dev), torch.empty(R, k, device=dev)
+    lse = torch.empty(R, device=dev)
+    lab_lp = torch.empty(R, device=dev) if labels is not None else None
+    lab_rank = torch.empty(R, dtype=torch.int32, device=dev) if labels is not None else None
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] < R:
+        raise ValueError("lm_topk_rows: logits must be [>= R, ld] with unit column stride")
+    L.check(L.load().crct_lm_topk_rows(L.ptr(_chk(logits, torch.float32)), logits.stride(0), L.ptr(_chk(labels, torch.int32)), L.ptr(ids), L.ptr(logprob),
+                                       L.ptr(lse), L.ptr(lab_lp), L.ptr(lab_rank), R, int(V), k, L.current_stream()), "lm_topk_rows")
+    return ids, logprob, lse, lab_lp, lab_rank
+
+
+def lm_scores_grad_pack(g, R, Rp, V, Vp, c, out=None):
+    """dL bf16 [Rp, Vp] = bf16(c * g[:R, :V]) with every pad row and pad column +0, from fp32 g [>= R, ldg] (unit column stride, a row stride
+    that is a multiple of 4): an upstream gradient on the logits in the form ``lm_ce_bwd`` leaves the loss's (crct_lm_scores_grad_pack)."""
+    if g.dim() != 2 or g.stride(1) != 1 or g.shape[0] < R:
+        raise ValueError("lm_scores_grad_pack: g must be [>= R, ldg] with unit column stride")
+    dL = torch.empty(int(Rp), int(Vp), device=g.device, dtype=torch.bfloat16) if out is None else out
+    L.check(L.load().crct_lm_scores_grad_pack(L.ptr(_chk(g, torch.float32)), g.stride(0), float(c), L.ptr(_chk(dL, torch.bfloat16)), dL.stride(0), int(R), int(Rp),
+                                              int(V), int(Vp), L.current_stream()), "lm_scores_grad_pack")
+    return dL

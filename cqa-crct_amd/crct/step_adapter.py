@@ -50,11 +50,15 @@ def forward(dialog_encoder, batch, params, output_nsp_scores=False, output_lm_sc
         attention_mask = attention_mask.materialize()
     sep_len = hist_len + 1
 
-    lm_loss, img_loss, nsp_loss, nsp_scores, regression, legend_loss = dialog_encoder(
+    out = dialog_encoder(
         tokens, txt_loc, features, image_loc, sep_indices=sep_indices, sep_len=sep_len, token_type_ids=segments,
         masked_lm_labels=mask, attention_mask=attention_mask, next_sentence_label=next_sentence_labels,
         output_nsp_scores=output_nsp_scores, output_lm_scores=output_lm_scores, image_attention_mask=image_mask,
         image_label=image_label, image_target=image_target, gt_reg=regression_target, areas=areas)
+    # with output_lm_scores the encoder appends prediction_scores_t behind the four (encoder_decorator.py:52-53), where the reference's
+    # six-name unpack dies; the return tuples here keep their lengths and the native model leaves the tensor on
+    # ``bert_pretrained.prediction_scores_t``
+    (lm_loss, img_loss, nsp_loss, nsp_scores), (regression, legend_loss) = out[:4], out[-2:]
 
     loss = None
     if not evaluation:

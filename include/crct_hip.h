@@ -247,7 +247,17 @@ int crct_hidden_grad_add(void* x_bf16, const float* g_f32, float c, int64_t n, c
  *                        dL^T z is produced as an own fp32 [Vp][H] scratch (a transposed GEMM operand needs M % 8 == 0, and V has no such
  *                        factor) and its first V rows land on the word-table gradient through this; same for the bias column sums.
  *  crct_lm_gelu_bwd      dx = bf16(dy * gelu'(pre)) over n bf16 elements (n % 8 == 0): the transform's GELU sits in front of a LayerNorm,
- *                        so no GEMM epilogue can carry its derivative. */
+ *                        so no GEMM epilogue can carry its derivative.
+ *  crct_lm_topk_rows     per row r < R over columns 0 .. V-1 of logits fp32 [R][ld] (ld % 4 == 0; pad columns are never read into a result),
+ *                        one workgroup per row: ids[r][K] (int32) = the first K columns in the order "larger value first, then smaller
+ *                        column", logprob[r][K] = x - lse, lse[r] (the bits of crct_lm_ce_fwd's: one shared sweep) and, with labels (int32,
+ *                        may be NULL, then the two outputs may be too), label_logprob[r] and label_rank[r] (int32) = the number of columns
+ *                        j < V in front of the label in that order, so rank < k means "label in the top k".  The order compares a monotone
+ *                        integer key of the float bits: total, -0 below +0, every NaN above +inf (as torch.topk).  A label outside [0, V)
+ *                        gives NaN and rank V.  Refused without a launch: K not 1, 5 or 8; V < K; ld % 4 != 0.  R == 0: no launch.
+ *  crct_lm_scores_grad_pack  dL bf16 [Rp][ldd]: bf16(c * g[r][j]) for r < R, j < V from fp32 g with row stride ldg (ldg % 4 == 0, ldg >= V;
+ *                        nothing of g at or past column V of a row is read); +0 for every pad column V .. Vp-1 and pad row R .. Rp-1: an
+ *                        upstream gradient on the logits in the form crct_lm_ce_bwd leaves the loss's. */
 int crct_lm_gather_rows(const float* src, const int32_t* rows, void* dst_bf16, int R, int Rp, int H, crct_stream_t stream);
 int crct_lm_scatter_rows(const float* src, const int32_t* rows, float* dst, int R, int H, crct_stream_t stream);
 int crct_lm_pad_operands(const void* table_bf16, const float* bias, void* table_pad, float* bias_pad, int V, int Vp, int H,
@@ -258,6 +268,10 @@ int crct_lm_ce_bwd(const float* logits, int64_t ld, const int32_t* labels, const
                    void* dL_bf16, int64_t ldd, int R, int Rp, int V, int Vp, crct_stream_t stream);
 int crct_lm_add_f32(float* dst, const float* src, int64_t n, int accumulate, crct_stream_t stream);
 int crct_lm_gelu_bwd(const void* dy, const void* pre, void* dx, int64_t n, crct_stream_t stream);
+int crct_lm_topk_rows(const float* logits, int64_t ld, const int32_t* labels, int32_t* ids, float* logprob, float* lse,
+                      float* label_logprob, int32_t* label_rank, int R, int V, int K, crct_stream_t stream);
+int crct_lm_scores_grad_pack(const float* g, int64_t ldg, float c, void* dL_bf16, int64_t ldd, int R, int Rp, int V, int Vp,
+                             crct_stream_t stream);
 
 /* Every amax "value" below and in CrctGemmArgs / CrctStepCfg / CrctFp8Shadow is CRCT_FP8_AMAX_LANES consecutive fp32 words
  * (the kernels spread their atomic maxima over them; crct_fp8_update_scales takes the maximum of the words): an amax array
