@@ -16,6 +16,8 @@ Layout rules (MI355X-first):
   * parameters that never receive a gradient on this path (biOutput.q_dense1/2,
     cls.predictions.*, cls.imagePredictions.*, v_embeddings.type_embeddings) sit at the end; the masked-LM head
     (cls.predictions.{bias, transform.*}) stays there when params['lm_loss_coeff'] > 0 makes it live: only its ``used`` flags change.
+    The same holds for the masked-region head (the six cls.imagePredictions.* tensors, directly behind it) and
+    params['img_loss_coeff'] > 0; they are no language weights and train at params['image_lr'].
 """
 import math
 from collections import namedtuple
@@ -192,13 +194,20 @@ def is_unused(name, params=None):
     if name.startswith("cls.predictions."):
         # the masked-LM head: live with params['lm_loss_coeff'] > 0 (its offsets are those of the dead tensors: the tail of the buffers)
         return lm_loss_coeff(params) <= 0.0
-    return (".biOutput.q_dense" in name or name.startswith("cls.imagePredictions.")
-            or name == "bert.v_embeddings.type_embeddings.weight")
+    if name.startswith("cls.imagePredictions."):
+        # the masked-region head: live with params['img_loss_coeff'] > 0, directly behind the masked-LM head in the same tail
+        return img_loss_coeff(params) <= 0.0
+    return ".biOutput.q_dense" in name or name == "bert.v_embeddings.type_embeddings.weight"
 
 
 def lm_loss_coeff(params):
     """params['lm_loss_coeff'] (encoder_decorator.py:148-150); absent, None or 0: the masked-LM loss is off."""
     return float((params or {}).get("lm_loss_coeff", 0.0) or 0.0)
+
+
+def img_loss_coeff(params):
+    """params['img_loss_coeff'] (encoder_decorator.py:148-150); absent, None or 0: the masked-region loss is off."""
+    return float((params or {}).get("img_loss_coeff", 0.0) or 0.0)
 
 
 def optional_grad(name):

@@ -247,6 +247,8 @@ PROTOTYPES = {
     "crct_lm_gelu_bwd": (C.c_int, [vp, vp, vp, c_i64, vp]),
     "crct_lm_topk_rows": (C.c_int, [vp, c_i64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "crct_lm_scores_grad_pack": (C.c_int, [vp, c_i64, c_f32, vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "crct_region_ce_fwd": (C.c_int, [vp, c_i64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, c_f32, vp]),
+    "crct_region_ce_bwd": (C.c_int, [vp, c_i64, vp, vp, vp, vp, vp, c_f32, vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "crct_engine_sequence_outputs": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "crct_engine_set_output_grads": (C.c_int, [vp, C.POINTER(OutputGrads)]),
     "crct_engine_set_score_grads": (C.c_int, [vp, C.POINTER(ScoreGrads)]),

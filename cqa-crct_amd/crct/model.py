@@ -24,7 +24,7 @@ from . import ops
 from .config import BertConfig
 from .engine import StepEngine
 from .fp8 import AMAX_WINDOW, Fp8State
-from .layout import frozen_tensors, is_frozen, lm_loss_coeff, model_variant, optional_grad, parameter_table
+from .layout import frozen_tensors, img_loss_coeff, is_frozen, lm_loss_coeff, model_variant, optional_grad, parameter_table
 
 
 class _Node(nn.Module):
@@ -74,6 +74,7 @@ class _StepFn(torch.autograd.Function):
             return slice(len(out) - 6 - len(ts), len(out) - 6)
         # the encoder's final hidden states, fresh fp32 tensors (StepEngine.sequence_outputs)
         # (also what the masked-LM head reads: _LmLossFn hangs on sequence_output_t, so its gradient comes back as that output's upstream)
+        # (... and the masked-region head: _RegionLossFn hangs on sequence_output_v in the same way)
         seq = family(eng.sequence_outputs() if model.return_sequence_outputs or model._lm_pending is not None or model.return_lm_scores else ())
         # the logits, and the PlotQA regressor's value: tensors of their own (two B-sized copies)
         with_value = model.variant[1] == "plotqa"
@@ -142,6 +143,33 @@ class _LmLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return ctx.model._lm_backward(ctx.job, ctx.saved, ctx.shape, g), None, None
+
+
+# One batch's masked regions as the masked-region head takes them: flat row indices into [B * V] (int32, device), R of them, 1 / n, and ONE of
+# labels (int32 [R], device: class ids, the hard form) and targets (fp32 [B * V, C] on the device, read in place at ``rows``: the soft form)
+_RegionJob = collections.namedtuple("_RegionJob", "rows labels targets R inv_n")
+
+# What one prediction head is made of, for the ONE head routine (``CrctModel._lm_logits`` / ``_lm_grads``): the names of the decoder bias, the
+# transform's Linear weight / bias and LayerNorm weight / bias and the decoder's weight (the tied word table for the text head), the hidden
+# width, the class count and which sequence output feeds it (0 = text, 1 = visual).  The padded decoder operands are cached per ``key``.
+_Head = collections.namedtuple("_Head", "key bias w b gamma beta table H C seq")
+
+
+class _RegionLossFn(torch.autograd.Function):
+    """The masked-region loss (params['img_loss_coeff'] > 0) as a node on ``sequence_output_v``, the twin of ``_LmLossFn``: forward =
+    ``CrctModel._region_forward`` (the head on the R masked regions, csrc/region_head.hip's loss), backward = ``CrctModel._region_backward``,
+    which accumulates the six head gradients into the flat gradient buffer and RETURNS d img_loss / d sequence_output_v, zero outside
+    the masked rows -- the upstream gradient of that output of ``_StepFn``, i.e. the engine's unchanged output-gradient request."""
+
+    @staticmethod
+    def forward(ctx, seq_v, model, job):
+        img_loss, ctx.saved = model._region_forward(seq_v, job)
+        ctx.model, ctx.job, ctx.shape = model, job, seq_v.shape
+        return img_loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.model._region_backward(ctx.job, ctx.saved, ctx.shape, g), None, None
 
 
 class _LmScoresFn(torch.autograd.Function):
@@ -306,8 +334,24 @@ class CrctModel(nn.Module):
         self._lm_all_rows = {}
         self._lm_book_pass = -1
         self._lm_pending = None
-        self._lm_pad, self._lm_pad_gen, self._shadow_gen = None, -1, 0
-        self._lm_host, self._lm_upload_done = None, None
+        self._head_pads, self._shadow_gen = {}, 0
+        self._staging = {}
+        # params['img_loss_coeff'] > 0: the masked-region objective, the visual twin of the above (ViLBERT's masked-region classification
+        # on BertImagePredictionHead, vilbert.py:1065-1077).  In the training branch slot 1 of the tuple is then img_loss = the mean over the
+        # n regions with image_label == 1 (the loader has zeroed their features, utils.py:194-217) of the head's loss against the region's
+        # class: hard targets (int64 [B, V] class ids) logsumexp(logits) - logits[c]; soft targets (float [B, V, C], t >= 0)
+        # sum_j t_j (log t_j - log_softmax(logits)_j), the original's KLDivLoss on detector distributions.  fp32 [1, 1], differentiable under
+        # grad; the six cls.imagePredictions.* tensors get gradients.  The targets are ``image_target`` unless ``image_class`` is given:
+        # image_target also indexes color_emb in the region's own INPUT embedding (vilbert.py:1479), so a loader that masks a region puts a
+        # placeholder there and the truth in image_class.  image_label is taken on the host; no labelled region: the constant zero and no
+        # launch.  The head runs in bf16, also with params['fp8'].  One wave holds a row of logits: v_target_size <= 2048.
+        self.img_loss_coeff = img_loss_coeff(params)
+        if self.img_loss_coeff > 0.0 and config.v_target_size > self.REGION_MAX_CLASSES:
+            raise NotImplementedError("params['img_loss_coeff'] with v_target_size = %d: the masked-region loss kernels hold a row of logits in one "
+                                      "wave's registers, at most %d classes" % (config.v_target_size, self.REGION_MAX_CLASSES))
+        self._heads = dict(
+            lm=_Head("lm", *self.LM_HEAD, self.WORD_TABLE, config.hidden_size, config.vocab_size, 0),
+            region=_Head("region", *self.REGION_HEAD, config.v_hidden_size, config.v_target_size, 1))
         self.init_weights(int(params.get("seed", 0)))
         self.register_load_state_dict_post_hook(lambda m, k: m._invalidate_shadow())
 
@@ -402,7 +446,7 @@ class CrctModel(nn.Module):
             self._const_zeros = None
             self._param_events = None
             self._opt_stream = None
-            self._lm_pad, self._lm_pad_gen = None, -1
+            self._head_pads = {}
             self._rebind()
         return self
 
@@ -692,6 +736,10 @@ class CrctModel(nn.Module):
         return d_feat, d_iloc, d_tloc, d_areas
 
     # ------------------------------------------------------------------ masked-LM head (csrc/lm_head.hip; see lm_loss_coeff above)
+    REGION_HEAD = ("cls.imagePredictions.decoder.bias", "cls.imagePredictions.transform.dense.weight", "cls.imagePredictions.transform.dense.bias",
+                   "cls.imagePredictions.transform.LayerNorm.weight", "cls.imagePredictions.transform.LayerNorm.bias",
+                   "cls.imagePredictions.decoder.weight")
+    REGION_MAX_CLASSES = 2048                    # csrc/region_head.hip: 8 float4 chunks per lane of one wave
     LM_HEAD = ("cls.predictions.bias", "cls.predictions.transform.dense.weight", "cls.predictions.transform.dense.bias",
                "cls.predictions.transform.LayerNorm.weight", "cls.predictions.transform.LayerNorm.bias")
     WORD_TABLE = "bert.embeddings.word_embeddings.weight"
@@ -711,41 +759,52 @@ class CrctModel(nn.Module):
         R = int(rows.numel())
         if R == 0:
             return None
-        if self._lm_upload_done is not None:
-            self._lm_upload_done.synchronize()                # the staging buffer is free again (long done in practice)
-        if self._lm_host is None or self._lm_host.numel() < 2 * R:
-            self._lm_host = torch.empty(max(2 * R, 4096), dtype=torch.int32).pin_memory()
-        self._lm_host[:R] = rows
-        self._lm_host[R:2 * R] = lab[rows]
-        dev = torch.empty(2 * R, dtype=torch.int32, device=self._flat_p.device)
-        dev.copy_(self._lm_host[:2 * R], non_blocking=True)
-        if self._lm_upload_done is None:
-            self._lm_upload_done = torch.cuda.Event()
-        self._lm_upload_done.record()
+        dev = self._upload_i32("lm", rows, lab[rows])
         return _LmJob(dev[:R], dev[R:], R, 1.0 / R)
+
+    def _upload_i32(self, key, *parts):
+        """The host integer tensors ``parts`` (R elements each) as ONE int32 device tensor, through head ``key``'s pinned staging buffer and one
+        asynchronous copy."""
+        R = int(parts[0].numel())
+        n = len(parts) * R
+        host, done = self._staging.get(key, (None, None))
+        if done is not None:
+            done.synchronize()                                # the staging buffer is free again (long done in practice)
+        if host is None or host.numel() < n:
+            host = torch.empty(max(n, 4096), dtype=torch.int32).pin_memory()
+        for i, part in enumerate(parts):
+            host[i * R:(i + 1) * R] = part
+        dev = torch.empty(n, dtype=torch.int32, device=self._flat_p.device)
+        dev.copy_(host[:n], non_blocking=True)
+        done = done or torch.cuda.Event()
+        done.record()
+        self._staging[key] = (host, done)
+        return dev
 
     def _flat_view(self, flat, name):
         e = self._entries[name]
         return flat[e.offset:e.offset + e.numel].view(e.shape)
 
-    def _lm_operands(self):
-        """(bf16 [Vp, H] copy of the word table's bf16 shadow with zero pad rows, fp32 [Vp] padded bias), refreshed whenever the shadow was."""
-        if self._lm_pad is None or self._lm_pad_gen != self._shadow_gen:
-            self._lm_pad = ops.lm_pad_operands(self._flat_view(self._flat_b16, self.WORD_TABLE), self._flat_view(self._flat_p, self.LM_HEAD[0]),
-                                               *(self._lm_pad or ()))
-            self._lm_pad_gen = self._shadow_gen
-        return self._lm_pad
+    def _head_operands(self, head):
+        """(bf16 [Vp, H] copy of the decoder weight's bf16 shadow -- the word table for the text head -- with zero pad rows, fp32 [Vp] padded
+        bias) of ``head``, refreshed whenever the shadow was."""
+        pad, gen = self._head_pads.get(head.key, (None, -1))
+        if pad is None or gen != self._shadow_gen:
+            pad = ops.lm_pad_operands(self._flat_view(self._flat_b16, head.table), self._flat_view(self._flat_p, head.bias), *(pad or ()))
+            self._head_pads[head.key] = (pad, self._shadow_gen)
+        return pad
 
-    def _lm_logits(self, seq_t, rows, R):
-        """The head on rows ``rows`` (int32 [R], device) of ``seq_t`` (fp32 [B, T, H]): z = LayerNorm(gelu(h W^T + b)), logits = z E^T + bias on the
-        padded operands.  Returns (logits fp32 [Rp, Vp] -- rows R .. and columns V .. are padding --, what ``_lm_grads`` needs).  The one
-        forward of the loss, the scores and the predictions."""
+    def _lm_logits(self, seq_t, rows, R, head=None):
+        """A prediction head (``head``: a ``_Head``, the text head by default) on rows ``rows`` (int32 [R], device) of its sequence output
+        ``seq_t`` (fp32 [B, T, H]): z = LayerNorm(gelu(h W^T + b)), logits = z E^T + bias on the padded operands.  Returns (logits fp32
+        [Rp, Vp] -- rows R .. and columns V .. are padding --, what ``_lm_grads`` needs).  The one forward of the masked-LM loss, the scores,
+        the predictions and the masked-region loss."""
+        head = head or self._heads["lm"]
         if self._opt_stream is not None:             # an overlapped optimizer update may still be writing the head's weights and shadow
             from .events import order_streams
             order_streams(self._opt_stream, torch.cuda.current_stream())
-        H = self.config.hidden_size
-        _, w, b, gamma, beta = self.LM_HEAD
-        table, bias = self._lm_operands()
+        H, w, b, gamma, beta = head.H, head.w, head.b, head.gamma, head.beta
+        table, bias = self._head_operands(head)
         hb = ops.lm_gather_rows(seq_t.view(-1, H), rows, R)
         Rp, Vp = hb.shape[0], table.shape[0]
         pre = torch.empty(Rp, H, device=hb.device, dtype=torch.bfloat16)
@@ -782,19 +841,21 @@ class CrctModel(nn.Module):
             self._flat_g.zero_()                     # (_run_backward would do this AFTER the head's gradients are in place)
             self._wgrad_overwrite_next = False
 
-    def _lm_grads(self, dL, saved, rows, R, shape, world):
+    def _lm_grads(self, dL, saved, rows, R, shape, world, head=None):
         """dL bf16 [Rp, Vp] (the gradient of the padded logits, pad rows and columns +0, 1 / world folded in) -> accumulates the gradients of
-        the five head tensors and the decoder term of the word table, each only where the tensor is part of the step and has a gradient,
-        and returns d / d sequence_output_t, fp32 ``shape``, zero outside ``rows``.  The one backward of the loss and the scores."""
+        ``head``'s five tensors and of its decoder weight (for the text head: the decoder term of the word table), each only where the
+        tensor is part of the step and has a gradient, and returns d / d (the head's sequence output), fp32 ``shape``, zero outside
+        ``rows``.  The one backward of the masked-LM loss, the scores and the masked-region loss."""
+        head = head or self._heads["lm"]
         hb, pre, a, mean, rstd, z, table = saved
-        H, V = self.config.hidden_size, self.config.vocab_size
+        H, V = head.H, head.C
         Rp, Vp = dL.shape
-        bias, w, b, gamma, beta = self.LM_HEAD
+        bias, w, b, gamma, beta = head.bias, head.w, head.b, head.gamma, head.beta
         live = lambda name: self._entries[name].used and name not in self._nograd      # noqa: E731
         if live(bias):
             ops.lm_add(self._flat_view(self._flat_g, bias), ops.colsum(dL, Rp, Vp), V, True)
-        if live(self.WORD_TABLE):
-            ops.lm_decoder_wgrad(dL, z, self._flat_view(self._flat_g, self.WORD_TABLE), V, True)
+        if live(head.table):
+            ops.lm_decoder_wgrad(dL, z, self._flat_view(self._flat_g, head.table), V, True)
         dz = ops.gemm(dL, table, Rp, H, Vp, tb=True)
         dx = ops.layernorm_bwd(dz, a, mean, rstd, self._flat_view(self._flat_p, gamma),
                                dgamma=self._flat_view(self._flat_g, gamma) if live(gamma) else None,
@@ -818,6 +879,67 @@ class CrctModel(nn.Module):
         world = self._lm_world()
         dL = ops.lm_ce_bwd(logits, job.labels, lse, g.reshape(1).float(), job.inv_n / world, job.R, self.config.vocab_size)
         return self._lm_grads(dL, saved, job.rows, job.R, shape, world)
+
+    # ------------------------------------------------------------------ masked-region head (csrc/region_head.hip; see img_loss_coeff above)
+    def _region_job(self, image_label, targets, keyword, B, V):
+        """Host side of one batch's masked-region loss, before any launch: the rows with image_label == 1 are compacted; their targets
+        (``keyword`` names the argument they came from) are checked -- a class id must lie in [0, C), a soft target must be finite and
+        >= 0; what other rows hold is never looked at -- and (rows | class ids) go up in one pinned, asynchronous copy; a soft target
+        tensor is taken on the device as fp32 [B * V, C] and read there by row.  None when no region is labelled."""
+        if image_label is None:
+            raise ValueError("image_label is required by params['img_loss_coeff'] > 0: 1 on the regions the loader masked (utils.py:194-217)")
+        C_ = self.config.v_target_size
+        lab = image_label.cpu() if image_label.is_cuda else image_label      # a device tensor costs one .cpu(), as for the LM labels
+        lab = lab.reshape(-1)
+        if lab.numel() != B * V:
+            raise ValueError("image_label has %d elements, the batch has B * V = %d * %d regions" % (lab.numel(), B, V))
+        rows = (lab == 1).nonzero().flatten()
+        R = int(rows.numel())
+        if R == 0:
+            return None
+        if not torch.is_floating_point(targets):
+            if targets.numel() != B * V:
+                raise ValueError("%s: class ids are [B, V] = [%d, %d]; got %s" % (keyword, B, V, tuple(targets.shape)))
+            ids = targets.reshape(-1)
+            ids = ids[rows.to(ids.device)].cpu().to(torch.int64)
+            bad = (ids < 0) | (ids >= C_)
+            if bool(bad.any()):
+                raise ValueError("%s: %d on a region with image_label == 1 is no class id in [0, v_target_size = %d)" % (keyword, int(ids[bad][0]), C_))
+            dev = self._upload_i32("region", rows, ids)
+            return _RegionJob(dev[:R], dev[R:], None, R, 1.0 / R)
+        if tuple(targets.shape) != (B, V, C_):
+            raise ValueError("%s: soft targets are [B, V, v_target_size] = [%d, %d, %d]; got %s" % (keyword, B, V, C_, tuple(targets.shape)))
+        flat = targets.reshape(B * V, C_)
+        picked = flat.index_select(0, rows.to(flat.device))
+        if bool(((picked < 0) | ~torch.isfinite(picked)).any()):
+            raise ValueError("%s: a soft target on a region with image_label == 1 is negative or not finite" % keyword)
+        flat = flat.to(device=self._flat_p.device, dtype=torch.float32, non_blocking=True).contiguous()
+        return _RegionJob(self._upload_i32("region", rows), None, flat, R, 1.0 / R)
+
+    def _region_forward(self, seq_v, job):
+        """img_loss fp32 [1, 1] of the masked rows of ``seq_v`` (fp32 [B, V, Hv]) and what the backward needs: the head routine on the region
+        head, then the loss over the C real columns -- soft targets: the one-wave-per-row kernels of csrc/region_head.hip."""
+        head = self._heads["region"]
+        logits, saved = self._lm_logits(seq_v, job.rows, job.R, head)
+        if job.targets is None:
+            # hard targets: the vocabulary kernels, which measured no slower than the one-wave-per-row ones at C = 1601 (EXPERIMENTS.md)
+            _, lse, img_loss = ops.lm_ce_fwd(logits, job.labels, job.R, head.C, job.inv_n)
+        else:
+            _, lse, img_loss = ops.region_ce_fwd(logits, job.R, head.C, job.inv_n, targets=job.targets, rows=job.rows)
+        return img_loss, (saved, logits, lse)
+
+    def _region_backward(self, job, saved, shape, g):
+        """Accumulates the gradients of the six head tensors (each only where it has a gradient) and returns d img_loss / d sequence_output_v,
+        fp32 ``shape``, zero outside the masked rows; bookkeeping, stream order and 1 / world as ``_lm_backward``."""
+        saved, logits, lse = saved
+        self._lm_bookkeeping()
+        world = self._lm_world()
+        head = self._heads["region"]
+        if job.targets is None:
+            dL = ops.lm_ce_bwd(logits, job.labels, lse, g.reshape(1).float(), job.inv_n / world, job.R, head.C)
+        else:
+            dL = ops.region_ce_bwd(logits, lse, g.reshape(1).float(), job.inv_n / world, job.R, head.C, targets=job.targets, rows=job.rows)
+        return self._lm_grads(dL, saved, job.rows, job.R, shape, world, head)
 
     def _lm_scores(self, seq_t):
         """(prediction_scores_t fp32 [B, T, V], a view of the padded logits; the identity row list; what the backward needs).  All B * T rows go
@@ -920,7 +1042,7 @@ class CrctModel(nn.Module):
     # ------------------------------------------------------------------ forward (vilbert.py:1540-1661)
     def forward(self, input_ids, txt_loc, image_feat, image_loc, sep_indices=None, sep_len=None, token_type_ids=None,
                 attention_mask=None, image_attention_mask=None, masked_lm_labels=None, image_label=None, image_target=None,
-                next_sentence_label=None, output_all_attention_masks=False, gt_reg=None, areas=None, legend_pred=None):
+                next_sentence_label=None, output_all_attention_masks=False, gt_reg=None, areas=None, legend_pred=None, image_class=None):
         if areas is not None and self.variant[0] == "plotqa":
             raise ValueError("'areas' belongs to the figure_qa / dvqa image embeddings (vilbert.py:1463-1464, 1488-1489)")
         if gt_reg is None:
@@ -941,6 +1063,11 @@ class CrctModel(nn.Module):
         train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
         # the masked-LM loss of this batch (host work only; a bad label is refused here, before any launch); None: off, or no token has a label
         lm_job = self._lm_job(masked_lm_labels) if train_branch and self.lm_loss_coeff > 0.0 else None
+        # ... and the masked-region loss: the targets are image_target unless image_class is given (it takes their place for the loss ONLY)
+        region_job = None
+        if train_branch and self.img_loss_coeff > 0.0:
+            region_job = self._region_job(image_label, image_target if image_class is None else image_class,
+                                          "image_target" if image_class is None else "image_class", *image_feat.shape[:2])
         tensors = self._device_inputs(input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
                                       image_attention_mask, image_target, R, next_sentence_label if train_branch else None, areas)
         B, T = tensors["tokens"].shape
@@ -968,13 +1095,14 @@ class CrctModel(nn.Module):
                 tensors = dict(tensors, image_feat=live[0].detach(), image_loc=live[1].detach(), loc=live[2].detach())
                 if live[3] is not None:
                     tensors["areas"] = live[3].detach()
-            self._lm_pending = lm_job
+            self._lm_pending = (lm_job, region_job) if lm_job is not None or region_job is not None else None
             try:
                 (loss, nsp, reg_loss, logits, reg, stats), seq, scores, maps = _StepFn.split(self, _StepFn.apply(self._anchor, self, tensors, step, *live))
             finally:
                 self._lm_pending = None
             lm_loss = _LmLossFn.apply(seq[0], self, lm_job) if lm_job is not None else None
             lm_scores = _LmScoresFn.apply(seq[0], self) if self.return_lm_scores else None
+            img_loss = _RegionLossFn.apply(seq[1], self, region_job) if region_job is not None else None
             value = scores[1] if len(scores) > 1 else None
             if scores:
                 logits = scores[0]                     # differentiable_scores: the copies that are part of the graph
@@ -983,9 +1111,10 @@ class CrctModel(nn.Module):
             eng.forward(self._flat_p, self._flat_b16, tensors, step)
             logits, reg, stats = eng.snapshot(B)
             loss, nsp, reg_loss = stats[0], stats[1:2], reg[1]
-            seq = eng.sequence_outputs() if self.return_sequence_outputs or lm_job is not None or self.return_lm_scores else ()
+            seq = eng.sequence_outputs() if self.return_sequence_outputs or lm_job is not None or region_job is not None or self.return_lm_scores else ()
             lm_loss = self._lm_forward(seq[0], lm_job)[0] if lm_job is not None else None      # torch.no_grad() in the training branch: forward only
             lm_scores = self._lm_scores(seq[0])[0] if self.return_lm_scores else None
+            img_loss = self._region_forward(seq[1], region_job)[0] if region_job is not None else None
             maps = [eng.attention_probs(*key) for key in map_keys]
             if output_all_attention_masks and not train_branch:
                 attention_maps = self._attention_maps(eng)
@@ -1009,7 +1138,7 @@ class CrctModel(nn.Module):
         self.sequence_output_t, self.sequence_output_v = seq if seq and self.return_sequence_outputs else (None, None)
         self.prediction_scores_t = lm_scores                 # (return_lm_scores; None otherwise)
         if train_branch:
-            return lm_zero if lm_loss is None else lm_loss, img_zero, nsp, self.sequence_output_t, lm_scores, logits, reg_out, legend_loss   # vilbert.py:1659
+            return lm_zero if lm_loss is None else lm_loss, img_zero if img_loss is None else img_loss, nsp, self.sequence_output_t, lm_scores, logits, reg_out, legend_loss   # vilbert.py:1659
         return lm_scores, None, logits, self.sequence_output_t, attention_maps, reg_out, legend_loss               # vilbert.py:1661
 
     def _attention_map_keys(self):
@@ -1074,12 +1203,12 @@ class VisualDialogEncoder(nn.Module):
     def forward(self, input_ids, txt_loc, image_feat, image_loc, sep_indices=None, sep_len=None, token_type_ids=None,
                 attention_mask=None, masked_lm_labels=None, next_sentence_label=None, head_mask=None,
                 random_round_indices=None, output_nsp_scores=False, output_lm_scores=False, image_attention_mask=None,
-                image_label=None, image_target=None, gt_reg=None, areas=None, legend_pred=None):
+                image_label=None, image_target=None, gt_reg=None, areas=None, legend_pred=None, image_class=None):
         masked_lm_loss = masked_img_loss = nsp_loss = prediction_scores_t = None
         kw = dict(sep_indices=sep_indices, sep_len=sep_len, token_type_ids=token_type_ids, attention_mask=attention_mask,
                   masked_lm_labels=masked_lm_labels, next_sentence_label=next_sentence_label,
                   image_attention_mask=image_attention_mask, image_label=image_label, image_target=image_target,
-                  gt_reg=gt_reg, areas=areas, legend_pred=legend_pred)
+                  gt_reg=gt_reg, areas=areas, legend_pred=legend_pred, image_class=image_class)
         core = self.bert_pretrained
         was = core.return_lm_scores
         if output_lm_scores:                 # the flag for this call: the appended element is the tensor (encoder_decorator.py:52-53)

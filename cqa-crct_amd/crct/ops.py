@@ -716,3 +716,36 @@ def lm_scores_grad_pack(g, R, Rp, V, Vp, c, out=None):
     L.check(L.load().crct_lm_scores_grad_pack(L.ptr(_chk(g, torch.float32)), g.stride(0), float(c), L.ptr(_chk(dL, torch.bfloat16)), dL.stride(0), int(R), int(Rp),
                                               int(V), int(Vp), L.current_stream()), "lm_scores_grad_pack")
     return dL
+
+
+# ---- masked-region head (csrc/region_head.hip): the two loss kernels; the rest of the head is the lm_* machinery above
+def _region_targets(labels, targets, rows, C):
+    if (labels is None) == (targets is None):
+        raise ValueError("region_ce: give either labels (hard) or targets with rows (soft)")
+    if targets is not None:
+        if rows is None or targets.dim() != 2 or targets.shape[1] != C or not targets.is_contiguous():
+            raise ValueError("region_ce: soft targets are a contiguous fp32 [N, C = %d] tensor read at rows (int32 [R])" % C)
+    return _chk(labels, torch.int32), _chk(targets, torch.float32), _chk(rows, torch.int32) if targets is not None else None
+
+
+def region_ce_fwd(logits, R, C, inv_n, labels=None, targets=None, rows=None):
+    """(loss fp32 [R], lse fp32 [R], img_loss fp32 [1, 1] = inv_n * sum loss) over the first C columns of the fp32 logits [>= R, ld].  Hard:
+    ``labels`` int32 [R]; soft: ``targets`` fp32 [N, C] read in place at ``rows`` int32 [R] (crct_region_ce_fwd)."""
+    dev = logits.device
+    labels, targets, rows = _region_targets(labels, targets, rows, int(C))
+    loss, lse, total = torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(1, 1, device=dev)
+    L.check(L.load().crct_region_ce_fwd(L.ptr(_chk(logits, torch.float32)), logits.stride(0), L.ptr(labels), L.ptr(targets), L.ptr(rows), L.ptr(loss),
+                                        L.ptr(lse), L.ptr(total), int(R), int(C), float(inv_n), L.current_stream()), "region_ce_fwd")
+    return loss, lse, total
+
+
+def region_ce_bwd(logits, lse, g, inv_n, R, C, labels=None, targets=None, rows=None):
+    """dL bf16 [Rp, Cp] = (softmax * s_r - t) * g * inv_n over the real rows and columns (s_r = sum_j t_rj; hard: t the one-hot), +0 in every
+    pad row and column; g: device fp32 scalar (crct_region_ce_bwd)."""
+    Rp, Cp = logits.shape
+    labels, targets, rows = _region_targets(labels, targets, rows, int(C))
+    dL = torch.empty(Rp, Cp, device=logits.device, dtype=torch.bfloat16)
+    L.check(L.load().crct_region_ce_bwd(L.ptr(_chk(logits, torch.float32)), logits.stride(0), L.ptr(labels), L.ptr(targets), L.ptr(rows),
+                                        L.ptr(_chk(lse, torch.float32)), L.ptr(_chk(g, torch.float32)), float(inv_n), L.ptr(dL), Cp, int(R), Rp, int(C), Cp,
+                                        L.current_stream()), "region_ce_bwd")
+    return dL

@@ -184,6 +184,9 @@ class FusedAdamW(torch.optim.Optimizer):
             # update waits for: not built
             raise RuntimeError("FusedAdamW.set_early(True) with params['lm_loss_coeff'] > 0 is not supported: use the overlapped update "
                                "(overlap = True) without early mode")
+        if on and getattr(self.core, "img_loss_coeff", 0.0) > 0.0:      # the masked-region head: the same node-in-front-of-the-pass order
+            raise RuntimeError("FusedAdamW.set_early(True) with params['img_loss_coeff'] > 0 is not supported: use the overlapped update "
+                               "(overlap = True) without early mode")
         self.early = bool(on)
         self.core.record_segment_events = bool(on)
 

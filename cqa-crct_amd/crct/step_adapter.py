@@ -40,6 +40,7 @@ def forward(dialog_encoder, batch, params, output_nsp_scores=False, output_lm_sc
     else:
         regression_target = [R, "L1"]                 # :106
     image_target = pick("image_target")
+    image_class = pick("image_class") if "image_class" in batch else None      # the masked regions' true classes (params['img_loss_coeff'])
 
     # text key mask = arange(T) < sep_indices[hist_len] + 1   (:118-120).  The native model takes the DESCRIPTION of that
     # mask and builds it inside its first launch; any other model gets the materialised tensor, as in the reference.
@@ -54,7 +55,8 @@ def forward(dialog_encoder, batch, params, output_nsp_scores=False, output_lm_sc
         tokens, txt_loc, features, image_loc, sep_indices=sep_indices, sep_len=sep_len, token_type_ids=segments,
         masked_lm_labels=mask, attention_mask=attention_mask, next_sentence_label=next_sentence_labels,
         output_nsp_scores=output_nsp_scores, output_lm_scores=output_lm_scores, image_attention_mask=image_mask,
-        image_label=image_label, image_target=image_target, gt_reg=regression_target, areas=areas)
+        image_label=image_label, image_target=image_target, gt_reg=regression_target, areas=areas,
+        **({} if image_class is None else dict(image_class=image_class)))
     # with output_lm_scores the encoder appends prediction_scores_t behind the four (encoder_decorator.py:52-53), where the reference's
     # six-name unpack dies; the return tuples here keep their lengths and the native model leaves the tensor on
     # ``bert_pretrained.prediction_scores_t``
@@ -75,6 +77,10 @@ def forward(dialog_encoder, batch, params, output_nsp_scores=False, output_lm_sc
         lm_coeff = float(params.get("lm_loss_coeff", 0.0) or 0.0)
         if lm_coeff > 0.0 and lm_loss is not None:
             loss = loss + lm_coeff * lm_loss.sum()
+        # the masked-region term (same lines): img_loss is the model's node on sequence_output_v
+        img_coeff = float(params.get("img_loss_coeff", 0.0) or 0.0)
+        if img_coeff > 0.0 and img_loss is not None:
+            loss = loss + img_coeff * img_loss.sum()
     if evaluation:
         return loss, lm_loss, nsp_loss, img_loss, nsp_scores, regression
     return loss, lm_loss, nsp_loss, img_loss, nsp_scores, regression, legend_loss

@@ -41,6 +41,9 @@ hipError_t crct_gemm_launch_grouped(const CrctGemmGroup& grp, hipStream_t s);
 // streams.hip: three streams on hardware queues other than main's (+ a second one on the last queue), found by probing
 int crct_streams_place(hipStream_t main, hipStream_t out[4], int* n_classes);
 
+// out[0] = inv_n * sum_r loss[r] in a fixed order, one workgroup (lm_head.hip): the mean of the masked-LM loss and of the masked-region loss
+void crct_loss_mean(const float* loss, float* out, int R, float inv_n, hipStream_t s);
+
 // upper bound of the workgroup count of the LayerNorm-backward style kernels (4 rows per workgroup and pass):
 // sizes the column-partials scratch [partials][blocks][H]
 #define CRCT_LN_BWD_MAX_BLOCKS 256

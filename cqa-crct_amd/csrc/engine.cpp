@@ -254,8 +254,9 @@ struct crct_engine {
   std::vector<hipEvent_t> evpool;
   size_t evnext = 0;
   std::vector<std::pair<int64_t, int64_t>> seg_range;
-  // 1: segment 0 is the masked-LM head's (cls.predictions.*, params['lm_loss_coeff'] > 0): its gradients are produced by the host side
-  // (csrc/lm_head.hip) before the pass starts, so it launches nothing here and only takes part in the events; the heads' segment and
+  // 1: segment 0 is the masked-LM head's (cls.predictions.*, params['lm_loss_coeff'] > 0) and / or the masked-region head's
+  // (cls.imagePredictions.*, params['img_loss_coeff'] > 0): its gradients are produced by the host side (csrc/lm_head.hip,
+  // csrc/region_head.hip) before the pass starts, so it launches nothing here and only takes part in the events; the heads' segment and
   // everything behind it then sit one place further back.  0 (those tensors have size 0): segments and ranges as without it.
   int lm_seg = 0;
   // weight-gradient ownership (CrctStepCfg.wgrad_overwrite): the Linear weights whose gradient is produced by exactly ONE
@@ -1510,7 +1511,9 @@ extern "C" crct_engine_t* crct_engine_create_variant(const CrctModelDims* dims, 
     return std::make_pair(lo, hi);
   };
   {
-    const auto lm = range_of({"cls.predictions."});
+    // ONE launch-free segment for the masked-LM head and the masked-region head (cls.imagePredictions.*, params['img_loss_coeff'] > 0),
+    // whichever is on: their tensors are adjacent in the tail of the buffers
+    const auto lm = range_of({"cls.predictions.", "cls.imagePredictions."});
     if (lm.second > lm.first) { e->lm_seg = 1; e->seg_range.push_back(lm); }
   }
   e->seg_range.push_back(range_of({"bert.t_pooler.", "bert.v_pooler.", "cls.bi_seq_relationship.", "regressor."}));

@@ -341,6 +341,10 @@ bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) 
 
 }  // namespace
 
+void crct_loss_mean(const float* loss, float* out, int R, float inv_n, hipStream_t s) {
+  crct_launch(lm_loss_mean_kernel, dim3(1), dim3(256), 0, s, loss, out, R, inv_n);
+}
+
 extern "C" int crct_lm_gather_rows(const float* src, const int32_t* rows, void* dst_bf16, int R, int Rp, int H, crct_stream_t stream) {
   CRCT_REQUIRE(src && dst_bf16 && (rows || R == 0), "lm_gather_rows: null argument");
   CRCT_REQUIRE(R >= 0 && Rp >= R && Rp >= 1 && H >= 8 && H % 8 == 0, "lm_gather_rows: R=%d Rp=%d H=%d (0 <= R <= Rp, H a multiple of 8)", R, Rp, H);
@@ -375,7 +379,7 @@ extern "C" int crct_lm_ce_fwd(const float* logits, int64_t ld, const int32_t* la
   CRCT_REQUIRE(logits && labels && loss && lse, "lm_ce_fwd: null argument");
   CRCT_REQUIRE(R >= 1 && V >= 1 && ld >= (V + 3) / 4 * 4 && ld % 4 == 0 && aligned16(logits), "lm_ce_fwd: R=%d V=%d ld=%ld (ld a multiple of 4 covering V, 16-byte aligned rows)", R, V, (long)ld);
   crct_launch(lm_ce_fwd_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, labels, loss, lse, V);
-  if (lm_loss) crct_launch(lm_loss_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)loss, lm_loss, R, inv_n);
+  if (lm_loss) crct_loss_mean(loss, lm_loss, R, inv_n, (hipStream_t)stream);
   CRCT_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -273,6 +273,25 @@ int crct_lm_topk_rows(const float* logits, int64_t ld, const int32_t* labels, in
 int crct_lm_scores_grad_pack(const float* g, int64_t ldg, float c, void* dL_bf16, int64_t ldd, int R, int Rp, int V, int Vp,
                              crct_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Masked-region head (BertImagePredictionHead, vilbert.py:1065-1077, with ViLBERT's masked-region classification over the regions whose
+ * image_label is 1): the two loss kernels; the rest of the head runs on the crct_lm_* row kernels and crct_gemm_bf16 from operands padded
+ * as there.  C = classes (v_target_size, at most 2048), Cp >= C the padded width, R = masked rows, Rp >= R.  One wave per row, four rows
+ * per workgroup, the row's logits read once into registers; bit-reproducible (no atomics, fixed summation order), vector stores only.
+ * Exactly one target form: hard = labels (int32 [R], 0 <= label < C: the caller checks), targets == rows == NULL; soft = targets (fp32
+ * [N][C], t >= 0, rows of C floats, 4-byte aligned) read in place at row rows[r] (int32 [R]), labels == NULL.
+ *  crct_region_ce_fwd   per row r < R over columns 0 .. C-1 of logits fp32 [R][ld] (ld % 4 == 0, 16-byte aligned; pad columns are never
+ *                       read into a result): lse[r] = max + log(sum exp(x - max)); hard: loss[r] = lse[r] - x[labels[r]]; soft: loss[r] =
+ *                       sum_j t_j (log t_j - (x_j - lse[r])), a term with t_j == 0 being 0.  img_loss (optional) = inv_n * sum_r loss[r],
+ *                       the one-workgroup mean launch of crct_lm_ce_fwd.
+ *  crct_region_ce_bwd   dL bf16 [Rp][ldd] (ldd % 4 == 0): (exp(x[r][j] - lse[r]) * s_r - t[r][j]) * (*g * inv_n) for r < R, j < C, with
+ *                       s_r = sum_j t[r][j] (hard: t = the one-hot, s_r = 1 and no product with it -- crct_lm_ce_bwd's formula); +0 for
+ *                       every pad column C .. Cp-1 and pad row R .. Rp-1.  g: device fp32 scalar. */
+int crct_region_ce_fwd(const float* logits, int64_t ld, const int32_t* labels, const float* targets, const int32_t* rows, float* loss,
+                       float* lse, float* img_loss, int R, int C, float inv_n, crct_stream_t stream);
+int crct_region_ce_bwd(const float* logits, int64_t ld, const int32_t* labels, const float* targets, const int32_t* rows, const float* lse,
+                       const float* g, float inv_n, void* dL_bf16, int64_t ldd, int R, int Rp, int C, int Cp, crct_stream_t stream);
+
 /* Every amax "value" below and in CrctGemmArgs / CrctStepCfg / CrctFp8Shadow is CRCT_FP8_AMAX_LANES consecutive fp32 words
  * (the kernels spread their atomic maxima over them; crct_fp8_update_scales takes the maximum of the words): an amax array
  * for n tensors has n * CRCT_FP8_AMAX_LANES words and entry i starts at word i * CRCT_FP8_AMAX_LANES. */
@@ -885,8 +904,9 @@ size_t crct_engine_workspace_bytes(const crct_engine_t*);
 int crct_engine_num_segments(const crct_engine_t*);
 /* Backward segment s (0 = heads ... last = embeddings) has finished writing gradient elements
  * [lo, hi) of the flat gradient buffer once crct_engine_backward(.., s, ..) returns.
- * An engine created with non-zero sizes for the cls.predictions.* tensors (the masked-LM head, crct_lm_* below) has ONE MORE segment in
- * front: 0 = the masked-LM head's tensors, 1 = heads, ... last = embeddings.  The caller produces those gradients itself before the pass;
+ * An engine created with non-zero sizes for the cls.predictions.* tensors (the masked-LM head, crct_lm_*) or the cls.imagePredictions.*
+ * tensors (the masked-region head, crct_region_*) has ONE MORE segment in front, one for both heads (their ranges are adjacent):
+ * 0 = those heads' tensors, 1 = heads, ... last = embeddings.  The caller produces those gradients itself before the pass;
  * the engine launches nothing for that segment and treats it like any other in its events, callbacks and CrctStepCfg arrays.  With size
  * 0 for those tensors the segments and every range are what they were. */
 int crct_engine_segment_range(const crct_engine_t*, int seg, int64_t* lo, int64_t* hi);
