@@ -24,6 +24,7 @@ from . import ops
 from .config import BertConfig
 from .engine import StepEngine
 from .fp8 import AMAX_WINDOW, Fp8State
+from .heads import HeadPort, LmPrediction, PredictionHead, _HeadLossFn, _LmScoresFn, lm_rows, region_rows      # noqa: F401 (LmPrediction: importable from here)
 from .layout import frozen_tensors, img_loss_coeff, is_frozen, lm_loss_coeff, model_variant, optional_grad, parameter_table
 
 
@@ -36,6 +37,10 @@ class _Node(nn.Module):
 
 # Where each family of extra outputs sits behind the six fixed ones of a _StepFn result: three slices of result[6:]
 _StepLayout = collections.namedtuple("_StepLayout", "seq scores maps")
+
+# What one step hands out behind the six, as ``CrctModel.forward`` decided it: the sequence outputs (asked for, or read by a prediction head's
+# loss or scores), the scores as tensors of their own (``differentiable_scores``), the keys of the requested attention maps
+_StepWants = collections.namedtuple("_StepWants", "seq scores map_keys")
 
 
 class _StepFn(torch.autograd.Function):
@@ -53,10 +58,10 @@ class _StepFn(torch.autograd.Function):
     scale) and is local: a data-parallel pass never exchanges it.  Extra outputs behind the six, in three families whose places
     ``ctx.layout`` records and ``split`` reads back: the encoder's final hidden states (``model.return_sequence_outputs``), the logits and
     the PlotQA regressor's value (``model.differentiable_scores``) and the requested attention maps (``model.attention_map_outputs``) --
-    see those attributes.  An output without an upstream gradient asks for nothing."""
+    see those attributes; which of them a call hands out is its ``wants`` argument.  An output without an upstream gradient asks for nothing."""
 
     @staticmethod
-    def forward(ctx, anchor, model, tensors, step, image_feat=None, image_loc=None, loc=None, areas=None):
+    def forward(ctx, anchor, model, tensors, step, wants, image_feat=None, image_loc=None, loc=None, areas=None):
         # (fp8 data gradients only: the forward pass is the plain bf16 one -- no fp8 state, no copies -- the backward pass gets it)
         fwd_step = {k: v for k, v in step.items() if k != "fp8"} if step.get("fp8_backward_only") else step
         eng = model._engine
@@ -73,14 +78,13 @@ class _StepFn(torch.autograd.Function):
             out.extend(ts)
             return slice(len(out) - 6 - len(ts), len(out) - 6)
         # the encoder's final hidden states, fresh fp32 tensors (StepEngine.sequence_outputs)
-        # (also what the masked-LM head reads: _LmLossFn hangs on sequence_output_t, so its gradient comes back as that output's upstream)
-        # (... and the masked-region head: _RegionLossFn hangs on sequence_output_v in the same way)
-        seq = family(eng.sequence_outputs() if model.return_sequence_outputs or model._lm_pending is not None or model.return_lm_scores else ())
+        # (also what the prediction heads read: heads._HeadLossFn / _LmScoresFn hang on them, so their gradients come back as these outputs' upstream)
+        seq = family(eng.sequence_outputs() if wants.seq else ())
         # the logits, and the PlotQA regressor's value: tensors of their own (two B-sized copies)
         with_value = model.variant[1] == "plotqa"
-        scores = family([t.clone() for t in ((logits, reg_all[0]) if with_value else (logits,))] if model.differentiable_scores else ())
+        scores = family([t.clone() for t in ((logits, reg_all[0]) if with_value else (logits,))] if wants.scores else ())
         # the requested attention maps, fresh fp32 tensors, one launch each (StepEngine.attention_probs)
-        ctx.map_keys = model._attention_map_keys()
+        ctx.map_keys = wants.map_keys
         maps = family([eng.attention_probs(*key) for key in ctx.map_keys])
         ctx.layout = model._step_layout = _StepLayout(seq, scores, maps)
         return tuple(out)
@@ -107,7 +111,7 @@ class _StepFn(torch.autograd.Function):
         if g_nsp is None and g_reg is None:
             if g_loss is None:
                 if not requests:
-                    return (None,) * 8
+                    return (None,) * 9
                 g_loss = torch.zeros(1, device=model._flat_p.device)   # only the sequence outputs / scores / maps are differentiated: the heads get zero loss seeds
             step["g_loss"] = g_loss.reshape(1).float()                 # views / no-ops for the fp32 scalar autograd hands over
         else:                                                          # a caller combining nsp_loss / reg_loss itself
@@ -117,85 +121,7 @@ class _StepFn(torch.autograd.Function):
             gr = g_reg.reshape(B).float() if g_reg is not None else torch.zeros(B, device=dev)
             step["g_nsp"] = (gn + gl * step["nsp_coeff"]).contiguous()
             step["g_reg"] = (gr + gl * (step["reg_coeff"] / B)).contiguous()
-        return (None, None, None, None) + model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[4:8], requests)
-
-
-# One batch's masked rows as the masked-LM head takes them: flat row indices into [B * T] and their labels (int32, on the device, one
-# pinned upload), R of them, 1 / n
-_LmJob = collections.namedtuple("_LmJob", "rows labels R inv_n")
-
-
-class _LmLossFn(torch.autograd.Function):
-    """The masked-LM loss (params['lm_loss_coeff'] > 0) as a node of its own on ``sequence_output_t``, the differentiable output of
-    ``_StepFn``: forward = ``CrctModel._lm_forward`` (gather, transform, vocabulary projection, cross-entropy over the R masked rows),
-    backward = ``CrctModel._lm_backward``, which accumulates the head's parameter gradients and the decoder term of the word table into
-    the flat gradient buffer and RETURNS d lm_loss / d sequence_output_t -- autograd hands it to ``_StepFn.backward`` as the upstream
-    gradient of that output, i.e. through the engine's output-gradient request, so the text stream, the co-attention and any
-    requested input gradient see it.  The upstream gradient of the loss (a GradScaler's scale, a caller's weight) is a device scalar
-    the gradient kernel reads: no ``.item()``."""
-
-    @staticmethod
-    def forward(ctx, seq_t, model, job):
-        lm_loss, ctx.saved = model._lm_forward(seq_t, job)
-        ctx.model, ctx.job, ctx.shape = model, job, seq_t.shape
-        return lm_loss
-
-    @staticmethod
-    def backward(ctx, g):
-        return ctx.model._lm_backward(ctx.job, ctx.saved, ctx.shape, g), None, None
-
-
-# One batch's masked regions as the masked-region head takes them: flat row indices into [B * V] (int32, device), R of them, 1 / n, and ONE of
-# labels (int32 [R], device: class ids, the hard form) and targets (fp32 [B * V, C] on the device, read in place at ``rows``: the soft form)
-_RegionJob = collections.namedtuple("_RegionJob", "rows labels targets R inv_n")
-
-# What one prediction head is made of, for the ONE head routine (``CrctModel._lm_logits`` / ``_lm_grads``): the names of the decoder bias, the
-# transform's Linear weight / bias and LayerNorm weight / bias and the decoder's weight (the tied word table for the text head), the hidden
-# width, the class count and which sequence output feeds it (0 = text, 1 = visual).  The padded decoder operands are cached per ``key``.
-_Head = collections.namedtuple("_Head", "key bias w b gamma beta table H C seq")
-
-
-class _RegionLossFn(torch.autograd.Function):
-    """The masked-region loss (params['img_loss_coeff'] > 0) as a node on ``sequence_output_v``, the twin of ``_LmLossFn``: forward =
-    ``CrctModel._region_forward`` (the head on the R masked regions, csrc/region_head.hip's loss), backward = ``CrctModel._region_backward``,
-    which accumulates the six head gradients into the flat gradient buffer and RETURNS d img_loss / d sequence_output_v, zero outside
-    the masked rows -- the upstream gradient of that output of ``_StepFn``, i.e. the engine's unchanged output-gradient request."""
-
-    @staticmethod
-    def forward(ctx, seq_v, model, job):
-        img_loss, ctx.saved = model._region_forward(seq_v, job)
-        ctx.model, ctx.job, ctx.shape = model, job, seq_v.shape
-        return img_loss
-
-    @staticmethod
-    def backward(ctx, g):
-        return ctx.model._region_backward(ctx.job, ctx.saved, ctx.shape, g), None, None
-
-
-class _LmScoresFn(torch.autograd.Function):
-    """``prediction_scores_t`` (``CrctModel.return_lm_scores``) as a node on ``sequence_output_t``, beside ``_LmLossFn``: forward =
-    ``CrctModel._lm_logits`` over ALL B * T rows, the output a [B, T, V] view of the padded logits; backward packs the upstream [B, T, V]
-    gradient into the bf16 [Rp, Vp] form the loss's gradient kernel leaves (``ops.lm_scores_grad_pack``) and runs the same chain,
-    ``CrctModel._lm_grads``: head gradients and the decoder term where the tensor has a gradient, d / d sequence_output_t returned."""
-
-    @staticmethod
-    def forward(ctx, seq_t, model):
-        scores, rows, ctx.saved = model._lm_scores(seq_t)
-        ctx.model, ctx.rows, ctx.shape = model, rows, seq_t.shape
-        ctx.set_materialize_grads(False)
-        return scores
-
-    @staticmethod
-    def backward(ctx, g):
-        if g is None:
-            return None, None
-        return ctx.model._lm_scores_backward(ctx.rows, ctx.saved, ctx.shape, g), None
-
-
-# What ``CrctModel.lm_predict`` returns: the flat row indices into [B * T] (int32), the k most probable token ids of each row (int32 [R, k], most
-# probable first, ties to the smaller id) with their log-probabilities (fp32 [R, k]), and -- with labels, else None -- each row's label
-# log-probability (fp32 [R]) and rank (int32 [R]: the number of tokens in front of the label; ``rank < k`` = "label in the top k")
-LmPrediction = collections.namedtuple("LmPrediction", "rows ids logprobs label_logprob label_rank")
+        return (None,) * 5 + model._run_backward_with_inputs(ctx.tensors, step, ctx.needs_input_grad[5:9], requests)
 
 
 def _upstream_f32(g):
@@ -331,11 +257,8 @@ class CrctModel(nn.Module):
         # on too the head runs twice, on the masked rows and on all rows; the loss keeps its launches and bits.
         self.return_lm_scores = False
         self.prediction_scores_t = None
-        self._lm_all_rows = {}
-        self._lm_book_pass = -1
-        self._lm_pending = None
-        self._head_pads, self._shadow_gen = {}, 0
-        self._staging = {}
+        self._opened_pass = -1
+        self._shadow_gen = 0
         # params['img_loss_coeff'] > 0: the masked-region objective, the visual twin of the above (ViLBERT's masked-region classification
         # on BertImagePredictionHead, vilbert.py:1065-1077).  In the training branch slot 1 of the tuple is then img_loss = the mean over the
         # n regions with image_label == 1 (the loader has zeroed their features, utils.py:194-217) of the head's loss against the region's
@@ -349,9 +272,12 @@ class CrctModel(nn.Module):
         if self.img_loss_coeff > 0.0 and config.v_target_size > self.REGION_MAX_CLASSES:
             raise NotImplementedError("params['img_loss_coeff'] with v_target_size = %d: the masked-region loss kernels hold a row of logits in one "
                                       "wave's registers, at most %d classes" % (config.v_target_size, self.REGION_MAX_CLASSES))
-        self._heads = dict(
-            lm=_Head("lm", *self.LM_HEAD, self.WORD_TABLE, config.hidden_size, config.vocab_size, 0),
-            region=_Head("region", *self.REGION_HEAD, config.v_hidden_size, config.v_target_size, 1))
+        # the two heads: decoder bias, transform Linear weight / bias, LayerNorm weight / bias, decoder weight (text: the tied word table)
+        t, v = "cls.predictions.", "cls.imagePredictions."
+        self.text_head = PredictionHead(self, t + "bias", t + "transform.dense.weight", t + "transform.dense.bias", t + "transform.LayerNorm.weight",
+                                        t + "transform.LayerNorm.bias", "bert.embeddings.word_embeddings.weight", config.hidden_size, config.vocab_size)
+        self.region_head = PredictionHead(self, v + "decoder.bias", v + "transform.dense.weight", v + "transform.dense.bias", v + "transform.LayerNorm.weight",
+                                          v + "transform.LayerNorm.bias", v + "decoder.weight", config.v_hidden_size, config.v_target_size)
         self.init_weights(int(params.get("seed", 0)))
         self.register_load_state_dict_post_hook(lambda m, k: m._invalidate_shadow())
 
@@ -446,7 +372,8 @@ class CrctModel(nn.Module):
             self._const_zeros = None
             self._param_events = None
             self._opt_stream = None
-            self._head_pads = {}
+            self.text_head.reset()
+            self.region_head.reset()
             self._rebind()
         return self
 
@@ -488,7 +415,7 @@ class CrctModel(nn.Module):
         therefore holds stale values between ``zero_grad()`` and ``backward()``; the values after backward are bit-identical
         to the eager path.  Falls back to the full fill until one backward pass has run."""
         self._set_optional_grads(False)
-        self._lm_book_pass = -1
+        self._opened_pass = -1
         plan = self._lazy_zero_plan() if lazy else None
         if plan is None:
             self._flat_g.zero_()
@@ -673,20 +600,32 @@ class CrctModel(nn.Module):
         waits, self._grad_waits = self._grad_waits, None
         return waits
 
-    def _run_backward(self, tensors, step):
-        if self._opt_stream is not None:             # overlapped optimizer update / gradient memset of the previous step
-            from .events import order_streams
-            order_streams(self._opt_stream, torch.cuda.current_stream())
+    def _open_grad_pass(self):
+        """What has to happen before anything accumulates into the gradient buffer: the engine's pass does it first thing, a prediction
+        head's node -- which autograd runs BEFORE the engine's pass of the same batch -- through ``_open_grad_pass_once``."""
+        self._wait_optimizer()
         self._ensure_grad_views()
         self._grads_dirty = True                     # gradients are being accumulated again (optimizer bookkeeping)
+        # first pass since a lazy clear: the owned weight gradients hold stale values, which this engine's pass will overwrite if it
+        # writes exactly those (an engine rebuilt for a larger batch in between owns the same set: it follows from the layout)
+        if self._wgrad_overwrite_next and not (self._lazy_plan_key is not None and self._engine.wgrad_owned_key() == self._lazy_plan_key):
+            self._flat_g.zero_()                     # an engine with another owned set: nothing else has been accumulated yet
+            self._wgrad_overwrite_next = False
+
+    def _open_grad_pass_once(self):
+        """``_open_grad_pass`` once per engine pass, whichever head node runs first: the token is the count of engine passes, which moves
+        with ``_run_backward``; a clear in between drops it."""
+        if self._opened_pass != self._backward_passes:
+            self._opened_pass = self._backward_passes
+            self._open_grad_pass()
+
+    def _run_backward(self, tensors, step):
+        self._open_grad_pass()
         eng = self._engine
         self._grad_waits = None
-        if self._wgrad_overwrite_next:               # first pass since a lazy clear: the owned weight gradients hold stale values
-            if self._lazy_plan_key is not None and eng.wgrad_owned_key() == self._lazy_plan_key:
-                step = dict(step, wgrad_overwrite=True)     # ... and this engine writes exactly those (an engine rebuilt for a
-            else:                                           # larger batch in between owns the same set: it follows from the layout)
-                self._flat_g.zero_()                 # an engine with another owned set: nothing else has been accumulated yet
-        self._wgrad_overwrite_next = False           # a further pass before the next clear accumulates
+        if self._wgrad_overwrite_next:               # a lazy clear is still pending: this pass writes the owned weight gradients,
+            step = dict(step, wgrad_overwrite=True)
+            self._wgrad_overwrite_next = False       # a further pass before the next clear accumulates
         self._backward_passes = getattr(self, "_backward_passes", 0) + 1
         if tensors.get("areas") is not None and not self._optional_live:
             self._set_optional_grads(True)
@@ -735,239 +674,20 @@ class CrctModel(nn.Module):
             d_feat = d_feat.to(tensors["image_feat"].dtype)
         return d_feat, d_iloc, d_tloc, d_areas
 
-    # ------------------------------------------------------------------ masked-LM head (csrc/lm_head.hip; see lm_loss_coeff above)
-    REGION_HEAD = ("cls.imagePredictions.decoder.bias", "cls.imagePredictions.transform.dense.weight", "cls.imagePredictions.transform.dense.bias",
-                   "cls.imagePredictions.transform.LayerNorm.weight", "cls.imagePredictions.transform.LayerNorm.bias",
-                   "cls.imagePredictions.decoder.weight")
+    # ------------------------------------------------------------------ prediction heads (crct/heads.py; see lm_loss_coeff / img_loss_coeff above)
     REGION_MAX_CLASSES = 2048                    # csrc/region_head.hip: 8 float4 chunks per lane of one wave
-    LM_HEAD = ("cls.predictions.bias", "cls.predictions.transform.dense.weight", "cls.predictions.transform.dense.bias",
-               "cls.predictions.transform.LayerNorm.weight", "cls.predictions.transform.LayerNorm.bias")
-    WORD_TABLE = "bert.embeddings.word_embeddings.weight"
 
-    def _lm_job(self, masked_lm_labels):
-        """Host side of one batch's masked-LM loss, before any launch: the labels are checked (-1 = no label, else a token id), the rows
-        with a label are compacted and (rows | labels) go up in one pinned, asynchronous copy.  None when no token has a label."""
-        lab = masked_lm_labels
-        if lab.is_cuda:
-            lab = lab.cpu()                                   # the loader leaves them on the host (encoder_decorator.py:85); this is a sync
-        lab = lab.reshape(-1).to(torch.int64)
-        V = self.config.vocab_size
-        if bool(((lab >= V) | (lab < -1)).any()):
-            bad = lab[(lab >= V) | (lab < -1)]
-            raise ValueError("masked_lm_labels: %d is neither -1 (no label) nor a token id below vocab_size = %d" % (int(bad[0]), V))
-        rows = (lab >= 0).nonzero().flatten()
-        R = int(rows.numel())
-        if R == 0:
-            return None
-        dev = self._upload_i32("lm", rows, lab[rows])
-        return _LmJob(dev[:R], dev[R:], R, 1.0 / R)
-
-    def _upload_i32(self, key, *parts):
-        """The host integer tensors ``parts`` (R elements each) as ONE int32 device tensor, through head ``key``'s pinned staging buffer and one
-        asynchronous copy."""
-        R = int(parts[0].numel())
-        n = len(parts) * R
-        host, done = self._staging.get(key, (None, None))
-        if done is not None:
-            done.synchronize()                                # the staging buffer is free again (long done in practice)
-        if host is None or host.numel() < n:
-            host = torch.empty(max(n, 4096), dtype=torch.int32).pin_memory()
-        for i, part in enumerate(parts):
-            host[i * R:(i + 1) * R] = part
-        dev = torch.empty(n, dtype=torch.int32, device=self._flat_p.device)
-        dev.copy_(host[:n], non_blocking=True)
-        done = done or torch.cuda.Event()
-        done.record()
-        self._staging[key] = (host, done)
-        return dev
-
-    def _flat_view(self, flat, name):
-        e = self._entries[name]
-        return flat[e.offset:e.offset + e.numel].view(e.shape)
-
-    def _head_operands(self, head):
-        """(bf16 [Vp, H] copy of the decoder weight's bf16 shadow -- the word table for the text head -- with zero pad rows, fp32 [Vp] padded
-        bias) of ``head``, refreshed whenever the shadow was."""
-        pad, gen = self._head_pads.get(head.key, (None, -1))
-        if pad is None or gen != self._shadow_gen:
-            pad = ops.lm_pad_operands(self._flat_view(self._flat_b16, head.table), self._flat_view(self._flat_p, head.bias), *(pad or ()))
-            self._head_pads[head.key] = (pad, self._shadow_gen)
-        return pad
-
-    def _lm_logits(self, seq_t, rows, R, head=None):
-        """A prediction head (``head``: a ``_Head``, the text head by default) on rows ``rows`` (int32 [R], device) of its sequence output
-        ``seq_t`` (fp32 [B, T, H]): z = LayerNorm(gelu(h W^T + b)), logits = z E^T + bias on the padded operands.  Returns (logits fp32
-        [Rp, Vp] -- rows R .. and columns V .. are padding --, what ``_lm_grads`` needs).  The one forward of the masked-LM loss, the scores,
-        the predictions and the masked-region loss."""
-        head = head or self._heads["lm"]
-        if self._opt_stream is not None:             # an overlapped optimizer update may still be writing the head's weights and shadow
-            from .events import order_streams
-            order_streams(self._opt_stream, torch.cuda.current_stream())
-        H, w, b, gamma, beta = head.H, head.w, head.b, head.gamma, head.beta
-        table, bias = self._head_operands(head)
-        hb = ops.lm_gather_rows(seq_t.view(-1, H), rows, R)
-        Rp, Vp = hb.shape[0], table.shape[0]
-        pre = torch.empty(Rp, H, device=hb.device, dtype=torch.bfloat16)
-        a = ops.gemm(hb, self._flat_view(self._flat_b16, w), Rp, H, H, bias=self._flat_view(self._flat_p, b), act="gelu", preact_out=pre)
-        z, mean, rstd = ops.layernorm_fwd(a, self._flat_view(self._flat_p, gamma), self._flat_view(self._flat_p, beta), eps=1e-12)
-        logits = ops.gemm(z, table, Rp, Vp, H, bias=bias, out_f32=True)
-        return logits, (hb, pre, a, mean, rstd, z, table)
-
-    def _lm_forward(self, seq_t, job):
-        """lm_loss fp32 [1, 1] of the masked rows of ``seq_t`` (fp32 [B, T, H]) and what the backward needs: ``_lm_logits``, loss over the V
-        real columns."""
-        logits, saved = self._lm_logits(seq_t, job.rows, job.R)
-        _, lse, lm_loss = ops.lm_ce_fwd(logits, job.labels, job.R, self.config.vocab_size, job.inv_n)
-        return lm_loss, (saved, logits, lse)
-
-    def _lm_world(self):
-        """A data-parallel pass folds 1 / world into the gradient seeds (crct/ddp.py); the engine applies it to the upstream of
-        sequence_output_t itself, so the row gradients handed back are taken out of it again."""
-        return float(self._ddp.world) if self._ddp is not None and getattr(self._ddp, "world", 1) > 1 else 1.0
-
-    def _lm_bookkeeping(self):
-        """The engine pass's bookkeeping on the gradient buffer, which a head node needs done BEFORE it accumulates (autograd runs the head's
-        nodes before the engine's pass of the same batch).  Once per pass, whichever node runs first: the token is the count of engine
-        passes, which moves with ``_run_backward``; a clear in between drops it."""
-        if self._lm_book_pass == self._backward_passes:
-            return
-        self._lm_book_pass = self._backward_passes
+    def _wait_optimizer(self):
+        """Order the current stream after the overlapped optimizer update / gradient memset of the previous step, if there is one."""
         if self._opt_stream is not None:
             from .events import order_streams
             order_streams(self._opt_stream, torch.cuda.current_stream())
-        self._ensure_grad_views()
-        self._grads_dirty = True
-        if self._wgrad_overwrite_next and not (self._lazy_plan_key is not None and self._engine.wgrad_owned_key() == self._lazy_plan_key):
-            self._flat_g.zero_()                     # (_run_backward would do this AFTER the head's gradients are in place)
-            self._wgrad_overwrite_next = False
 
-    def _lm_grads(self, dL, saved, rows, R, shape, world, head=None):
-        """dL bf16 [Rp, Vp] (the gradient of the padded logits, pad rows and columns +0, 1 / world folded in) -> accumulates the gradients of
-        ``head``'s five tensors and of its decoder weight (for the text head: the decoder term of the word table), each only where the
-        tensor is part of the step and has a gradient, and returns d / d (the head's sequence output), fp32 ``shape``, zero outside
-        ``rows``.  The one backward of the masked-LM loss, the scores and the masked-region loss."""
-        head = head or self._heads["lm"]
-        hb, pre, a, mean, rstd, z, table = saved
-        H, V = head.H, head.C
-        Rp, Vp = dL.shape
-        bias, w, b, gamma, beta = head.bias, head.w, head.b, head.gamma, head.beta
-        live = lambda name: self._entries[name].used and name not in self._nograd      # noqa: E731
-        if live(bias):
-            ops.lm_add(self._flat_view(self._flat_g, bias), ops.colsum(dL, Rp, Vp), V, True)
-        if live(head.table):
-            ops.lm_decoder_wgrad(dL, z, self._flat_view(self._flat_g, head.table), V, True)
-        dz = ops.gemm(dL, table, Rp, H, Vp, tb=True)
-        dx = ops.layernorm_bwd(dz, a, mean, rstd, self._flat_view(self._flat_p, gamma),
-                               dgamma=self._flat_view(self._flat_g, gamma) if live(gamma) else None,
-                               dbeta=self._flat_view(self._flat_g, beta) if live(beta) else None, accumulate=True)[0]
-        dpre = ops.lm_gelu_bwd(dx, pre)
-        if live(w):
-            ops.gemm(dpre, hb, H, H, Rp, ta=True, tb=True, out=self._flat_view(self._flat_g, w), accumulate=True)
-        if live(b):
-            ops.colsum(dpre, Rp, H, out=self._flat_view(self._flat_g, b), accumulate=True)
-        dh = ops.gemm(dpre, self._flat_view(self._flat_b16, w), Rp, H, H, tb=True, out_f32=True, alpha=world)
-        d_seq = torch.zeros(shape, dtype=torch.float32, device=dh.device)
-        ops.lm_scatter_rows(dh, rows, d_seq.view(-1, H), R)
-        return d_seq
-
-    def _lm_backward(self, job, saved, shape, g):
-        """Accumulates the gradients of the five head tensors and the decoder term of the word table (each only where the tensor has a
-        gradient) and returns d lm_loss / d sequence_output_t, fp32 ``shape``, zero outside the masked rows.  Runs before the engine's
-        backward pass of the same batch (autograd orders it so) and does that pass's bookkeeping on the gradient buffer first."""
-        saved, logits, lse = saved
-        self._lm_bookkeeping()
-        world = self._lm_world()
-        dL = ops.lm_ce_bwd(logits, job.labels, lse, g.reshape(1).float(), job.inv_n / world, job.R, self.config.vocab_size)
-        return self._lm_grads(dL, saved, job.rows, job.R, shape, world)
-
-    # ------------------------------------------------------------------ masked-region head (csrc/region_head.hip; see img_loss_coeff above)
-    def _region_job(self, image_label, targets, keyword, B, V):
-        """Host side of one batch's masked-region loss, before any launch: the rows with image_label == 1 are compacted; their targets
-        (``keyword`` names the argument they came from) are checked -- a class id must lie in [0, C), a soft target must be finite and
-        >= 0; what other rows hold is never looked at -- and (rows | class ids) go up in one pinned, asynchronous copy; a soft target
-        tensor is taken on the device as fp32 [B * V, C] and read there by row.  None when no region is labelled."""
-        if image_label is None:
-            raise ValueError("image_label is required by params['img_loss_coeff'] > 0: 1 on the regions the loader masked (utils.py:194-217)")
-        C_ = self.config.v_target_size
-        lab = image_label.cpu() if image_label.is_cuda else image_label      # a device tensor costs one .cpu(), as for the LM labels
-        lab = lab.reshape(-1)
-        if lab.numel() != B * V:
-            raise ValueError("image_label has %d elements, the batch has B * V = %d * %d regions" % (lab.numel(), B, V))
-        rows = (lab == 1).nonzero().flatten()
-        R = int(rows.numel())
-        if R == 0:
-            return None
-        if not torch.is_floating_point(targets):
-            if targets.numel() != B * V:
-                raise ValueError("%s: class ids are [B, V] = [%d, %d]; got %s" % (keyword, B, V, tuple(targets.shape)))
-            ids = targets.reshape(-1)
-            ids = ids[rows.to(ids.device)].cpu().to(torch.int64)
-            bad = (ids < 0) | (ids >= C_)
-            if bool(bad.any()):
-                raise ValueError("%s: %d on a region with image_label == 1 is no class id in [0, v_target_size = %d)" % (keyword, int(ids[bad][0]), C_))
-            dev = self._upload_i32("region", rows, ids)
-            return _RegionJob(dev[:R], dev[R:], None, R, 1.0 / R)
-        if tuple(targets.shape) != (B, V, C_):
-            raise ValueError("%s: soft targets are [B, V, v_target_size] = [%d, %d, %d]; got %s" % (keyword, B, V, C_, tuple(targets.shape)))
-        flat = targets.reshape(B * V, C_)
-        picked = flat.index_select(0, rows.to(flat.device))
-        if bool(((picked < 0) | ~torch.isfinite(picked)).any()):
-            raise ValueError("%s: a soft target on a region with image_label == 1 is negative or not finite" % keyword)
-        flat = flat.to(device=self._flat_p.device, dtype=torch.float32, non_blocking=True).contiguous()
-        return _RegionJob(self._upload_i32("region", rows), None, flat, R, 1.0 / R)
-
-    def _region_forward(self, seq_v, job):
-        """img_loss fp32 [1, 1] of the masked rows of ``seq_v`` (fp32 [B, V, Hv]) and what the backward needs: the head routine on the region
-        head, then the loss over the C real columns -- soft targets: the one-wave-per-row kernels of csrc/region_head.hip."""
-        head = self._heads["region"]
-        logits, saved = self._lm_logits(seq_v, job.rows, job.R, head)
-        if job.targets is None:
-            # hard targets: the vocabulary kernels, which measured no slower than the one-wave-per-row ones at C = 1601 (EXPERIMENTS.md)
-            _, lse, img_loss = ops.lm_ce_fwd(logits, job.labels, job.R, head.C, job.inv_n)
-        else:
-            _, lse, img_loss = ops.region_ce_fwd(logits, job.R, head.C, job.inv_n, targets=job.targets, rows=job.rows)
-        return img_loss, (saved, logits, lse)
-
-    def _region_backward(self, job, saved, shape, g):
-        """Accumulates the gradients of the six head tensors (each only where it has a gradient) and returns d img_loss / d sequence_output_v,
-        fp32 ``shape``, zero outside the masked rows; bookkeeping, stream order and 1 / world as ``_lm_backward``."""
-        saved, logits, lse = saved
-        self._lm_bookkeeping()
-        world = self._lm_world()
-        head = self._heads["region"]
-        if job.targets is None:
-            dL = ops.lm_ce_bwd(logits, job.labels, lse, g.reshape(1).float(), job.inv_n / world, job.R, head.C)
-        else:
-            dL = ops.region_ce_bwd(logits, lse, g.reshape(1).float(), job.inv_n / world, job.R, head.C, targets=job.targets, rows=job.rows)
-        return self._lm_grads(dL, saved, job.rows, job.R, shape, world, head)
-
-    def _lm_scores(self, seq_t):
-        """(prediction_scores_t fp32 [B, T, V], a view of the padded logits; the identity row list; what the backward needs).  All B * T rows go
-        through the head; the row list is cached per row count and needs no host labels."""
-        B, T, _ = seq_t.shape
-        N, V = B * T, self.config.vocab_size
-        rows = self._lm_all_rows.get(N)
-        if rows is None or rows.device != seq_t.device:
-            rows = self._lm_all_rows[N] = torch.arange(N, dtype=torch.int32, device=seq_t.device)
-        logits, saved = self._lm_logits(seq_t, rows, N)
-        return logits[:N].view(B, T, logits.shape[1])[:, :, :V], rows, saved
-
-    def _lm_scores_backward(self, rows, saved, shape, g):
-        """d (upstream g on the scores) / d sequence_output_t; the head's and the word table's gradients are accumulated (``_lm_grads``).  g is
-        taken where autograd left it when its rows are 16-byte aligned fp32 with a stride that is a multiple of 4, else through one copy
-        into such rows (vocab_size itself need not be a multiple of 4)."""
-        self._lm_bookkeeping()
-        world = self._lm_world()
-        V = self.config.vocab_size
-        N = int(rows.numel())
-        table = saved[-1]
-        g = g.reshape(N, V)
-        if g.dtype != torch.float32 or g.stride(1) != 1 or g.stride(0) % 4 or g.data_ptr() % 16:
-            buf = torch.empty(N, ops.pad64(V), dtype=torch.float32, device=g.device)
-            buf[:, :V].copy_(g)
-            g = buf[:, :V]
-        dL = ops.lm_scores_grad_pack(g, N, ops.pad64(max(N, 1)), V, table.shape[0], 1.0 / world)
-        return self._lm_grads(dL, saved, rows, N, shape, world)
+    def _head_port(self):
+        """All a prediction head sees of the model (``heads.HeadPort``)."""
+        world = float(self._ddp.world) if self._ddp is not None and getattr(self._ddp, "world", 1) > 1 else 1.0
+        return HeadPort(self._flat_p, self._flat_g, self._flat_b16, self._entries, self._nograd, self._shadow_gen, world,
+                        self._wait_optimizer, self._open_grad_pass_once)
 
     @torch.no_grad()
     def lm_predict(self, labels=None, rows=None, k=5):
@@ -976,33 +696,7 @@ class CrctModel(nn.Module):
         or the device (``batch['mask']``; a device tensor costs one ``.cpu()``), compacted as the loss compacts them -- and ``rows``: flat row
         indices into [B * T], without labels.  k in {1, 5, 8}.  Returns an ``LmPrediction``; no row selected: empty tensors and no launch.
         The head runs on the selected rows only (gather, two GEMMs, LayerNorm, one top-k launch per call)."""
-        if (labels is None) == (rows is None):
-            raise ValueError("lm_predict: give exactly one of labels= ([B, T], -1 = skip) and rows= (flat row indices)")
-        if int(k) not in (1, 5, 8):
-            raise ValueError("lm_predict: k = %r must be 1, 5 or 8" % (k,))
-        eng = self._engine
-        if eng is None or eng._keep is None:
-            raise RuntimeError("lm_predict: run a forward pass first")
-        B, T = eng._keep[0]["tokens"].shape
-        dev = self._flat_p.device
-        if labels is not None:
-            if labels.numel() != B * T:
-                raise ValueError("lm_predict: labels has %d elements, the last forward had B * T = %d * %d rows" % (labels.numel(), B, T))
-            job = self._lm_job(labels)
-            row_idx, lab, R = (job.rows, job.labels, job.R) if job is not None else (None, None, 0)
-        else:
-            r64 = torch.as_tensor(rows).reshape(-1).to(torch.int64).cpu()
-            R, lab = int(r64.numel()), None
-            if R and bool(((r64 < 0) | (r64 >= B * T)).any()):
-                raise ValueError("lm_predict: rows must lie in [0, B * T = %d)" % (B * T))
-            row_idx = r64.to(torch.int32).to(dev) if R else None
-        if R == 0:
-            e_i, e_f = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, device=dev)
-            return LmPrediction(e_i, e_i.reshape(0, int(k)), e_f.reshape(0, int(k)), e_f if labels is not None else None, e_i if labels is not None else None)
-        seq_t = eng.sequence_outputs(visual=False)[0]
-        logits, _ = self._lm_logits(seq_t, row_idx, R)
-        ids, logprob, _, lab_lp, lab_rank = ops.lm_topk_rows(logits, R, self.config.vocab_size, int(k), lab)
-        return LmPrediction(row_idx, ids, logprob, lab_lp, lab_rank)
+        return self.text_head.predict(self._engine, labels, rows, k)
 
     def _device_inputs(self, input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
                        image_attention_mask, image_target, R, labels, areas=None):
@@ -1062,12 +756,17 @@ class CrctModel(nn.Module):
         R, kind = gt_reg[0], gt_reg[1]
         train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
         # the masked-LM loss of this batch (host work only; a bad label is refused here, before any launch); None: off, or no token has a label
-        lm_job = self._lm_job(masked_lm_labels) if train_branch and self.lm_loss_coeff > 0.0 else None
+        text_head, region_head = self.text_head, self.region_head
+        lm_job = lm_rows(masked_lm_labels, self.config.vocab_size) if train_branch and self.lm_loss_coeff > 0.0 else None
+        lm_job = text_head.upload(lm_job) if lm_job is not None else None
         # ... and the masked-region loss: the targets are image_target unless image_class is given (it takes their place for the loss ONLY)
         region_job = None
         if train_branch and self.img_loss_coeff > 0.0:
-            region_job = self._region_job(image_label, image_target if image_class is None else image_class,
-                                          "image_target" if image_class is None else "image_class", *image_feat.shape[:2])
+            region_job = region_rows(image_label, image_target if image_class is None else image_class,
+                                     "image_target" if image_class is None else "image_class", *image_feat.shape[:2], self.config.v_target_size)
+            region_job = region_head.upload(region_job) if region_job is not None else None
+        # what the step hands out: the sequence outputs on request or for a head's loss or scores, the scores' own tensors, the maps
+        want_seq = bool(self.return_sequence_outputs or lm_job is not None or region_job is not None or self.return_lm_scores)
         tensors = self._device_inputs(input_ids, txt_loc, image_feat, image_loc, token_type_ids, attention_mask,
                                       image_attention_mask, image_target, R, next_sentence_label if train_branch else None, areas)
         B, T = tensors["tokens"].shape
@@ -1095,14 +794,11 @@ class CrctModel(nn.Module):
                 tensors = dict(tensors, image_feat=live[0].detach(), image_loc=live[1].detach(), loc=live[2].detach())
                 if live[3] is not None:
                     tensors["areas"] = live[3].detach()
-            self._lm_pending = (lm_job, region_job) if lm_job is not None or region_job is not None else None
-            try:
-                (loss, nsp, reg_loss, logits, reg, stats), seq, scores, maps = _StepFn.split(self, _StepFn.apply(self._anchor, self, tensors, step, *live))
-            finally:
-                self._lm_pending = None
-            lm_loss = _LmLossFn.apply(seq[0], self, lm_job) if lm_job is not None else None
-            lm_scores = _LmScoresFn.apply(seq[0], self) if self.return_lm_scores else None
-            img_loss = _RegionLossFn.apply(seq[1], self, region_job) if region_job is not None else None
+            wants = _StepWants(want_seq, bool(self.differentiable_scores), map_keys)
+            (loss, nsp, reg_loss, logits, reg, stats), seq, scores, maps = _StepFn.split(self, _StepFn.apply(self._anchor, self, tensors, step, wants, *live))
+            lm_loss = _HeadLossFn.apply(seq[0], text_head, lm_job) if lm_job is not None else None
+            lm_scores = _LmScoresFn.apply(seq[0], text_head) if self.return_lm_scores else None
+            img_loss = _HeadLossFn.apply(seq[1], region_head, region_job) if region_job is not None else None
             value = scores[1] if len(scores) > 1 else None
             if scores:
                 logits = scores[0]                     # differentiable_scores: the copies that are part of the graph
@@ -1111,10 +807,10 @@ class CrctModel(nn.Module):
             eng.forward(self._flat_p, self._flat_b16, tensors, step)
             logits, reg, stats = eng.snapshot(B)
             loss, nsp, reg_loss = stats[0], stats[1:2], reg[1]
-            seq = eng.sequence_outputs() if self.return_sequence_outputs or lm_job is not None or region_job is not None or self.return_lm_scores else ()
-            lm_loss = self._lm_forward(seq[0], lm_job)[0] if lm_job is not None else None      # torch.no_grad() in the training branch: forward only
-            lm_scores = self._lm_scores(seq[0])[0] if self.return_lm_scores else None
-            img_loss = self._region_forward(seq[1], region_job)[0] if region_job is not None else None
+            seq = eng.sequence_outputs() if want_seq else ()
+            lm_loss = text_head.loss(seq[0], lm_job)[0] if lm_job is not None else None      # torch.no_grad() in the training branch: forward only
+            lm_scores = text_head.scores(seq[0])[0] if self.return_lm_scores else None
+            img_loss = region_head.loss(seq[1], region_job)[0] if region_job is not None else None
             maps = [eng.attention_probs(*key) for key in map_keys]
             if output_all_attention_masks and not train_branch:
                 attention_maps = self._attention_maps(eng)

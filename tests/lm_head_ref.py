@@ -1,4 +1,4 @@
-"""fp64 reference, emulation and error budget of the masked-LM head (crct/model.py ``_lm_forward`` / ``_lm_backward``, csrc/lm_head.hip).
+"""fp64 reference, emulation and error budget of the masked-LM head (crct/heads.py ``PredictionHead.loss`` / ``loss_backward``, csrc/lm_head.hip).
 
 The head, for the rows r of ``seq`` [N, H] that carry a label (-1 = none):
 

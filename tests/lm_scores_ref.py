@@ -1,4 +1,4 @@
-"""fp64 reference, emulation and error budget of the masked-LM head's SCORES (crct/model.py ``_lm_logits`` / ``_lm_grads``, ``return_lm_scores``,
+"""fp64 reference, emulation and error budget of the masked-LM head's SCORES (crct/heads.py ``PredictionHead.logits`` / ``grads``, ``return_lm_scores``,
 ``lm_predict``), and a numpy restatement of the order ``lm_topk_rows`` sorts a row by.  Built from the pieces of tests/lm_head_ref.py.
 
 The head on the rows ``rows`` of ``seq`` [N, H] (default: all of them):

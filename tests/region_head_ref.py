@@ -1,4 +1,4 @@
-"""fp64 reference, emulation and error budget of the masked-region head (crct/model.py ``_region_forward`` / ``_region_backward``,
+"""fp64 reference, emulation and error budget of the masked-region head (crct/heads.py ``PredictionHead.loss`` / ``loss_backward``,
 csrc/region_head.hip), in the ``run / reference / emulate / budget`` shape of tests/lm_head_ref.py, whose rounding helpers and constants
 it uses.
 

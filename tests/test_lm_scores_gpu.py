@@ -389,7 +389,7 @@ def test_the_bert_vocabulary_end_to_end():
     scores, seq = core.prediction_scores_t, core.sequence_output_t
     assert tuple(scores.shape) == (b, t, V) and scores.stride() == (t * 30528, 30528, 1)
     # the device's own logits: a second evaluation of the head on the same states gives the same bits, and the view stops at column V
-    logits, _ = core._lm_logits(seq.detach(), torch.arange(b * t, dtype=torch.int32, device=DEV), b * t)
+    logits, _ = core.text_head.logits(seq.detach(), torch.arange(b * t, dtype=torch.int32, device=DEV), b * t)
     assert tuple(logits.shape) == (64, 30528) and torch.equal(bits(logits[:b * t, :V]), bits(scores.detach().reshape(-1, V)))
     xs = scores.detach().cpu().reshape(-1, V)
     labels = batch["mask"].reshape(-1)

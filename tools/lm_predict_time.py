@@ -23,6 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "cqa-crct_amd"))
 from crct import config as C                       # noqa: E402
 from crct import ops                               # noqa: E402
 from crct import synthetic as S                    # noqa: E402
+from crct.heads import lm_rows                     # noqa: E402
 from crct.model import VisualDialogEncoder         # noqa: E402
 from crct.step_adapter import forward as step_forward   # noqa: E402
 
@@ -92,11 +93,11 @@ def main():
             say(what="forward", return_lm_scores=k, B=B, T=T, vocab=vocab, ms=[round(v, 3) for v in ms[k]], ms_min=round(min(ms[k]), 3),
                 scores_bytes=B * T * vocab * 4 if k == "on" else 0, padded_buffer_bytes=buf_bytes if k == "on" else 0)
         # ---- the row kernels on the same logits: the labelled rows, then all rows
-        job = core._lm_job(labels)
+        job = core.text_head.upload(lm_rows(labels, vocab))
         seq_t = core._engine.sequence_outputs(visual=False)[0]
         for name, rows, lab, R in (("labelled", job.rows, job.labels, job.R),
                                    ("all", torch.arange(B * T, dtype=torch.int32, device=dev), batch["tokens"].reshape(-1).to(torch.int32), B * T)):
-            logits, _ = core._lm_logits(seq_t, rows, R)
+            logits, _ = core.text_head.logits(seq_t, rows, R)
             forms = {"lm_ce_fwd": lambda: ops.lm_ce_fwd(logits, lab, R, vocab, 1.0 / R)}
             for k in (1, 5, 8):
                 forms["lm_topk_rows k=%d" % k] = lambda k=k: ops.lm_topk_rows(logits, R, vocab, k, lab)
